@@ -15,13 +15,22 @@ cutoff 5 A, 1152 edges each), per rank.  With N ranks the crystals are sharded b
 all_gather_into_tensor of the [B,21] predictions (configs[4]).  value = edge tensor-products/s over
 all ranks: one edge-TP = one (edge, conv layer) evaluation, 4 conv layers => 4 per edge per forward.
 
-Printed by rank 0: one JSON line with the driver contract fields plus
+Printed by rank 0: one JSON line with the driver contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  A plain run does only what that line needs: set up, warm up, time --steps forwards, print.
+With --full the line also holds
   "roofline"     -- the dominant kernel (tp_fused_kernel, mean over its launches) against the HBM roofline
+                    (HIP events around its launches inside the timed loop), plus "calibration" (fixed VALU / copy kernels
+                    and a clock probe around the timed region; --no-calibration skips), "hipgraph_replay" and the
+                    full-last-layer loop ("value_full_layers"; --no-full-layers skips)
   "cpu_baseline" -- the CPU oracle (a restatement of the reference's e3nn path, NOT e3nn itself;
-                    e3nn cannot be installed on either box) timed on a bounded sample, rank 0, N=1
+                    e3nn cannot be installed on either box) timed on a bounded sample, rank 0, N=1 (--no-cpu-baseline skips)
   "extras"       -- short driver-timed runs of the other single-GPU configurations (N = 1 only; --no-extras skips):
                     configs[1] n100 forward, configs[3] training step (batch 32, eager and hipGraph) with the roofline
                     of its dominant kernel, predict() end to end at batch_size 200 / 1000
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (the [B, 21] predictions,
+[N * B, 21] after the all_gather) as DIR/elastic_tensor_full.npy, float32.  Inputs and weights are seeded: two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -51,6 +60,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--crystals", type=int, default=1000, help="crystals per rank per step (one batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's predictions to DIR/elastic_tensor_full.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure: per-kernel HIP-event timings and rooflines, "
+                         "calibration, hipGraph replay, full-last-layer loop, CPU baseline, extras (the --no-* options "
+                         "below act inside --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=8, help="crystals in the CPU-oracle sample batch")
     ap.add_argument("--no-extras", action="store_true", help="skip the configs[1] / configs[3] / predict() extras")
@@ -548,6 +563,25 @@ def algorithmic_bytes_tp_kernel(plan, deg: float) -> float:
     return 8.0 + 12.0 + 4.0 * plan.weight_numel + 4.0 * (plan.d_in + plan.d_mid) / deg
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path: str, arrays) -> None:
+    """--dump-outputs: one DIR/<name>.npy (float32) per array the timed path returned.  An array above DUMP_BYTES_MAX
+    keeps a fixed, seeded sample of its rows (sorted row order), the same rows for the same arguments."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() * 4 > DUMP_BYTES_MAX:
+            row_bytes = 4 * (a.numel() // a.shape[0])
+            keep = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:DUMP_BYTES_MAX // row_bytes]
+            a = a[keep.sort().values]
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+
+
 def main():
     args = parse()
     args.force_dist = args.force_dist or os.environ.get("MATTEN_FORCE_DIST") == "1"
@@ -633,14 +667,16 @@ def run_rank(args):
     calibration = None
     from matten_amd import lab as _lab_probe
 
-    if rank == 0 and not args.no_calibration and _lab_probe.load() is not None:   # (also in the --share-gpu rehearsal)
+    if (args.full and rank == 0 and not args.no_calibration
+            and _lab_probe.load() is not None):   # (also in the --share-gpu rehearsal)
         calibration = {"before": calibrate(dev)}
         for _ in range(2):          # the calibration kernels evicted the caches the warm-up filled
             forward_only()          # (rank-local: no collective, the other ranks are waiting in the barrier below)
     barrier()
-    # HIP events around the dominant kernel (roofline) and the radial-MLP kernel (mfma) only: an event pair costs a few
-    # microseconds of queue time, the timed region should not pay it for every launch
-    ops.enable_event_timing(True, only=("tp_scatter", "agg_linear", "radial_hidden"))
+    # --full: HIP events around the dominant kernel (roofline) and the radial-MLP kernel (mfma) only: an event pair costs
+    # a few microseconds of queue time, the timed region should not pay it for every launch
+    if args.full:
+        ops.enable_event_timing(True, only=("tp_scatter", "agg_linear", "radial_hidden"))
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
@@ -650,6 +686,8 @@ def run_rank(args):
     kernel_ms = ops.event_timings_ms()
     ops.enable_event_timing(False)
     assert os.environ.get("MATTEN_BENCH_NO_CHECK") == "1" or torch.isfinite(out).all()  # the env is for ablation builds only
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"elastic_tensor_full": out})
 
     if calibration is not None:
         # the shader clock the chip sustains UNDER THE FORWARD's load: a one-wave probe on a side stream watches the clocks
@@ -718,7 +756,7 @@ def run_rank(args):
         },
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel, tp_fused_kernel, averaged over its launches of the timed region (one per
         # conv layer and step) -- the same average rocprofv3 --stats reports for the kernel ----
         deg = n_edges / n_nodes
@@ -992,6 +1030,7 @@ def run_rank(args):
             del batch, out
             torch.cuda.empty_cache()
             result["extras"] = extras(dev)
+    if rank == 0:
         print(json.dumps(result), flush=True)
 
     if distributed:

@@ -31,7 +31,7 @@ def test_bench_rccl_branch_with_one_rank():
     """`bench.py --gpus 1 --force-dist`: init_process_group("nccl") = RCCL, barrier, all_gather_into_tensor of the [B, 21]
     predictions, max-over-ranks all_reduce -- everything `--gpus 8` runs, with one rank.  Rank 0's calibration (fixed
     kernels + clock probe beside untimed forwards) stays on: it must not issue a collective."""
-    d = _bench_line(["--gpus", "1", "--force-dist", "--no-extras", "--no-cpu-baseline", "--steps", "3", "--warmup", "2"])
+    d = _bench_line(["--gpus", "1", "--force-dist", "--full", "--no-extras", "--no-cpu-baseline", "--steps", "3", "--warmup", "2"])
     assert d["rccl_ranks"] == 1 and d["n_gpus"] == 1 and d["backend"] == "nccl (RCCL)"
     assert d["output_shape"] == [1000, 21] and d["steps"] == 3 and d["scaling"] == "weak"
     assert d["value"] > 0 and d["config"]["sharding"].startswith("batch-index x1")
@@ -42,11 +42,39 @@ def test_bench_two_rank_rehearsal_keeps_calibration():
     """`--gpus 2 --backend gloo --share-gpu`: two ranks on cuda:0, predictions gathered through host tensors.  Measures
     nothing; what it proves is that the N > 1 branch terminates with calibration ON (rank 0 alone runs side work between
     the barriers) and gathers [2 B, 21]."""
-    d = _bench_line(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--no-extras", "--no-cpu-baseline", "--steps", "3",
+    d = _bench_line(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--full", "--no-extras", "--no-cpu-baseline", "--steps", "3",
                      "--warmup", "1", "--crystals", "100"])
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 0 and "REHEARSAL" in d["backend"]
     assert d["output_shape"] == [200, 21]
     assert d["calibration"]["before"]["valu"]["ms"] > 0 and d["calibration"]["after"]["copy"]["GBps"] > 0
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields for exactly --steps timed steps and nothing that needs side work;
+    --dump-outputs holds the last timed step's [B, 21] predictions, equal to the same model's forward of the same seeded
+    batch in this process."""
+    import numpy as np
+
+    from __graft_entry__ import PAPER_HPARAMS
+    from matten_amd.data import synthetic as S
+    from matten_amd.data.graph import collate
+    from matten_amd.model_factory.tfn_scalar_tensor import ScalarTensorModel
+
+    B = 100
+    d = _bench_line(["--gpus", "1", "--steps", "3", "--warmup", "1", "--crystals", str(B), "--dump-outputs", str(tmp_path)])
+    assert d["metric"] == "edge_tensor_products_per_sec" and d["unit"] == "edge-TP/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert not {"roofline", "kernel_ms_per_launch", "calibration", "hipgraph_replay", "cpu_baseline", "extras"} & set(d)
+    got = np.load(tmp_path / "elastic_tensor_full.npy")
+    assert got.dtype == np.float32 and got.shape == (B, 21) and np.isfinite(got).all()
+    torch.manual_seed(35)
+    ds = {"allowed_species": list(S.FCC_METALS), "average_num_neighbors": 18.0}
+    model = ScalarTensorModel(backbone_hparams=dict(PAPER_HPARAMS), dataset_hparams=ds).to("cuda:0").eval()
+    with torch.no_grad():
+        want = model(collate(S.fcc64_shard(0, 1, B), device="cuda:0"))[0]["elastic_tensor_full"].cpu().numpy()
+    for lo, hi in ((0, 2), (2, 12), (12, 21)):     # per irrep block of the 21 components, against the block's scale
+        err = np.abs(got[:, lo:hi] - want[:, lo:hi]).max()
+        assert err <= 2e-6 * np.abs(want[:, lo:hi]).max() + 1e-12, (lo, err)
 
 
 def test_eight_rank_shards_tile_one_set():

@@ -609,6 +609,24 @@ def test_bench_rehearsal_flags(monkeypatch):
         bench.main()
 
 
+def test_bench_dump_outputs_writes_float32_and_bounds_the_size(tmp_path, monkeypatch):
+    """--dump-outputs: DIR/<name>.npy in float32 with the values as returned; above the size cap a seeded sample of rows,
+    the same rows on every call."""
+    import bench
+
+    t = torch.arange(40 * 21, dtype=torch.float64).reshape(40, 21)
+    bench.dump_outputs(str(tmp_path / "a"), {"elastic_tensor_full": t})
+    a = np.load(tmp_path / "a" / "elastic_tensor_full.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 10 * 21 * 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"elastic_tensor_full": t})
+    b, c = (np.load(tmp_path / d / "elastic_tensor_full.npy") for d in ("b", "c"))
+    assert b.shape == (10, 21) and np.array_equal(b, c)
+    rows = b[:, 0].astype(np.int64) // 21
+    assert len(set(rows)) == 10 and np.all(np.diff(rows) > 0) and np.array_equal(b, t.float().numpy()[rows])
+
+
 def test_reference_training_script_call_sequence_under_the_matten_alias(golden_dir):
     """scripts/train_materials_tensor.py:11-14,34-52 of the reference, line by line, with `import matten` resolving to
     this package: data module -> get_to_model_info -> ScalarTensorModel(tasks=TensorRegressionTask(...), ...) ->

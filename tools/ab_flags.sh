@@ -14,7 +14,7 @@ for rep in $(seq 1 ${REPS:-3}); do
   for fl in "${SETS[@]}"; do
     cp build/tp_fused_$i.o build/tp_fused.o
     hipcc --offload-arch=gfx950 -shared -fPIC $(ls build/*.o | grep -v 'tp_fused_') -o ../libmatten_hip.so
-    python3 ../../bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+    python3 ../../bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_launch']
 print('rep $rep [$fl]: step %.3f ms' % d['ms_per_step'], 'tp', ' '.join('%.3f'%v for n,v in k.items() if n.startswith('tp')))"
     i=$((i+1))

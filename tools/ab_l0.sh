@@ -9,7 +9,7 @@ for rep in 1 2 3; do
   for c in 96 64; do
     cp build/tp_fused_$c.o build/tp_fused.o
     hipcc --offload-arch=gfx950 -shared -fPIC $(ls build/*.o | grep -v 'tp_fused_') -o ../libmatten_hip.so
-    MATTEN_TP_MAX_COLS_L0=$c python3 ../../bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+    MATTEN_TP_MAX_COLS_L0=$c python3 ../../bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_launch']
 print('rep $rep [l0 cols $c]: step %.3f ms' % d['ms_per_step'], 'tp', ' '.join('%.3f'%v for n,v in k.items() if n.startswith('tp')))"
   done

@@ -13,7 +13,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for sch in ${SCHEMES:-A D}; do
     cp build/tp_fused_$sch.o build/tp_fused.o; cp build/tp_path_$sch.o build/tp_path.o
     hipcc --offload-arch=gfx950 -shared -fPIC $(ls build/*.o | grep -v "_[A-E]\.o" | grep -v calib) -o ../libmatten_hip.so
-    MATTEN_TP_GROUPS=$sch python3 ../../bench.py --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-extras --no-calibration 2>/dev/null | tail -1 | python3 -c "
+    MATTEN_TP_GROUPS=$sch python3 ../../bench.py --full --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-extras --no-calibration 2>/dev/null | tail -1 | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_launch']
 print('rep $rep [scheme $sch]: step %.3f ms  full-layers %.3f' % (d['ms_per_step'], d.get('ms_per_step_full_layers', 0)), 'tp', ' '.join('%.3f'%v for n,v in k.items() if n.startswith('tp')))"
   done
