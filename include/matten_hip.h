@@ -34,8 +34,16 @@ typedef void* matten_stream_t; /* hipStream_t */
 #define MATTEN_ELAUNCH (-2) /* hipGetLastError() != hipSuccess after a launch */
 #define MATTEN_ENOMEM (-3)  /* caller-provided workspace too small */
 
-/* ABI version of this header; bumped on any signature change. */
+/* ABI version of this header; bumped on any signature change (45: the _deep radial MLP entries). */
 int matten_abi_version(void);
+
+/* Radial MLP depth.  The reference builds every conv layer's radial network as FullyConnectedNet([nb] + L x [32] + [W],
+ * silu) with L = invariant_layers (nn/utils.py:244-251).  The entries without a suffix take the L = 2 shape (w1p, one
+ * middle layer); each has a _deep sibling that takes (w_mid, n_mid) in place of w1p / w1: n_mid = L - 1 middle layers
+ * 32 -> 32 (silu), their weights ONE buffer w_mid[n_mid][32][32] (packed: each pre-scaled like w1p; raw: like w1), NULL
+ * allowed for n_mid = 0.  n_mid outside 0..MATTEN_RADIAL_MAX_MID is MATTEN_EINVAL.  n_mid = 1 runs the same kernels as
+ * the unsuffixed entry. */
+#define MATTEN_RADIAL_MAX_MID 3
 
 /* ------------------------------------------------------------------------------------------
  * Graph indexing.  Replaces the implicit ordering torch_scatter.scatter(msg, edge_dst) relies
@@ -126,6 +134,9 @@ int matten_edge_geom(const float* pos, const int64_t* edge_index, const float* e
 int matten_radial_mlp(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
                       const float* w0p, int nb_pad, const float* w1p, const float* w2p, int hidden, int w_pad,
                       float act_cst, void* w_edge, int out_is_bf16, matten_stream_t stream);
+int matten_radial_mlp_deep(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                           const float* w0p, int nb_pad, const float* w_mid, int n_mid, const float* w2p, int hidden,
+                           int w_pad, float act_cst, void* w_edge, int out_is_bf16, matten_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * 'uvu' TensorProduct + gather + scatter-add + neighbour normalisation over MATERIALISED per-edge weights
@@ -230,6 +241,15 @@ int matten_radial_hidden_multi(const float* geom_sorted, int64_t n_edges, int n_
                                const float* const* w0p, int nb_pad, const float* const* w1p, int hidden,
                                uint16_t* const* h2s, const float* const* h_scale, int n_layers,
                                matten_stream_t stream);
+/* any depth: h2s holds the LAST hidden layer's features (same form); w_mid of the multi launch is a host array of
+ * n_layers device pointers, every MLP with the same n_mid */
+int matten_radial_hidden_deep(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                              const float* w0p, int nb_pad, const float* w_mid, int n_mid, int hidden, uint16_t* h2s,
+                              const float* h_scale, matten_stream_t stream);
+int matten_radial_hidden_multi_deep(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                                    const float* const* w0p, int nb_pad, const float* const* w_mid, int n_mid, int hidden,
+                                    uint16_t* const* h2s, const float* const* h_scale, int n_layers,
+                                    matten_stream_t stream);
 int matten_tp_fused(const float* x, int64_t d_in, const uint16_t* h2s, const float* w2p, int64_t w_pad,
                     const float* sh_sorted, int64_t sh_stride, const int32_t* rowptr, const int32_t* src_sorted,
                     int64_t n_nodes, const int32_t* group_entries, const int32_t* unit_map, int64_t n_entries,
@@ -317,18 +337,31 @@ int matten_radial_mlp_bwd(const float* geom_sorted, int64_t n_edges, int n_basis
                           float* part_small, float* part_w2, float scale0, float scale1, float scale2,
                           float* grad_small, float* grad_w2, matten_stream_t stream);
 /* grad_small [nb_pad*32 + 32*32] / grad_w2 [32, w_pad] (both or neither, may be NULL): the partial sums added up in slice
- * order by a third launch of the same call */
+ * order by a third launch of the same call.
+ * _deep: a slice of part_small / grad_small is [nb_pad*32 + n_mid*32*32]: scale0 d/dW0p, then scale1 d/dWmid_p[i] for
+ * i = 0 .. n_mid-1; h2_scratch holds the last hidden layer.  The slice count does not depend on n_mid, the range
+ * count does: part_w2 has matten_radial_mlp_bwd_w2_ranges_deep(E, w_pad, n_mid) rows. */
+int64_t matten_radial_mlp_bwd_w2_ranges_deep(int64_t n_edges, int64_t w_pad, int n_mid);
+int matten_radial_mlp_bwd_deep(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                               const float* w0p, int nb_pad, const float* w_mid, int n_mid, const float* w2p, int hidden,
+                               int w_pad, int w_cols, const void* dw, int64_t dw_ld, int dw_is_bf16, float* h2_scratch,
+                               float* part_small, float* part_w2, float scale0, float scale1, float scale2,
+                               float* grad_small, float* grad_w2, matten_stream_t stream);
 /* the raw layers (w0 [nb,32], w1 [32,32], w2 [32,W]) -> packed operands w0p = scale0 w0 (rows padded to nb_pad),
  * w1p = scale1 w1, w2p = scale2 w2 (columns padded to w_pad), one launch; matten_radial_mlp_bwd multiplies its partial
  * sums by the same three factors, so they are gradients w.r.t. the RAW layers */
 int matten_radial_pack(const float* w0, const float* w1, const float* w2, int n_basis, int nb_pad, int w_cols, int w_pad,
                        float scale0, float scale1, float scale2, float* w0p, float* w1p, float* w2p,
                        matten_stream_t stream);
+/* _deep: w_mid [n_mid,32,32] raw -> w_mid_p = scale1 w_mid (the same factor for every middle layer) */
+int matten_radial_pack_deep(const float* w0, const float* w_mid, int n_mid, const float* w2, int n_basis, int nb_pad,
+                            int w_cols, int w_pad, float scale0, float scale1, float scale2, float* w0p, float* w_mid_p,
+                            float* w2p, matten_stream_t stream);
 /* Operands of matten_tp_fused derived from the RAW radial layers by kernels (training on the production kernel):
  * matten_radial_pack_cols: as matten_radial_pack, the last layer gathered through cols[n_cols] int64 (fused column order
  *   of plan.fused_cols, -1 = zero column), zero up to w_pad;
  * matten_radial_h_scale: out2 = [s, 1/s], the power of two <= 1 that keeps the hidden features inside the fp16 range
- *   (bound from the two layers' column-sum norms, as nn/utils.py RadialMLP._fp16_scale);
+ *   (bound from the hidden layers' column-sum norms, as nn/utils.py RadialMLP._fp16_scale: P(c) n0 n_1 ... n_{n_mid});
  * matten_split_a_tiles: w2p [32, w_pad] -> the fp16 hi / lo A fragments of every group entry (word 5 = first column,
  *   6 = first tile, 7 = tile count) + scale_inv[n_entries] = 1 / (entry scale) * h_scale[1] (h_scale may be NULL). */
 int matten_radial_pack_cols(const float* w0, const float* w1, const float* w2, int n_basis, int nb_pad, int w_cols,
@@ -336,6 +369,11 @@ int matten_radial_pack_cols(const float* w0, const float* w1, const float* w2, i
                             float* w1p, float* w2p, matten_stream_t stream);
 int matten_radial_h_scale(const float* w0, const float* w1, int n_basis, float r_start, float r_end, float act_cst,
                           float* out2, matten_stream_t stream);
+int matten_radial_pack_cols_deep(const float* w0, const float* w_mid, int n_mid, const float* w2, int n_basis, int nb_pad,
+                                 int w_cols, const int64_t* cols, int n_cols, int w_pad, float scale0, float scale1,
+                                 float scale2, float* w0p, float* w_mid_p, float* w2p, matten_stream_t stream);
+int matten_radial_h_scale_deep(const float* w0, const float* w_mid, int n_mid, int n_basis, float r_start, float r_end,
+                               float act_cst, float* out2, matten_stream_t stream);
 int matten_split_a_tiles(const float* w2p, int64_t w_pad, const int32_t* group_entries, int64_t n_entries,
                          const float* h_scale, uint16_t* frag, float* scale_inv, matten_stream_t stream);
 /* out[i] = src[idx[i]] * scale[(scale_by_source ? idx[i] : i) % scale_period]: the per-species re-packing of a flat e3nn

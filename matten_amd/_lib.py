@@ -14,7 +14,7 @@ from ctypes import c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmatten_hip.so")
 
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 # name -> (restype, argtypes); must match include/matten_hip.h
 P = c_void_p
@@ -30,10 +30,13 @@ SIGNATURES = {
     "matten_species_embed": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P, P, c_int64, P, P, P, P, P, P]),
     "matten_edge_geom": (c_int, [P, P, P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_float, c_float, P, P, c_int, P, P, P, P, P]),
     "matten_radial_mlp": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, P, c_int, c_int, c_float, P, c_int, P]),
+    "matten_radial_mlp_deep": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, P, c_int, c_int, c_float, P, c_int,
+                                       P]),
     "matten_tp_tile_nodes": (c_int, []),
     "matten_tp_paths": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, c_int64, P, P, c_int64, c_int64, c_int64, c_float, P, P, c_int,
                                 P]),
     "matten_radial_hidden_multi": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, P, P, c_int, P]),
+    "matten_radial_hidden_multi_deep": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, c_int, P, P, c_int, P]),
     "matten_agg_linear_max_mt": (c_int, []),
     "matten_agg_linear_block_chunks": (c_int, []),
     "matten_agg_linear_lds_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
@@ -44,6 +47,7 @@ SIGNATURES = {
                                        c_int64, P, P, P, P, c_int64, P, P]),
     "matten_agg_linear_gate_sets": (c_int, []),
     "matten_radial_hidden": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, P, P, P]),
+    "matten_radial_hidden_deep": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, c_int, P, P, P]),
     "matten_tp_max_cols": (c_int, []),
     "matten_tp_max_cols_l0": (c_int, []),
     "matten_tp_max_cols_l1": (c_int, []),
@@ -53,11 +57,18 @@ SIGNATURES = {
     "matten_species_linear_rows": (c_int, [P, c_int64, P, P, c_int64, P, c_int64, P, c_int64, c_int64, P, c_int64, c_int64, P, P]),
     "matten_radial_mlp_bwd_small_slices": (c_int64, [c_int64]),
     "matten_radial_mlp_bwd_w2_ranges": (c_int64, [c_int64, c_int64]),
+    "matten_radial_mlp_bwd_w2_ranges_deep": (c_int64, [c_int64, c_int64, c_int]),
     "matten_radial_mlp_bwd": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, P, c_int, c_int, c_int, P, c_int64,
                                       c_int, P, P, P, c_float, c_float, c_float, P, P, P]),
+    "matten_radial_mlp_bwd_deep": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, P, c_int, c_int, c_int, P,
+                                           c_int64, c_int, P, P, P, c_float, c_float, c_float, P, P, P]),
     "matten_radial_pack": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),
+    "matten_radial_pack_deep": (c_int, [P, P, c_int, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),
     "matten_radial_pack_cols": (c_int, [P, P, P, c_int, c_int, c_int, P, c_int, c_int, c_float, c_float, c_float, P, P, P, P]),
+    "matten_radial_pack_cols_deep": (c_int, [P, P, c_int, P, c_int, c_int, c_int, P, c_int, c_int, c_float, c_float, c_float, P, P,
+                                             P, P]),
     "matten_radial_h_scale": (c_int, [P, P, c_int, c_float, c_float, c_float, P, P]),
+    "matten_radial_h_scale_deep": (c_int, [P, P, c_int, c_int, c_float, c_float, c_float, P, P]),
     "matten_split_a_tiles": (c_int, [P, c_int64, P, c_int64, P, P, P, P]),
     "matten_gather_scale": (c_int, [P, P, P, c_int64, c_int64, c_int, P, P, P, P]),
     "matten_species_linear_wgrad_scratch_floats": (c_int64, [c_int64, c_int64, c_int64]),

@@ -92,26 +92,51 @@ def set_edge_storage_dtype(dtype) -> None:
     EDGE_STORAGE_DTYPE = dtype
 
 
+# The radial MLP of any depth (nn.utils.RadialMLP: layer0 .. layer{L}): the shipped L = 2 on the original entries (one
+# middle layer w1), every other depth on the _deep ones (the middle layers as one [L-1, 32, 32] tensor).
+def _radial_pack(mlp, ws):
+    """raw layers -> (w0p, middle layers packed, w2p) in the reference's column order, one launch"""
+    if not mlp.deep:
+        return ops.radial_pack(*ws, mlp.pack_scales())
+    return ops.radial_pack_deep(ws[0], _stack_mid(ws), ws[-1], mlp.pack_scales())
+
+
+def _stack_mid(ws):
+    return torch.stack(ws[1:-1]) if len(ws) > 2 else ws[0].new_zeros(0, 32, 32)
+
+
+def _radial_mlp(mlp, geom, rbf, w0p, w1p, w2p):
+    return (ops.radial_mlp_deep if mlp.deep else ops.radial_mlp)(geom, *rbf, w0p, w1p, w2p, out_dtype=EDGE_STORAGE_DTYPE)
+
+
+def _radial_mlp_bwd(mlp, geom, rbf, w0p, w1p, w2p, dw, scales) -> tuple:
+    """one gradient per raw layer (layer0 .. layer{L})"""
+    nb, W = mlp.hs[0], mlp.hs[-1]
+    # the kernels multiply their partial sums by the packing factors: gradients w.r.t. the raw layers come back
+    if not mlp.deep:
+        d0, d1, d2 = ops.radial_mlp_bwd(geom, *rbf, w0p, w1p, w2p, W, dw, scales=scales)
+        return d0[:nb], d1, d2[:, :W]
+    d0, dm, d2 = ops.radial_mlp_bwd_deep(geom, *rbf, w0p, w1p, w2p, W, dw, scales=scales)
+    return (d0[:nb], *dm.unbind(0), d2[:, :W])
+
+
 class RadialMLPFn(torch.autograd.Function):
     """w[E, w_pad] = MLP(bessel(|edge|)) in the reference's weight-column order (pad columns zero); the adjoint maps
-    dL/dw back to the three raw weight matrices (the packing is a per-layer scale and a row padding)."""
+    dL/dw back to the raw weight matrices ws = (layer0 .. layer{L}) (the packing is a per-layer scale and a row padding)."""
 
     @staticmethod
-    def forward(ctx, w0, w1, w2, mod, geom_sorted, n_basis, r_start, r_end):
-        w0p, w1p, w2p = ops.radial_pack(w0, w1, w2, mod.pack_scales())          # one launch for the three layers
+    def forward(ctx, mod, geom_sorted, n_basis, r_start, r_end, *ws):
+        w0p, w1p, w2p = _radial_pack(mod, ws)          # one launch for all layers
         ctx.mod, ctx.rbf = mod, (int(n_basis), float(r_start), float(r_end))
         ctx.save_for_backward(geom_sorted, w0p, w1p, w2p)
-        return ops.radial_mlp(geom_sorted, int(n_basis), float(r_start), float(r_end), w0p, w1p, w2p,
-                              out_dtype=EDGE_STORAGE_DTYPE)
+        return _radial_mlp(mod, geom_sorted, ctx.rbf, w0p, w1p, w2p)
 
     @staticmethod
     def backward(ctx, g):
         geom, w0p, w1p, w2p = ctx.saved_tensors
         mod = ctx.mod
-        nb, W = mod.hs[0], mod.hs[3]
-        # the kernels multiply their partial sums by the packing factors: gradients w.r.t. the raw layers come back
-        d0, d1, d2 = ops.radial_mlp_bwd(geom, *ctx.rbf, w0p, w1p, w2p, W, g.contiguous(), scales=mod.pack_scales())
-        return d0[:nb], d1, d2[:, :W], None, None, None, None, None
+        grads = _radial_mlp_bwd(mod, geom, ctx.rbf, w0p, w1p, w2p, g.contiguous(), mod.pack_scales())
+        return (None, None, None, None, None) + grads
 
 
 # training forward: batches below this many nodes walk their CSR segments in pieces (see TensorProductScatterFn.forward)
@@ -188,7 +213,7 @@ class FusedTensorProductFn(torch.autograd.Function):
     (ops.fused_operands), so the step stays capturable."""
 
     @staticmethod
-    def forward(ctx, x, w0, w1, w2, mod, data, avg, num_neigh):
+    def forward(ctx, x, mod, data, avg, num_neigh, *ws):
         from .data.irreps import DataKey
 
         dev = x.device
@@ -198,13 +223,19 @@ class FusedTensorProductFn(torch.autograd.Function):
         ctx.rbf = (int(nb), float(r0), float(r1))
         ctx.graph = (data[DataKey.AMD_GEOM], data[DataKey.AMD_SH], data[DataKey.AMD_SRC], data["_amd_dst_sorted"])
         ctx.out_csr = data.get("_amd_out_csr")
-        ctx.save_for_backward(x, w0, w1, w2)
+        ctx.save_for_backward(x, *ws)
         # the fused kernel's operands from the raw layers: four small launches, nothing read on the host (the inference
         # path derives them once with library ops and caches them; here the parameters change every step)
         gent = mod._tables.get("gentries", dev)
-        w0p, w1p, w2p, hs, frag, inv = ops.fused_operands(w0, w1, w2, mlp.pack_scales(), mod._tables.get("fused_cols", dev),
-                                                          gent, p.fused_a_tiles, r0, r1, mlp.act_cst)
-        h2p = ops.radial_hidden(data[DataKey.AMD_GEOM], int(nb), r0, r1, w0p, w1p, hs)
+        if mlp.deep:
+            w0p, w1p, w2p, hs, frag, inv = ops.fused_operands_deep(ws[0], _stack_mid(ws), ws[-1], mlp.pack_scales(),
+                                                                   mod._tables.get("fused_cols", dev), gent, p.fused_a_tiles,
+                                                                   r0, r1, mlp.act_cst)
+            h2p = ops.radial_hidden_deep(data[DataKey.AMD_GEOM], int(nb), r0, r1, w0p, w1p, hs)
+        else:
+            w0p, w1p, w2p, hs, frag, inv = ops.fused_operands(*ws, mlp.pack_scales(), mod._tables.get("fused_cols", dev),
+                                                              gent, p.fused_a_tiles, r0, r1, mlp.act_cst)
+            h2p = ops.radial_hidden(data[DataKey.AMD_GEOM], int(nb), r0, r1, w0p, w1p, hs)
         # the hidden features (128 B per edge) are what the backward re-evaluates w from; a layer with an input block wider
         # than the w-free kernel's workgroup (ops.WFREE_MAX_MUL channels) keeps the adjoint on a materialised w instead
         if W_FREE_ADJOINT and p.bw_max_mul <= ops.WFREE_MAX_MUL:
@@ -215,12 +246,12 @@ class FusedTensorProductFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        x, w0, w1, w2 = ctx.saved_tensors
+        x, *ws = ctx.saved_tensors
         mod, dev = ctx.mod, g.device
         mlp = mod.weight_nn
         geom, sh, src, dst = ctx.graph
         scales = mlp.pack_scales()
-        w0p, w1p, w2p = ops.radial_pack(w0, w1, w2, scales)                       # reference column order
+        w0p, w1p, w2p = _radial_pack(mlp, ws)                                     # reference column order
         out_csr = ctx.out_csr if os.environ.get("MATTEN_TP_BWD_DX", "ordered") != "atomic" else None
         covered = int(mod.plan.bw_blocks[:, 1].dot(2 * mod.plan.bw_blocks[:, 2] + 1)) == mod.plan.d_in
         h2p = getattr(ctx, "h2p", None)
@@ -236,14 +267,12 @@ class FusedTensorProductFn(torch.autograd.Function):
                                          max_mul=mod.plan.bw_max_mul)
             # (h2p stays on the ctx until autograd releases it: a second backward under retain_graph takes the same route)
         else:
-            w_edge = ops.radial_mlp(geom, *ctx.rbf, w0p, w1p, w2p, out_dtype=EDGE_STORAGE_DTYPE)   # transient
+            w_edge = _radial_mlp(mlp, geom, ctx.rbf, w0p, w1p, w2p)   # transient
             dx, dw = ops.tp_backward_lit(x, w_edge, sh, src, dst, mod._tables.get("bw_blocks", dev),
                                          mod._tables.get("bw_paths", dev), mod.plan.bw_sum_lanes, g.contiguous(), ctx.avg,
                                          ctx.num_neigh, out_csr=out_csr, blocks_cover_input=covered, max_l=mod.plan.bw_max_l)
             del w_edge
-        nb, W = mlp.hs[0], mlp.hs[3]
-        d0, d1, d2 = ops.radial_mlp_bwd(geom, *ctx.rbf, w0p, w1p, w2p, W, dw, scales=scales)
-        return dx, d0[:nb], d1, d2[:, :W], None, None, None, None
+        return (dx, None, None, None, None) + _radial_mlp_bwd(mlp, geom, ctx.rbf, w0p, w1p, w2p, dw, scales)
 
 
 class GateFn(torch.autograd.Function):

@@ -1,6 +1,8 @@
 // Adjoint of the radial MLP (training step): given dL/dw[E, w_ld] from the tensor-product adjoint, the gradients of the
-// three bias-free layers of e3nn FullyConnectedNet([nb, 32, 32, W], silu)  (reference nn/utils.py:246-251,260; the
-// reference gets them from autograd through three torch.mm).
+// bias-free layers of e3nn FullyConnectedNet([nb] + L x [32] + [W], silu)  (reference nn/utils.py:246-251,260; the
+// reference gets them from autograd through torch.mm).  The comments below spell out the shipped L = 2 (N_MID = 1
+// middle layer W1p); every kernel takes N_MID = L - 1 in 0..3 as a template parameter and chains all middle layers the
+// same way (z_{i+1} = h_i Wm_i, dh_i = dz_{i+1} Wm_i^T, dWm_i = h_i^T dz_{i+1}).
 //
 // In the packed form the forward kernel (radial_mlp.hip) evaluates:
 //      b = bessel(|v|) [nb]   z1 = b W0p   h1 = silu(z1)   z2 = h1 W1p   h2 = silu(z2)   w = h2 W2p
@@ -80,11 +82,88 @@ __device__ __forceinline__ float load1(const void* base, int64_t idx) {
     else return reinterpret_cast<const float*>(base)[idx];
 }
 
-// part_small[wave slice][nb_pad*32 (dW0p) + 32*32 (dW1p)]
-template <int KS0, bool BF16>
+// middle-layer arrays keep one element at N_MID = 0 (unused)
+constexpr int nm1(int n) { return n > 0 ? n : 1; }
+
+// The small weight gradients of one 16-edge tile: contraction over the tile's edges, operands transposed through the
+// wave's LDS tiles (t_h1 / t_dz2: input and output-gradient of a middle layer, t_dz1 / t_b: those of layer 0).  Pass p
+// adds dWm_p += h_p^T dz_{p+1}; pass 0 adds dW0 += b^T dz_0 too.  Passes N_MID-1 .. 0, one tile write + read each.
+template <int KS0, int N_MID>
+__device__ __forceinline__ void small_grads_tile(float* t_h1, float* t_dz2, float* t_dz1, float* t_b, const f32x4 (&h)[nm1(N_MID)][2],
+                                                 const f32x4 (&dz)[N_MID + 1][2], const float (&bes)[KS0], int g, int c,
+                                                 f32x4 (&g_wm)[nm1(N_MID)][2][2], f32x4 (&g_w0)[2]) {
+#pragma unroll
+    for (int p = (N_MID > 0 ? N_MID - 1 : 0); p >= 0; --p) {
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 16 * t + 4 * g + r;
+                if (p < N_MID) {
+                    t_h1[k * TS + c] = h[p][t][r];
+                    t_dz2[k * TS + c] = dz[p < N_MID ? p + 1 : 0][t][r];
+                }
+                if (p == 0) t_dz1[k * TS + c] = dz[0][t][r];
+            }
+        if (p == 0) {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) t_b[(4 * kk + g) * TS + c] = kk < KS0 ? bes[kk < KS0 ? kk : 0] : 0.0f;
+        }
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {   // K step s: edges 4 s + g
+            const int ee = 4 * s + g;
+            if (p < N_MID) {
+                const float h1a = t_h1[c * TS + ee], h1b = t_h1[(16 + c) * TS + ee];
+                const float d2a = t_dz2[c * TS + ee], d2b = t_dz2[(16 + c) * TS + ee];
+                f32x4 (&gw)[2][2] = g_wm[p < N_MID ? p : 0];
+                gw[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1a, d2a, gw[0][0], 0, 0, 0);
+                gw[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1a, d2b, gw[0][1], 0, 0, 0);
+                gw[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1b, d2a, gw[1][0], 0, 0, 0);
+                gw[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1b, d2b, gw[1][1], 0, 0, 0);
+            }
+            if (p == 0) {
+                const float d1a = t_dz1[c * TS + ee], d1b = t_dz1[(16 + c) * TS + ee];
+                const float bb = t_b[c * TS + ee];
+                g_w0[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bb, d1a, g_w0[0], 0, 0, 0);
+                g_w0[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bb, d1b, g_w0[1], 0, 0, 0);
+            }
+        }
+        if (p > 0) __builtin_amdgcn_wave_barrier();   // (pass 0: the caller's barrier follows)
+    }
+}
+
+// this wave's partial sums of the small gradients: D[row 4 g + r][col c]; slice = [nb_pad*32 (dW0p) + N_MID*32*32 (dWm_p)]
+template <int KS0, int N_MID>
+__device__ __forceinline__ void store_small(float* out, const f32x4 (&g_w0)[2], const f32x4 (&g_wm)[nm1(N_MID)][2][2], int g,
+                                            int c, float s0, float s1) {
+    const int nb_pad = 4 * KS0;
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k0 = 4 * g + r;
+            if (k0 < nb_pad) out[k0 * HID + 16 * tn + c] = g_w0[tn][r] * s0;
+        }
+#pragma unroll
+    for (int m = 0; m < N_MID; ++m) {
+        float* out1 = out + nb_pad * HID + m * HID * HID;
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) out1[(16 * tm + 4 * g + r) * HID + 16 * tn + c] = g_wm[m][tm][tn][r] * s1;
+    }
+}
+
+// part_small[wave slice][nb_pad*32 (dW0p) + N_MID*32*32 (dWm_p)]
+template <int KS0, bool BF16, int N_MID>
 __global__ __launch_bounds__(BW_WAVES * 64) void radial_mlp_bwd_edges(
     const float4* __restrict__ geom, int64_t E, int n_basis, float r_start, float r_end, const float* __restrict__ w0p,
-    const float* __restrict__ w1p, const float* __restrict__ w2p, int w_pad, int w_cols, const void* __restrict__ dw,
+    const float* __restrict__ w_mid, const float* __restrict__ w2p, int w_pad, int w_cols, const void* __restrict__ dw,
     int64_t dw_ld, float* __restrict__ h2_out, float* __restrict__ part_small, int tiles_per_wave, float s0, float s1) {
     __shared__ float lds[BW_WAVES][(3 * HID + 16) * TS];
     const int lane = threadIdx.x & 63;
@@ -97,26 +176,33 @@ __global__ __launch_bounds__(BW_WAVES * 64) void radial_mlp_bwd_edges(
     float* t_dz1 = t_dz2 + HID * TS;         // [32][TS]
     float* t_b = t_dz1 + HID * TS;           // [16][TS]  bessel[k0][e]
     // weights as matrix operands, fixed for the whole walk
-    float a0[2][KS0], a1[2][8], a1t[2][8];
+    float a0[2][KS0], a1[nm1(N_MID)][2][8], a1t[nm1(N_MID)][2][8];
 #pragma unroll
     for (int kk = 0; kk < KS0; ++kk) {
         a0[0][kk] = w0p[(4 * kk + g) * HID + c];
         a0[1][kk] = w0p[(4 * kk + g) * HID + 16 + c];
     }
 #pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-        const int k = 16 * (kk >> 2) + 4 * g + (kk & 3);    // pi(kk, g): the feature the lane's D register (kk) holds
-        a1[0][kk] = w1p[k * HID + c];                        // forward:  A[m = out c][K = in k]
-        a1[1][kk] = w1p[k * HID + 16 + c];
-        a1t[0][kk] = w1p[c * HID + k];                       // adjoint:  A[m = in c][K = out k]
-        a1t[1][kk] = w1p[(16 + c) * HID + k];
+    for (int m = 0; m < N_MID; ++m) {
+        const float* __restrict__ w1p = w_mid + m * HID * HID;
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+            const int k = 16 * (kk >> 2) + 4 * g + (kk & 3);    // pi(kk, g): the feature the lane's D register (kk) holds
+            a1[m][0][kk] = w1p[k * HID + c];                     // forward:  A[m = out c][K = in k]
+            a1[m][1][kk] = w1p[k * HID + 16 + c];
+            a1t[m][0][kk] = w1p[c * HID + k];                    // adjoint:  A[m = in c][K = out k]
+            a1t[m][1][kk] = w1p[(16 + c) * HID + k];
+        }
     }
-    f32x4 g_w1[2][2], g_w0[2];   // dW1p[m-tile over in][n-tile over out], dW0p[n-tile over hidden] (rows = basis index)
+    // dWm_p[m-tile over in][n-tile over out] per middle layer, dW0p[n-tile over hidden] (rows = basis index)
+    f32x4 g_w1[nm1(N_MID)][2][2], g_w0[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         g_w0[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int j = 0; j < 2; ++j) g_w1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < nm1(N_MID); ++m)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) g_w1[m][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     for (int tile = 0; tile < tiles_per_wave; ++tile) {
         const int64_t e0 = e_first + tile * 16;
@@ -125,31 +211,36 @@ __global__ __launch_bounds__(BW_WAVES * 64) void radial_mlp_bwd_edges(
         const bool e_ok = e < E;
         const int64_t ec = e_ok ? e : E - 1;
         const float len = geom[ec].w;
-        // ---- forward recomputation (same operand order as radial_mlp_kernel) ----
+        // ---- forward recomputation (same operand order as radial_mlp_kernel): z[i] of layer i, h[i] = silu(z[i]) the input
+        // of middle layer i, h2 = silu(z[N_MID]) that of the last layer ----
         float bes[KS0];
-        f32x4 z1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, z2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        f32x4 z[N_MID + 1][2], h[nm1(N_MID)][2], h2[2];
+#pragma unroll
+        for (int i = 0; i <= N_MID; ++i) z[i][0] = z[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < KS0; ++kk) {
             const int k = 4 * kk + g;
             bes[kk] = (k < n_basis && e_ok) ? matten::bessel_basis(len, k, n_basis, r_start, r_end) : 0.0f;
-            z1[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[0][kk], bes[kk], z1[0], 0, 0, 0);
-            z1[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[1][kk], bes[kk], z1[1], 0, 0, 0);
+            z[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[0][kk], bes[kk], z[0][0], 0, 0, 0);
+            z[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[1][kk], bes[kk], z[0][1], 0, 0, 0);
         }
-        f32x4 h1[2], h2[2];
+#pragma unroll
+        for (int m = 0; m < N_MID; ++m) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) h[m][t][r] = silu(z[m][t][r]);
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk) {
+                const float b = h[m][kk >> 2][kk & 3];
+                z[m + 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[m][0][kk], b, z[m + 1][0], 0, 0, 0);
+                z[m + 1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[m][1][kk], b, z[m + 1][1], 0, 0, 0);
+            }
+        }
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) h1[t][r] = silu(z1[t][r]);
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            const float b = h1[kk >> 2][kk & 3];
-            z2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[0][kk], b, z2[0], 0, 0, 0);
-            z2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[1][kk], b, z2[1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h2[t][r] = silu(z2[t][r]);
+            for (int r = 0; r < 4; ++r) h2[t][r] = silu(z[N_MID][t][r]);
         if (e_ok) {   // h2[e, 16 t + 4 g + r]: four consecutive floats per tile
             *reinterpret_cast<f32x4*>(h2_out + e * HID + 4 * g) = h2[0];
             *reinterpret_cast<f32x4*>(h2_out + e * HID + 16 + 4 * g) = h2[1];
@@ -168,70 +259,30 @@ __global__ __launch_bounds__(BW_WAVES * 64) void radial_mlp_bwd_edges(
                 dh2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[s], b, dh2[1], 0, 0, 0);
             }
         }
-        // ---- dz2, dh1 = W1p dz2 (contraction over the out index: the D registers are the B operand), dz1 ----
-        f32x4 dz2[2], dh1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, dz1[2];
+        // ---- dz_{i+1}, dh_i = Wm_i dz_{i+1} (contraction over the out index: the D registers are the B operand), ..., dz_0 ----
+        f32x4 dz[N_MID + 1][2];
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int i = N_MID; i >= 0; --i) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) dz2[t][r] = dh2[t][r] * dsilu(z2[t][r]);
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            const float b = dz2[kk >> 2][kk & 3];
-            dh1[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1t[0][kk], b, dh1[0], 0, 0, 0);
-            dh1[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1t[1][kk], b, dh1[1], 0, 0, 0);
-        }
+                for (int r = 0; r < 4; ++r) dz[i][t][r] = dh2[t][r] * dsilu(z[i][t][r]);
+            if (i > 0) {
+                dh2[0] = dh2[1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz1[t][r] = dh1[t][r] * dsilu(z1[t][r]);
-        // ---- the two small weight gradients: contraction over the tile's 16 edges, operands through LDS ----
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k = 16 * t + 4 * g + r;
-                t_h1[k * TS + c] = h1[t][r];
-                t_dz2[k * TS + c] = dz2[t][r];
-                t_dz1[k * TS + c] = dz1[t][r];
+                for (int kk = 0; kk < 8; ++kk) {
+                    const float b = dz[i][kk >> 2][kk & 3];
+                    dh2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1t[i > 0 ? i - 1 : 0][0][kk], b, dh2[0], 0, 0, 0);
+                    dh2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1t[i > 0 ? i - 1 : 0][1][kk], b, dh2[1], 0, 0, 0);
+                }
             }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) t_b[(4 * kk + g) * TS + c] = kk < KS0 ? bes[kk < KS0 ? kk : 0] : 0.0f;
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {   // K step s: edges 4 s + g
-            const int ee = 4 * s + g;
-            const float h1a = t_h1[c * TS + ee], h1b = t_h1[(16 + c) * TS + ee];
-            const float d2a = t_dz2[c * TS + ee], d2b = t_dz2[(16 + c) * TS + ee];
-            const float d1a = t_dz1[c * TS + ee], d1b = t_dz1[(16 + c) * TS + ee];
-            const float bb = t_b[c * TS + ee];
-            g_w1[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1a, d2a, g_w1[0][0], 0, 0, 0);
-            g_w1[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1a, d2b, g_w1[0][1], 0, 0, 0);
-            g_w1[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1b, d2a, g_w1[1][0], 0, 0, 0);
-            g_w1[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1b, d2b, g_w1[1][1], 0, 0, 0);
-            g_w0[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bb, d1a, g_w0[0], 0, 0, 0);
-            g_w0[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bb, d1b, g_w0[1], 0, 0, 0);
         }
+        // ---- the small weight gradients: contraction over the tile's 16 edges, operands through LDS ----
+        small_grads_tile<KS0, N_MID>(t_h1, t_dz2, t_dz1, t_b, h, dz, bes, g, c, g_w1, g_w0);
         __builtin_amdgcn_wave_barrier();
     }
-    // ---- this wave's partial sums: D[row 4 g + r][col c] ----
     const int nb_pad = 4 * KS0;
-    float* out = part_small + slice * (int64_t)(nb_pad * HID + HID * HID);
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int k0 = 4 * g + r;
-            if (k0 < nb_pad) out[k0 * HID + 16 * tn + c] = g_w0[tn][r] * s0;
-        }
-    float* out1 = out + nb_pad * HID;
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out1[(16 * tm + 4 * g + r) * HID + 16 * tn + c] = g_w1[tm][tn][r] * s1;
+    store_small<KS0, N_MID>(part_small + slice * (int64_t)(nb_pad * HID + N_MID * HID * HID), g_w0, g_w1, g, c, s0, s1);
 }
 
 // ---- both halves in ONE kernel, dw read ONCE (w_pad <= 16 * 4 * FU_MAXCH) ---------------------------------------------
@@ -251,10 +302,10 @@ constexpr int FU_HS = HID + 1;              // row stride of the published h2 ti
 constexpr int FU_TT = 20;                   // row stride of the dw transpose tile (16-byte aligned rows)
 constexpr int FU_POOL = BW_WAVES * 64 * 8;  // floats per wave of the shared pool: partial dh2 [tile][lane][8] / the phase-B tiles
 static_assert((3 * HID + 16) * TS <= FU_POOL, "the phase-B transposes live in the wave's share of the pool");
-template <int KS0, bool BF16, int MAXCH>
+template <int KS0, bool BF16, int MAXCH, int N_MID>
 __global__ __launch_bounds__(BW_WAVES * 64, 2) void radial_mlp_bwd_fused(
     const float4* __restrict__ geom, int64_t E, int n_basis, float r_start, float r_end, const float* __restrict__ w0p,
-    const float* __restrict__ w1p, const float* __restrict__ w2p, int w_pad, int w_cols, const void* __restrict__ dw,
+    const float* __restrict__ w_mid, const float* __restrict__ w2p, int w_pad, int w_cols, const void* __restrict__ dw,
     int64_t dw_ld, float* __restrict__ part_small, float* __restrict__ part_w2, int tiles_per_wave, float s0, float s1,
     float s2) {
     // pool[wave]: the wave's partial dh2 [tile][lane][m, r] during phase A, its transposes in phase B (barrier between)
@@ -271,17 +322,19 @@ __global__ __launch_bounds__(BW_WAVES * 64, 2) void radial_mlp_bwd_fused(
     float* t_b = t_dz1 + HID * TS;
     float* tt = tts[wave];
     // the small layers' weights as matrix operands: from LDS at every use (kept in registers they cost the kernel its
-    // second wave per SIMD)
-    __shared__ float w0s[16 * HID], w1s[HID * HID];
+    // second wave per SIMD); 4 KB per middle layer
+    __shared__ float w0s[16 * HID], wms[nm1(N_MID) * HID * HID];
     for (int i = threadIdx.x; i < 4 * KS0 * HID; i += BW_WAVES * 64) w0s[i] = w0p[i];
-    for (int i = threadIdx.x; i < HID * HID; i += BW_WAVES * 64) w1s[i] = w1p[i];
+    for (int i = threadIdx.x; i < N_MID * HID * HID; i += BW_WAVES * 64) wms[i] = w_mid[i];
     __syncthreads();
-    f32x4 g_w1[2][2], g_w0[2], g_w2[MAXCH][2];
+    f32x4 g_w1[nm1(N_MID)][2][2], g_w0[2], g_w2[MAXCH][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         g_w0[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int j = 0; j < 2; ++j) g_w1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < nm1(N_MID); ++m)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) g_w1[m][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int j = 0; j < MAXCH; ++j) g_w2[j][0] = g_w2[j][1] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -295,42 +348,49 @@ __global__ __launch_bounds__(BW_WAVES * 64, 2) void radial_mlp_bwd_fused(
         const int64_t e = e0 + c;
         const bool e_ok = e < E;
         const float len = geom[e_ok ? e : E - 1].w;
-        auto forward_tile = [&](float (&bes)[KS0], f32x4 (&z1)[2], f32x4 (&h1)[2], f32x4 (&z2)[2]) {
-            z1[0] = z1[1] = z2[0] = z2[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // z[i] of layer i, h[i] = silu(z[i]) the input of middle layer i (as in radial_mlp_bwd_edges)
+        auto forward_tile = [&](float (&bes)[KS0], f32x4 (&z)[N_MID + 1][2], f32x4 (&h)[nm1(N_MID)][2]) {
+#pragma unroll
+            for (int i = 0; i <= N_MID; ++i) z[i][0] = z[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < KS0; ++kk) {
                 const int k = 4 * kk + g;
                 bes[kk] = (k < n_basis && e_ok) ? matten::bessel_basis(len, k, n_basis, r_start, r_end) : 0.0f;
-                z1[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0s[k * HID + c], bes[kk], z1[0], 0, 0, 0);
-                z1[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0s[k * HID + 16 + c], bes[kk], z1[1], 0, 0, 0);
+                z[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0s[k * HID + c], bes[kk], z[0][0], 0, 0, 0);
+                z[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0s[k * HID + 16 + c], bes[kk], z[0][1], 0, 0, 0);
             }
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
+            for (int m = 0; m < N_MID; ++m) {
+                const float* w1s = wms + m * HID * HID;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) h1[t][r] = silu(z1[t][r]);
+                for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {
-                const float b = h1[kk >> 2][kk & 3];
-                const int kf = 16 * (kk >> 2) + 4 * g + (kk & 3);   // pi(kk, g): the feature the lane's D register (kk) holds
-                z2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1s[kf * HID + c], b, z2[0], 0, 0, 0);
-                z2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1s[kf * HID + 16 + c], b, z2[1], 0, 0, 0);
+                    for (int r = 0; r < 4; ++r) h[m][t][r] = silu(z[m][t][r]);
+#pragma unroll
+                for (int kk = 0; kk < 8; ++kk) {
+                    const float b = h[m][kk >> 2][kk & 3];
+                    const int kf = 16 * (kk >> 2) + 4 * g + (kk & 3);   // pi(kk, g): the feature the lane's D register (kk) holds
+                    z[m + 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1s[kf * HID + c], b, z[m + 1][0], 0, 0, 0);
+                    z[m + 1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1s[kf * HID + 16 + c], b, z[m + 1][1], 0, 0, 0);
+                }
             }
         };
-        // wide layers (more than 4 chunks per wave) recompute z1, h1, z2 in phase B: held across phase A they would spill;
+        // wide layers (more than 4 chunks per wave) recompute z, h in phase B: held across phase A they would spill;
         // narrow layers keep them (their phase A is short, the second evaluation would show: 0.20 vs 0.18 ms at 128 columns)
-        constexpr bool RECOMPUTE = MAXCH > 4;
+        // -- unless there is more than one middle layer to hold
+        constexpr bool RECOMPUTE = MAXCH > 4 || N_MID > 1;
         float bes[KS0];
-        f32x4 z1[2], h1[2], z2[2];
+        f32x4 z[N_MID + 1][2], h[nm1(N_MID)][2];
         {
             float bes0[KS0];
-            f32x4 z1a[2], h1a[2], z2a[2];
-            if constexpr (RECOMPUTE) forward_tile(bes0, z1a, h1a, z2a);
-            else forward_tile(bes, z1, h1, z2);
+            f32x4 za[N_MID + 1][2], ha[nm1(N_MID)][2];
+            if constexpr (RECOMPUTE) forward_tile(bes0, za, ha);
+            else forward_tile(bes, z, h);
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)   // (0 for an edge past the end: its Bessel row is 0)
-                    h2s[wave][c * FU_HS + 16 * t + 4 * g + r] = silu(RECOMPUTE ? z2a[t][r] : z2[t][r]);
+                    h2s[wave][c * FU_HS + 16 * t + 4 * g + r] = silu(RECOMPUTE ? za[N_MID][t][r] : z[N_MID][t][r]);
         }
         __syncthreads();
         // ---- phase A: this wave's column chunks over the round's four tiles ----
@@ -397,68 +457,31 @@ __global__ __launch_bounds__(BW_WAVES * 64, 2) void radial_mlp_bwd_fused(
             dh2[1] += *reinterpret_cast<const f32x4*>(&pool[w][(wave * 64 + lane) * 8 + 4]);
         }
         __syncthreads();   // every wave has its sums: the pool now takes the transposes
-        if constexpr (RECOMPUTE) forward_tile(bes, z1, h1, z2);
-        f32x4 dz2[2], dh1[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, dz1[2];
+        if constexpr (RECOMPUTE) forward_tile(bes, z, h);
+        f32x4 dz[N_MID + 1][2];
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int i = N_MID; i >= 0; --i) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) dz2[t][r] = dh2[t][r] * dsilu(z2[t][r]);
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            const float b = dz2[kk >> 2][kk & 3];
-            const int kf = 16 * (kk >> 2) + 4 * g + (kk & 3);
-            dh1[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1s[c * HID + kf], b, dh1[0], 0, 0, 0);
-            dh1[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1s[(16 + c) * HID + kf], b, dh1[1], 0, 0, 0);
-        }
+                for (int r = 0; r < 4; ++r) dz[i][t][r] = dh2[t][r] * dsilu(z[i][t][r]);
+            if (i > 0) {
+                const float* w1s = wms + (i > 0 ? i - 1 : 0) * HID * HID;
+                dh2[0] = dh2[1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dz1[t][r] = dh1[t][r] * dsilu(z1[t][r]);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k = 16 * t + 4 * g + r;
-                t_h1[k * TS + c] = h1[t][r];
-                t_dz2[k * TS + c] = dz2[t][r];
-                t_dz1[k * TS + c] = dz1[t][r];
+                for (int kk = 0; kk < 8; ++kk) {
+                    const float b = dz[i][kk >> 2][kk & 3];
+                    const int kf = 16 * (kk >> 2) + 4 * g + (kk & 3);
+                    dh2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1s[c * HID + kf], b, dh2[0], 0, 0, 0);
+                    dh2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1s[(16 + c) * HID + kf], b, dh2[1], 0, 0, 0);
+                }
             }
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) t_b[(4 * kk + g) * TS + c] = kk < KS0 ? bes[kk < KS0 ? kk : 0] : 0.0f;
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int sst = 0; sst < 4; ++sst) {
-            const int ee = 4 * sst + g;
-            const float h1a = t_h1[c * TS + ee], h1b = t_h1[(16 + c) * TS + ee];
-            const float d2a = t_dz2[c * TS + ee], d2b = t_dz2[(16 + c) * TS + ee];
-            const float d1a = t_dz1[c * TS + ee], d1b = t_dz1[(16 + c) * TS + ee];
-            const float bb = t_b[c * TS + ee];
-            g_w1[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1a, d2a, g_w1[0][0], 0, 0, 0);
-            g_w1[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1a, d2b, g_w1[0][1], 0, 0, 0);
-            g_w1[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1b, d2a, g_w1[1][0], 0, 0, 0);
-            g_w1[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(h1b, d2b, g_w1[1][1], 0, 0, 0);
-            g_w0[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bb, d1a, g_w0[0], 0, 0, 0);
-            g_w0[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(bb, d1b, g_w0[1], 0, 0, 0);
         }
+        small_grads_tile<KS0, N_MID>(t_h1, t_dz2, t_dz1, t_b, h, dz, bes, g, c, g_w1, g_w0);
         __syncthreads();   // the next round overwrites h2s / dh2p
     }
     const int nb_pad = 4 * KS0;
-    float* out = part_small + slice * (int64_t)(nb_pad * HID + HID * HID);
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int k0 = 4 * g + r;
-            if (k0 < nb_pad) out[k0 * HID + 16 * tn + c] = g_w0[tn][r] * s0;
-        }
-    float* out1 = out + nb_pad * HID;
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out1[(16 * tm + 4 * g + r) * HID + 16 * tn + c] = g_w1[tm][tn][r] * s1;
+    store_small<KS0, N_MID>(part_small + slice * (int64_t)(nb_pad * HID + N_MID * HID * HID), g_w0, g_w1, g, c, s0, s1);
     // dW2p[k = 16 m + 4 g + r][column 16 j + c] of this workgroup
     float* out2 = part_w2 + (int64_t)blockIdx.x * HID * w_pad;
 #pragma unroll
@@ -552,55 +575,86 @@ extern "C" int64_t matten_radial_mlp_bwd_small_slices(int64_t n_edges) {
 #ifndef BW_FUSED_MIN_W
 #define BW_FUSED_MIN_W 128   // narrower layers: too few column chunks for four waves (48 columns: 0.16 vs 0.13 ms at 293 k edges)
 #endif
-static inline bool bw_fused(int64_t w_pad) { return BW_FUSED && w_pad >= BW_FUSED_MIN_W && w_pad <= 16 * BW_WAVES * FU_MAXCH; }
+// column chunks per wave the one-kernel adjoint takes without scratch, by the number of middle layers (their weight
+// gradients and recomputed activations take the registers of dW2p's chunks; 1: the shipped shape, as before)
+constexpr int fu_maxch(int n_mid) { return n_mid == 1 ? FU_MAXCH : (n_mid == 0 ? 6 : (n_mid == 2 ? 4 : 0)); }
+static inline bool bw_fused(int64_t w_pad, int n_mid) {
+    return BW_FUSED && w_pad >= BW_FUSED_MIN_W && w_pad <= 16 * BW_WAVES * fu_maxch(n_mid);
+}
 // partial rows of dW2p: one per workgroup of the fused kernel, else one per edge range of radial_mlp_bwd_w2
-extern "C" int64_t matten_radial_mlp_bwd_w2_ranges(int64_t n_edges, int64_t w_pad) {
-    if (bw_fused(w_pad)) return matten_radial_mlp_bwd_small_slices(n_edges) / BW_WAVES;
+extern "C" int64_t matten_radial_mlp_bwd_w2_ranges_deep(int64_t n_edges, int64_t w_pad, int n_mid) {
+    if (bw_fused(w_pad, n_mid)) return matten_radial_mlp_bwd_small_slices(n_edges) / BW_WAVES;
     return matten_cdiv(n_edges, w2_range(n_edges, w_pad));
 }
+extern "C" int64_t matten_radial_mlp_bwd_w2_ranges(int64_t n_edges, int64_t w_pad) {
+    return matten_radial_mlp_bwd_w2_ranges_deep(n_edges, w_pad, 1);
+}
 
-extern "C" int matten_radial_mlp_bwd(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
-                                     const float* w0p, int nb_pad, const float* w1p, const float* w2p, int hidden,
-                                     int w_pad, int w_cols, const void* dw, int64_t dw_ld, int dw_is_bf16,
-                                     float* h2_scratch, float* part_small, float* part_w2, float scale0, float scale1,
-                                     float scale2, float* grad_small, float* grad_w2, matten_stream_t stream_) {
+// the one-kernel adjoint at the smallest chunk count that covers w_pad; only the (N_MID, chunks) pairs bw_fused admits
+// are instantiated
+template <int K, bool B, int NM>
+static void launch_bwd_fused(unsigned grid1, hipStream_t stream, const float* geom_sorted, int64_t n_edges, int n_basis,
+                             float r_start, float r_end, const float* w0p, const float* w_mid, const float* w2p, int w_pad,
+                             int w_cols, const void* dw, int64_t dw_ld, float* part_small, float* part_w2, float scale0,
+                             float scale1, float scale2) {
+#define LAUNCH_FUSED_M(M)                                                                                              \
+    radial_mlp_bwd_fused<K, B, M, NM><<<grid1, BW_WAVES * 64, 0, stream>>>((const float4*)geom_sorted, n_edges, n_basis, \
+                                                                           r_start, r_end, w0p, w_mid, w2p, w_pad, w_cols, \
+                                                                           dw, dw_ld, part_small, part_w2,                 \
+                                                                           bw_tiles(n_edges), scale0, scale1, scale2)
+    if constexpr (fu_maxch(NM) >= 4) {
+        if (w_pad <= 16 * BW_WAVES * 4) { LAUNCH_FUSED_M(4); return; }
+    }
+    if constexpr (fu_maxch(NM) >= 6) {
+        if (w_pad <= 16 * BW_WAVES * 6) { LAUNCH_FUSED_M(6); return; }
+    }
+    if constexpr (fu_maxch(NM) >= FU_MAXCH) LAUNCH_FUSED_M(FU_MAXCH);
+#undef LAUNCH_FUSED_M
+}
+
+static int radial_mlp_bwd_launch(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                                 const float* w0p, int nb_pad, const float* w_mid, int n_mid, const float* w2p, int hidden,
+                                 int w_pad, int w_cols, const void* dw, int64_t dw_ld, int dw_is_bf16, float* h2_scratch,
+                                 float* part_small, float* part_w2, float scale0, float scale1, float scale2,
+                                 float* grad_small, float* grad_w2, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_edges < 0 || hidden != HID || (w_pad & 15) || w_pad <= 0 || w_cols <= 0 || w_cols > w_pad || (nb_pad & 3) ||
-        nb_pad < n_basis || nb_pad > 16 || dw_ld < w_pad || (dw_ld & 3))
+        nb_pad < n_basis || nb_pad > 16 || dw_ld < w_pad || (dw_ld & 3) || n_mid < 0 || n_mid > MATTEN_RADIAL_MAX_MID)
         return MATTEN_EINVAL;
     if (n_edges == 0) return MATTEN_OK;
-    if (!geom_sorted || !w0p || !w1p || !w2p || !dw || !h2_scratch || !part_small || !part_w2) return MATTEN_EINVAL;
+    if (!geom_sorted || !w0p || (n_mid > 0 && !w_mid) || !w2p || !dw || !h2_scratch || !part_small || !part_w2)
+        return MATTEN_EINVAL;
     const unsigned grid1 = (unsigned)(matten_radial_mlp_bwd_small_slices(n_edges) / BW_WAVES);
-    const bool fused = bw_fused(w_pad);
-#define LAUNCH_FUSED_M(K, B, M)                                                                                       \
-    radial_mlp_bwd_fused<K, B, M><<<grid1, BW_WAVES * 64, 0, stream>>>((const float4*)geom_sorted, n_edges, n_basis,  \
-                                                                        r_start, r_end, w0p, w1p, w2p, w_pad, w_cols,  \
-                                                                        dw, dw_ld, part_small, part_w2,                \
-                                                                        bw_tiles(n_edges), scale0, scale1, scale2)
-#define LAUNCH_FUSED(K, B)                                                          \
-    do {                                                                            \
-        if (w_pad <= 16 * BW_WAVES * 4) LAUNCH_FUSED_M(K, B, 4);                    \
-        else if (w_pad <= 16 * BW_WAVES * 6) LAUNCH_FUSED_M(K, B, 6);               \
-        else LAUNCH_FUSED_M(K, B, FU_MAXCH);                                        \
-    } while (0)
-#define LAUNCH(K, B) if (fused) LAUNCH_FUSED(K, B); else                                                                                                  \
-    radial_mlp_bwd_edges<K, B><<<grid1, BW_WAVES * 64, 0, stream>>>((const float4*)geom_sorted, n_edges, n_basis,     \
-                                                                     r_start, r_end, w0p, w1p, w2p, w_pad, w_cols, dw, \
+    const bool fused = bw_fused(w_pad, n_mid);
+#define LAUNCH_FUSED(K, B, NM)                                                                                          \
+    launch_bwd_fused<K, B, NM>(grid1, stream, geom_sorted, n_edges, n_basis, r_start, r_end, w0p, w_mid, w2p, w_pad, w_cols, \
+                               dw, dw_ld, part_small, part_w2, scale0, scale1, scale2)
+#define LAUNCH(K, B, NM) if (fused) LAUNCH_FUSED(K, B, NM); else                                                          \
+    radial_mlp_bwd_edges<K, B, NM><<<grid1, BW_WAVES * 64, 0, stream>>>((const float4*)geom_sorted, n_edges, n_basis,     \
+                                                                     r_start, r_end, w0p, w_mid, w2p, w_pad, w_cols, dw, \
                                                                      dw_ld, h2_scratch, part_small, bw_tiles(n_edges), scale0, scale1)
-#define LAUNCH_K(B)                     \
-    switch (nb_pad >> 2) {              \
-        case 1: LAUNCH(1, B); break;    \
-        case 2: LAUNCH(2, B); break;    \
-        case 3: LAUNCH(3, B); break;    \
-        default: LAUNCH(4, B); break;   \
+#define LAUNCH_NM(K, B)                   \
+    switch (n_mid) {                      \
+        case 0: LAUNCH(K, B, 0); break;   \
+        case 1: LAUNCH(K, B, 1); break;   \
+        case 2: LAUNCH(K, B, 2); break;   \
+        default: LAUNCH(K, B, 3); break;  \
+    }
+#define LAUNCH_K(B)                       \
+    switch (nb_pad >> 2) {                \
+        case 1: LAUNCH_NM(1, B); break;   \
+        case 2: LAUNCH_NM(2, B); break;   \
+        case 3: LAUNCH_NM(3, B); break;   \
+        default: LAUNCH_NM(4, B); break;  \
     }
     if (dw_is_bf16) { LAUNCH_K(true) } else { LAUNCH_K(false) }
 #undef LAUNCH_K
+#undef LAUNCH_NM
 #undef LAUNCH
 #undef LAUNCH_FUSED
-#undef LAUNCH_FUSED_M
     MATTEN_LAUNCH_CHECK();
-    dim3 grid2((unsigned)matten_cdiv(w_pad, 16 * BW_WAVES), (unsigned)matten_radial_mlp_bwd_w2_ranges(n_edges, w_pad));
+    dim3 grid2((unsigned)matten_cdiv(w_pad, 16 * BW_WAVES),
+               (unsigned)matten_radial_mlp_bwd_w2_ranges_deep(n_edges, w_pad, n_mid));
     if (fused) {
     } else if (dw_is_bf16)
         radial_mlp_bwd_w2<true><<<grid2, BW_WAVES * 64, 0, stream>>>(h2_scratch, dw, dw_ld, n_edges, w_pad, part_w2,
@@ -611,23 +665,46 @@ extern "C" int matten_radial_mlp_bwd(const float* geom_sorted, int64_t n_edges, 
     MATTEN_LAUNCH_CHECK();
     if (grad_small || grad_w2) {   // the final, ordered sums in the same call (both or neither)
         if (!grad_small || !grad_w2) return MATTEN_EINVAL;
-        const int small_len = nb_pad * HID + HID * HID, w2_len = HID * w_pad;
+        const int small_len = nb_pad * HID + n_mid * HID * HID, w2_len = HID * w_pad;
         radial_mlp_bwd_reduce<<<dim3((unsigned)matten_cdiv(std::max(small_len, w2_len), RED_COLS), 2), RED_COLS * RED_GROUPS, 0, stream>>>(
             part_small, matten_radial_mlp_bwd_small_slices(n_edges), small_len, part_w2,
-            matten_radial_mlp_bwd_w2_ranges(n_edges, w_pad), w2_len, grad_small, grad_w2);
+            matten_radial_mlp_bwd_w2_ranges_deep(n_edges, w_pad, n_mid), w2_len, grad_small, grad_w2);
         MATTEN_LAUNCH_CHECK();
     }
     return MATTEN_OK;
 }
 
-// (w0 [nb,32], w1 [32,32], w2 [32,W] raw parameters) -> the packed operands of matten_radial_mlp / _bwd in ONE launch:
-// w0p [nb_pad,32] = s0 w0 (zero rows past nb), w1p = s1 w1, w2p [32,w_pad] = s2 w2 (zero columns past W).
+extern "C" int matten_radial_mlp_bwd(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                                     const float* w0p, int nb_pad, const float* w1p, const float* w2p, int hidden,
+                                     int w_pad, int w_cols, const void* dw, int64_t dw_ld, int dw_is_bf16,
+                                     float* h2_scratch, float* part_small, float* part_w2, float scale0, float scale1,
+                                     float scale2, float* grad_small, float* grad_w2, matten_stream_t stream_) {
+    if (!w1p && n_edges > 0) return MATTEN_EINVAL;
+    return radial_mlp_bwd_launch(geom_sorted, n_edges, n_basis, r_start, r_end, w0p, nb_pad, w1p, 1, w2p, hidden, w_pad,
+                                 w_cols, dw, dw_ld, dw_is_bf16, h2_scratch, part_small, part_w2, scale0, scale1, scale2,
+                                 grad_small, grad_w2, stream_);
+}
+
+extern "C" int matten_radial_mlp_bwd_deep(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start,
+                                          float r_end, const float* w0p, int nb_pad, const float* w_mid, int n_mid,
+                                          const float* w2p, int hidden, int w_pad, int w_cols, const void* dw,
+                                          int64_t dw_ld, int dw_is_bf16, float* h2_scratch, float* part_small,
+                                          float* part_w2, float scale0, float scale1, float scale2, float* grad_small,
+                                          float* grad_w2, matten_stream_t stream_) {
+    return radial_mlp_bwd_launch(geom_sorted, n_edges, n_basis, r_start, r_end, w0p, nb_pad, w_mid, n_mid, w2p, hidden,
+                                 w_pad, w_cols, dw, dw_ld, dw_is_bf16, h2_scratch, part_small, part_w2, scale0, scale1,
+                                 scale2, grad_small, grad_w2, stream_);
+}
+
+// (w0 [nb,32], w1 [N_MID,32,32], w2 [32,W] raw parameters) -> the packed operands of matten_radial_mlp / _bwd in ONE
+// launch: w0p [nb_pad,32] = s0 w0 (zero rows past nb), w1p = s1 w1, w2p [32,w_pad] = s2 w2 (zero columns past W).
 namespace {
+template <int N_MID>
 __global__ void radial_pack_kernel(const float* __restrict__ w0, const float* __restrict__ w1, const float* __restrict__ w2,
                                    int nb, int nb_pad, int W, int w_pad, float s0, float s1, float s2,
                                    float* __restrict__ w0p, float* __restrict__ w1p, float* __restrict__ w2p) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n0 = nb_pad * HID, n1 = HID * HID, n2 = HID * w_pad;
+    const int n0 = nb_pad * HID, n1 = N_MID * HID * HID, n2 = HID * w_pad;
     if (i < n0) {
         w0p[i] = (i / HID) < nb ? w0[i] * s0 : 0.0f;
     } else if (i < n0 + n1) {
@@ -639,17 +716,40 @@ __global__ void radial_pack_kernel(const float* __restrict__ w0, const float* __
 }
 }  // namespace
 
+static int radial_pack_launch(const float* w0, const float* w1, int n_mid, const float* w2, int n_basis, int nb_pad,
+                              int w_cols, int w_pad, float scale0, float scale1, float scale2, float* w0p, float* w1p,
+                              float* w2p, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_basis <= 0 || nb_pad < n_basis || w_cols <= 0 || w_pad < w_cols || n_mid < 0 || n_mid > MATTEN_RADIAL_MAX_MID)
+        return MATTEN_EINVAL;
+    if (!w0 || (n_mid > 0 && (!w1 || !w1p)) || !w2 || !w0p || !w2p) return MATTEN_EINVAL;
+    const int n = nb_pad * HID + n_mid * HID * HID + HID * w_pad;
+#define LAUNCH(M)                                                                                                      \
+    radial_pack_kernel<M><<<(unsigned)matten_cdiv(n, 256), 256, 0, stream>>>(w0, w1, w2, n_basis, nb_pad, w_cols, w_pad, \
+                                                                            scale0, scale1, scale2, w0p, w1p, w2p)
+    switch (n_mid) {
+        case 0: LAUNCH(0); break;
+        case 1: LAUNCH(1); break;
+        case 2: LAUNCH(2); break;
+        default: LAUNCH(3); break;
+    }
+#undef LAUNCH
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
 extern "C" int matten_radial_pack(const float* w0, const float* w1, const float* w2, int n_basis, int nb_pad, int w_cols,
                                   int w_pad, float scale0, float scale1, float scale2, float* w0p, float* w1p, float* w2p,
                                   matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n_basis <= 0 || nb_pad < n_basis || w_cols <= 0 || w_pad < w_cols) return MATTEN_EINVAL;
-    if (!w0 || !w1 || !w2 || !w0p || !w1p || !w2p) return MATTEN_EINVAL;
-    const int n = nb_pad * HID + HID * HID + HID * w_pad;
-    radial_pack_kernel<<<(unsigned)matten_cdiv(n, 256), 256, 0, stream>>>(w0, w1, w2, n_basis, nb_pad, w_cols, w_pad, scale0,
-                                                                         scale1, scale2, w0p, w1p, w2p);
-    MATTEN_LAUNCH_CHECK();
-    return MATTEN_OK;
+    if (!w1 || !w1p) return MATTEN_EINVAL;
+    return radial_pack_launch(w0, w1, 1, w2, n_basis, nb_pad, w_cols, w_pad, scale0, scale1, scale2, w0p, w1p, w2p, stream_);
+}
+
+extern "C" int matten_radial_pack_deep(const float* w0, const float* w_mid, int n_mid, const float* w2, int n_basis,
+                                       int nb_pad, int w_cols, int w_pad, float scale0, float scale1, float scale2,
+                                       float* w0p, float* w_mid_p, float* w2p, matten_stream_t stream_) {
+    return radial_pack_launch(w0, w_mid, n_mid, w2, n_basis, nb_pad, w_cols, w_pad, scale0, scale1, scale2, w0p, w_mid_p,
+                              w2p, stream_);
 }
 
 // ---- operands of matten_tp_fused derived from the RAW radial layers by kernels (training on the production kernel: the
@@ -657,12 +757,13 @@ extern "C" int matten_radial_pack(const float* w0, const float* w1, const float*
 namespace {
 
 // as radial_pack_kernel, the last layer's columns gathered through `cols` (fused column order; -1 = structural zero)
+template <int N_MID>
 __global__ void radial_pack_cols_kernel(const float* __restrict__ w0, const float* __restrict__ w1,
                                         const float* __restrict__ w2, int nb, int nb_pad, int W,
                                         const int64_t* __restrict__ cols, int n_cols, int w_pad, float s0, float s1, float s2,
                                         float* __restrict__ w0p, float* __restrict__ w1p, float* __restrict__ w2p) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n0 = nb_pad * HID, n1 = HID * HID, n2 = HID * w_pad;
+    const int n0 = nb_pad * HID, n1 = N_MID * HID * HID, n2 = HID * w_pad;
     if (i < n0) {
         w0p[i] = (i / HID) < nb ? w0[i] * s0 : 0.0f;
     } else if (i < n0 + n1) {
@@ -674,23 +775,34 @@ __global__ void radial_pack_cols_kernel(const float* __restrict__ w0, const floa
     }
 }
 
-// [s, 1 / s]: the power of two the hidden features are multiplied by so that |s h2| < 2^15 for every edge length
-// (nn/utils.py RadialMLP._fp16_scale, same bound: |h2| <= sqrt(2/c) sqrt(nb) pi / c * n0 * n1 with the column-sum norms
-// n0 = max_col sum_k |W0[k,col]| (k+1) / sqrt(nb), n1 = max_col sum_k |W1[k,col]| act_cst / sqrt(h))
+// [s, 1 / s]: the power of two the last hidden features are multiplied by so that |s h| < 2^15 for every edge length
+// (nn/utils.py RadialMLP._fp16_scale, same bound: |h| <= sqrt(2/c) sqrt(nb) pi / c * n0 * n_1 ... n_{N_MID} with the
+// column-sum norms n0 = max_col sum_k |W0[k,col]| (k+1) / sqrt(nb), n_i = max_col sum_k |Wm_i[k,col]| act_cst / sqrt(h))
+template <int N_MID>
 __global__ void radial_h_scale_kernel(const float* __restrict__ w0, const float* __restrict__ w1, int nb, float c,
                                       float act_cst, float* __restrict__ out) {
-    __shared__ float red[2][HID];
+    __shared__ float red[1 + N_MID][HID];
     const int col = threadIdx.x;   // 32 threads
-    float a0 = 0.0f, a1 = 0.0f;
+    float a0 = 0.0f;
     for (int k = 0; k < nb; ++k) a0 += fabsf(w0[k * HID + col]) * (float)(k + 1);
-    for (int k = 0; k < HID; ++k) a1 += fabsf(w1[k * HID + col]);
     red[0][col] = a0 / sqrtf((float)nb);
-    red[1][col] = a1 * (act_cst / sqrtf((float)HID));
+#pragma unroll
+    for (int m = 0; m < N_MID; ++m) {
+        float a1 = 0.0f;
+        for (int k = 0; k < HID; ++k) a1 += fabsf(w1[m * HID * HID + k * HID + col]);
+        red[1 + m][col] = a1 * (act_cst / sqrtf((float)HID));
+    }
     __syncthreads();
     if (col == 0) {
-        float n0 = 0.0f, n1 = 0.0f;
-        for (int i = 0; i < HID; ++i) n0 = fmaxf(n0, red[0][i]), n1 = fmaxf(n1, red[1][i]);
-        const float bound = sqrtf(2.0f / c) * sqrtf((float)nb) * 3.141592653589793f / c * n0 * n1;
+        float n0 = 0.0f;
+        for (int i = 0; i < HID; ++i) n0 = fmaxf(n0, red[0][i]);
+        float bound = sqrtf(2.0f / c) * sqrtf((float)nb) * 3.141592653589793f / c * n0;
+#pragma unroll
+        for (int m = 0; m < N_MID; ++m) {
+            float n1 = 0.0f;
+            for (int i = 0; i < HID; ++i) n1 = fmaxf(n1, red[1 + m][i]);
+            bound = bound * n1;
+        }
         float s = 1.0f;
         if (bound > 32768.0f) s = exp2f(floorf(log2f(16384.0f / fmaxf(bound, 1e-30f))));
         if (!(s > 0.0f) || isinf(s) || isnan(s)) s = exp2f(-100.0f);
@@ -748,27 +860,73 @@ __global__ void split_a_tiles_kernel(const float* __restrict__ w2p, int w_pad, c
 
 }  // namespace
 
+static int radial_pack_cols_launch(const float* w0, const float* w1, int n_mid, const float* w2, int n_basis, int nb_pad,
+                                   int w_cols, const int64_t* cols, int n_cols, int w_pad, float scale0, float scale1,
+                                   float scale2, float* w0p, float* w1p, float* w2p, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_basis <= 0 || nb_pad < n_basis || w_cols <= 0 || n_cols <= 0 || w_pad < n_cols || n_mid < 0 ||
+        n_mid > MATTEN_RADIAL_MAX_MID)
+        return MATTEN_EINVAL;
+    if (!w0 || (n_mid > 0 && (!w1 || !w1p)) || !w2 || !cols || !w0p || !w2p) return MATTEN_EINVAL;
+    const int n = nb_pad * HID + n_mid * HID * HID + HID * w_pad;
+#define LAUNCH(M)                                                                                                            \
+    radial_pack_cols_kernel<M><<<(unsigned)matten_cdiv(n, 256), 256, 0, stream>>>(w0, w1, w2, n_basis, nb_pad, w_cols, cols, \
+                                                                                  n_cols, w_pad, scale0, scale1, scale2, w0p, \
+                                                                                  w1p, w2p)
+    switch (n_mid) {
+        case 0: LAUNCH(0); break;
+        case 1: LAUNCH(1); break;
+        case 2: LAUNCH(2); break;
+        default: LAUNCH(3); break;
+    }
+#undef LAUNCH
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
 extern "C" int matten_radial_pack_cols(const float* w0, const float* w1, const float* w2, int n_basis, int nb_pad, int w_cols,
                                        const int64_t* cols, int n_cols, int w_pad, float scale0, float scale1, float scale2,
                                        float* w0p, float* w1p, float* w2p, matten_stream_t stream_) {
+    if (!w1 || !w1p) return MATTEN_EINVAL;
+    return radial_pack_cols_launch(w0, w1, 1, w2, n_basis, nb_pad, w_cols, cols, n_cols, w_pad, scale0, scale1, scale2, w0p,
+                                   w1p, w2p, stream_);
+}
+
+extern "C" int matten_radial_pack_cols_deep(const float* w0, const float* w_mid, int n_mid, const float* w2, int n_basis,
+                                            int nb_pad, int w_cols, const int64_t* cols, int n_cols, int w_pad, float scale0,
+                                            float scale1, float scale2, float* w0p, float* w_mid_p, float* w2p,
+                                            matten_stream_t stream_) {
+    return radial_pack_cols_launch(w0, w_mid, n_mid, w2, n_basis, nb_pad, w_cols, cols, n_cols, w_pad, scale0, scale1, scale2,
+                                   w0p, w_mid_p, w2p, stream_);
+}
+
+static int radial_h_scale_launch(const float* w0, const float* w1, int n_mid, int n_basis, float r_start, float r_end,
+                                 float act_cst, float* out2, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n_basis <= 0 || nb_pad < n_basis || w_cols <= 0 || n_cols <= 0 || w_pad < n_cols) return MATTEN_EINVAL;
-    if (!w0 || !w1 || !w2 || !cols || !w0p || !w1p || !w2p) return MATTEN_EINVAL;
-    const int n = nb_pad * HID + HID * HID + HID * w_pad;
-    radial_pack_cols_kernel<<<(unsigned)matten_cdiv(n, 256), 256, 0, stream>>>(w0, w1, w2, n_basis, nb_pad, w_cols, cols,
-                                                                              n_cols, w_pad, scale0, scale1, scale2, w0p,
-                                                                              w1p, w2p);
+    if (n_basis <= 0 || !(r_end > r_start) || !w0 || (n_mid > 0 && !w1) || !out2 || n_mid < 0 ||
+        n_mid > MATTEN_RADIAL_MAX_MID)
+        return MATTEN_EINVAL;
+#define LAUNCH(M) radial_h_scale_kernel<M><<<1, HID, 0, stream>>>(w0, w1, n_basis, r_end - r_start, act_cst, out2)
+    switch (n_mid) {
+        case 0: LAUNCH(0); break;
+        case 1: LAUNCH(1); break;
+        case 2: LAUNCH(2); break;
+        default: LAUNCH(3); break;
+    }
+#undef LAUNCH
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }
 
 extern "C" int matten_radial_h_scale(const float* w0, const float* w1, int n_basis, float r_start, float r_end, float act_cst,
                                      float* out2, matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n_basis <= 0 || !(r_end > r_start) || !w0 || !w1 || !out2) return MATTEN_EINVAL;
-    radial_h_scale_kernel<<<1, HID, 0, stream>>>(w0, w1, n_basis, r_end - r_start, act_cst, out2);
-    MATTEN_LAUNCH_CHECK();
-    return MATTEN_OK;
+    if (!w1) return MATTEN_EINVAL;
+    return radial_h_scale_launch(w0, w1, 1, n_basis, r_start, r_end, act_cst, out2, stream_);
+}
+
+extern "C" int matten_radial_h_scale_deep(const float* w0, const float* w_mid, int n_mid, int n_basis, float r_start,
+                                          float r_end, float act_cst, float* out2, matten_stream_t stream_) {
+    return radial_h_scale_launch(w0, w_mid, n_mid, n_basis, r_start, r_end, act_cst, out2, stream_);
 }
 
 extern "C" int matten_split_a_tiles(const float* w2p, int64_t w_pad, const int32_t* group_entries, int64_t n_entries,

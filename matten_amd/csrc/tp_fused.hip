@@ -325,7 +325,8 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64, TPF_MIN_BLOCKS) void tp_fused
 #endif
 }
 
-// Hidden layers of the radial MLP: rbf(|v|) -> 32 -> 32, written as the split fp16 form h2s [E,2,32] (see header comment).
+// Hidden layers of the radial MLP: rbf(|v|) -> 32 -> (N_MID x) 32, the last one written as the split fp16 form h2s [E,2,32]
+// (see header comment).  The shipped configs have N_MID = 1 (rbf -> 32 -> 32).
 constexpr int NT = 4;
 // silu on the hardware transcendental units: v_exp_f32 (2^x) + v_rcp_f32, ~1 ulp each, against the ~25-instruction
 // expf + IEEE division; the hidden kernel is bound by exactly this arithmetic (64 silu per edge and layer)
@@ -336,11 +337,11 @@ __device__ __forceinline__ float silu(float z) {
     return z * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
 }
 
-template <int KS0>
+template <int KS0, int N_MID>
 __global__ __launch_bounds__(256) void radial_hidden_kernel(const float4* __restrict__ geom, int64_t E, int n_basis,
                                                             float r_start, float r_end,
                                                             const float* __restrict__ w0p,
-                                                            const float* __restrict__ w1p, _Float16* __restrict__ h2s,
+                                                            const float* __restrict__ w_mid, _Float16* __restrict__ h2s,
                                                             const float* __restrict__ h_scale) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -350,13 +351,15 @@ __global__ __launch_bounds__(256) void radial_hidden_kernel(const float4* __rest
     const float hs = h_scale ? *h_scale : 1.0f;
     const float inv_c = 1.0f / (r_end - r_start);
     const float bes_pref = sqrtf(2.0f * inv_c) * sqrtf((float)n_basis);  // soft_one_hot_linspace 'bessel' x sqrt(nb)
-    float a1[2][8];
+    float a1[N_MID > 0 ? N_MID : 1][2][8];
 #pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-        int k = 16 * (kk >> 2) + 4 * g + (kk & 3);
-        a1[0][kk] = w1p[k * HID + c];
-        a1[1][kk] = w1p[k * HID + 16 + c];
-    }
+    for (int m = 0; m < N_MID; ++m)
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+            int k = 16 * (kk >> 2) + 4 * g + (kk & 3);
+            a1[m][0][kk] = w_mid[m * HID * HID + k * HID + c];
+            a1[m][1][kk] = w_mid[m * HID * HID + k * HID + 16 + c];
+        }
     // all NT edge lengths of the wave are requested up front: the tiles below are long dependent chains (Bessel ->
     // MFMA -> silu -> MFMA -> silu -> split -> store) and would otherwise each start with an exposed load
     float lens[NT];
@@ -388,26 +391,30 @@ __global__ __launch_bounds__(256) void radial_hidden_kernel(const float4* __rest
             h0[r] = silu(h0[r]);
             h1[r] = silu(h1[r]);
         }
-        f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            float b = kk < 4 ? h0[kk & 3] : h1[kk & 3];
-            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[0][kk], b, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[1][kk], b, o1, 0, 0, 0);
-        }
+        for (int m = 0; m < N_MID; ++m) {
+            f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            o0[r] = silu(o0[r]);
-            o1[r] = silu(o1[r]);
+            for (int kk = 0; kk < 8; ++kk) {
+                float b = kk < 4 ? h0[kk & 3] : h1[kk & 3];
+                o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[m][0][kk], b, o0, 0, 0, 0);
+                o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[m][1][kk], b, o1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                o0[r] = silu(o0[r]);
+                o1[r] = silu(o1[r]);
+            }
+            h0 = o0, h1 = o1;
         }
         if (e < E) {
             f16x8 hi, lo;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 _Float16 h, l;
-                split_f16(o0[r] * hs, h, l);
+                split_f16(h0[r] * hs, h, l);
                 hi[r] = h, lo[r] = l;
-                split_f16(o1[r] * hs, h, l);
+                split_f16(h1[r] * hs, h, l);
                 hi[4 + r] = h, lo[4 + r] = l;
             }
             f16x8* dst = reinterpret_cast<f16x8*>(h2s + e * (2 * HID) + g * 8);
@@ -423,13 +430,13 @@ __global__ __launch_bounds__(256) void radial_hidden_kernel(const float4* __rest
 constexpr int RH_MAX_LAYERS = 8;
 struct RadialLayers {
     const float* w0p[RH_MAX_LAYERS];
-    const float* w1p[RH_MAX_LAYERS];
+    const float* w_mid[RH_MAX_LAYERS];   // per MLP: [N_MID][32][32]
     _Float16* h2s[RH_MAX_LAYERS];
     const float* h_scale[RH_MAX_LAYERS];   // per MLP: device pointer to its power-of-two output scale, or NULL (1)
     int n_layers;
 };
 
-template <int KS0>
+template <int KS0, int N_MID>
 __global__ __launch_bounds__(256) void radial_hidden_multi_kernel(const float4* __restrict__ geom, int64_t E, int n_basis,
                                                                   float r_start, float r_end, RadialLayers L) {
     const int lane = threadIdx.x & 63;
@@ -457,21 +464,23 @@ __global__ __launch_bounds__(256) void radial_hidden_multi_kernel(const float4* 
     }
     for (int l = 0; l < L.n_layers; ++l) {
         const float* __restrict__ w0p = L.w0p[l];
-        const float* __restrict__ w1p = L.w1p[l];
+        const float* __restrict__ w_mid = L.w_mid[l];
         _Float16* __restrict__ h2s = L.h2s[l];
         const float hs = L.h_scale[l] ? *L.h_scale[l] : 1.0f;
-        float a0[2][KS0], a1[2][8];
+        float a0[2][KS0], a1[N_MID > 0 ? N_MID : 1][2][8];
 #pragma unroll
         for (int kk = 0; kk < KS0; ++kk) {
             a0[0][kk] = w0p[(4 * kk + g) * HID + c];
             a0[1][kk] = w0p[(4 * kk + g) * HID + 16 + c];
         }
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            const int k = 16 * (kk >> 2) + 4 * g + (kk & 3);
-            a1[0][kk] = w1p[k * HID + c];
-            a1[1][kk] = w1p[k * HID + 16 + c];
-        }
+        for (int m = 0; m < N_MID; ++m)
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk) {
+                const int k = 16 * (kk >> 2) + 4 * g + (kk & 3);
+                a1[m][0][kk] = w_mid[m * HID * HID + k * HID + c];
+                a1[m][1][kk] = w_mid[m * HID * HID + k * HID + 16 + c];
+            }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int64_t e = e0 + nt * 16 + c;
@@ -486,26 +495,30 @@ __global__ __launch_bounds__(256) void radial_hidden_multi_kernel(const float4* 
                 h0[r] = silu(h0[r]);
                 h1[r] = silu(h1[r]);
             }
-            f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {
-                const float b = kk < 4 ? h0[kk & 3] : h1[kk & 3];
-                o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[0][kk], b, o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[1][kk], b, o1, 0, 0, 0);
-            }
+            for (int m = 0; m < N_MID; ++m) {
+                f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                o0[r] = silu(o0[r]);
-                o1[r] = silu(o1[r]);
+                for (int kk = 0; kk < 8; ++kk) {
+                    const float b = kk < 4 ? h0[kk & 3] : h1[kk & 3];
+                    o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[m][0][kk], b, o0, 0, 0, 0);
+                    o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[m][1][kk], b, o1, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    o0[r] = silu(o0[r]);
+                    o1[r] = silu(o1[r]);
+                }
+                h0 = o0, h1 = o1;
             }
             if (e < E) {
                 f16x8 hi, lo;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     _Float16 h, ll;
-                    split_f16(o0[r] * hs, h, ll);
+                    split_f16(h0[r] * hs, h, ll);
                     hi[r] = h, lo[r] = ll;
-                    split_f16(o1[r] * hs, h, ll);
+                    split_f16(h1[r] * hs, h, ll);
                     hi[4 + r] = h, lo[4 + r] = ll;
                 }
                 f16x8* dst = reinterpret_cast<f16x8*>(h2s + e * (2 * HID) + g * 8);
@@ -518,32 +531,88 @@ __global__ __launch_bounds__(256) void radial_hidden_multi_kernel(const float4* 
 
 }  // namespace
 
+static int radial_hidden_multi_launch(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                                      const float* const* w0p, int nb_pad, const float* const* w_mid, int n_mid, int hidden,
+                                      uint16_t* const* h2s, const float* const* h_scale, int n_layers,
+                                      matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_edges < 0 || hidden != HID || (nb_pad & 3) || nb_pad < n_basis || nb_pad > 16 || n_layers < 1 ||
+        n_layers > RH_MAX_LAYERS || n_mid < 0 || n_mid > MATTEN_RADIAL_MAX_MID)
+        return MATTEN_EINVAL;
+    if (n_edges == 0) return MATTEN_OK;
+    if (!geom_sorted || !w0p || (n_mid > 0 && !w_mid) || !h2s) return MATTEN_EINVAL;
+    RadialLayers L{};
+    L.n_layers = n_layers;
+    for (int l = 0; l < n_layers; ++l) {
+        if (!w0p[l] || (n_mid > 0 && !w_mid[l]) || !h2s[l]) return MATTEN_EINVAL;
+        L.w0p[l] = w0p[l], L.w_mid[l] = n_mid > 0 ? w_mid[l] : nullptr, L.h2s[l] = (_Float16*)h2s[l];
+        L.h_scale[l] = h_scale ? h_scale[l] : nullptr;
+    }
+    unsigned grid = (unsigned)matten_cdiv(n_edges, 4 * NT * 16);
+#define LAUNCH(K, M) \
+    radial_hidden_multi_kernel<K, M><<<grid, 256, 0, stream>>>((const float4*)geom_sorted, n_edges, n_basis, r_start, r_end, L)
+#define LAUNCH_M(K)                  \
+    switch (n_mid) {                 \
+        case 0: LAUNCH(K, 0); break; \
+        case 1: LAUNCH(K, 1); break; \
+        case 2: LAUNCH(K, 2); break; \
+        default: LAUNCH(K, 3); break; \
+    }
+    switch (nb_pad >> 2) {
+        case 1: LAUNCH_M(1); break;
+        case 2: LAUNCH_M(2); break;
+        case 3: LAUNCH_M(3); break;
+        default: LAUNCH_M(4); break;
+    }
+#undef LAUNCH_M
+#undef LAUNCH
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
 extern "C" int matten_radial_hidden_multi(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start,
                                           float r_end, const float* const* w0p, int nb_pad, const float* const* w1p,
                                           int hidden, uint16_t* const* h2s, const float* const* h_scale, int n_layers,
                                           matten_stream_t stream_) {
+    if (!w1p && n_edges > 0) return MATTEN_EINVAL;
+    return radial_hidden_multi_launch(geom_sorted, n_edges, n_basis, r_start, r_end, w0p, nb_pad, w1p, 1, hidden, h2s,
+                                      h_scale, n_layers, stream_);
+}
+
+extern "C" int matten_radial_hidden_multi_deep(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start,
+                                               float r_end, const float* const* w0p, int nb_pad, const float* const* w_mid,
+                                               int n_mid, int hidden, uint16_t* const* h2s, const float* const* h_scale,
+                                               int n_layers, matten_stream_t stream_) {
+    return radial_hidden_multi_launch(geom_sorted, n_edges, n_basis, r_start, r_end, w0p, nb_pad, w_mid, n_mid, hidden, h2s,
+                                      h_scale, n_layers, stream_);
+}
+
+static int radial_hidden_launch(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                                const float* w0p, int nb_pad, const float* w_mid, int n_mid, int hidden, uint16_t* h2s,
+                                const float* h_scale, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n_edges < 0 || hidden != HID || (nb_pad & 3) || nb_pad < n_basis || nb_pad > 16 || n_layers < 1 ||
-        n_layers > RH_MAX_LAYERS)
+    if (n_edges < 0 || hidden != HID || (nb_pad & 3) || nb_pad < n_basis || nb_pad > 16 || n_mid < 0 ||
+        n_mid > MATTEN_RADIAL_MAX_MID)
         return MATTEN_EINVAL;
     if (n_edges == 0) return MATTEN_OK;
-    if (!geom_sorted || !w0p || !w1p || !h2s) return MATTEN_EINVAL;
-    RadialLayers L{};
-    L.n_layers = n_layers;
-    for (int l = 0; l < n_layers; ++l) {
-        if (!w0p[l] || !w1p[l] || !h2s[l]) return MATTEN_EINVAL;
-        L.w0p[l] = w0p[l], L.w1p[l] = w1p[l], L.h2s[l] = (_Float16*)h2s[l];
-        L.h_scale[l] = h_scale ? h_scale[l] : nullptr;
-    }
+    if (!geom_sorted || !w0p || (n_mid > 0 && !w_mid) || !h2s) return MATTEN_EINVAL;
     unsigned grid = (unsigned)matten_cdiv(n_edges, 4 * NT * 16);
-#define LAUNCH(K) \
-    radial_hidden_multi_kernel<K><<<grid, 256, 0, stream>>>((const float4*)geom_sorted, n_edges, n_basis, r_start, r_end, L)
-    switch (nb_pad >> 2) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        default: LAUNCH(4); break;
+#define LAUNCH(K, M) \
+    radial_hidden_kernel<K, M><<<grid, 256, 0, stream>>>((const float4*)geom_sorted, n_edges, n_basis, r_start, r_end, w0p, w_mid, (_Float16*)h2s, h_scale)
+#define LAUNCH_M(K)                  \
+    switch (n_mid) {                 \
+        case 0: LAUNCH(K, 0); break; \
+        case 1: LAUNCH(K, 1); break; \
+        case 2: LAUNCH(K, 2); break; \
+        default: LAUNCH(K, 3); break; \
     }
+    switch (nb_pad >> 2) {
+        case 1: LAUNCH_M(1); break;
+        case 2: LAUNCH_M(2); break;
+        case 3: LAUNCH_M(3); break;
+        default: LAUNCH_M(4); break;
+    }
+#undef LAUNCH_M
 #undef LAUNCH
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
@@ -552,22 +621,16 @@ extern "C" int matten_radial_hidden_multi(const float* geom_sorted, int64_t n_ed
 extern "C" int matten_radial_hidden(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
                                     const float* w0p, int nb_pad, const float* w1p, int hidden, uint16_t* h2s,
                                     const float* h_scale, matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n_edges < 0 || hidden != HID || (nb_pad & 3) || nb_pad < n_basis || nb_pad > 16) return MATTEN_EINVAL;
-    if (n_edges == 0) return MATTEN_OK;
-    if (!geom_sorted || !w0p || !w1p || !h2s) return MATTEN_EINVAL;
-    unsigned grid = (unsigned)matten_cdiv(n_edges, 4 * NT * 16);
-#define LAUNCH(K) \
-    radial_hidden_kernel<K><<<grid, 256, 0, stream>>>((const float4*)geom_sorted, n_edges, n_basis, r_start, r_end, w0p, w1p, (_Float16*)h2s, h_scale)
-    switch (nb_pad >> 2) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        default: LAUNCH(4); break;
-    }
-#undef LAUNCH
-    MATTEN_LAUNCH_CHECK();
-    return MATTEN_OK;
+    if (!w1p && n_edges > 0) return MATTEN_EINVAL;
+    return radial_hidden_launch(geom_sorted, n_edges, n_basis, r_start, r_end, w0p, nb_pad, w1p, 1, hidden, h2s, h_scale,
+                                stream_);
+}
+
+extern "C" int matten_radial_hidden_deep(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                                         const float* w0p, int nb_pad, const float* w_mid, int n_mid, int hidden,
+                                         uint16_t* h2s, const float* h_scale, matten_stream_t stream_) {
+    return radial_hidden_launch(geom_sorted, n_edges, n_basis, r_start, r_end, w0p, nb_pad, w_mid, n_mid, hidden, h2s,
+                                h_scale, stream_);
 }
 
 #if TPF_TRACING

@@ -52,7 +52,8 @@ def validate_hparams(hparams: Dict, dataset_hparams: Dict = None) -> None:
     scripts/configs/{materials_tensor,atomic_tensor}.yaml, tests/model/test_tfn_tensor.py):
       irreps_edge_sh            0e+1o+...+lmax with lmax <= 4, parity (-1)^l
       radial_basis_type         bessel                          (reference nn/embedding.py:189-199)
-      invariant_layers/neurons  2 x 32  (radial MLP [nb,32,32,W]; nb <= 16)   (nn/utils.py:246-251)
+      invariant_layers          1 .. 4  (radial MLP [nb] + invariant_layers x [32] + [W]; nb <= 16)   (nn/utils.py:244-251)
+      invariant_neurons         32
       nonlinearity_type         gate | norm                     (nn/utils.py:96-150)
       normalization             batch | instance | none         (nn/utils.py:414-418, 448-588)
       reduce                    mean | sum | min | max          (nn/nodewise.py:131,142-148)
@@ -73,9 +74,10 @@ def validate_hparams(hparams: Dict, dataset_hparams: Dict = None) -> None:
         problems.append(f"radial_basis_type={hparams['radial_basis_type']!r}: only 'bessel'")
     if int(hparams.get("num_radial_basis", 8)) > 16:
         problems.append(f"num_radial_basis={hparams['num_radial_basis']}: at most 16")
-    if int(hparams.get("invariant_layers", 2)) != 2 or int(hparams.get("invariant_neurons", 32)) != 32:
-        problems.append(f"invariant_layers={hparams.get('invariant_layers')}, invariant_neurons="
-                        f"{hparams.get('invariant_neurons')}: the radial MLP is fixed at 2 hidden layers of 32")
+    if int(hparams.get("invariant_neurons", 32)) != 32:
+        problems.append(f"invariant_neurons={hparams.get('invariant_neurons')}: the radial MLP's hidden layers are 32 wide")
+    if not 1 <= int(hparams.get("invariant_layers", 2)) <= 4:
+        problems.append(f"invariant_layers={hparams.get('invariant_layers')}: the radial MLP has 1 to 4 hidden layers")
     if str(hparams.get("nonlinearity_type", "gate")).lower() not in ("gate", "norm"):
         problems.append(f"nonlinearity_type={hparams['nonlinearity_type']!r}: only 'gate' or 'norm'")
     norm = hparams.get("normalization")

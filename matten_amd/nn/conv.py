@@ -149,10 +149,12 @@ class PointConv(ModuleIrreps, torch.nn.Module):
         if m_sc is None or m_l2 is None or not cols:
             return False
         v.lin1 = self.lin1
-        mlp = v.tp.weight_nn
-        mlp.layer0, mlp.layer1 = self.tp.weight_nn.layer0, self.tp.weight_nn.layer1
-        mlp.__dict__["_hidden_from"] = self.tp.weight_nn
-        for mod in (v.sc, v.lin2, mlp.layer2):
+        mlp, full = v.tp.weight_nn, self.tp.weight_nn
+        last = len(full.hs) - 2   # layer{last}: the last radial layer, every one before it is a hidden layer
+        for i in range(last):
+            setattr(mlp, f"layer{i}", getattr(full, f"layer{i}"))
+        mlp.__dict__["_hidden_from"] = full
+        for mod in (v.sc, v.lin2, getattr(mlp, f"layer{last}")):
             del mod._parameters["weight"]
         v.__dict__["_slices"] = (WeightSlice(m_sc), WeightSlice(m_l2), WeightSlice(np.concatenate(cols), dim=1))
         self.__dict__["_view"] = v
@@ -166,8 +168,9 @@ class PointConv(ModuleIrreps, torch.nn.Module):
         # autograd gives the weights of paths that never reach the loss
         pick = (lambda sl, w: sl.select(w)) if differentiable else (lambda sl, w: sl.get(w))
         # (plain instance attributes: Module.__setattr__ would register a Parameter that select() hands back unchanged)
+        last = f"layer{len(self.tp.weight_nn.hs) - 2}"
         targets = ((v.sc, s_sc, self.sc.weight), (v.lin2, s_l2, self.lin2.weight),
-                   (v.tp.weight_nn.layer2, s_w2, self.tp.weight_nn.layer2.weight))
+                   (getattr(v.tp.weight_nn, last), s_w2, getattr(self.tp.weight_nn, last).weight))
         for mod, sl, w in targets:
             mod.__dict__["weight"] = pick(sl, w)
         try:

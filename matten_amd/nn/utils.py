@@ -106,18 +106,25 @@ def radial_group_of(mlp) -> list:
 
 
 class RadialMLP(torch.nn.Module):
-    """Bias-free MLP [n_basis, h, h, W]: x <- c*silu(x @ W/sqrt(h_in)) on hidden layers."""
+    """Bias-free MLP [n_basis] + L*[h] + [W], h = 32, L = 1..4 hidden layers (the reference's invariant_layers; the shipped
+    configs have L = 2): x <- c*silu(x @ W/sqrt(h_in)) on hidden layers.  The L - 1 middle layers (h -> h)
+    reach the kernels as one [L-1, h, h] tensor through the C ABI's _deep entries; L = 2 keeps the original entries."""
+
+    MAX_HIDDEN_LAYERS = ops.RADIAL_MAX_MID + 1
 
     def __init__(self, hs: List[int], act: str = "silu", out_cols=None):
         """out_cols (int64 array, optional): emit output column j = reference column out_cols[j] (-1: zeros).
         The state_dict keeps the reference layout; only the packed copy the kernel reads is permuted."""
         super().__init__()
         self.out_cols = None if out_cols is None else torch.as_tensor(out_cols, dtype=torch.int64)
-        if len(hs) != 4 or hs[1] != 32 or hs[2] != 32:
-            raise NotImplementedError(f"radial MLP must be [nb, 32, 32, W] (invariant_layers=2, neurons=32); got {hs}")
+        if not 3 <= len(hs) <= self.MAX_HIDDEN_LAYERS + 2 or any(h != 32 for h in hs[1:-1]):
+            raise NotImplementedError(f"radial MLP must be [nb] + L*[32] + [W] with 1 <= L <= {self.MAX_HIDDEN_LAYERS} "
+                                      f"(invariant_layers 1..{self.MAX_HIDDEN_LAYERS}, invariant_neurons=32); got {hs}")
         if act != "silu":
             raise NotImplementedError("radial MLP activation must be silu (reference nn/conv.py:72)")
         self.hs = list(hs)
+        self.n_mid = len(hs) - 3        # middle (32 -> 32) layers
+        self.deep = len(hs) != 4        # anything but the shipped [nb, 32, 32, W]: the _deep entries
         self.act_cst = normalize2mom_const(act)
         for i, (a, b) in enumerate(zip(hs, hs[1:])):
             setattr(self, f"layer{i}", _RadialLayer(a, b))
@@ -125,19 +132,25 @@ class RadialMLP(torch.nn.Module):
         self._h_scale = DerivedWeight(self._fp16_scale)
         self._h_scale_c = None
 
-    def _fp16_scale(self, w0: Tensor, w1: Tensor) -> Tensor:
-        """[s, 1/s]: the power of two s <= 1 the hidden features are multiplied by before their fp16 hi/lo split
-        (csrc/tp_fused.hip) so that |s h2| < 2^15 for EVERY possible edge length -- a bound, not a measurement, so no
+    def weights(self) -> tuple:
+        """(layer0.weight, ..., layer{L}.weight)"""
+        return tuple(getattr(self, f"layer{i}").weight for i in range(len(self.hs) - 1))
+
+    def _fp16_scale(self, w0: Tensor, *w_mid: Tensor) -> Tensor:
+        """[s, 1/s]: the power of two s <= 1 the last hidden features are multiplied by before their fp16 hi/lo split
+        (csrc/tp_fused.hip) so that |s h_L| < 2^15 for EVERY possible edge length -- a bound, not a measurement, so no
         host sync and no data dependence:  |bessel_k| <= sqrt(2/c) sqrt(nb) pi (k+1) / c  (sin(x)/x <= 1),
-        |silu(z)| <= |z|, hence |h2| <= P(c) * max_col sum_k |W0p[k,col]| (k+1) * max_col sum_k |W1p[k,col]|.
+        |silu(z)| <= |z|, hence |h_L| <= P(c) * max_col sum_k |W0p[k,col]| (k+1) * prod_i max_col sum_k |Wm_ip[k,col]|
+        over the middle layers (none for L = 1).
         s = 1 whenever the bound is below 2^15 (every normally scaled MLP: the results are then bit-identical to an
         unscaled run); a checkpoint whose radial weights are orders of magnitude larger gets s < 1 instead of inf."""
         nb, h = self.hs[0], self.hs[1]
         c = self._h_scale_c
         k1 = torch.arange(1, nb + 1, device=w0.device, dtype=w0.dtype)[:, None]
         n0 = ((w0.abs() / nb**0.5) * k1).sum(0).max()
-        n1 = (w1.abs() * (self.act_cst / h**0.5)).sum(0).max()
-        bound = (2.0 / c) ** 0.5 * nb**0.5 * 3.141592653589793 / c * n0 * n1
+        bound = (2.0 / c) ** 0.5 * nb**0.5 * 3.141592653589793 / c * n0
+        for w in w_mid:
+            bound = bound * (w.abs() * (self.act_cst / h**0.5)).sum(0).max()
         s = torch.where(bound > 2.0**15, torch.exp2(torch.floor(torch.log2(2.0**14 / bound.clamp(min=1e-30)))),
                         torch.ones_like(bound))
         s = torch.where(torch.isfinite(s) & (s > 0), s, torch.full_like(s, 2.0**-100))
@@ -148,10 +161,20 @@ class RadialMLP(torch.nn.Module):
         if c != self._h_scale_c:
             self._h_scale_c = c
             self._h_scale._key = None
-        return self._h_scale.get(self.layer0.weight, self.layer1.weight)
+        return self._h_scale.get(*self.weights()[:-1])
 
-    def _pack(self, w0: Tensor, w1: Tensor, w2: Tensor):
-        nb, h, W = self.hs[0], self.hs[1], self.hs[3]
+    def _pack_mid(self, w_mid) -> Tensor:
+        """packed middle layers: [32, 32] for the shipped L = 2 (the original entries' w1p), else [L-1, 32, 32]"""
+        h = self.hs[1]
+        if not self.deep:
+            return (w_mid[0] * (self.act_cst / h**0.5)).contiguous()
+        if not w_mid:
+            return torch.zeros(0, h, h, dtype=torch.float32, device=self.layer0.weight.device)
+        return (torch.stack(w_mid) * (self.act_cst / h**0.5)).contiguous()
+
+    def _pack(self, w0: Tensor, *ws: Tensor):
+        nb, h, W = self.hs[0], self.hs[1], self.hs[-1]
+        w2 = ws[-1]
         w2s = w2 * (self.act_cst / h**0.5)
         if self.out_cols is not None:
             cols = self.out_cols.to(w2.device)
@@ -161,7 +184,7 @@ class RadialMLP(torch.nn.Module):
         nb_pad, w_pad = (nb + 3) // 4 * 4, (W + 15) // 16 * 16 + 16
         w0p = w0.new_zeros(nb_pad, h)
         w0p[:nb] = w0 / nb**0.5
-        w1p = (w1 * (self.act_cst / h**0.5)).contiguous()
+        w1p = self._pack_mid(ws[:-1])
         w2p = w2.new_zeros(h, w_pad)
         w2p[:, :W] = w2s
         return w0p, w1p, w2p
@@ -179,59 +202,65 @@ class RadialMLP(torch.nn.Module):
         return w2p
 
     def forward(self, geom_sorted: Tensor, n_basis: int, r_start: float, r_end: float) -> Tensor:
-        """Per-edge weights w[E, w_pad] (all three layers)."""
+        """Per-edge weights w[E, w_pad] (all layers)."""
         if n_basis != self.hs[0]:
             raise ValueError(f"radial basis size {n_basis} != MLP input {self.hs[0]}")
-        w0p, w1p, w2p = self._packed.get(self.layer0.weight, self.layer1.weight, self.layer2.weight)
-        return ops.radial_mlp(geom_sorted, n_basis, r_start, r_end, w0p, w1p, w2p)
+        w0p, w1p, w2p = self._packed.get(*self.weights())
+        return (ops.radial_mlp_deep if self.deep else ops.radial_mlp)(geom_sorted, n_basis, r_start, r_end, w0p, w1p, w2p)
 
     def pack_scales(self):
-        """(1/sqrt(nb), c/sqrt(h), c/sqrt(h)): what turns the raw layers into the kernels' operands"""
+        """(1/sqrt(nb), c/sqrt(h), c/sqrt(h)): what turns the raw layers (first, every middle one, last) into the kernels'
+        operands"""
         nb, h = self.hs[0], self.hs[1]
         return 1.0 / nb**0.5, self.act_cst / h**0.5, self.act_cst / h**0.5
 
-    def pack_reference_order(self, w0: Tensor, w1: Tensor, w2: Tensor):
-        """(w0p, w1p, w2p) with the LAST layer's columns in the reference's order (what the training tensor product and
-        its adjoint index), padded to a multiple of 16"""
-        nb, h, W = self.hs[0], self.hs[1], self.hs[3]
+    def pack_reference_order(self, w0: Tensor, *ws: Tensor):
+        """(w0p, middle layers packed as in _pack, w2p) with the LAST layer's columns in the reference's order (what the
+        training tensor product and its adjoint index), padded to a multiple of 16"""
+        nb, h, W = self.hs[0], self.hs[1], self.hs[-1]
         nb_pad, w_pad = (nb + 3) // 4 * 4, (W + 15) // 16 * 16
         w0p = w0.new_zeros(nb_pad, h)
         w0p[:nb] = w0 / nb**0.5
-        w1p = (w1 * (self.act_cst / h**0.5)).contiguous()
-        w2p = w2.new_zeros(h, w_pad)
-        w2p[:, :W] = w2 * (self.act_cst / h**0.5)
+        w1p = self._pack_mid(ws[:-1])
+        w2p = ws[-1].new_zeros(h, w_pad)
+        w2p[:, :W] = ws[-1] * (self.act_cst / h**0.5)
         return w0p, w1p, w2p
 
     def forward_train(self, geom_sorted: Tensor, n_basis: int, r_start: float, r_end: float) -> Tensor:
-        """w[E, w_pad] in the reference column order, differentiable w.r.t. the three weight matrices: forward and
-        adjoint are this library's MFMA kernels (matten_radial_mlp / matten_radial_mlp_bwd).  Same arithmetic as e3nn
-        FullyConnectedNet: x <- c*silu(x @ W/sqrt(h_in)); last layer linear."""
+        """w[E, w_pad] in the reference column order, differentiable w.r.t. every weight matrix: forward and adjoint are
+        this library's MFMA kernels (matten_radial_mlp / matten_radial_mlp_bwd, or their _deep siblings).  Same
+        arithmetic as e3nn FullyConnectedNet: x <- c*silu(x @ W/sqrt(h_in)); last layer linear."""
         if n_basis != self.hs[0]:
             raise ValueError(f"radial basis size {n_basis} != MLP input {self.hs[0]}")
-        return _ag.RadialMLPFn.apply(self.layer0.weight, self.layer1.weight, self.layer2.weight, self, geom_sorted,
-                                     n_basis, r_start, r_end)
+        return _ag.RadialMLPFn.apply(self, geom_sorted, n_basis, r_start, r_end, *self.weights())
+
+    def _hidden_one(self, geom_sorted: Tensor, n_basis: int, r_start: float, r_end: float, w0p, w1p) -> Tensor:
+        fn = ops.radial_hidden_deep if self.deep else ops.radial_hidden
+        return fn(geom_sorted, n_basis, r_start, r_end, w0p, w1p, self.h_scale(r_start, r_end))
 
     def hidden(self, geom_sorted: Tensor, n_basis: int, r_start: float, r_end: float, data=None):
-        """(h2s[E,2,32] scaled by h_scale(), w2p): the two hidden layers evaluated, the last layer left to the fused TP kernel.
+        """(h2s[E,2,32] scaled by h_scale(), w2p): the hidden layers evaluated, the last layer left to the fused TP kernel.
         With `data` (the batch dict) and a sibling group (set by the model factory: every conv layer's radial MLP reads
         the same edge lengths) the first call evaluates ALL siblings in one launch and parks the results in the dict."""
         if n_basis != self.hs[0]:
             raise ValueError(f"radial basis size {n_basis} != MLP input {self.hs[0]}")
-        w0p, w1p, w2p = self._packed.get(self.layer0.weight, self.layer1.weight, self.layer2.weight)
+        w0p, w1p, w2p = self._packed.get(*self.weights())
         src = self.__dict__.get("_hidden_from")
         if src is not None:   # an inference view (nn/conv.py): the hidden layers ARE the full layer's (shared weights)
             return src.hidden(geom_sorted, n_basis, r_start, r_end, data)[0], w2p
         group = radial_group_of(self)
-        if data is not None and len(group) > 1 and os.environ.get("MATTEN_RADIAL_MULTI", "1") != "0":
+        if data is not None and len(group) > 1 and os.environ.get("MATTEN_RADIAL_MULTI", "1") != "0" and \
+                all(m.hs[:-1] == self.hs[:-1] for m in group):
             cache = data.get("_amd_h2s")
             if cache is None or cache.get("geom") is not geom_sorted or id(self) not in cache:
-                packs = [m._packed.get(m.layer0.weight, m.layer1.weight, m.layer2.weight) for m in group]
-                outs = ops.radial_hidden_multi(geom_sorted, n_basis, r_start, r_end, [p[0] for p in packs],
-                                               [p[1] for p in packs], [m.h_scale(r_start, r_end) for m in group])
+                packs = [m._packed.get(*m.weights()) for m in group]
+                fn = ops.radial_hidden_multi_deep if self.deep else ops.radial_hidden_multi
+                outs = fn(geom_sorted, n_basis, r_start, r_end, [p[0] for p in packs], [p[1] for p in packs],
+                          [m.h_scale(r_start, r_end) for m in group])
                 cache = {"geom": geom_sorted, **{id(m): h for m, h in zip(group, outs)}}
                 data["_amd_h2s"] = cache
             return cache.pop(id(self)), w2p   # popped: the 147 MB per layer are released after use
-        return ops.radial_hidden(geom_sorted, n_basis, r_start, r_end, w0p, w1p, self.h_scale(r_start, r_end)), w2p
+        return self._hidden_one(geom_sorted, n_basis, r_start, r_end, w0p, w1p), w2p
 
 
 # small batches: CSR segments longer than the piece length are walked in pieces (ops.csr_split); 0 = off.  Large batches
@@ -303,12 +332,12 @@ class UVUTensorProduct(torch.nn.Module):
         self._a_split = DerivedWeight(self._split_last_layer)
         self._a_split_c = None
 
-    def _split_last_layer(self, w0: Tensor, w1: Tensor, w2: Tensor):
+    def _split_last_layer(self, *ws: Tensor):
         """the last radial layer as the fp16 hi/lo MFMA fragments of matten_tp_fused, with 1 / (entry scale x hidden
         feature scale) as the per-entry output factor (rebuilt when the weights change)"""
-        w2p = self.weight_nn._packed.get(w0, w1, w2)[2]
+        w2p = self.weight_nn._packed.get(*ws)[2]
         frag, scale_inv = ops.split_a_tiles(w2p, self.plan.group_entries)
-        return frag, (scale_inv * self.weight_nn._h_scale.get(w0, w1)[1]).contiguous()
+        return frag, (scale_inv * self.weight_nn._h_scale.get(*ws[:-1])[1]).contiguous()
 
     def a_split(self, r_start: float, r_end: float):
         """(fragments, a_scale_inv) for matten_tp_fused / matten_tp_lin2, consistent with weight_nn.hidden()"""
@@ -318,7 +347,7 @@ class UVUTensorProduct(torch.nn.Module):
         if c != self._a_split_c:     # the folded 1 / h_scale belongs to ONE cutoff range: a new range, new fragments' factor
             self._a_split_c = c
             self._a_split._key = None
-        return self._a_split.get(mlp.layer0.weight, mlp.layer1.weight, mlp.layer2.weight)
+        return self._a_split.get(*mlp.weights())
 
     @property
     def irreps_out(self) -> Irreps:
@@ -350,9 +379,7 @@ class UVUTensorProduct(torch.nn.Module):
                 # forward on the production kernel, w[E, W] re-evaluated per layer inside the backward only: the same step time
                 # as the materialised-w forward at batch 2048 (5.14 vs 5.15 ms) with 4 x E x W x 4 bytes less live memory
                 # between the passes; small batches keep the path kernels (fewer launches: 10 % faster at batch 32)
-                mlp = self.weight_nn
-                return _ag.FusedTensorProductFn.apply(node_feats, mlp.layer0.weight, mlp.layer1.weight, mlp.layer2.weight,
-                                                      self, data, avg, num_neigh)
+                return _ag.FusedTensorProductFn.apply(node_feats, self, data, avg, num_neigh, *self.weight_nn.weights())
             w_edge = self.weight_nn.forward_train(data[DataKey.AMD_GEOM], int(nb), r0, r1)
             return _ag.TensorProductScatterFn.apply(node_feats, w_edge, self, data, avg, num_neigh)
         if self.impl == "fused":

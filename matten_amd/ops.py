@@ -290,6 +290,136 @@ def fused_operands(w0, w1, w2, scales, cols, group_entries, n_tiles: int, r_star
     return w0p, w1p, w2p, hs, frag, inv
 
 
+# ---- radial MLPs of any depth (invariant_layers = L in 1..4): the _deep entries of the C ABI ---------------------------
+# The middle layers (32 -> 32, L - 1 of them) travel as ONE tensor w_mid [L-1, 32, 32] (raw or packed); L = 2 models keep
+# the entries above (the _deep ones with n_mid = 1 run the same kernels).
+RADIAL_MAX_MID = 3
+
+
+def _mid(w_mid, name: str):
+    """-> (contiguous fp32 [n_mid, 32, 32] or None when empty, n_mid)"""
+    if not isinstance(w_mid, torch.Tensor) or w_mid.dim() != 3 or tuple(w_mid.shape[1:]) != (32, 32):
+        raise ValueError(f"{name}: expected [n_mid, 32, 32]")
+    n_mid = w_mid.shape[0]
+    if n_mid > RADIAL_MAX_MID:
+        raise ValueError(f"{name}: at most {RADIAL_MAX_MID} middle layers (invariant_layers <= {RADIAL_MAX_MID + 1})")
+    return (_need(w_mid, torch.float32, name) if n_mid else None), n_mid
+
+
+def radial_mlp_deep(geom_sorted, n_basis: int, r_start: float, r_end: float, w0p, w_mid, w2p,
+                    out_dtype=torch.float32) -> torch.Tensor:
+    """radial_mlp with w_mid [n_mid, 32, 32] packed middle layers in place of w1p"""
+    lib = _lib.load()
+    geom_sorted = _need(geom_sorted, torch.float32, "geom_sorted")
+    w0p, w2p = _need(w0p, torch.float32, "w0p"), _need(w2p, torch.float32, "w2p")
+    w_mid, n_mid = _mid(w_mid, "w_mid")
+    E = geom_sorted.shape[0]
+    nb_pad, hidden = w0p.shape
+    w_pad = w2p.shape[1]
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("radial_mlp: out_dtype must be fp32 or bf16")
+    out = torch.empty(E, w_pad, dtype=out_dtype, device=geom_sorted.device)
+    with _timed(f"radial_mlp/w_pad={w_pad}"):
+        rc = lib.matten_radial_mlp_deep(_ptr(geom_sorted), E, n_basis, r_start, r_end, _ptr(w0p), nb_pad, _ptr(w_mid), n_mid,
+                                        _ptr(w2p), hidden, w_pad, 1.0, _ptr(out), int(out_dtype == torch.bfloat16), _stream())
+    _lib.check(rc, "matten_radial_mlp_deep")
+    return out
+
+
+def radial_pack_deep(w0, w_mid, w2, scales):
+    """radial_pack with the raw middle layers w_mid [n_mid, 32, 32] in place of w1 -> (w0p, w_mid_p, w2p)"""
+    lib = _lib.load()
+    w0, w2 = _need(w0, torch.float32, "layer0.weight"), _need(w2, torch.float32, "last layer weight")
+    w_mid, n_mid = _mid(w_mid, "middle layer weights")
+    nb, h = w0.shape
+    W = w2.shape[1]
+    nb_pad, w_pad = (nb + 3) // 4 * 4, (W + 15) // 16 * 16
+    dev = w0.device
+    w0p = torch.empty(nb_pad, h, dtype=torch.float32, device=dev)
+    wmp = torch.empty(n_mid, h, h, dtype=torch.float32, device=dev)
+    w2p = torch.empty(h, w_pad, dtype=torch.float32, device=dev)
+    _lib.check(lib.matten_radial_pack_deep(_ptr(w0), _ptr(w_mid), n_mid, _ptr(w2), nb, nb_pad, W, w_pad, float(scales[0]),
+                                           float(scales[1]), float(scales[2]), _ptr(w0p), _ptr(wmp) if n_mid else None,
+                                           _ptr(w2p), _stream()), "matten_radial_pack_deep")
+    return w0p, wmp, w2p
+
+
+def radial_h_scale_deep(w0, w_mid, r_start: float, r_end: float, act_cst: float) -> torch.Tensor:
+    """[s, 1/s] of RadialMLP._fp16_scale computed on the device from the RAW layers (w0 [nb, 32], w_mid [n_mid, 32, 32])"""
+    lib = _lib.load()
+    w0 = _need(w0, torch.float32, "layer0.weight")
+    w_mid, n_mid = _mid(w_mid, "middle layer weights")
+    hs = torch.empty(2, dtype=torch.float32, device=w0.device)
+    _lib.check(lib.matten_radial_h_scale_deep(_ptr(w0), _ptr(w_mid), n_mid, w0.shape[0], float(r_start), float(r_end),
+                                              float(act_cst), _ptr(hs), _stream()), "matten_radial_h_scale_deep")
+    return hs
+
+
+def fused_operands_deep(w0, w_mid, w2, scales, cols, group_entries, n_tiles: int, r_start: float, r_end: float,
+                        act_cst: float):
+    """fused_operands with the raw middle layers w_mid [n_mid, 32, 32] in place of w1 -> (w0p, w_mid_p, w2p, h_scale,
+    a_split fragments, a_scale_inv)"""
+    lib = _lib.load()
+    w0, w2 = _need(w0, torch.float32, "layer0.weight"), _need(w2, torch.float32, "last layer weight")
+    w_mid, n_mid = _mid(w_mid, "middle layer weights")
+    cols = _need(cols, torch.int64, "fused_cols")
+    group_entries = _need(group_entries, torch.int32, "group_entries")
+    nb, h = w0.shape
+    W, n_cols = w2.shape[1], cols.numel()
+    nb_pad, w_pad = (nb + 3) // 4 * 4, (n_cols + 15) // 16 * 16 + 16   # +16: whole tiles may start at any entry
+    dev = w0.device
+    w0p = torch.empty(nb_pad, h, dtype=torch.float32, device=dev)
+    wmp = torch.empty(n_mid, h, h, dtype=torch.float32, device=dev)
+    w2p = torch.empty(h, w_pad, dtype=torch.float32, device=dev)
+    hs = torch.empty(2, dtype=torch.float32, device=dev)
+    n_ent = group_entries.shape[0]
+    frag = torch.empty(n_tiles, 64, 16, dtype=torch.float16, device=dev)
+    inv = torch.empty(n_ent, dtype=torch.float32, device=dev)
+    st = _stream()
+    _lib.check(lib.matten_radial_pack_cols_deep(_ptr(w0), _ptr(w_mid), n_mid, _ptr(w2), nb, nb_pad, W, _ptr(cols), n_cols,
+                                                w_pad, float(scales[0]), float(scales[1]), float(scales[2]), _ptr(w0p),
+                                                _ptr(wmp) if n_mid else None, _ptr(w2p), st), "matten_radial_pack_cols_deep")
+    _lib.check(lib.matten_radial_h_scale_deep(_ptr(w0), _ptr(w_mid), n_mid, nb, float(r_start), float(r_end), float(act_cst),
+                                              _ptr(hs), st), "matten_radial_h_scale_deep")
+    _lib.check(lib.matten_split_a_tiles(_ptr(w2p), w_pad, _ptr(group_entries), n_ent, _ptr(hs), _ptr(frag), _ptr(inv), st),
+               "matten_split_a_tiles")
+    return w0p, wmp, w2p, hs, frag, inv
+
+
+def radial_mlp_bwd_deep(geom_sorted, n_basis: int, r_start: float, r_end: float, w0p, w_mid, w2p, w_cols: int, dw,
+                        scales=(1.0, 1.0, 1.0)):
+    """radial_mlp_bwd with the packed middle layers w_mid [n_mid, 32, 32] in place of w1p
+    -> (dW0 [nb_pad,32], dWmid [n_mid,32,32], dW2 [32,w_pad])"""
+    lib = _lib.load()
+    geom_sorted = _need(geom_sorted, torch.float32, "geom_sorted")
+    w0p, w2p = _need(w0p, torch.float32, "w0p"), _need(w2p, torch.float32, "w2p")
+    w_mid, n_mid = _mid(w_mid, "w_mid")
+    if dw.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("dw must be fp32 or bf16")
+    dw = _need(dw, dw.dtype, "dw")
+    E = geom_sorted.shape[0]
+    nb_pad, hidden = w0p.shape
+    w_pad = w2p.shape[1]
+    dev = geom_sorted.device
+    small_len = nb_pad * hidden + n_mid * hidden * hidden
+    if E == 0:
+        return w0p.new_zeros(nb_pad, hidden), w0p.new_zeros(n_mid, hidden, hidden), w2p.new_zeros(hidden, w_pad)
+    n_small, n_rng = lib.matten_radial_mlp_bwd_small_slices(E), lib.matten_radial_mlp_bwd_w2_ranges_deep(E, w_pad, n_mid)
+    h2 = torch.empty(E, hidden, dtype=torch.float32, device=dev)
+    part_small = torch.empty(max(n_small, 1), small_len, dtype=torch.float32, device=dev)
+    part_w2 = torch.empty(max(n_rng, 1), hidden, w_pad, dtype=torch.float32, device=dev)
+    small = torch.empty(small_len, dtype=torch.float32, device=dev)
+    d2 = torch.empty(hidden, w_pad, dtype=torch.float32, device=dev)
+    with _timed(f"radial_mlp_bwd/w_pad={w_pad}"):
+        rc = lib.matten_radial_mlp_bwd_deep(_ptr(geom_sorted), E, n_basis, r_start, r_end, _ptr(w0p), nb_pad, _ptr(w_mid),
+                                            n_mid, _ptr(w2p), hidden, w_pad, int(w_cols), _ptr(dw), dw.shape[1],
+                                            int(dw.dtype == torch.bfloat16), _ptr(h2), _ptr(part_small), _ptr(part_w2),
+                                            float(scales[0]), float(scales[1]), float(scales[2]), _ptr(small), _ptr(d2),
+                                            _stream())
+    _lib.check(rc, "matten_radial_mlp_bwd_deep")
+    return small[: nb_pad * hidden].reshape(nb_pad, hidden), small[nb_pad * hidden:].reshape(n_mid, hidden, hidden), d2
+
+
 def gather_scale(src, idx, scale, scale_by_source: bool = False, perm2=None):
     """out[i] = src.flat[idx.flat[i]] * scale[(idx.flat[i] if scale_by_source else i) % len(scale)], shaped like idx.
     perm2 (int64 [len(scale)]): also return out2[r, q] = out[r, perm2[q]] (the same launch)"""
@@ -414,6 +544,51 @@ def radial_hidden_multi(geom_sorted, n_basis: int, r_start: float, r_end: float,
                                             arr(w1ps), w0ps[0].shape[1], arr(out),
                                             arr(h_scales) if h_scales is not None else None, L, _stream())
     _lib.check(rc, "matten_radial_hidden_multi")
+    return out
+
+
+def radial_hidden_deep(geom_sorted, n_basis: int, r_start: float, r_end: float, w0p, w_mid, h_scale=None) -> torch.Tensor:
+    """radial_hidden with the packed middle layers w_mid [n_mid, 32, 32] in place of w1p: h2s [E,2,32] fp16 of the LAST
+    hidden layer"""
+    lib = _lib.load()
+    geom_sorted = _need(geom_sorted, torch.float32, "geom_sorted")
+    w0p = _need(w0p, torch.float32, "w0p")
+    w_mid, n_mid = _mid(w_mid, "w_mid")
+    E = geom_sorted.shape[0]
+    h2p = torch.empty(E, 2, 32, dtype=torch.float16, device=geom_sorted.device)
+    with _timed("radial_hidden"):
+        if h_scale is not None:
+            h_scale = _need(h_scale, torch.float32, "h_scale")
+        rc = lib.matten_radial_hidden_deep(_ptr(geom_sorted), E, n_basis, r_start, r_end, _ptr(w0p), w0p.shape[0],
+                                           _ptr(w_mid), n_mid, w0p.shape[1], _ptr(h2p), _ptr(h_scale), _stream())
+    _lib.check(rc, "matten_radial_hidden_deep")
+    return h2p
+
+
+def radial_hidden_multi_deep(geom_sorted, n_basis: int, r_start: float, r_end: float, w0ps, w_mids, h_scales=None):
+    """radial_hidden_multi for MLPs of one depth: w_mids = their packed middle layers [n_mid, 32, 32]"""
+    import ctypes
+
+    lib = _lib.load()
+    geom_sorted = _need(geom_sorted, torch.float32, "geom_sorted")
+    w0ps = [_need(w, torch.float32, "w0p") for w in w0ps]
+    mids = [_mid(w, "w_mid") for w in w_mids]
+    L, E = len(w0ps), geom_sorted.shape[0]
+    if not 1 <= L <= 8 or len(mids) != L or any(w.shape != w0ps[0].shape for w in w0ps) or \
+            any(m[1] != mids[0][1] for m in mids):
+        raise ValueError("radial_hidden_multi_deep: 1..8 layers with equal basis / hidden sizes and depth")
+    n_mid = mids[0][1]
+    out = [torch.empty(E, 2, 32, dtype=torch.float16, device=geom_sorted.device) for _ in range(L)]
+    arr = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])
+    if h_scales is not None:
+        h_scales = [_need(h, torch.float32, "h_scale") for h in h_scales]
+        if len(h_scales) != L:
+            raise ValueError("one h_scale per layer")
+    with _timed("radial_hidden_multi"):
+        rc = lib.matten_radial_hidden_multi_deep(_ptr(geom_sorted), E, n_basis, r_start, r_end, arr(w0ps), w0ps[0].shape[0],
+                                                 arr([m[0] for m in mids]) if n_mid else None, n_mid, w0ps[0].shape[1],
+                                                 arr(out), arr(h_scales) if h_scales is not None else None, L, _stream())
+    _lib.check(rc, "matten_radial_hidden_multi_deep")
     return out
 
 
