@@ -427,7 +427,8 @@ int matten_adam_step(float* params, const float* grads, float* exp_avg, float* e
  * fixed).  dx_edges != NULL (scratch [E, d_in]; every input block's columns are written, columns of input irreps without
  * a path must be zero on entry): each edge's contribution is stored and dx[n] = the sum over the edges leaving n in the
  * order of out_perm[out_ptr[n] .. out_ptr[n+1]) -- sorted-edge indices grouped by source node (the CSR of src_sorted:
- * matten_csr_build on it) -- bitwise reproducible; dx [n_nodes, d_in] need not be initialised. */
+ * matten_csr_build on it) -- bitwise reproducible; dx [n_nodes, d_in] need not be initialised.  With n_edges == 0 the
+ * scratch has no bytes and may be NULL: dx is then zeroed whenever out_ptr is given. */
 int matten_tp_backward_lit(const float* x, int64_t d_in, const void* w_edge, int64_t w_ld, const float* sh_sorted,
                            int64_t sh_stride, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* blocks,
                            int64_t n_blocks, int64_t max_mul, const int32_t* paths, int64_t n_paths, const float* g_agg,

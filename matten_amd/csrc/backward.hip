@@ -1384,7 +1384,9 @@ extern "C" int matten_tp_backward_lit(const float* x, int64_t d_in, const void* 
         return MATTEN_EINVAL;
     if (dx_edges && (!out_ptr || !out_perm || n_nodes < 0)) return MATTEN_EINVAL;
     if (n_edges == 0) {
-        if (dx_edges && n_nodes > 0) {
+        // the fixed-order mode's dx is not initialised by the caller; its dx_edges scratch has no bytes now (a caller may pass
+        // NULL for it), so out_ptr marks the mode here (in the atomic mode dx is zero already: zeroing it again is harmless)
+        if ((dx_edges || out_ptr) && n_nodes > 0) {
             if (!dx) return MATTEN_EINVAL;
             if (hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n_nodes * (size_t)d_in, stream) != hipSuccess) return MATTEN_ELAUNCH;
         }
@@ -1431,7 +1433,9 @@ extern "C" int matten_tp_backward_lit_wfree(const float* x, int64_t d_in, const 
         return MATTEN_EINVAL;
     if (dx_edges && (!out_ptr || !out_perm || n_nodes < 0)) return MATTEN_EINVAL;
     if (n_edges == 0) {
-        if (dx_edges && n_nodes > 0) {
+        // the fixed-order mode's dx is not initialised by the caller; its dx_edges scratch has no bytes now (a caller may pass
+        // NULL for it), so out_ptr marks the mode here (in the atomic mode dx is zero already: zeroing it again is harmless)
+        if ((dx_edges || out_ptr) && n_nodes > 0) {
             if (!dx) return MATTEN_EINVAL;
             if (hipMemsetAsync(dx, 0, sizeof(float) * (size_t)n_nodes * (size_t)d_in, stream) != hipSuccess) return MATTEN_ELAUNCH;
         }
