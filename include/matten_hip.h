@@ -34,7 +34,7 @@ typedef void* matten_stream_t; /* hipStream_t */
 #define MATTEN_ELAUNCH (-2) /* hipGetLastError() != hipSuccess after a launch */
 #define MATTEN_ENOMEM (-3)  /* caller-provided workspace too small */
 
-/* ABI version of this header; bumped on any signature change (45: the _deep radial MLP entries). */
+/* ABI version of this header; bumped on any signature change (46: the eval-mode BatchNorm adjoints). */
 int matten_abi_version(void);
 
 /* Radial MLP depth.  The reference builds every conv layer's radial network as FullyConnectedNet([nb] + L x [32] + [W],
@@ -503,6 +503,27 @@ int matten_norm_act(const float* x, int64_t dim, int64_t n_rows, const int32_t* 
                     const float* bn_bias, float bn_eps, float* y, matten_stream_t stream);
 int matten_norm_act_bwd(const float* x, const float* dy, int64_t dim, int64_t n_rows, const int32_t* chan, int64_t n_chan,
                         int act, float epsilon, float* dx, matten_stream_t stream);
+
+/* Backpropagation through the activation followed by eval-mode BatchNorm (frozen running statistics; the reference
+ * gets it from autograd through e3nn's Gate / NormActivation, nn/utils.py:96-150, and its BatchNorm outside training,
+ * nn/utils.py:414-418).  The forward is matten_gate_bn / matten_norm_act with the running statistics; nothing but x is
+ * kept, the activated value a is re-evaluated.  One pass over x and dy writes every column of dx and, when dweight is
+ * given, one partial record per (16-row block, column or channel); a second launch adds a channel's records in a fixed
+ * order (no atomics, bitwise reproducible):
+ *   dweight [n_chan] = sum dy (a - running_mean) / sqrt(running_var + eps),  dbias [number of 0e channels] = sum dy.
+ * dweight == NULL: dx only (frozen affine), dbias / scratch / bn_chan are not touched.  running_mean / running_var /
+ * bn_weight are only read.  scratch: the floats the _scratch_floats entry returns for (n_rows, d_out) (Gate) or
+ * (n_rows, n_chan) (norm activation).  meta / act_cst as for matten_gate_bn, chan as for matten_norm_act; bn_chan
+ * [n_chan,4] is the BatchNorm's channel table over the OUTPUT columns (as for matten_bn_train_fwd). */
+int64_t matten_bn_eval_bwd_scratch_floats(int64_t n_rows, int64_t n_cols);
+int matten_gate_bn_eval_bwd(const float* x, int64_t d_in, const int32_t* meta, int64_t d_out, const float* act_cst,
+                            const int32_t* bn_chan, int64_t n_chan, const float* running_mean, const float* running_var,
+                            const float* bn_weight, float eps, const float* dy, int64_t n_rows, float* dx, float* dweight,
+                            float* dbias, float* scratch, matten_stream_t stream);
+int matten_norm_act_bn_eval_bwd(const float* x, const float* dy, int64_t dim, int64_t n_rows, const int32_t* chan,
+                                int64_t n_chan, int act, float epsilon, const float* running_mean,
+                                const float* running_var, const float* bn_weight, float bn_eps, float* dx, float* dweight,
+                                float* dbias, float* scratch, matten_stream_t stream);
 
 /* Instance ("graph") normalisation, reference nn/utils.py:448-588 (the reference's own InstanceNorm: one set of
  * statistics per crystal, nodes as samples): matten_bn_train_fwd / _bwd with per-crystal statistics, in training and in

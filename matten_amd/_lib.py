@@ -14,7 +14,7 @@ from ctypes import c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmatten_hip.so")
 
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 # name -> (restype, argtypes); must match include/matten_hip.h
 P = c_void_p
@@ -86,6 +86,10 @@ SIGNATURES = {
     "matten_bn_train_bwd": (c_int, [P, P, c_int64, c_int64, P, P, c_int64, P, P, P, c_float, P, P, P, P, P, P, P]),
     "matten_norm_act": (c_int, [P, c_int64, c_int64, P, c_int64, c_int, c_float, P, P, P, P, c_float, P, P]),
     "matten_norm_act_bwd": (c_int, [P, P, c_int64, c_int64, P, c_int64, c_int, c_float, P, P]),
+    "matten_bn_eval_bwd_scratch_floats": (c_int64, [c_int64, c_int64]),
+    "matten_gate_bn_eval_bwd": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, P, P, P, c_float, P, c_int64, P, P, P, P, P]),
+    "matten_norm_act_bn_eval_bwd": (c_int, [P, P, c_int64, c_int64, P, c_int64, c_int, c_float, P, P, P, c_float, P, P, P, P,
+                                            P]),
     "matten_instance_norm_fwd": (c_int, [P, c_int64, c_int64, P, P, c_int64, P, P, c_int64, P, P, c_float, P, P, P, P]),
     "matten_instance_norm_bwd": (c_int, [P, P, c_int64, c_int64, P, P, c_int64, P, P, c_int64, P, P, P, c_float, P, P, P, P]),
     "matten_segment_reduce_bwd": (c_int, [P, c_int64, P, c_int64, c_int, P, P]),

@@ -305,6 +305,50 @@ class NormActFn(torch.autograd.Function):
                                 mod.plan.epsilon), None
 
 
+class GateBnEvalFn(torch.autograd.Function):
+    """BatchNorm(Gate(x)) with the BatchNorm in eval mode (frozen running statistics): the forward is the inference kernel
+    (matten_gate_bn with the running statistics), the adjoint re-evaluates the activated value from x
+    (matten_gate_bn_eval_bwd) -- gradients for x and the affine parameters, the running statistics are only read."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, bn):
+        dev = x.device
+        ctx.mod, ctx.bn = mod, bn
+        ctx.save_for_backward(x, weight, bn.running_mean, bn.running_var)
+        return ops.gate_bn(x, mod._tables.get("meta", dev), mod._tables.get("act_cst", dev), bn.running_mean,
+                           bn.running_var, weight, bias, eps=bn.eps)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, rm, rv = ctx.saved_tensors
+        mod, bn, dev = ctx.mod, ctx.bn, g.device
+        dx, dweight, dbias = ops.gate_bn_eval_bwd(
+            x, mod._tables.get("meta", dev), mod._tables.get("act_cst", dev), bn._tables.get("chan", dev), rm, rv, weight,
+            bn.eps, g, bn.bias.numel(), param_grads=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        return dx, dweight, dbias, None, None
+
+
+class NormActBnEvalFn(torch.autograd.Function):
+    """BatchNorm(NormActivation(x)) with the BatchNorm in eval mode: matten_norm_act with the running statistics forward,
+    matten_norm_act_bn_eval_bwd backward (see GateBnEvalFn)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, bn):
+        ctx.mod, ctx.bn = mod, bn
+        ctx.save_for_backward(x, weight, bn.running_mean, bn.running_var)
+        return ops.norm_act(x, mod._tables.get("chan", x.device), mod.plan.act_code, mod.plan.epsilon, bn.running_mean,
+                            bn.running_var, weight, bias, bn.eps)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, rm, rv = ctx.saved_tensors
+        mod, bn = ctx.mod, ctx.bn
+        dx, dweight, dbias = ops.norm_act_bn_eval_bwd(
+            x, g, mod._tables.get("chan", g.device), mod.plan.act_code, mod.plan.epsilon, rm, rv, weight, bn.eps,
+            bn.bias.numel(), param_grads=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        return dx, dweight, dbias, None, None
+
+
 class BatchNormTrainFn(torch.autograd.Function):
     """e3nn BatchNorm with batch statistics; the running averages are updated in place by the statistics kernel
     (running = (1 - momentum) running + momentum batch), so the step needs no small library launches for them."""

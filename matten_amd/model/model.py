@@ -50,6 +50,43 @@ class TimeMeter:
         return delta, now - self.t0
 
 
+def _batchnorms(model):
+    from ..nn.utils import _IrrepBatchNorm
+
+    return [m for m in model.modules() if isinstance(m, _IrrepBatchNorm)]
+
+
+def freeze_batchnorm(model, freeze_affine: bool = False):
+    """Fine-tuning with frozen statistics: every BatchNorm of `model` goes to eval mode -- it normalises with its running
+    averages, which no step writes any more, and gradients flow through it to the layers below and to its own weight /
+    bias -- and STAYS there: the modules are flagged, and their ``train()`` ignores later ``model.train()`` calls (what a
+    trainer issues at the start of every epoch) until ``unfreeze_batchnorm``.  freeze_affine=True also takes weight and
+    bias out of the optimisation (requires_grad = False).  No parameter, buffer or state_dict key changes.  Returns the
+    model."""
+    for bn in _batchnorms(model):
+        bn.__dict__["_frozen_stats"] = True
+        bn.eval()
+        if freeze_affine:
+            if "_frozen_affine" not in bn.__dict__:
+                bn.__dict__["_frozen_affine"] = (bn.weight.requires_grad, bn.bias.requires_grad)
+            bn.weight.requires_grad_(False)
+            bn.bias.requires_grad_(False)
+    return model
+
+
+def unfreeze_batchnorm(model):
+    """Undo ``freeze_batchnorm``: the BatchNorms follow the model's mode again and a frozen affine gets its earlier
+    requires_grad flags back."""
+    for bn in _batchnorms(model):
+        if bn.__dict__.pop("_frozen_stats", False):
+            bn.train(model.training)
+        flags = bn.__dict__.pop("_frozen_affine", None)
+        if flags is not None:
+            bn.weight.requires_grad_(flags[0])
+            bn.bias.requires_grad_(flags[1])
+    return model
+
+
 class BaseModel(_Base):
     monitor_key = "val/score"
 
@@ -175,6 +212,13 @@ class BaseModel(_Base):
 
     # ---- reference model/model.py:447-479 ----
     def configure_optimizers(self):
+        # optimizer_hparams["freeze_batchnorm"] (absent: nothing changes): True / "statistics" fine-tunes with frozen
+        # running statistics, "affine" also freezes the BatchNorm weight / bias (model.freeze_batchnorm)
+        frozen = (self.optimizer_hparams or {}).get("freeze_batchnorm")
+        if frozen:
+            if frozen not in (True, "statistics", "affine"):
+                raise ValueError(f'optimizer_hparams["freeze_batchnorm"] must be True, "statistics" or "affine", got {frozen!r}')
+            freeze_batchnorm(self, freeze_affine=frozen == "affine")
         params = (filter(lambda p: p.requires_grad, self.parameters()),)
         optimizer = instantiate_class(params, self.optimizer_hparams)
         scheduler = self._config_lr_scheduler(optimizer)

@@ -295,7 +295,8 @@ class PointConvWithActivation(ModuleIrreps, torch.nn.Module):
     def forward(self, data: DataKey.Type) -> DataKey.Type:
         x = data[DataKey.NODE_FEATURES]
         fuse = None
-        if not _ag.needs_grad_lazy(lambda: (x, *_ag.params_of(self.conv))) and x.shape[0] >= AGG_KM_MIN_ROWS:
+        if not _ag.needs_grad_lazy(lambda: (x, *_ag.params_of(self.conv), *_ag.params_of(self.norm))) \
+                and x.shape[0] >= AGG_KM_MIN_ROWS:
             fuse = self._gate_fuse_args(x.device)
         self.conv.__dict__["_gate_fuse"] = fuse
         try:

@@ -454,6 +454,9 @@ class ActivationLayer(torch.nn.Module):
     def _forward_norm_act(self, x: Tensor, norm, data) -> Tensor:
         dev = x.device
         bn = norm.n if (norm is not None and norm.method == "batch") else None
+        if bn is not None and not bn.training and _ag.needs_grad(x, bn.weight, bn.bias):
+            # frozen statistics under autograd: the inference kernel forward, its own adjoint backward
+            return _ag.NormActBnEvalFn.apply(x, bn.weight, bn.bias, self, bn)
         if _ag.needs_grad(x) or (bn is not None and bn.training) or (norm is not None and norm.method == "instance"):
             y = _ag.NormActFn.apply(x, self) if _ag.needs_grad(x) else ops.norm_act(
                 x, self._tables.get("chan", dev), self.plan.act_code, self.plan.epsilon)
@@ -461,8 +464,6 @@ class ActivationLayer(torch.nn.Module):
                 return norm.n(y, data)
             if bn is None:
                 return y
-            if not bn.training:
-                raise NotImplementedError("gradients through eval-mode BatchNorm: call model.train()")
             return bn.forward_train(y)
         return ops.norm_act(x, self._tables.get("chan", dev), self.plan.act_code, self.plan.epsilon,
                             *((bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps) if bn is not None else ()))
@@ -482,9 +483,10 @@ class ActivationLayer(torch.nn.Module):
             y = _ag.GateFn.apply(x, self) if x.requires_grad else ops.gate_bn(
                 x, self._tables.get("meta", dev), self._tables.get("act_cst", dev))
             return bn.forward_train(y)
+        if bn is not None and _ag.needs_grad(x, bn.weight, bn.bias):
+            # frozen statistics under autograd (fine-tuning with BatchNorm in eval mode, gradients of an eval-mode model)
+            return _ag.GateBnEvalFn.apply(x, bn.weight, bn.bias, self, bn)
         if _ag.needs_grad(x):
-            if bn is not None:
-                raise NotImplementedError("gradients through eval-mode BatchNorm: call model.train()")
             return _ag.GateFn.apply(x, self)
         return ops.gate_bn(
             x, self._tables.get("meta", dev), self._tables.get("act_cst", dev),
@@ -513,6 +515,10 @@ class _IrrepBatchNorm(torch.nn.Module):
     def forward_train(self, x: Tensor) -> Tensor:
         # e3nn: running = (1 - momentum) * running + momentum * batch -- done by the statistics kernel itself
         return _ag.BatchNormTrainFn.apply(x, self.weight, self.bias, self)
+
+    def train(self, mode: bool = True):
+        """frozen statistics (model.freeze_batchnorm): a later ``model.train()`` leaves this module in eval mode"""
+        return super().train(mode and not self.__dict__.get("_frozen_stats", False))
 
 
 class _IrrepInstanceNorm(torch.nn.Module):

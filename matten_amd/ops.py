@@ -1007,6 +1007,53 @@ def norm_act_bwd(x, dy, chan, act: int, epsilon: float = 1e-8) -> torch.Tensor:
     return dx
 
 
+def _bn_eval_bwd_outputs(lib, x, n_cols: int, n_chan: int, n_bias: int, param_grads: bool):
+    dx = torch.empty_like(x)   # every input column is written exactly once
+    if not param_grads:
+        return dx, None, None, None
+    dweight = torch.empty(n_chan, dtype=torch.float32, device=x.device)
+    dbias = torch.empty(n_bias, dtype=torch.float32, device=x.device)
+    scratch = torch.empty(lib.matten_bn_eval_bwd_scratch_floats(x.shape[0], n_cols), dtype=torch.float32, device=x.device)
+    return dx, dweight, dbias, scratch
+
+
+def gate_bn_eval_bwd(x, meta, act_cst, bn_chan, running_mean, running_var, bn_weight, eps: float, dy, n_bias: int,
+                     param_grads: bool = True):
+    """adjoint of gate_bn WITH the running statistics (eval-mode BatchNorm) -> (dx, dweight [C], dbias [n_bias]);
+    param_grads=False: (dx, None, None) from one launch (frozen affine)"""
+    lib = _lib.load()
+    x = _need(x, torch.float32, "x")
+    dy = _need(dy, torch.float32, "dy")
+    if x.shape[0] == 0:
+        z = (lambda n: torch.zeros(n, dtype=torch.float32, device=x.device)) if param_grads else (lambda n: None)
+        return torch.empty_like(x), z(bn_chan.shape[0]), z(n_bias)
+    d_out, C = meta.shape[0], bn_chan.shape[0]
+    dx, dweight, dbias, scratch = _bn_eval_bwd_outputs(lib, x, d_out, C, n_bias, param_grads)
+    _lib.check(lib.matten_gate_bn_eval_bwd(_ptr(x), x.shape[1], _ptr(meta), d_out, _ptr(act_cst), _ptr(bn_chan), C,
+                                           _ptr(running_mean), _ptr(running_var), _ptr(bn_weight), float(eps), _ptr(dy),
+                                           x.shape[0], _ptr(dx), _ptr(dweight), _ptr(dbias), _ptr(scratch), _stream()),
+               "matten_gate_bn_eval_bwd")
+    return dx, dweight, dbias
+
+
+def norm_act_bn_eval_bwd(x, dy, chan, act: int, epsilon: float, running_mean, running_var, bn_weight, bn_eps: float,
+                         n_bias: int, param_grads: bool = True):
+    """adjoint of norm_act WITH the running statistics (eval-mode BatchNorm) -> (dx, dweight [C], dbias [n_bias])"""
+    lib = _lib.load()
+    x = _need(x, torch.float32, "x")
+    dy = _need(dy, torch.float32, "dy")
+    C = chan.shape[0]
+    if x.shape[0] == 0:
+        z = (lambda n: torch.zeros(n, dtype=torch.float32, device=x.device)) if param_grads else (lambda n: None)
+        return torch.empty_like(x), z(C), z(n_bias)
+    dx, dweight, dbias, scratch = _bn_eval_bwd_outputs(lib, x, C, C, n_bias, param_grads)
+    _lib.check(lib.matten_norm_act_bn_eval_bwd(_ptr(x), _ptr(dy), x.shape[1], x.shape[0], _ptr(chan), C, int(act),
+                                               float(epsilon), _ptr(running_mean), _ptr(running_var), _ptr(bn_weight),
+                                               float(bn_eps), _ptr(dx), _ptr(dweight), _ptr(dbias), _ptr(scratch),
+                                               _stream()), "matten_norm_act_bn_eval_bwd")
+    return dx, dweight, dbias
+
+
 def instance_norm_fwd(x, seg_ptr, seg_of_row, col2chan, chan, weight, bias, eps: float):
     """per-crystal statistics (reference InstanceNorm, nn/utils.py:448-588) -> (y, mean [B, C], nu [B, C])"""
     lib = _lib.load()
