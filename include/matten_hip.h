@@ -34,7 +34,7 @@ typedef void* matten_stream_t; /* hipStream_t */
 #define MATTEN_ELAUNCH (-2) /* hipGetLastError() != hipSuccess after a launch */
 #define MATTEN_ENOMEM (-3)  /* caller-provided workspace too small */
 
-/* ABI version of this header; bumped on any signature change (46: the eval-mode BatchNorm adjoints). */
+/* ABI version of this header; bumped on any signature change (47: open / partly periodic graph prologue, pair-free neighbour search). */
 int matten_abi_version(void);
 
 /* Radial MLP depth.  The reference builds every conv layer's radial network as FullyConnectedNet([nb] + L x [32] + [W],
@@ -565,10 +565,35 @@ int matten_segment_reduce_bwd(const float* dy, int64_t dim, const int64_t* ptr, 
  * pair's count at its j-major number pair_ptr[b] + (j - lo) n_b + (i - lo); the caller scans it into offsets_t like
  * offsets (offsets_t[0] is subtracted: the scan may continue the i-major one), and matten_neighbor_fill then also writes rowptr[n_atoms + 1], src_sorted[n_edges], perm[n_edges] (int32; all
  * four of offsets_t / rowptr / src_sorted / perm or none: NULL) -- bit for bit matten_csr_build's outputs.
+ *
+ * matten_graph_prep_pbc (reference data/data.py:285-413: neighbor_list_and_relative_vec(..., cell, pbc) hands a bool
+ *   per axis to ASE): matten_graph_prep with pbc[B,3] (uint8, non-zero = periodic).  An open axis generates no image
+ *   (S_k = 0); a cell row on an open axis may be zero and is not used by the search.  The cell is completed for the
+ *   inverse (open rows := unit vectors orthogonal to the periodic rows); frac and bound are written as by
+ *   matten_graph_prep on the periodic axes and as 0 on the open ones, which makes the search kernels walk exactly
+ *   S_k = 0 there -- they take these outputs unchanged.  cell_f32 is the caller's cell.  singular[B] (int32) := 1 where
+ *   the periodic vectors of a crystal are linearly dependent (|det| of the completed cell <= 1e-12; that crystal is
+ *   searched as if open), and *n_singular (int64, zeroed by the caller) is incremented once per such crystal.
+ * matten_neighbor_rows_count / matten_neighbor_rows_fill (reference data/data.py:285-413, same edge contract and the
+ *   same canonical order): the search without per-pair bookkeeping, for large structures.  One wave per centre atom;
+ *   batch[N] (int64, matten_graph_prep) names its crystal.  _count -> counts[n_atoms] (int32, edges of each centre
+ *   atom); the caller scans them into offsets[n_atoms + 1] (exclusive, int64; matten_neighbor_summary with ptr in the
+ *   place of pair_ptr gives the read-back); _fill writes edge_index[2,n_edges], edge_cell_shift[n_edges,3] and
+ *   num_neigh[n_atoms] (optional).  No CSR is emitted here: matten_csr_build derives it.  n_atoms < 2^32.
  * ========================================================================================== */
 int matten_graph_prep(const double* pos, const double* cell, const int64_t* ptr, int64_t n_crystals, double r_cut,
                       double* frac, double* bound, int64_t* batch, float* pos_f32, float* cell_f32,
                       matten_stream_t stream);
+int matten_graph_prep_pbc(const double* pos, const double* cell, const int64_t* ptr, const uint8_t* pbc,
+                          int64_t n_crystals, double r_cut, double* frac, double* bound, int64_t* batch, float* pos_f32,
+                          float* cell_f32, int32_t* singular, int64_t* n_singular, matten_stream_t stream);
+int matten_neighbor_rows_count(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                               const double* frac, const double* bound, double r_cut, int64_t n_atoms, int32_t* counts,
+                               matten_stream_t stream);
+int matten_neighbor_rows_fill(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                              const double* frac, const double* bound, double r_cut, int64_t n_atoms,
+                              const int64_t* offsets, int64_t n_edges, int64_t* edge_index, float* edge_cell_shift,
+                              float* num_neigh, matten_stream_t stream);
 int matten_neighbor_count(const double* pos, const double* cell, const int64_t* ptr, const double* frac,
                           const double* bound, const int64_t* pair_ptr, double r_cut, int64_t n_crystals,
                           int64_t max_atoms, int32_t* counts, int32_t* counts_t, matten_stream_t stream);

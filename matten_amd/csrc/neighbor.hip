@@ -20,9 +20,27 @@
 // pair's edges in shift order, i.e. in ascending edge id.  rowptr[j] is the j-major offset of pair (first atom, j).
 // Distances use the host builder's fp64 expression with contraction disabled; the square root is only evaluated for the pairs within 1e-15
 // (relative) of the cutoff, which leaves the decision bit-identical.
+//
+// Open and partly periodic structures (matten_graph_prep_pbc; the reference passes pbc to ASE, data/data.py:285-413):
+// an open axis generates no image, S_k = 0.  The prologue completes the cell -- every open-axis row is replaced by a
+// unit vector orthogonal to the periodic rows, so the inverse exists whenever the periodic vectors are independent --
+// and writes frac = 0 and bound = 0 on the open axes.  shift_range(bound = 0, df = 0) has slack = 1e-6 and returns
+// lo = (int)ceil(-1e-6) = 0, hi = (int)floor(1e-6) = 0: exactly [0, 0].  The search kernels therefore walk only S_k = 0
+// on an open axis and need no knowledge of pbc; T = S @ cell adds 0 * row there, so a non-zero vector on an open axis
+// (kept in `cell` for the model) moves nothing.  On a periodic axis k the column inv[:, k] of the completed inverse
+// lies in the span of the periodic rows and does not depend on how the open rows were chosen, so frac and bound are
+// those of the periodic sub-lattice.  With all three axes periodic the prologue computes what matten_graph_prep does.
+//
+// Large structures (matten_neighbor_rows_count / _fill): the pair kernels keep 24 bytes per ordered atom pair.  The rows
+// kernels give one wave to each centre atom i; lanes take j = j0 + lane over the atoms of i's crystal in chunks of 64
+// and call the same pair_walk.  The counting pass writes ONE count per atom; the fill pass recomputes the lane counts,
+// places a chunk's edges with a wave prefix sum plus a running base, and the edges of i come out j-ascending and
+// shift-lexicographic: the canonical order again, with O(N) bookkeeping.  No CSR is emitted on this route.
 #include "common.h"
 
 #pragma clang fp contract(off)
+
+#define MATTEN_SINGULAR_CELL 1e-12   // the host packer's threshold (predict.pack_structures)
 
 namespace {
 
@@ -35,34 +53,85 @@ struct Cry {
     const int64_t* pair_ptr;  // [B+1] first pair of each crystal (sum of n^2)
 };
 
+__device__ __forceinline__ void unit_cross(double ux, double uy, double uz, double vx, double vy, double vz, double& x,
+                                           double& y, double& z) {
+    x = uy * vz - uz * vy, y = uz * vx - ux * vz, z = ux * vy - uy * vx;
+    const double n = sqrt((x * x + y * y) + z * z);
+    x /= n, y /= n, z /= n;
+}
+
+// rows r1, r2 := unit vectors orthogonal to row r0 and to each other (r0 is the only periodic row)
+__device__ __forceinline__ void complete_two(const double* r0, double* r1, double* r2) {
+    const double fx = fabs(r0[0]), fy = fabs(r0[1]), fz = fabs(r0[2]);
+    double ex = 0.0, ey = 0.0, ez = 0.0;   // the coordinate axis r0 leans on least
+    if (fx <= fy && fx <= fz) ex = 1.0;
+    else if (fy <= fz) ey = 1.0;
+    else ez = 1.0;
+    unit_cross(r0[0], r0[1], r0[2], ex, ey, ez, r1[0], r1[1], r1[2]);
+    unit_cross(r0[0], r0[1], r0[2], r1[0], r1[1], r1[2], r2[0], r2[1], r2[2]);
+}
+
+// PBC = false: matten_graph_prep (three periodic axes).  PBC = true: matten_graph_prep_pbc (header comment); the cell
+// that the model receives (cell_f32) is the caller's, the completed one serves the inverse and nothing else.
+template <bool PBC>
 __global__ __launch_bounds__(64) void graph_prep_kernel(const double* __restrict__ pos, const double* __restrict__ cell,
                                                         const int64_t* __restrict__ ptr, double r_cut,
                                                         double* __restrict__ frac, double* __restrict__ bound,
                                                         int64_t* __restrict__ batch, float* __restrict__ pos_f32,
-                                                        float* __restrict__ cell_f32) {
+                                                        float* __restrict__ cell_f32, const uint8_t* __restrict__ pbc,
+                                                        int32_t* __restrict__ singular, int64_t* __restrict__ n_singular) {
     const int64_t b = blockIdx.x;
     const double* cl = cell + 9 * b;
-    const double ax = cl[0], ay = cl[1], az = cl[2], bx = cl[3], by = cl[4], bz = cl[5], cx = cl[6], cy = cl[7], cz = cl[8];
+    double m[9];
+    for (int k = 0; k < 9; ++k) m[k] = cl[k];
+    bool p0 = true, p1 = true, p2 = true;
+    if (PBC) {
+        p0 = pbc[3 * b] != 0, p1 = pbc[3 * b + 1] != 0, p2 = pbc[3 * b + 2] != 0;
+        const int n_per = (int)p0 + (int)p1 + (int)p2;
+        if (n_per == 2) {   // the open row: the unit normal of the two periodic ones (cyclic order keeps the handedness)
+            const int o = !p0 ? 0 : (!p1 ? 1 : 2);
+            const double* u = m + 3 * ((o + 1) % 3);
+            const double* v = m + 3 * ((o + 2) % 3);
+            unit_cross(u[0], u[1], u[2], v[0], v[1], v[2], m[3 * o], m[3 * o + 1], m[3 * o + 2]);
+        } else if (n_per == 1) {
+            const int k = p0 ? 0 : (p1 ? 1 : 2);
+            complete_two(m + 3 * k, m + 3 * ((k + 1) % 3), m + 3 * ((k + 2) % 3));
+        } else if (n_per == 0) {
+            for (int k = 0; k < 9; ++k) m[k] = (k % 4 == 0) ? 1.0 : 0.0;
+        }
+    }
+    const double ax = m[0], ay = m[1], az = m[2], bx = m[3], by = m[4], bz = m[5], cx = m[6], cy = m[7], cz = m[8];
     // inv = [b x c, c x a, a x b] (as columns) / det
     const double c0x = by * cz - bz * cy, c0y = bz * cx - bx * cz, c0z = bx * cy - by * cx;
     const double c1x = cy * az - cz * ay, c1y = cz * ax - cx * az, c1z = cx * ay - cy * ax;
     const double c2x = ay * bz - az * by, c2y = az * bx - ax * bz, c2z = ax * by - ay * bx;
     const double det = (ax * c0x + ay * c0y) + az * c0z;
+    if (PBC) {
+        // |det| of the completed cell is the volume / area / length of the periodic sub-lattice: the periodic vectors
+        // are dependent (or not finite) when it vanishes.  Such a crystal is searched as if open, so that the image
+        // loops stay bounded; the host raises from the flag, which rides on the builder's one read-back.
+        const bool bad = (p0 || p1 || p2) && !(fabs(det) > MATTEN_SINGULAR_CELL);
+        if (threadIdx.x == 0) {
+            singular[b] = bad;
+            if (bad) atomicAdd((unsigned long long*)n_singular, 1ull);
+        }
+        if (bad) p0 = p1 = p2 = false;
+    }
     const double i00 = c0x / det, i10 = c0y / det, i20 = c0z / det;   // column 0
     const double i01 = c1x / det, i11 = c1y / det, i21 = c1z / det;
     const double i02 = c2x / det, i12 = c2y / det, i22 = c2z / det;
     if (threadIdx.x < 9) cell_f32[9 * b + threadIdx.x] = (float)cl[threadIdx.x];
     if (threadIdx.x == 0) {
-        bound[3 * b] = r_cut * sqrt((i00 * i00 + i10 * i10) + i20 * i20);
-        bound[3 * b + 1] = r_cut * sqrt((i01 * i01 + i11 * i11) + i21 * i21);
-        bound[3 * b + 2] = r_cut * sqrt((i02 * i02 + i12 * i12) + i22 * i22);
+        bound[3 * b] = p0 ? r_cut * sqrt((i00 * i00 + i10 * i10) + i20 * i20) : 0.0;
+        bound[3 * b + 1] = p1 ? r_cut * sqrt((i01 * i01 + i11 * i11) + i21 * i21) : 0.0;
+        bound[3 * b + 2] = p2 ? r_cut * sqrt((i02 * i02 + i12 * i12) + i22 * i22) : 0.0;
     }
     const int64_t lo = ptr[b], hi = ptr[b + 1];
     for (int64_t n = lo + threadIdx.x; n < hi; n += blockDim.x) {
         const double x = pos[3 * n], y = pos[3 * n + 1], z = pos[3 * n + 2];
-        frac[3 * n] = (x * i00 + y * i10) + z * i20;
-        frac[3 * n + 1] = (x * i01 + y * i11) + z * i21;
-        frac[3 * n + 2] = (x * i02 + y * i12) + z * i22;
+        frac[3 * n] = p0 ? (x * i00 + y * i10) + z * i20 : 0.0;
+        frac[3 * n + 1] = p1 ? (x * i01 + y * i11) + z * i21 : 0.0;
+        frac[3 * n + 2] = p2 ? (x * i02 + y * i12) + z * i22 : 0.0;
         pos_f32[3 * n] = (float)x, pos_f32[3 * n + 1] = (float)y, pos_f32[3 * n + 2] = (float)z;
         batch[n] = b;
     }
@@ -73,6 +142,38 @@ __device__ __forceinline__ void shift_range(double bound, double df, int& lo, in
     const double slack = 1e-6 * (1.0 + fabs(df) + bound);
     lo = (int)ceil(-bound - df - slack);
     hi = (int)floor(bound - df + slack);
+}
+
+// The distance test of the search, shared by the pair and the rows kernels so that their decisions cannot diverge: walks
+// the shifts [x0,x1] x [y0,y1] x [z0,z1] of one ordered pair in lexicographic order, calls emit(sx, sy, sz) for every
+// edge and returns their number.  `self`: i == j, whose zero shift is no edge.
+template <class Emit>
+__device__ __forceinline__ int pair_walk(const double* __restrict__ cl, int x0, int x1, int y0, int y1, int z0, int z1,
+                                         const double* pi, const double* pj, double r_cut, bool self, Emit&& emit) {
+    const double r2 = r_cut * r_cut;
+    const double r2_in = r2 * (1.0 - 1e-15), r2_out = r2 * (1.0 + 1e-15);
+    int cnt = 0;
+    for (int sx = x0; sx <= x1; ++sx)
+        for (int sy = y0; sy <= y1; ++sy) {
+            // T = S @ cell : ((sx*c0 + sy*c1) + sz*c2) per component, as the host builder's matmul
+            const double ax = (double)sx * cl[0] + (double)sy * cl[3];
+            const double ay = (double)sx * cl[1] + (double)sy * cl[4];
+            const double az = (double)sx * cl[2] + (double)sy * cl[5];
+            for (int sz = z0; sz <= z1; ++sz) {
+                const double tx = ax + (double)sz * cl[6];
+                const double ty = ay + (double)sz * cl[7];
+                const double tz = az + (double)sz * cl[8];
+                const double dx = (pj[0] + tx) - pi[0], dy = (pj[1] + ty) - pi[1], dz = (pj[2] + tz) - pi[2];
+                const double d2 = (dx * dx + dy * dy) + dz * dz;
+                bool hit = d2 < r2_in;
+                if (!hit && d2 <= r2_out) hit = sqrt(d2) < r_cut;  // the reference's test, needed only at the boundary
+                if (hit && !(self && sx == 0 && sy == 0 && sz == 0)) {
+                    emit(sx, sy, sz);
+                    ++cnt;
+                }
+            }
+        }
+    return cnt;
 }
 
 struct CsrOut {                // optional outputs of the fill pass: the destination-sorted view (all or none)
@@ -102,10 +203,8 @@ __global__ __launch_bounds__(256) void neighbor_kernel(Cry c, double r_cut, int3
     shift_range(c.bound[3 * b], c.frac[3 * j] - c.frac[3 * i], x0, x1);
     shift_range(c.bound[3 * b + 1], c.frac[3 * j + 1] - c.frac[3 * i + 1], y0, y1);
     shift_range(c.bound[3 * b + 2], c.frac[3 * j + 2] - c.frac[3 * i + 2], z0, z1);
-    const double pix = c.pos[3 * i], piy = c.pos[3 * i + 1], piz = c.pos[3 * i + 2];
-    const double pjx = c.pos[3 * j], pjy = c.pos[3 * j + 1], pjz = c.pos[3 * j + 2];
-    const double r2 = r_cut * r_cut;
-    const double r2_in = r2 * (1.0 - 1e-15), r2_out = r2 * (1.0 + 1e-15);
+    const double pi[3] = {c.pos[3 * i], c.pos[3 * i + 1], c.pos[3 * i + 2]};
+    const double pj[3] = {c.pos[3 * j], c.pos[3 * j + 1], c.pos[3 * j + 2]};
     int64_t out = FILL ? offsets[pair] : 0;
     if (FILL && num_neigh && j == lo) num_neigh[i] = (float)(offsets[pair + n] - offsets[pair]);   // atom i's n pairs
     const int64_t pair_t = c.pair_ptr[b] + (j - lo) * n + (i - lo);   // the same pair numbered j-major
@@ -115,39 +214,21 @@ __global__ __launch_bounds__(256) void neighbor_kernel(Cry c, double r_cut, int3
         if (i == lo) csr.rowptr[j] = (int32_t)out_t;
         if (pair == 0) csr.rowptr[csr.n_atoms] = (int32_t)n_edges;
     }
-    int cnt = 0;
-    for (int sx = x0; sx <= x1; ++sx)
-        for (int sy = y0; sy <= y1; ++sy) {
-            // T = S @ cell : ((sx*c0 + sy*c1) + sz*c2) per component, as the host builder's matmul
-            const double ax = (double)sx * cl[0] + (double)sy * cl[3];
-            const double ay = (double)sx * cl[1] + (double)sy * cl[4];
-            const double az = (double)sx * cl[2] + (double)sy * cl[5];
-            for (int sz = z0; sz <= z1; ++sz) {
-                const double tx = ax + (double)sz * cl[6];
-                const double ty = ay + (double)sz * cl[7];
-                const double tz = az + (double)sz * cl[8];
-                const double dx = (pjx + tx) - pix, dy = (pjy + ty) - piy, dz = (pjz + tz) - piz;
-                const double d2 = (dx * dx + dy * dy) + dz * dz;
-                bool hit = d2 < r2_in;
-                if (!hit && d2 <= r2_out) hit = sqrt(d2) < r_cut;  // the reference's test, needed only at the boundary
-                if (hit && !(i == j && sx == 0 && sy == 0 && sz == 0)) {
-                    if (FILL) {
-                        edge_index[out] = i;
-                        edge_index[n_edges + out] = j;
-                        shifts[3 * out] = (float)sx;
-                        shifts[3 * out + 1] = (float)sy;
-                        shifts[3 * out + 2] = (float)sz;
-                        if (csr.rowptr) {
-                            csr.perm[out_t] = (int32_t)out;
-                            csr.src_sorted[out_t] = (int32_t)i;
-                            ++out_t;
-                        }
-                        ++out;
-                    }
-                    ++cnt;
-                }
+    const int cnt = pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [&](int sx, int sy, int sz) {
+        if (FILL) {
+            edge_index[out] = i;
+            edge_index[n_edges + out] = j;
+            shifts[3 * out] = (float)sx;
+            shifts[3 * out + 1] = (float)sy;
+            shifts[3 * out + 2] = (float)sz;
+            if (csr.rowptr) {
+                csr.perm[out_t] = (int32_t)out;
+                csr.src_sorted[out_t] = (int32_t)i;
+                ++out_t;
             }
+            ++out;
         }
+    });
     if (!FILL) {
         counts[pair] = cnt;
         if (counts_t) counts_t[pair_t] = cnt;
@@ -174,6 +255,72 @@ __global__ __launch_bounds__(256) void neighbor_summary_kernel(const int64_t* __
     }
 }
 
+// ---- rows route: one wave per centre atom (header comment) ----
+struct Rows {
+    const double* pos;      // [N,3]
+    const double* cell;     // [B,9]
+    const int64_t* ptr;     // [B+1]
+    const int64_t* batch;   // [N] crystal of each atom (matten_graph_prep)
+    const double* frac;     // [N,3]
+    const double* bound;    // [B,3]
+    int64_t n_atoms;
+};
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void neighbor_rows_kernel(Rows c, double r_cut, int32_t* __restrict__ counts,
+                                                            const int64_t* __restrict__ offsets,
+                                                            int64_t* __restrict__ edge_index, int64_t n_edges,
+                                                            float* __restrict__ shifts, float* __restrict__ num_neigh) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // wave-uniform
+    if (i >= c.n_atoms) return;
+    const int64_t b = c.batch[i];
+    const int64_t lo = c.ptr[b], hi = c.ptr[b + 1];
+    const double* cl = c.cell + 9 * b;
+    const double bx = c.bound[3 * b], by = c.bound[3 * b + 1], bz = c.bound[3 * b + 2];
+    const double fi[3] = {c.frac[3 * i], c.frac[3 * i + 1], c.frac[3 * i + 2]};
+    const double pi[3] = {c.pos[3 * i], c.pos[3 * i + 1], c.pos[3 * i + 2]};
+    int64_t base = FILL ? offsets[i] : 0;   // first edge of atom i; advanced chunk by chunk
+    if (FILL && num_neigh && lane == 0) num_neigh[i] = (float)(offsets[i + 1] - offsets[i]);
+    int total = 0;
+    for (int64_t j0 = lo; j0 < hi; j0 += 64) {   // every lane stays in the loop: the prefix sum below needs all 64
+        const int64_t j = j0 + lane;
+        const bool live = j < hi;
+        int x0 = 0, x1 = -1, y0 = 0, y1 = -1, z0 = 0, z1 = -1;   // empty ranges for the lanes past the last atom
+        double pj[3] = {0.0, 0.0, 0.0};
+        if (live) {
+            shift_range(bx, c.frac[3 * j] - fi[0], x0, x1);
+            shift_range(by, c.frac[3 * j + 1] - fi[1], y0, y1);
+            shift_range(bz, c.frac[3 * j + 2] - fi[2], z0, z1);
+            pj[0] = c.pos[3 * j], pj[1] = c.pos[3 * j + 1], pj[2] = c.pos[3 * j + 2];
+        }
+        const int cnt = pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [](int, int, int) {});
+        if (!FILL) {
+            total += cnt;
+            continue;
+        }
+        int incl = cnt;   // inclusive prefix sum of the lane counts across the wave
+        for (int off = 1; off < 64; off <<= 1) {
+            const int v = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += v;
+        }
+        int64_t out = base + (incl - cnt);
+        pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [&](int sx, int sy, int sz) {
+            edge_index[out] = i;
+            edge_index[n_edges + out] = j;
+            shifts[3 * out] = (float)sx;
+            shifts[3 * out + 1] = (float)sy;
+            shifts[3 * out + 2] = (float)sz;
+            ++out;
+        });
+        base += __shfl(incl, 63, 64);
+    }
+    if (!FILL) {
+        for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
+        if (lane == 0) counts[i] = total;
+    }
+}
+
 }  // namespace
 
 extern "C" int matten_graph_prep(const double* pos, const double* cell, const int64_t* ptr, int64_t n_crystals,
@@ -183,7 +330,23 @@ extern "C" int matten_graph_prep(const double* pos, const double* cell, const in
     if (n_crystals < 0 || !(r_cut > 0.0) || n_crystals >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
     if (n_crystals == 0) return MATTEN_OK;
     if (!pos || !cell || !ptr || !frac || !bound || !batch || !pos_f32 || !cell_f32) return MATTEN_EINVAL;
-    graph_prep_kernel<<<(unsigned)n_crystals, 64, 0, stream>>>(pos, cell, ptr, r_cut, frac, bound, batch, pos_f32, cell_f32);
+    graph_prep_kernel<false><<<(unsigned)n_crystals, 64, 0, stream>>>(pos, cell, ptr, r_cut, frac, bound, batch, pos_f32,
+                                                                      cell_f32, nullptr, nullptr, nullptr);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_graph_prep_pbc(const double* pos, const double* cell, const int64_t* ptr, const uint8_t* pbc,
+                                     int64_t n_crystals, double r_cut, double* frac, double* bound, int64_t* batch,
+                                     float* pos_f32, float* cell_f32, int32_t* singular, int64_t* n_singular,
+                                     matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_crystals < 0 || !(r_cut > 0.0) || n_crystals >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
+    if (n_crystals == 0) return MATTEN_OK;
+    if (!pos || !cell || !ptr || !pbc || !frac || !bound || !batch || !pos_f32 || !cell_f32 || !singular || !n_singular)
+        return MATTEN_EINVAL;
+    graph_prep_kernel<true><<<(unsigned)n_crystals, 64, 0, stream>>>(pos, cell, ptr, r_cut, frac, bound, batch, pos_f32,
+                                                                     cell_f32, pbc, singular, n_singular);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }
@@ -230,6 +393,41 @@ extern "C" int matten_neighbor_fill(const double* pos, const double* cell, const
     dim3 grid((unsigned)matten_cdiv(max_atoms * max_atoms, 256), (unsigned)n_crystals);
     neighbor_kernel<true><<<grid, 256, 0, stream>>>(c, r_cut, nullptr, nullptr, offsets, edge_index, n_edges, edge_cell_shift,
                                                     num_neigh, csr);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+static int rows_args_ok(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch, const double* frac,
+                        const double* bound, double r_cut, int64_t n_atoms) {
+    if (n_atoms < 0 || !(r_cut > 0.0) || n_atoms >= ((int64_t)1 << 32)) return 0;
+    return n_atoms == 0 || (pos && cell && ptr && batch && frac && bound);
+}
+
+extern "C" int matten_neighbor_rows_count(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                                          const double* frac, const double* bound, double r_cut, int64_t n_atoms,
+                                          int32_t* counts, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!rows_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms)) return MATTEN_EINVAL;
+    if (n_atoms == 0) return MATTEN_OK;
+    if (!counts) return MATTEN_EINVAL;
+    Rows c{pos, cell, ptr, batch, frac, bound, n_atoms};
+    neighbor_rows_kernel<false><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, counts, nullptr, nullptr, 0,
+                                                                                     nullptr, nullptr);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_neighbor_rows_fill(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                                         const double* frac, const double* bound, double r_cut, int64_t n_atoms,
+                                         const int64_t* offsets, int64_t n_edges, int64_t* edge_index,
+                                         float* edge_cell_shift, float* num_neigh, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!rows_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms) || n_edges < 0) return MATTEN_EINVAL;
+    if (n_atoms == 0) return MATTEN_OK;
+    if (!offsets || (n_edges > 0 && (!edge_index || !edge_cell_shift))) return MATTEN_EINVAL;
+    Rows c{pos, cell, ptr, batch, frac, bound, n_atoms};
+    neighbor_rows_kernel<true><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, nullptr, offsets, edge_index,
+                                                                                    n_edges, edge_cell_shift, num_neigh);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }

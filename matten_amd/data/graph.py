@@ -6,13 +6,16 @@ Contract kept from the reference (data/data.py:285-413, which delegates to ASE):
     periodic in x, y, z, minus the true self edges (i == j and S == 0)
   * edge_index[0] = i (centre), edge_index[1] = j (neighbour); edge_cell_shift = S as float
   * num_neigh = bincount(i); cell rows are lattice vectors
+  * ``pbc`` (a bool or one per axis, as the reference hands it to ASE): an open axis generates no image, S_k = 0 there;
+    its cell row may be zero (``cell=None``: a molecule) and, when it is not, stays in ``cell`` without any effect on
+    the edges.  Atoms are never wrapped.
 ASE leaves the order within a centre atom unspecified; here edges come out in the canonical
 lexicographic order (i, j, Sx, Sy, Sz).
 
 ``collate`` lays a list of crystals out as the flat struct-of-arrays batch that PyG's
 ``Batch.from_data_list`` + ``tensor_property_to_dict`` (data/data.py:146-159) would produce.
 """
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import os
 
@@ -31,14 +34,88 @@ def image_reach(pos: np.ndarray, cell: np.ndarray, r_cut: float) -> np.ndarray:
     return np.ceil(float(r_cut) / plane_dist + span).astype(int)
 
 
-def neighbor_list(pos: np.ndarray, cell: np.ndarray, r_cut: float):
+SINGULAR_CELL = 1e-12   # smallest volume / area / length of the periodic sub-lattice that counts as independent vectors
+
+
+def normalize_pbc(pbc) -> Tuple[bool, bool, bool]:
+    """a bool or three bools -> three bools (what ASE does with the reference's ``pbc`` argument)"""
+    if isinstance(pbc, (bool, np.bool_)):
+        return (bool(pbc),) * 3
+    flags = tuple(bool(p) for p in np.asarray(pbc).reshape(-1))
+    if len(flags) != 3:
+        raise ValueError(f"pbc must be a bool or three bools, got {pbc!r}")
+    return flags
+
+
+def complete_cell(cell: np.ndarray, pbc) -> np.ndarray:
+    """The cell the image bounds are derived from: every open-axis row replaced by a unit vector orthogonal to the
+    periodic rows (``ase.geometry.complete_cell`` for the rows a molecule, wire or slab leaves zero; a non-zero row on
+    an open axis generates no image, so it is treated as absent too and can never make the cell singular).  It serves
+    the inverse and nothing else: the column of the inverse that belongs to a periodic axis lies in the span of the
+    periodic rows whatever the completion, and the open axes get no fractional coordinate or bound at all."""
+    pbc = normalize_pbc(pbc)
+    cell = np.array(cell, dtype=np.float64).reshape(3, 3)
+    per = [k for k in range(3) if pbc[k]]
+    if len(per) == 3:
+        return cell
+    if len(per) == 0:
+        return np.eye(3)
+    with np.errstate(all="ignore"):
+        if len(per) == 2:
+            o = 3 - per[0] - per[1]
+            n = np.cross(cell[(o + 1) % 3], cell[(o + 2) % 3])
+            cell[o] = n / np.linalg.norm(n)
+        else:
+            k = per[0]
+            e = np.zeros(3)
+            e[int(np.argmin(np.abs(cell[k])))] = 1.0
+            u = np.cross(cell[k], e)
+            u = u / np.linalg.norm(u)
+            v = np.cross(cell[k], u)
+            cell[(k + 1) % 3], cell[(k + 2) % 3] = u, v / np.linalg.norm(v)
+    return cell
+
+
+def periodic_volume(cell: np.ndarray, pbc: np.ndarray) -> np.ndarray:
+    """cell [B,3,3], pbc [B,3] -> [B]: volume (three periodic axes: |det|), area (two) or length (one) spanned by the
+    periodic vectors, 1 for an open structure.  > SINGULAR_CELL <=> the periodic vectors are linearly independent: the
+    validity test of the packers and of the device prologue (|det| of the completed cell is this number)."""
+    cell = np.asarray(cell, dtype=np.float64).reshape(-1, 3, 3)
+    pbc = np.asarray(pbc, dtype=bool).reshape(-1, 3)
+    n_per = pbc.sum(1)
+    with np.errstate(all="ignore"):
+        out = np.abs(np.linalg.det(cell))
+        for b in np.nonzero(n_per < 3)[0]:
+            rows = cell[b][pbc[b]]
+            out[b] = (1.0 if len(rows) == 0 else np.linalg.norm(rows[0]) if len(rows) == 1
+                      else np.linalg.norm(np.cross(rows[0], rows[1])))
+    return out
+
+
+def image_reach_pbc(pos: np.ndarray, cell: np.ndarray, r_cut: float, pbc) -> np.ndarray:
+    """``image_reach`` with open axes: 0 images there; on the periodic axes the bound of the completed cell."""
+    pbc = normalize_pbc(pbc)
+    if all(pbc):
+        return image_reach(pos, cell, r_cut)
+    if not any(pbc):
+        return np.zeros(3, dtype=int)
+    if not periodic_volume(cell, pbc)[0] > SINGULAR_CELL:   # (also catches NaN)
+        raise ValueError(f"zero or linearly dependent lattice vectors on the periodic axes (pbc={pbc})")
+    reach = image_reach(pos, complete_cell(cell, pbc), r_cut)
+    reach[~np.asarray(pbc)] = 0
+    return reach
+
+
+def neighbor_list(pos: np.ndarray, cell: np.ndarray, r_cut: float, pbc=True):
     """-> edge_index [2,E] int64, shifts [E,3] int64 (canonical order).  Host builder (scipy KD-tree); the
-    production path for batches is ``batch_graphs_gpu`` below, which emits the identical list on the device."""
+    production path for batches is ``batch_graphs_gpu`` below, which emits the identical list on the device.
+    ``pbc``: see the module docstring; ``cell`` may be None (or hold zero rows) only where no image is generated."""
     pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
-    cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    pbc = normalize_pbc(pbc)
+    cell = np.zeros((3, 3)) if cell is None else np.asarray(cell, dtype=np.float64).reshape(3, 3)
     n = pos.shape[0]
     rc = float(r_cut)
-    reach = image_reach(pos, cell, rc)
+    reach = image_reach(pos, cell, rc) if all(pbc) else image_reach_pbc(pos, cell, rc, pbc)
 
     # candidate images: every lattice shift in the reach box; a KD-tree over the image atoms prunes
     # the pair search, the strict fp64 test below decides (same expression as the brute-force form)
@@ -62,11 +139,12 @@ def neighbor_list(pos: np.ndarray, cell: np.ndarray, r_cut: float):
 
 
 def crystal_graph(pos, cell, atomic_numbers, r_cut: float, y: Optional[Dict[str, torch.Tensor]] = None,
-                  **extra) -> Dict[str, torch.Tensor]:
-    """One crystal as the tensors a reference ``Crystal`` data point carries (data/data.py:134-144)."""
+                  pbc=True, **extra) -> Dict[str, torch.Tensor]:
+    """One crystal as the tensors a reference ``Crystal`` data point carries (data/data.py:134-144).  ``cell`` is
+    returned as given (zeros for None), like the reference's ``Crystal.from_points``: never the completed cell."""
     pos = np.asarray(pos, dtype=np.float64)
-    cell = np.asarray(cell, dtype=np.float64)
-    edge_index, shifts = neighbor_list(pos, cell, r_cut)
+    cell = np.zeros((3, 3)) if cell is None else np.asarray(cell, dtype=np.float64)
+    edge_index, shifts = neighbor_list(pos, cell, r_cut, pbc)
     g = {
         "pos": torch.as_tensor(pos, dtype=torch.float32),
         "edge_index": torch.as_tensor(edge_index),
@@ -118,30 +196,59 @@ class EdgelessStructures(ValueError):
         self.indices = list(indices)
 
 
+class SingularCells(ValueError):
+    """Some crystals of a batch have zero or linearly dependent lattice vectors on their periodic axes."""
+
+    def __init__(self, indices):
+        super().__init__(f"zero or linearly dependent lattice vectors on the periodic axes (structures {list(indices)}).")
+        self.indices = list(indices)
+
+
+def rows_min_atoms() -> int:
+    """Size of the largest structure of a batch from which the device builder takes the pair-free search
+    (matten_neighbor_rows_count / _fill) instead of the per-pair one.  The pair kernels keep 24 bytes per ordered atom
+    pair and launch max_atoms^2 threads for EVERY crystal of the batch: 0.15 GB at 2000 atoms, 0.6 GB at 4000, 2.4 GB at 8000 (measured); the rows
+    kernels walk every pair three times (count, recount, emit) with O(N) scratch.  Measured
+    (docs/LAB_NOTES.md, tools/pbc_graph_bench.py): the rows build is level with the pair build at 1000 atoms (where the CSR
+    the pair route emits still saves the forward its own build), 0.07-0.10 ms faster at 2000, 2.5x faster at 8000, and a
+    batch of 200 fcc-64 crystals with ONE 2000-atom cluster builds in 0.32 instead of 1.69 ms.  Existing inputs (64 atoms
+    at most) stay far below.  Read per call, so MATTEN_NEIGHBOR_ROWS_MIN_ATOMS=1 / a huge value force either route (tests, tools/pbc_graph_bench.py)."""
+    return int(os.environ.get("MATTEN_NEIGHBOR_ROWS_MIN_ATOMS", "2048"))
+
+
 def batch_graphs_gpu(structures: Sequence, r_cut: float, device="cuda", y: Optional[Dict[str, torch.Tensor]] = None,
                      ) -> Dict[str, torch.Tensor]:
     """Crystals -> collated batch, with the neighbour search on the GPU (matten_neighbor_count/_fill).
 
-    ``structures`` is a sequence of (pos [n,3], cell [3,3], atomic_numbers [n]) triples; they are packed into the
-    flat struct-of-arrays form of ``batch_graphs_gpu_soa``, which callers that already hold their crystals as
-    arrays should use directly (no per-structure Python work)."""
+    ``structures`` is a sequence of (pos [n,3], cell [3,3], atomic_numbers [n]) triples or (pos, cell, atomic_numbers,
+    pbc) items (cell may be None where no axis is periodic); they are packed into the flat struct-of-arrays form of
+    ``batch_graphs_gpu_soa``, which callers that already hold their crystals as arrays should use directly (no
+    per-structure Python work)."""
     sizes = np.array([len(s[0]) for s in structures], dtype=np.int64)
     ptr = np.zeros(len(structures) + 1, dtype=np.int64)
     np.cumsum(sizes, out=ptr[1:])
     pos = np.concatenate([np.asarray(s[0], dtype=np.float64).reshape(-1, 3) for s in structures])
-    cell = np.stack([np.asarray(s[1], dtype=np.float64).reshape(3, 3) for s in structures])
+    cell = np.stack([np.zeros((3, 3)) if s[1] is None else np.asarray(s[1], dtype=np.float64).reshape(3, 3)
+                     for s in structures])
     Z = np.concatenate([np.asarray(s[2], dtype=np.int64).reshape(-1) for s in structures])
-    return batch_graphs_gpu_soa(pos, cell, Z, ptr, r_cut, device, y)
+    pbc = None
+    if any(len(s) > 3 for s in structures):
+        pbc = np.array([normalize_pbc(s[3]) if len(s) > 3 else (True, True, True) for s in structures], dtype=bool)
+    return batch_graphs_gpu_soa(pos, cell, Z, ptr, r_cut, device, y, pbc=pbc)
 
 
 def batch_graphs_gpu_soa(pos: np.ndarray, cell: np.ndarray, Z: np.ndarray, ptr: np.ndarray, r_cut: float,
-                         device="cuda", y: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                         device="cuda", y: Optional[Dict[str, torch.Tensor]] = None, *, pbc=None) -> Dict[str, torch.Tensor]:
     """Flat batch (pos [N,3] fp64, cell [B,3,3] fp64, Z [N] int64, ptr [B+1] int64) ->
     collated graph batch on the device.
 
     The result has exactly the keys, dtypes and edge order of ``collate([crystal_graph(...) ...], device)``; only
     positions, cells and species cross PCIe (fp64 for the distance test, as in the host builder).  A crystal without
-    any edge raises ``EdgelessStructures`` (a ValueError, like the reference data/data.py:398-402)."""
+    any edge raises ``EdgelessStructures`` (a ValueError, like the reference data/data.py:398-402).
+
+    ``pbc``: [B,3] bools (None: every axis of every crystal periodic); a crystal whose periodic vectors are linearly
+    dependent raises ``SingularCells``.  A batch whose largest structure has ``rows_min_atoms()`` atoms or more is
+    searched without per-pair bookkeeping and carries no CSR keys (the forward builds the CSR itself)."""
     from .. import ops
 
     pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
@@ -150,17 +257,26 @@ def batch_graphs_gpu_soa(pos: np.ndarray, cell: np.ndarray, Z: np.ndarray, ptr: 
     ptr = np.ascontiguousarray(ptr, dtype=np.int64)
     sizes = np.diff(ptr)
     n_crystals = len(sizes)
+    if pbc is not None:
+        pbc = np.ascontiguousarray(pbc, dtype=bool).reshape(-1, 3)
+        if len(pbc) != n_crystals:
+            raise ValueError(f"pbc holds {len(pbc)} rows for {n_crystals} structures")
+        if pbc.all():
+            pbc = None   # fully periodic: the prologue and the kernels of every batch before pbc existed
     if n_crystals > _MAX_CRYSTALS_PER_LAUNCH:  # blockIdx.y of the neighbour kernels: build in slabs and concatenate
         parts = []
         for lo in range(0, n_crystals, _MAX_CRYSTALS_PER_LAUNCH):
             hi = min(n_crystals, lo + _MAX_CRYSTALS_PER_LAUNCH)
             a, b = ptr[lo], ptr[hi]
             try:
-                parts.append(batch_graphs_gpu_soa(pos[a:b], cell[lo:hi], Z[a:b], ptr[lo : hi + 1] - a, r_cut, device))
+                parts.append(batch_graphs_gpu_soa(pos[a:b], cell[lo:hi], Z[a:b], ptr[lo : hi + 1] - a, r_cut, device,
+                                                  pbc=None if pbc is None else pbc[lo:hi]))
                 for k in [k for k in parts[-1] if k.startswith("_amd_")]:
                     del parts[-1][k]   # a slab's own CSR does not concatenate: the forward builds the whole batch's
             except EdgelessStructures as e:
                 raise EdgelessStructures([lo + k for k in e.indices]) from None
+            except SingularCells as e:
+                raise SingularCells([lo + k for k in e.indices]) from None
         out, node_off, cry_off = {}, 0, 0
         for p in parts:
             p["edge_index"] = p["edge_index"] + node_off
@@ -181,20 +297,55 @@ def batch_graphs_gpu_soa(pos: np.ndarray, cell: np.ndarray, Z: np.ndarray, ptr: 
     # read-back sizes the outputs.  (The first device builder did this prologue with ~45 small library launches: 0.5 ms
     # of host time per call, and bounded the image loops per crystal instead of per pair.)
     n_atoms = int(ptr[-1])
-    pair_ptr = np.zeros(n_crystals + 1, dtype=np.int64)
-    np.cumsum(sizes * sizes, out=pair_ptr[1:])
-    n_pairs = int(pair_ptr[-1])
     dev = torch.device(device)
     pos_d = torch.from_numpy(pos).to(dev)
     cell_d = torch.from_numpy(cell.reshape(-1, 9)).to(dev)
-    ptrs_d = torch.from_numpy(np.stack([ptr, pair_ptr])).to(dev)
-    ptr_d, pair_ptr_d = ptrs_d[0], ptrs_d[1]
-    frac_d, bound_d, batch_d, pos32, cell32 = ops.graph_prep(pos_d, cell_d, ptr_d, r_cut)
-    edge_index, shifts, num_neigh, pair_off, min_edges, csr = ops.neighbor_list(
-        pos_d, cell_d, ptr_d, frac_d, bound_d, pair_ptr_d, r_cut, int(sizes.max()), n_pairs)
-    if min_edges == 0:   # (came back with the edge count: no second sync on the common path)
-        per_crystal = pair_off[pair_ptr_d[1:]] - pair_off[pair_ptr_d[:-1]]
-        raise EdgelessStructures(torch.nonzero(per_crystal == 0).flatten().tolist())
+    rows = n_crystals > 0 and int(sizes.max()) >= rows_min_atoms()
+    if pbc is None and not rows:   # the common path: crystals of ordinary size
+        pair_ptr = np.zeros(n_crystals + 1, dtype=np.int64)
+        np.cumsum(sizes * sizes, out=pair_ptr[1:])
+        n_pairs = int(pair_ptr[-1])
+        ptrs_d = torch.from_numpy(np.stack([ptr, pair_ptr])).to(dev)
+        ptr_d, pair_ptr_d = ptrs_d[0], ptrs_d[1]
+        frac_d, bound_d, batch_d, pos32, cell32 = ops.graph_prep(pos_d, cell_d, ptr_d, r_cut)
+        edge_index, shifts, num_neigh, pair_off, min_edges, csr = ops.neighbor_list(
+            pos_d, cell_d, ptr_d, frac_d, bound_d, pair_ptr_d, r_cut, int(sizes.max()), n_pairs)
+        if min_edges == 0:   # (came back with the edge count: no second sync on the common path)
+            per_crystal = pair_off[pair_ptr_d[1:]] - pair_off[pair_ptr_d[:-1]]
+            raise EdgelessStructures(torch.nonzero(per_crystal == 0).flatten().tolist())
+    else:
+        # open axes and / or large structures.  The read-back is three numbers here: the prologue's count of singular
+        # cells travels with the edge count and the smallest edge count of a crystal.
+        summary = torch.zeros(3, dtype=torch.int64, device=dev)
+        singular = None
+        if rows:
+            ptr_d = torch.from_numpy(ptr).to(dev)
+        else:
+            pair_ptr = np.zeros(n_crystals + 1, dtype=np.int64)
+            np.cumsum(sizes * sizes, out=pair_ptr[1:])
+            ptrs_d = torch.from_numpy(np.stack([ptr, pair_ptr])).to(dev)
+            ptr_d, pair_ptr_d = ptrs_d[0], ptrs_d[1]
+        if pbc is None:
+            frac_d, bound_d, batch_d, pos32, cell32 = ops.graph_prep(pos_d, cell_d, ptr_d, r_cut)
+        else:
+            pbc_d = torch.from_numpy(pbc.astype(np.uint8)).to(dev)
+            frac_d, bound_d, batch_d, pos32, cell32, singular = ops.graph_prep_pbc(pos_d, cell_d, ptr_d, pbc_d, r_cut,
+                                                                                   summary[2:])
+        if rows:
+            csr = None
+            edge_index, shifts, num_neigh, first, min_edges, host = ops.neighbor_list_rows(
+                pos_d, cell_d, ptr_d, batch_d, frac_d, bound_d, r_cut, summary)
+            seg = ptr_d
+        else:
+            edge_index, shifts, num_neigh, first, min_edges, csr, host = ops.neighbor_list_flagged(
+                pos_d, cell_d, ptr_d, frac_d, bound_d, pair_ptr_d, r_cut, int(sizes.max()), int(pair_ptr[-1]),
+                summary=summary)
+            seg = pair_ptr_d
+        if host[2]:
+            raise SingularCells(torch.nonzero(singular).flatten().tolist())
+        if min_edges == 0:
+            per_crystal = first[seg[1:]] - first[seg[:-1]]
+            raise EdgelessStructures(torch.nonzero(per_crystal == 0).flatten().tolist())
     out = {
         "pos": pos32,
         "edge_index": edge_index,

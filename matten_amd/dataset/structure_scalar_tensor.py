@@ -55,6 +55,7 @@ class TensorDataModule:
         reuse: bool = True,
         loader_kwargs: Optional[Dict[str, Any]] = None,
         device=None,
+        pbc=None,
         **unsupported,
     ):
         bad = {k: v for k, v in unsupported.items() if v not in (None, False, [], {})
@@ -69,6 +70,7 @@ class TensorDataModule:
         self.tensor_target_formula, self.tensor_target_scale = tensor_target_formula, float(tensor_target_scale)
         self.loader_kwargs = dict(loader_kwargs or {})
         self.device = device
+        self.pbc = pbc   # a bool or one per axis, applied to every structure; None: each record's own (Molecule: open)
         self._data: Dict[str, List[Dict[str, torch.Tensor]]] = {}
 
     # Lightning's DataModule protocol
@@ -87,7 +89,8 @@ class TensorDataModule:
                 if self.tensor_target_format == "irreps":   # reference dataset/structure_scalar_tensor.py:262-267
                     t = converter.from_cartesian(t)
                 y[self.tensor_target_name] = t.to(torch.float32).unsqueeze(0)
-            graphs.append(crystal_graph(r["cart_coords"], r["lattice"], r["atomic_numbers"], self.r_cut, y=y))
+            pbc = self.pbc if self.pbc is not None else r.get("pbc", "lattice" in r)
+            graphs.append(crystal_graph(r["cart_coords"], r.get("lattice"), r["atomic_numbers"], self.r_cut, y=y, pbc=pbc))
         return graphs
 
     def setup(self, stage: Optional[str] = None):

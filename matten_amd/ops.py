@@ -1130,13 +1130,22 @@ def graph_prep(pos64, cell64, ptr, r_cut: float):
 
 
 def neighbor_list(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: float, max_atoms: int, n_pairs: int, want_csr: bool = True):
+    """see neighbor_list_flagged, which this is without the prologue's flags: -> its first six results"""
+    return neighbor_list_flagged(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut, max_atoms, n_pairs, want_csr)[:6]
+
+
+def neighbor_list_flagged(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: float, max_atoms: int, n_pairs: int,
+                          want_csr: bool = True, summary: torch.Tensor = None):
     """Periodic neighbour list of a batch of crystals, canonical (i, j, Sx, Sy, Sz) order.
     frac / bound: ops.graph_prep; pair_ptr[B+1] = running sum of n_b^2 (ordered pairs numbered crystal by crystal,
     i-major), n_pairs = pair_ptr[B].
     -> (edge_index [2,E] i64 (global ids), edge_cell_shift [E,3] f32, num_neigh [N] f32 (edges per centre atom),
         pair_offsets [n_pairs+1] i64, smallest edge count of a crystal: an int, read back together with the edge count,
         csr = (perm [E] i32, rowptr [N+1] i32, src_sorted [E] i32) -- the destination-sorted view ops.csr_build would derive
-        from edge_index, bit for bit -- or None)"""
+        from edge_index, bit for bit -- or None)
+    summary (optional): an int64 tensor of more than two elements whose first two receive the read-back; the others
+    (flags of the prologue, e.g. graph_prep_pbc's n_singular) cross in the same copy.  The read-back as a host list is
+    the seventh result, always (as in neighbor_list_rows)."""
     lib = _lib.load()
     pos64 = _need(pos64, torch.float64, "pos")
     cell64 = _need(cell64, torch.float64, "cell")
@@ -1161,13 +1170,16 @@ def neighbor_list(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: float, max_a
     offsets = scan[: n_pairs + 1]
     # the one host sync of graph construction: the edge count sizes the outputs; the smallest edge count of a crystal
     # (0: the caller has to find and report the edgeless ones) rides on the same read-back
+    extra = summary is not None
     if n_pairs:
-        summary = torch.empty(2, dtype=torch.int64, device=dev)
+        if not extra:
+            summary = torch.empty(2, dtype=torch.int64, device=dev)
         _lib.check(lib.matten_neighbor_summary(_ptr(offsets), _ptr(pair_ptr), B, _ptr(summary), _stream()),
                    "matten_neighbor_summary")
-        E, min_edges = summary.tolist()
+        host = summary.tolist()
+        E, min_edges = host[0], host[1]
     else:
-        E, min_edges = 0, 0
+        E, min_edges, host = 0, 0, [0] * (len(summary) if extra else 2)
     edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
     shifts = torch.empty(E, 3, dtype=torch.float32, device=dev)
     num_neigh = torch.empty(N, dtype=torch.float32, device=dev)
@@ -1184,4 +1196,66 @@ def neighbor_list(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: float, max_a
                                      _ptr(csr[2]) if csr else None, _ptr(csr[0]) if csr else None, _stream()),
             "matten_neighbor_fill",
         )
-    return edge_index, shifts, num_neigh, offsets, int(min_edges), csr
+    return edge_index, shifts, num_neigh, offsets, int(min_edges), csr, host
+
+
+def graph_prep_pbc(pos64, cell64, ptr, pbc, r_cut: float, n_singular: torch.Tensor):
+    """graph_prep for open / partly periodic crystals (include/matten_hip.h matten_graph_prep_pbc): pbc [B,3] uint8.
+    -> graph_prep's five outputs + singular [B] i32 (1: the periodic vectors of that crystal are linearly dependent).
+    n_singular: a zeroed int64 element that receives the number of such crystals (the caller reads it back with the
+    edge count: see neighbor_list(summary=))."""
+    lib = _lib.load()
+    pos64 = _need(pos64, torch.float64, "pos")
+    cell64 = _need(cell64, torch.float64, "cell")
+    ptr = _need(ptr, torch.int64, "ptr")
+    pbc = _need(pbc, torch.uint8, "pbc")
+    N, B, dev = pos64.shape[0], ptr.shape[0] - 1, pos64.device
+    if pbc.numel() != 3 * B or n_singular.dtype != torch.int64 or n_singular.numel() != 1:
+        raise ValueError("pbc must hold [B,3] flags, n_singular one int64")
+    frac = torch.empty(N, 3, dtype=torch.float64, device=dev)
+    bound = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    batch = torch.empty(N, dtype=torch.int64, device=dev)
+    pos32 = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    cell32 = torch.empty(3 * B, 3, dtype=torch.float32, device=dev)
+    singular = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.matten_graph_prep_pbc(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(pbc), B, float(r_cut), _ptr(frac),
+                                         _ptr(bound), _ptr(batch), _ptr(pos32), _ptr(cell32), _ptr(singular),
+                                         n_singular.data_ptr(), _stream()), "matten_graph_prep_pbc")
+    return frac, bound, batch, pos32, cell32, singular
+
+
+def neighbor_list_rows(pos64, cell64, ptr, batch, frac, bound, r_cut: float, summary: torch.Tensor = None):
+    """The same list as neighbor_list without per-pair bookkeeping (matten_neighbor_rows_count / _fill: one wave per
+    centre atom, O(N) scratch): for large structures.  batch / frac / bound: ops.graph_prep.
+    -> (edge_index [2,E] i64, edge_cell_shift [E,3] f32, num_neigh [N] f32, offsets [N+1] i64 (first edge of each centre
+        atom), smallest edge count of a crystal, summary [3] i64 on the host).  No CSR on this route (ops.csr_build)."""
+    lib = _lib.load()
+    pos64 = _need(pos64, torch.float64, "pos")
+    cell64 = _need(cell64, torch.float64, "cell")
+    ptr = _need(ptr, torch.int64, "ptr")
+    batch = _need(batch, torch.int64, "batch")
+    frac = _need(frac, torch.float64, "frac")
+    bound = _need(bound, torch.float64, "bound")
+    B, N, dev = ptr.shape[0] - 1, pos64.shape[0], pos64.device
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    with _timed("neighbor_rows_count"):
+        _lib.check(lib.matten_neighbor_rows_count(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound),
+                                                  float(r_cut), N, _ptr(counts), _stream()), "matten_neighbor_rows_count")
+    offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    if summary is None:
+        summary = torch.zeros(3, dtype=torch.int64, device=dev)
+    if N:   # crystals are runs of atoms, as they are runs of pairs on the other route: ptr takes pair_ptr's place
+        _lib.check(lib.matten_neighbor_summary(_ptr(offsets), _ptr(ptr), B, _ptr(summary), _stream()), "matten_neighbor_summary")
+        host = summary.tolist()   # the one host sync of graph construction
+    else:
+        host = [0, 0, 0]
+    E, min_edges = host[0], host[1]
+    edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
+    shifts = torch.empty(E, 3, dtype=torch.float32, device=dev)
+    num_neigh = torch.empty(N, dtype=torch.float32, device=dev)
+    with _timed("neighbor_rows_fill"):
+        _lib.check(lib.matten_neighbor_rows_fill(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound),
+                                                 float(r_cut), N, _ptr(offsets), E, _ptr(edge_index), _ptr(shifts),
+                                                 _ptr(num_neigh), _stream()), "matten_neighbor_rows_fill")
+    return edge_index, shifts, num_neigh, offsets, int(min_edges), host

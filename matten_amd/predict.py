@@ -9,6 +9,11 @@ model was not trained on.  Differences, all forced by the environment: structure
 ``is_elasticity_tensor`` is set the result is wrapped in ``ElasticTensor`` exactly like the reference,
 otherwise a ``numpy [3,3,3,3]`` array is returned -- and the checkpoint is a plain ``torch.save`` of
 {"state_dict", "hyper_parameters"} or a Lightning ``.ckpt`` with the same two keys.
+
+Boundary conditions: a dict may carry ``"pbc"`` (a bool or one per axis); a dict without ``"lattice"`` or an object
+without ``.lattice`` (a pymatgen ``Molecule``: ``.cart_coords`` / ``.atomic_numbers``) is an open structure; an object
+with ``.lattice`` is fully periodic whatever ``lattice.pbc`` says, which is what the reference's ``from_pymatgen`` does.
+``predict(..., pbc=...)`` overrides every structure.
 """
 import warnings
 from pathlib import Path
@@ -17,7 +22,8 @@ from typing import Any, Dict, List, Sequence, Union
 import numpy as np
 import torch
 
-from .data.graph import EdgelessStructures, batch_graphs_gpu, collate, crystal_graph, image_reach
+from .data.graph import (SINGULAR_CELL, EdgelessStructures, SingularCells, batch_graphs_gpu, collate, crystal_graph,
+                         image_reach, image_reach_pbc, normalize_pbc, periodic_volume)
 from .model_factory.tfn_atomic_tensor import AtomicTensorModel
 from .model_factory.tfn_scalar_tensor import ScalarTensorModel
 from .parallel import sharded_apply
@@ -62,12 +68,29 @@ def get_pretrained_model(identifier: str, checkpoint: str = "model_final.ckpt", 
     return model.to(device).eval()
 
 
-def _fields(s) -> Dict[str, np.ndarray]:
+_OPEN, _PERIODIC = (False, False, False), (True, True, True)
+
+
+def _raw_fields(s, pbc=None):
+    """-> (cart_coords, lattice or None, atomic_numbers, pbc as three bools) of a dict or a pymatgen-like object (module
+    docstring); ``pbc`` overrides the structure's own flags"""
     if isinstance(s, dict):
-        return {"lattice": np.asarray(s["lattice"]), "cart_coords": np.asarray(s["cart_coords"]),
-                "atomic_numbers": np.asarray(s["atomic_numbers"])}
-    return {"lattice": np.asarray(s.lattice.matrix), "cart_coords": np.asarray(s.cart_coords),
-            "atomic_numbers": np.asarray(s.atomic_numbers)}
+        lattice = s.get("lattice")
+        own = s["pbc"] if "pbc" in s else (lattice is not None)
+        p, z = s["cart_coords"], s["atomic_numbers"]
+    else:
+        lattice = getattr(s, "lattice", None)
+        own = lattice is not None
+        if lattice is not None:
+            lattice = lattice.matrix
+        p, z = s.cart_coords, s.atomic_numbers
+    return p, lattice, z, normalize_pbc(own if pbc is None else pbc)
+
+
+def _fields(s, pbc=None) -> Dict[str, np.ndarray]:
+    p, lattice, z, flags = _raw_fields(s, pbc)
+    return {"lattice": np.zeros((3, 3)) if lattice is None else np.asarray(lattice), "cart_coords": np.asarray(p),
+            "atomic_numbers": np.asarray(z), "pbc": flags}
 
 
 def check_species(model, structures: Sequence, Z=None, ptr=None, index=None):
@@ -94,13 +117,16 @@ def check_species(model, structures: Sequence, Z=None, ptr=None, index=None):
 
 def _pack_fast(structures: Sequence):
     """pack_structures for the common case -- every structure a dict whose three fields already are well-formed numpy arrays
-    ([n, 3] float64 coordinates, [3, 3] float64 lattice, [n] integer species, n > 0, everything finite, cell not singular) --
+    ([n, 3] float64 coordinates, [3, 3] float64 lattice, [n] integer species, n > 0, everything finite, cell not singular,
+    every axis periodic: no "pbc" key) --
     without a per-structure Python body: three list comprehensions, three concatenations and vectorised checks (0.4 instead
     of 2.1 ms per 1000 fcc-64 structures).  Anything else -> None, and the per-structure path decides and warns."""
     try:
         ps = [s["cart_coords"] for s in structures]
-        cs = [s["lattice"] for s in structures]
+        cs = [s["lattice"] for s in structures]     # (an open structure without a lattice leaves through the KeyError)
         zs = [s["atomic_numbers"] for s in structures]
+        if any("pbc" in s for s in structures):
+            return None
         if not ps or not all(type(p) is np.ndarray and p.ndim == 2 for p in ps):
             return None
         pos, cell, Z = np.concatenate(ps), np.concatenate(cs), np.concatenate(zs)
@@ -121,23 +147,28 @@ def _pack_fast(structures: Sequence):
         return None
 
 
-def pack_structures(structures: Sequence, first: int = 0):
+def pack_structures(structures: Sequence, first: int = 0, with_pbc: bool = False, pbc=None):
     """One pass over the structures -> flat struct-of-arrays batch (pos [N,3] f64, cell [B,3,3] f64, Z [N] i64,
     ptr [B+1]) of the usable ones, plus the indices that cannot be used (same role as the per-structure try/except of
     the reference dataset, dataset/structure_scalar_tensor.py:296-362): malformed arrays, no atoms, non-finite
-    numbers, singular cell.  Everything after the attribute access is vectorised."""
-    fast = _pack_fast(structures)
+    numbers, linearly dependent (or zero) lattice vectors on the periodic axes.  Everything after the attribute access
+    is vectorised.
+
+    Open and partly periodic structures (module docstring) are kept, with zeros for a missing lattice.  The result
+    stays the 6-tuple (pos, cell, Z, ptr, keep, failed); ``with_pbc=True`` appends the flags of the kept structures,
+    [B,3] bools or None when every axis of every one is periodic -- what ``batch_graphs_gpu_soa(pbc=)`` takes.
+    ``pbc`` (a bool or three) overrides the structures' own flags."""
+    override = None if pbc is None else normalize_pbc(pbc)
+    fast = _pack_fast(structures) if override in (None, _PERIODIC) else None
     if fast is not None:
-        return fast
-    pos_l, cell_l, z_l, keep, failed = [], [], [], [], []
+        return fast + (None,) if with_pbc else fast
+    pos_l, cell_l, z_l, pbc_l, keep, failed = [], [], [], [], [], []
     asarray, f64, i64 = np.asarray, np.float64, np.int64
+    zero_cell = np.zeros((3, 3))
     for i, s in enumerate(structures):
         try:
-            if isinstance(s, dict):
-                p, c, z = s["cart_coords"], s["lattice"], s["atomic_numbers"]
-            else:
-                p, c, z = s.cart_coords, s.lattice.matrix, s.atomic_numbers
-            p, c, z = asarray(p, dtype=f64), asarray(c, dtype=f64), asarray(z, dtype=i64)
+            p, c, z, flags = _raw_fields(s, override)
+            p, c, z = asarray(p, dtype=f64), zero_cell if c is None else asarray(c, dtype=f64), asarray(z, dtype=i64)
             if p.ndim != 2 or p.shape[1] != 3:
                 p = p.reshape(-1, 3)
             if c.shape != (3, 3):
@@ -150,7 +181,7 @@ def pack_structures(structures: Sequence, first: int = 0):
             warnings.warn(f"Failed converting structure {first + i}, Skip it. {e}")
             failed.append(i)
             continue
-        pos_l.append(p); cell_l.append(c); z_l.append(z); keep.append(i)
+        pos_l.append(p); cell_l.append(c); z_l.append(z); pbc_l.append(flags); keep.append(i)
     if not keep:
         raise RuntimeError("Cannot successfully convert any structures.")
 
@@ -161,8 +192,10 @@ def pack_structures(structures: Sequence, first: int = 0):
         return np.concatenate(pos_l), np.stack(cell_l), np.concatenate(z_l), ptr
 
     pos, cell, Z, ptr = flat(pos_l, cell_l, z_l)
+    flags = np.array(pbc_l, dtype=bool).reshape(-1, 3)
     with np.errstate(all="ignore"):
-        ok = np.isfinite(cell).all(axis=(1, 2)) & (np.abs(np.linalg.det(cell)) > 1e-12)
+        # periodic vectors linearly independent (three periodic axes: |det| > 1e-12, the test of every earlier version)
+        ok = np.isfinite(cell).all(axis=(1, 2)) & (periodic_volume(cell, flags) > SINGULAR_CELL)
         ok &= np.logical_and.reduceat(np.isfinite(pos).all(axis=1), ptr[:-1])
     if not ok.all():
         for k in np.nonzero(~ok)[0]:
@@ -173,7 +206,9 @@ def pack_structures(structures: Sequence, first: int = 0):
             raise RuntimeError("Cannot successfully convert any structures.")
         keep = [keep[k] for k in sel]
         pos, cell, Z, ptr = flat([pos_l[k] for k in sel], [cell_l[k] for k in sel], [z_l[k] for k in sel])
-    return pos, cell, Z, ptr, keep, sorted(failed)
+        flags = flags[sel]
+    out = (pos, cell, Z, ptr, keep, sorted(failed))
+    return out + (None if flags.all() else flags,) if with_pbc else out
 
 
 _SIDE_STREAMS: Dict[Any, Any] = {}
@@ -256,18 +291,21 @@ class _deferred_input_checks:
 
 def evaluate_soa(model, pos, cell, Z, ptr, r_cut: float, batch_size: int = 200,
                  tensor_target_name: str = "elastic_tensor_full", tensor_target_formula: str = "ijkl=jikl=klij",
-                 node_budget: int = None):
-    """Batched forward straight from the flat arrays of ``pack_structures``.  Graphs are built on the device batch
+                 node_budget: int = None, *, pbc=None):
+    """Batched forward straight from the flat arrays of ``pack_structures`` (``pbc``: the [B,3] flags its
+    ``with_pbc=True`` appends; None: every axis periodic).  Graphs are built on the device batch
     by batch on a SECOND stream: the neighbour search of batch k+1 (and its one host sync, the edge count) overlaps
     the forward of batch k, which runs on the caller's stream.
-    -> (Cartesian tensors [B, 3, ...] on the host as one array, indices of crystals without any edge)."""
+    -> (Cartesian tensors [B, 3, ...] on the host as one array, indices of the crystals no graph could be built of: no
+    edge inside the cutoff, or linearly dependent periodic vectors; their rows are NaN)."""
     model.eval()
     with _deferred_input_checks(model):
         return _soa_end(model, _soa_begin(model, pos, cell, Z, ptr, r_cut, batch_size, tensor_target_name,
-                                          tensor_target_formula, node_budget))
+                                          tensor_target_formula, node_budget, pbc))
 
 
-def _soa_begin(model, pos, cell, Z, ptr, r_cut, batch_size, tensor_target_name, tensor_target_formula, node_budget=None):
+def _soa_begin(model, pos, cell, Z, ptr, r_cut, batch_size, tensor_target_name, tensor_target_formula, node_budget=None,
+               pbc=None):
     """enqueue every forward of the packed structures (inside _deferred_input_checks) -> (device tensors [B, 3, ...],
     indices of crystals without any edge); nothing here waits for the forwards"""
     from .data.graph import batch_graphs_gpu_soa
@@ -295,8 +333,10 @@ def _soa_begin(model, pos, cell, Z, ptr, r_cut, batch_size, tensor_target_name, 
         with torch.cuda.stream(side):
             while len(ids):
                 try:
-                    return ids, batch_graphs_gpu_soa(*slice_of(ids), r_cut, device)
-                except EdgelessStructures as e:
+                    return ids, batch_graphs_gpu_soa(*slice_of(ids), r_cut, device, pbc=None if pbc is None else pbc[ids])
+                except (EdgelessStructures, SingularCells) as e:
+                    # (SingularCells: a cell at the packer's threshold that the device's own arithmetic puts below it, or
+                    # arrays that did not come from pack_structures: no graph either, reported the same way)
                     edgeless.extend(int(ids[k]) for k in e.indices)
                     ids = np.delete(ids, e.indices)
         return ids, None
@@ -347,26 +387,29 @@ def _evaluate_soa_loop(model, chunks, build, main, side, out, edgeless, converte
             nxt = build(chunks[k + 1]) if k + 1 < len(chunks) else None  # overlaps the forward just enqueued
 
 
-def build_graphs(structures: Sequence, r_cut: float, on_gpu: bool = False):
+def build_graphs(structures: Sequence, r_cut: float, on_gpu: bool = False, pbc=None):
     """-> (graphs, failed indices): per-structure try/except like the reference dataset
     (dataset/structure_scalar_tensor.py:296-362).
 
-    ``on_gpu``: only validate on the host and return (pos, cell, Z) triples; the neighbour search then runs on
-    the device, batch by batch, inside ``evaluate`` (crystals that turn out to have no edge come back as NaN
-    rows and are reported as failed by ``predict``)."""
+    ``on_gpu``: only validate on the host and return (pos, cell, Z) triples -- (pos, cell, Z, pbc) for a structure
+    with an open axis; the neighbour search then runs on the device, batch by batch, inside ``evaluate`` (crystals
+    that turn out to have no edge come back as NaN rows and are reported as failed by ``predict``).
+    ``pbc`` overrides the structures' own boundary conditions (module docstring)."""
     graphs, failed = [], []
     for i, s in enumerate(structures):
         try:
-            f = _fields(s)
+            f = _fields(s, pbc)
             if on_gpu:
                 pos = np.asarray(f["cart_coords"], dtype=np.float64).reshape(-1, 3)
                 cell = np.asarray(f["lattice"], dtype=np.float64).reshape(3, 3)
                 Z = np.asarray(f["atomic_numbers"], dtype=np.int64).reshape(-1)
-                if len(pos) == 0 or len(pos) != len(Z) or not np.all(np.isfinite(image_reach(pos, cell, r_cut))):
+                if len(pos) == 0 or len(pos) != len(Z) or not np.all(np.isfinite(image_reach_pbc(pos, cell, r_cut, f["pbc"]))):
                     raise ValueError("malformed structure")
-                graphs.append((pos, cell, Z))
+                if not all(f["pbc"]) and not (np.all(np.isfinite(pos)) and np.all(np.isfinite(cell))):
+                    raise ValueError("malformed structure")   # (an open axis has no reach that would go non-finite)
+                graphs.append((pos, cell, Z) if all(f["pbc"]) else (pos, cell, Z, f["pbc"]))
                 continue
-            graphs.append(crystal_graph(f["cart_coords"], f["lattice"], f["atomic_numbers"], r_cut))
+            graphs.append(crystal_graph(f["cart_coords"], f["lattice"], f["atomic_numbers"], r_cut, pbc=f["pbc"]))
         except Exception as e:  # noqa: BLE001
             warnings.warn(f"Failed converting structure {i}, Skip it. {e}")
             failed.append(i)
@@ -455,19 +498,20 @@ PREDICT_SLAB = int(__import__("os").environ.get("MATTEN_PREDICT_SLAB", "1024")) 
 # structures, 5.1-5.3 either way at 4000 -- inside the run-to-run spread, not kept)
 
 
-def _predict_slabs(model, structures, r_cut, batch_size, tensor_target_name, tensor_target_formula, node_budget=None):
+def _predict_slabs(model, structures, r_cut, batch_size, tensor_target_name, tensor_target_formula, node_budget=None,
+                   pbc=None):
     """-> (predictions of the usable structures in input order, sorted indices of the failed ones)"""
     n = len(structures)
     budget = effective_node_budget(batch_size, node_budget)
 
     def pack(lo, hi):
         try:
-            pos, cell, Z, ptr, keep, failed = pack_structures(structures[lo:hi], first=lo)
+            pos, cell, Z, ptr, keep, failed, flags = pack_structures(structures[lo:hi], first=lo, with_pbc=True, pbc=pbc)
         except RuntimeError:                       # not one usable structure in this slab (each one was warned about)
             return None, list(range(lo, hi))
         keep = [lo + k for k in keep]
         check_species(model, structures, Z, ptr, keep)   # (raises like the reference, naming the structure's own index)
-        return (pos, cell, Z, ptr, keep), [lo + k for k in failed]
+        return (pos, cell, Z, ptr, keep, flags), [lo + k for k in failed]
 
     failed, inflight = [], []
     model.eval()
@@ -479,9 +523,9 @@ def _predict_slabs(model, structures, r_cut, batch_size, tensor_target_name, ten
             failed += bad
             lo = min(n, lo + size)
             if cur is not None:
-                pos, cell, Z, ptr, keep = cur
+                pos, cell, Z, ptr, keep, flags = cur
                 inflight.append((keep, _soa_begin(model, pos, cell, Z, ptr, r_cut, batch_size, tensor_target_name,
-                                                  tensor_target_formula, node_budget)))
+                                                  tensor_target_formula, node_budget, flags)))
                 # a slab should fill a forward: ~NODE_BUDGET atoms (1024 fcc-64 crystals, ~14 000 of the reference's
                 # 4.7-atom ones), between PREDICT_SLAB and 16 PREDICT_SLAB structures
                 per = max(1.0, len(pos) / max(1, len(keep)))
@@ -492,7 +536,7 @@ def _predict_slabs(model, structures, r_cut, batch_size, tensor_target_name, ten
             tensors, edgeless = _soa_end(model, handle)
             for j in edgeless:
                 warnings.warn(f"Failed converting structure {keep[j]}, Skip it. After eliminating self edges, no edges "
-                              "remain in this system.")
+                              "remain in this system (or its periodic lattice vectors are linearly dependent).")
             dropped = set(edgeless)
             failed += [keep[j] for j in edgeless]
             predictions += [tensors[j] for j in range(len(keep)) if j not in dropped]
@@ -510,6 +554,7 @@ def predict(
     model: ScalarTensorModel = None,
     config: Dict[str, Any] = None,
     node_budget: int = None,
+    pbc=None,
 ):
     """See the module docstring.  ``model`` / ``config`` let a caller reuse an already loaded model.
     ``batch_size`` (reference predict.py:155) is the memory knob it is there: consecutive batches are merged into one forward
@@ -535,7 +580,7 @@ def predict(
         # one tensor per atom; the reference returns them as one flat list over all structures and never unwraps a
         # single structure (predict.py:210-242).  A structure whose graph cannot be built fails the whole call
         # here: with per-atom outputs the reference's "None at the failed index" bookkeeping has no meaning.
-        graphs, failed = build_graphs(structures, r_cut=r_cut, on_gpu=True)
+        graphs, failed = build_graphs(structures, r_cut=r_cut, on_gpu=True, pbc=pbc)
         if failed:
             raise RuntimeError(f"Cannot build the graph of structures {failed}.")
         preds = evaluate_atomic(model, graphs, batch_size=batch_size,
@@ -546,7 +591,7 @@ def predict(
     # device runs the forwards of slab k the host packs slab k + 1 (a 1000-structure slab packs in 2-3 ms, its forwards
     # take 4-5 ms: the host work of all slabs but the first disappears behind the device)
     predictions, failed = _predict_slabs(model, structures, r_cut, batch_size, config["data"]["tensor_target_name"],
-                                         config["data"]["tensor_target_formula"], node_budget)
+                                         config["data"]["tensor_target_formula"], node_budget, pbc)
     if not predictions:
         raise RuntimeError("Cannot successfully convert any structures.")
     if is_elasticity_tensor:
