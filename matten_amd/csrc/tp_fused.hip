@@ -53,7 +53,8 @@ struct StoreAgg {
                                           float a_scale_inv, int node, int j, int u, bool valid) const {
         if (TPF_LAB_NO_STORE ? (valid && acc[0] == 12345.678f) : valid) {
             const float nn = a.avg_nn > 0.0f ? a.avg_nn : a.num_neigh[node];
-            const float norm = a_scale_inv / sqrtf(nn);
+            // num_neigh = 0 (per-node normalisation, nothing arrives): the empty sum stays 0, not 0 x 1/sqrt(0) = NaN
+            const float norm = nn > 0.0f ? a_scale_inv / sqrtf(nn) : 0.0f;
             float* orow = a.agg + (int64_t)node * a.d_mid;
             const bool merged = (ge.kind & KIND_MERGED) != 0;          // wave-uniform
             const GroupEntry& g2 = (&ge)[merged ? 1 : 0];

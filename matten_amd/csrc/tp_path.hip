@@ -75,7 +75,8 @@ __device__ __forceinline__ void run_path(const Args& a, const PathEntry& pe, int
     }
     if (valid) {
         const float nn = a.avg_nn > 0.0f ? a.avg_nn : a.num_neigh[node];
-        const float norm = 1.0f / sqrtf(nn);
+        // num_neigh = 0 (per-node normalisation, nothing arrives): the empty sum stays 0, not 0 x 1/sqrt(0) = NaN
+        const float norm = nn > 0.0f ? 1.0f / sqrtf(nn) : 0.0f;
         float* op = a.agg + (int64_t)node * a.d_mid + pe.out_off + u * D3;
 #pragma unroll
         for (int k = 0; k < D3; ++k) op[k] = acc[k] * norm;
