@@ -391,6 +391,33 @@ int64_t matten_species_linear_wgrad_scratch_floats(int64_t n_rows, int64_t n_spe
 int matten_dense_rows(const float* x, int64_t n_in, const float* q, int64_t n_out, int64_t n_rows, float* out,
                       matten_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Derived elastic properties (predict.py:217-218: `predictions = [ElasticTensor(t) for t in predictions]` -- what the
+ * reference's users read off pymatgen's ElasticTensor, one Python object per crystal there).  fp64 arithmetic.
+ * Voigt order xx, yy, zz, yz, xz, xy; C_IJ = C_ijkl without factors, S = inverse of that 6x6 matrix (engineering
+ * convention: the factors 2 and 4 live in S).  Values are in the units of the input (pymatgen's y_mod alone is
+ * multiplied by 1e9; not here).
+ * matten_elastic_props: one crystal per thread.
+ *   c: fp32 (is_fp64 = 0) or fp64 (1); layout 0 = Cartesian [n,81] (= [n,3,3,3,3]), 1 = Voigt [n,36].  The input is
+ *   symmetrised first: the mean of the 8 Cartesian entries equivalent under ij<->ji, kl<->lk, (ij)<->(kl), or (C + C^T)/2.
+ *   voigt [n,36], compliance [n,36] (Gauss-Jordan with partial pivoting: indefinite tensors are inverted too),
+ *   props [n,10] = k_voigt, g_voigt, k_reuss, g_reuss, k_vrh, g_vrh, y_mod (9KG/(3K+G) of the VRH means),
+ *   homogeneous_poisson, universal_anisotropy (5 g_voigt/g_reuss + k_voigt/k_reuss - 6), pugh_ratio (k_vrh/g_vrh);
+ *   flags [n] int32: bit 0 = singular or non-finite input, every output of the row is NaN; bit 1 = not positive definite
+ *   (un-pivoted LDL^T; the values are still computed; also set on every row with bit 0).
+ * matten_elastic_directional: one workgroup per crystal over unit directions dirs [n_dirs,3] (fp64, n_dirs >= 1).  With
+ *   v(n) = (n1^2, n2^2, n3^2, n2 n3, n1 n3, n1 n2): Young's modulus E(n) = 1 / (v^T S v), linear compressibility
+ *   beta(n) = sum_I (S_I1 + S_I2 + S_I3) v_I, S = the mean of the two triangles of compliance [n,36].
+ *   young / beta [n,n_dirs]: optional, NULL = not written.  ext [n,4] = E_min, E_max, beta_min, beta_max; arg [n,4] int32 =
+ *   their direction indices, equal values resolved to the lowest index (bitwise reproducible).  Rows with flag bit 0: NaN
+ *   and -1.
+ * ------------------------------------------------------------------------------------------ */
+int matten_elastic_props(const void* c, int is_fp64, int layout, int64_t n, double* voigt, double* compliance,
+                         double* props, int32_t* flags, matten_stream_t stream);
+int matten_elastic_directional(const double* compliance, const int32_t* flags, const double* dirs, int64_t n,
+                               int64_t n_dirs, double* young, double* beta, double* ext, int32_t* arg,
+                               matten_stream_t stream);
+
 
 /* ==========================================================================================
  * Adjoint (backward) operators for the training step (reference: autograd through

@@ -1,0 +1,212 @@
+"""
+Derived elastic properties of (predicted) elasticity tensors, on the device.
+
+The reference ends ``predict`` with ``predictions = [ElasticTensor(t) for t in predictions]`` (predict.py:217-218) and its
+users read bulk and shear moduli, Young's modulus, Poisson's ratio, the anisotropy index, the compliance tensor and
+directional moduli off that pymatgen object, one Python object per crystal.  Here two kernels
+(``matten_elastic_props`` / ``matten_elastic_directional``, csrc/elastic.hip) compute them for a whole batch in fp64.
+
+Conventions ("Derived elastic properties"): Voigt order xx, yy, zz, yz, xz, xy as in pymatgen;
+``C_IJ = C_ijkl`` without factors and ``compliance = inv(C_IJ)``, the engineering convention (the factors 2 and 4 live in
+the compliance); the input is symmetrised, never trusted.  Every value is in the units of the input tensor -- pymatgen's
+``y_mod`` alone is multiplied by 1e9 (GPa -> Pa); this module does not copy that.
+"""
+import numpy as np
+import torch
+
+from . import o3, ops
+
+PROP_NAMES = ("k_voigt", "g_voigt", "k_reuss", "g_reuss", "k_vrh", "g_vrh", "y_mod", "homogeneous_poisson",
+              "universal_anisotropy", "pugh_ratio")
+FLAG_SINGULAR, FLAG_NOT_POSITIVE_DEFINITE, FLAG_FAILED_STRUCTURE = 1, 2, 4
+
+# Voigt index -> Cartesian pair, pymatgen's order
+VOIGT_PAIRS = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
+
+class ElasticProperties:
+    """Batch of derived properties: ``voigt`` / ``compliance`` [B,6,6], one [B] tensor per name of ``PROP_NAMES``,
+    ``flags`` [B] int32 (bit 0 singular or non-finite input: the row is NaN; bit 1 not positive definite; bit 2 the
+    structure failed in ``predict``), ``is_stable`` / ``is_singular`` [B] bool.  With directions also ``directions`` [D,3],
+    ``young_min`` / ``young_max`` / ``compressibility_min`` / ``compressibility_max`` [B] with their ``*_argmin`` /
+    ``*_argmax`` direction indices (-1 on singular rows), and ``young`` / ``compressibility`` [B,D] when they were kept
+    (else None).  An unbatched input ([3,3,3,3] or [6,6]) gives the same without the leading dimension."""
+
+    def __init__(self, **fields):
+        self._names = tuple(fields)
+        for k, v in fields.items():
+            setattr(self, k, v)
+
+    @property
+    def has_directions(self) -> bool:
+        return "directions" in self._names
+
+    def _map(self, fn) -> "ElasticProperties":
+        return ElasticProperties(**{k: (None if getattr(self, k) is None else fn(getattr(self, k))) for k in self._names})
+
+    def cpu(self) -> "ElasticProperties":
+        return self._map(lambda t: t.cpu())
+
+    def to_dict(self) -> dict:
+        """name -> numpy array on the host (None for directional maps that were not kept)"""
+        return {k: (None if getattr(self, k) is None else getattr(self, k).cpu().numpy()) for k in self._names}
+
+    def __repr__(self):
+        shape = tuple(self.flags.shape)
+        return f"ElasticProperties(batch={shape}, directions={self.directions.shape[0] if self.has_directions else None})"
+
+
+def fibonacci_hemisphere(D: int) -> np.ndarray:
+    """D unit vectors [D,3] (fp64) spread evenly over the hemisphere z >= 0 by the golden-angle spiral: E(n) = E(-n), so
+    the other half adds nothing.  Deterministic."""
+    D = int(D)
+    if D < 1:
+        raise ValueError(f"directions: at least one direction is needed, got {D}")
+    k = np.arange(D, dtype=np.float64)
+    z = 1.0 - (k + 0.5) / D                         # equal-area rings, z in (0, 1)
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    n = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+    return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+
+def check_directions(directions) -> np.ndarray:
+    """int D -> ``fibonacci_hemisphere(D)``; an array [D,3] is validated on the host (finite, non-zero: else ValueError)
+    and normalised there -> [D,3] fp64 unit vectors"""
+    if isinstance(directions, (int, np.integer)) and not isinstance(directions, bool):
+        return fibonacci_hemisphere(int(directions))
+    if isinstance(directions, torch.Tensor):
+        directions = directions.detach().cpu().numpy()
+    n = np.array(directions, dtype=np.float64)
+    if n.ndim == 1 and n.shape[0] == 3:
+        n = n[None]
+    if n.ndim != 2 or n.shape[1] != 3 or n.shape[0] < 1:
+        raise ValueError(f"directions: expected an int or an array [D,3] with D >= 1, got shape {n.shape}")
+    if not np.isfinite(n).all():
+        raise ValueError("directions: non-finite component")
+    # (scaled by the largest component first: the norm of a tiny or huge but valid vector neither under- nor overflows)
+    big = np.abs(n).max(axis=1, keepdims=True)
+    if (big == 0.0).any():
+        raise ValueError(f"directions: zero vector at index {int(np.nonzero(big[:, 0] == 0.0)[0][0])}")
+    n = n / big
+    return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+
+_VOIGT_BASIS = {}
+
+
+def voigt_basis(formula: str = "ijkl=jikl=klij") -> np.ndarray:
+    """[21,36] fp64: the model's irreps components of a rank-4 elasticity tensor straight to the row-major Voigt matrix,
+    ``voigt.reshape(36) = x @ voigt_basis()`` -- the 36 Voigt columns of ``o3.cartesian_tensor_basis``'s [21,81]"""
+    if formula not in _VOIGT_BASIS:
+        _, Q = o3.cartesian_tensor_basis(formula)
+        if Q.ndim != 5:
+            raise ValueError(f"voigt_basis: {formula!r} is not a rank-4 tensor")
+        cols = [Q[:, i, j, k, l] for (i, j) in VOIGT_PAIRS for (k, l) in VOIGT_PAIRS]
+        V = np.ascontiguousarray(np.stack(cols, axis=1), dtype=np.float64)
+        V.setflags(write=False)
+        _VOIGT_BASIS[formula] = V
+    return _VOIGT_BASIS[formula]
+
+
+def _default_device() -> torch.device:
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _as_rows(tensors):
+    """-> (rows [B,81] or [B,36] on the device, layout, unbatched?, failed [B] bool on the host or None)"""
+    failed = None
+    if isinstance(tensors, (list, tuple)):
+        if not tensors:
+            raise ValueError("tensors: empty list")
+        missing = [t is None for t in tensors]
+        if all(missing):
+            raise ValueError("tensors: every entry is None")
+        if any(missing):      # what predict() returns for structures it could not use: NaN rows, flag bit 2
+            first = next(t for t in tensors if t is not None)
+            if isinstance(first, torch.Tensor):
+                hole = torch.full_like(first, float("nan"))
+            else:
+                first = np.asarray(first)
+                hole = np.full(first.shape, np.nan, dtype=first.dtype if first.dtype.kind == "f" else np.float64)
+            tensors = [hole if t is None else t for t in tensors]
+            failed = np.array(missing)
+        if isinstance(tensors[0], torch.Tensor):
+            tensors = torch.stack(list(tensors))
+        else:
+            tensors = np.stack([np.asarray(t) for t in tensors])
+    if not isinstance(tensors, torch.Tensor):
+        a = np.asarray(tensors)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        tensors = torch.from_numpy(np.ascontiguousarray(a))
+    if tensors.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"tensors: expected fp32 or fp64, got {tensors.dtype}")
+    shape = tuple(tensors.shape)
+    if shape[-4:] == (3, 3, 3, 3) and len(shape) in (4, 5):
+        layout, single, width = 0, len(shape) == 4, 81
+    elif shape[-2:] == (6, 6) and len(shape) in (2, 3):
+        layout, single, width = 1, len(shape) == 2, 36
+    else:
+        raise ValueError(f"tensors: expected [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], got {shape}")
+    rows = tensors.detach().reshape(-1, width)
+    if not rows.is_cuda:
+        rows = rows.to(_default_device())          # the one copy of a host input
+    return rows.contiguous(), layout, single, failed
+
+
+def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, failed=None) -> ElasticProperties:
+    """rows on the device -> ElasticProperties; ``dirs``: unit vectors out of ``check_directions`` (host) or None"""
+    voigt, compliance, props, flags = ops.elastic_props(rows, layout)
+    if failed is not None and failed.any():
+        flags |= torch.as_tensor(failed.astype(np.int32) * FLAG_FAILED_STRUCTURE, device=flags.device)
+    fields = {"voigt": voigt, "compliance": compliance}
+    for q, name in enumerate(PROP_NAMES):
+        fields[name] = props[:, q]
+    fields["flags"] = flags
+    fields["is_stable"] = flags == 0
+    fields["is_singular"] = (flags & FLAG_SINGULAR) != 0
+    if dirs is not None:
+        dirs = torch.from_numpy(np.ascontiguousarray(dirs)).to(rows.device)
+        young, beta, ext, arg = ops.elastic_directional(compliance, flags, dirs, keep=keep_directional)
+        fields.update(young=young, compressibility=beta,
+                      young_min=ext[:, 0], young_max=ext[:, 1], young_argmin=arg[:, 0], young_argmax=arg[:, 1],
+                      compressibility_min=ext[:, 2], compressibility_max=ext[:, 3],
+                      compressibility_argmin=arg[:, 2], compressibility_argmax=arg[:, 3], directions=dirs)
+    if single:
+        fields = {k: (v if v is None or k == "directions" else v[0]) for k, v in fields.items()}
+    return ElasticProperties(**fields)
+
+
+def elastic_properties(tensors, directions=None, keep_directional: bool = False) -> ElasticProperties:
+    """``tensors``: a torch tensor or numpy array [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], fp32 or fp64, on the device or
+    on the host (copied once), or a list of such tensors as ``predict`` returns (stacked; a ``None`` entry becomes a NaN
+    row with flag bit 2).  ``directions``: an int D (``fibonacci_hemisphere(D)``) or an array [D,3] (validated and
+    normalised on the host); with them the extremes of Young's modulus and of the linear compressibility over the
+    directions are returned, and the full [B,D] maps when ``keep_directional``.  The results stay on the device."""
+    dirs = None if directions is None else check_directions(directions)      # (before anything is uploaded)
+    rows, layout, single, failed = _as_rows(tensors)
+    return _from_rows(rows, layout, dirs, keep_directional, single, failed)
+
+
+_VOIGT_Q = {}
+
+
+def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = False,
+                                   formula: str = "ijkl=jikl=klij") -> ElasticProperties:
+    """The same from the model's irreps rows ``x`` [B,21] (fp32, on the device): one ``dense_rows`` with ``voigt_basis``
+    gives the Voigt matrices [B,36] directly -- no [B,81] Cartesian intermediate."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
+        raise ValueError("x: expected a tensor [B,21] or [21]")
+    dirs = None if directions is None else check_directions(directions)
+    single = x.dim() == 1
+    x = x.detach().reshape(-1, x.shape[-1])
+    V = voigt_basis(formula)
+    if x.shape[1] != V.shape[0]:
+        raise ValueError(f"x: expected {V.shape[0]} irreps components per row, got {x.shape[1]}")
+    if not x.is_cuda:
+        x = x.to(_default_device())
+    key = (formula, x.device)
+    if key not in _VOIGT_Q:
+        _VOIGT_Q[key] = torch.tensor(V, dtype=torch.float32, device=x.device)
+    rows = ops.dense_rows(x.to(torch.float32), _VOIGT_Q[key])
+    return _from_rows(rows, 1, dirs, keep_directional, single)

@@ -824,6 +824,46 @@ def dense_rows(x, q) -> torch.Tensor:
     return out
 
 
+def elastic_props(c, layout: int):
+    """c [B,81] (layout 0, Cartesian) or [B,36] (layout 1, Voigt), fp32 or fp64 -> (voigt [B,6,6], compliance [B,6,6],
+    props [B,10], flags [B] int32), all fp64 (include/matten_hip.h: matten_elastic_props)"""
+    lib = _lib.load()
+    if not isinstance(c, torch.Tensor) or c.dtype not in (torch.float32, torch.float64):
+        raise TypeError("c: expected an fp32 or fp64 tensor")
+    c = _need(c, c.dtype, "c")
+    if layout not in (0, 1) or c.dim() != 2 or c.shape[1] != (81, 36)[layout]:
+        raise ValueError(f"c: expected [B,{(81, 36)[layout] if layout in (0, 1) else '?'}] for layout {layout}, got {tuple(c.shape)}")
+    B = c.shape[0]
+    voigt = torch.empty(B, 6, 6, dtype=torch.float64, device=c.device)
+    compliance = torch.empty(B, 6, 6, dtype=torch.float64, device=c.device)
+    props = torch.empty(B, 10, dtype=torch.float64, device=c.device)
+    flags = torch.empty(B, dtype=torch.int32, device=c.device)
+    _lib.check(lib.matten_elastic_props(_ptr(c), int(c.dtype == torch.float64), layout, B, _ptr(voigt), _ptr(compliance),
+                                        _ptr(props), _ptr(flags), _stream()), "matten_elastic_props")
+    return voigt, compliance, props, flags
+
+
+def elastic_directional(compliance, flags, dirs, keep: bool = False):
+    """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64 -> (young [B,D] or None, beta [B,D] or
+    None, ext [B,4] = E_min, E_max, beta_min, beta_max, arg [B,4] int32) (matten_elastic_directional)"""
+    lib = _lib.load()
+    compliance = _need(compliance, torch.float64, "compliance")
+    flags = _need(flags, torch.int32, "flags")
+    dirs = _need(dirs, torch.float64, "dirs")
+    B = flags.shape[0]
+    if compliance.shape != (B, 6, 6) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
+        raise ValueError(f"expected compliance [B,6,6], flags [B], dirs [D>=1,3]; got {tuple(compliance.shape)}, "
+                         f"{tuple(flags.shape)}, {tuple(dirs.shape)}")
+    D = dirs.shape[0]
+    young = torch.empty(B, D, dtype=torch.float64, device=dirs.device) if keep else None
+    beta = torch.empty(B, D, dtype=torch.float64, device=dirs.device) if keep else None
+    ext = torch.empty(B, 4, dtype=torch.float64, device=dirs.device)
+    arg = torch.empty(B, 4, dtype=torch.int32, device=dirs.device)
+    _lib.check(lib.matten_elastic_directional(_ptr(compliance), _ptr(flags), _ptr(dirs), B, D, _ptr(young), _ptr(beta),
+                                              _ptr(ext), _ptr(arg), _stream()), "matten_elastic_directional")
+    return young, beta, ext, arg
+
+
 # ---------------------------------------------------------------------------------------------------
 # adjoint operators (training step)
 # ---------------------------------------------------------------------------------------------------

@@ -499,8 +499,10 @@ PREDICT_SLAB = int(__import__("os").environ.get("MATTEN_PREDICT_SLAB", "1024")) 
 
 
 def _predict_slabs(model, structures, r_cut, batch_size, tensor_target_name, tensor_target_formula, node_budget=None,
-                   pbc=None):
-    """-> (predictions of the usable structures in input order, sorted indices of the failed ones)"""
+                   pbc=None, device_rows=None):
+    """-> (predictions of the usable structures in input order, sorted indices of the failed ones)
+    ``device_rows`` (a list): receives one (structure indices, device tensors [len, 3, ...]) pair per slab -- the forwards'
+    own output buffers, NaN rows for crystals without a graph -- for a consumer that works on the device"""
     n = len(structures)
     budget = effective_node_budget(batch_size, node_budget)
 
@@ -534,6 +536,8 @@ def _predict_slabs(model, structures, r_cut, batch_size, tensor_target_name, ten
         predictions = []
         for keep, handle in inflight:
             tensors, edgeless = _soa_end(model, handle)
+            if device_rows is not None:
+                device_rows.append((keep, handle[0]))
             for j in edgeless:
                 warnings.warn(f"Failed converting structure {keep[j]}, Skip it. After eliminating self edges, no edges "
                               "remain in this system (or its periodic lattice vectors are linearly dependent).")
@@ -541,6 +545,23 @@ def _predict_slabs(model, structures, r_cut, batch_size, tensor_target_name, ten
             failed += [keep[j] for j in edgeless]
             predictions += [tensors[j] for j in range(len(keep)) if j not in dropped]
     return predictions, sorted(set(failed))
+
+
+def _properties_of_slabs(device_rows, n, failed, directions, single):
+    """ElasticProperties of all n input structures from the slabs' device tensors: they never come back from the host.
+    Structures without a prediction (``failed``) keep NaN rows and get flag bit 2."""
+    from .elastic import _from_rows
+
+    first = device_rows[0][1]
+    rows = torch.full((n, 81), float("nan"), dtype=first.dtype, device=first.device)
+    for keep, t in device_rows:
+        if keep and keep[-1] - keep[0] + 1 == len(keep):
+            rows[keep[0] : keep[-1] + 1] = t.reshape(len(keep), 81)
+        elif keep:
+            rows[torch.as_tensor(keep, device=first.device)] = t.reshape(len(keep), 81)
+    mask = np.zeros(n, dtype=bool)
+    mask[list(failed)] = True
+    return _from_rows(rows, 0, directions, False, single, mask)
 
 
 def predict(
@@ -555,8 +576,14 @@ def predict(
     config: Dict[str, Any] = None,
     node_budget: int = None,
     pbc=None,
+    properties: bool = False,
+    directions=None,
 ):
     """See the module docstring.  ``model`` / ``config`` let a caller reuse an already loaded model.
+    ``properties=True`` (elasticity tensors only: ``ValueError`` with ``is_atomic_tensor``) returns ``(tensors, props)``:
+    the usual return value and an ``elastic.ElasticProperties`` with one row per input structure (bulk and shear moduli,
+    Young's modulus, compliance, ...; with ``directions`` -- an int or an array [D,3] -- also the directional extremes),
+    computed from the forwards' device buffers.  Rows of failed structures are NaN and carry flag bit 2.
     ``batch_size`` (reference predict.py:155) is the memory knob it is there: consecutive batches are merged into one forward
     only while the merged batch stays within ``node_budget`` atoms (default MATTEN_PREDICT_NODE_BUDGET = 65536, ~2 GB) and
     only when batch_size is at least the reference's default of 200; ``node_budget=0`` never merges.  A merged forward
@@ -566,6 +593,9 @@ def predict(
     set_logger(logger_level)  # reference predict.py:194
     if is_atomic_tensor:  # reference predict.py:196-199
         is_elasticity_tensor = False
+    if properties and is_atomic_tensor:
+        raise ValueError("properties=True derives elastic moduli from a rank-4 elasticity tensor per structure; "
+                         "per-atom tensors (is_atomic_tensor=True) have none")
     single = not isinstance(structure, (list, tuple))
     structures = [structure] if single else list(structure)
 
@@ -590,10 +620,21 @@ def predict(
     # fast path: the structures are packed into flat arrays slab by slab (PREDICT_SLAB structures each); while the
     # device runs the forwards of slab k the host packs slab k + 1 (a 1000-structure slab packs in 2-3 ms, its forwards
     # take 4-5 ms: the host work of all slabs but the first disappears behind the device)
+    device_rows = None
+    if properties:
+        from .elastic import check_directions
+
+        if len(config["data"]["tensor_target_formula"].split("=")[0].replace("-", "")) != 4:
+            raise ValueError(f"properties=True needs a rank-4 tensor target, not {config['data']['tensor_target_formula']!r}")
+        if directions is not None:
+            directions = check_directions(directions)      # (a bad direction set fails before any forward runs)
+        device_rows = []
     predictions, failed = _predict_slabs(model, structures, r_cut, batch_size, config["data"]["tensor_target_name"],
-                                         config["data"]["tensor_target_formula"], node_budget, pbc)
+                                         config["data"]["tensor_target_formula"], node_budget, pbc, device_rows)
     if not predictions:
         raise RuntimeError("Cannot successfully convert any structures.")
+    if properties:
+        props = _properties_of_slabs(device_rows, len(structures), failed, directions, single)
     if is_elasticity_tensor:
         try:
             from pymatgen.analysis.elasticity import ElasticTensor
@@ -611,4 +652,5 @@ def predict(
         )
     else:
         out = predictions
-    return out[0] if single else out
+    out = out[0] if single else out
+    return (out, props) if properties else out
