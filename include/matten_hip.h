@@ -411,12 +411,38 @@ int matten_dense_rows(const float* x, int64_t n_in, const float* q, int64_t n_ou
  *   young / beta [n,n_dirs]: optional, NULL = not written.  ext [n,4] = E_min, E_max, beta_min, beta_max; arg [n,4] int32 =
  *   their direction indices, equal values resolved to the lowest index (bitwise reproducible).  Rows with flag bit 0: NaN
  *   and -1.
+ * matten_elastic_pair (predict.py:217-218: what pymatgen's users compute one pair at a time from the compliance tensor):
+ *   shear modulus and Poisson's ratio over pairs of perpendicular unit directions, one workgroup per crystal, a lane per
+ *   direction n, the lane looping over the n_angles directions m_k = cos(chi_k) e1 + sin(chi_k) e2 perpendicular to it.
+ *   cos_sin [n_angles,2] fp64 = (cos chi_k, sin chi_k), made by the host (chi_k = pi k / n_angles: m and -m count once);
+ *   (e1, e2) the branch-free orthonormal frame of n: s = n3 >= 0 ? 1 : -1, a = -1/(s + n3), b = n1 n2 a,
+ *   e1 = (1 + s n1^2 a, s b, -s n1), e2 = (b, s + n2^2 a, -n2).  With v() as above and
+ *   w(n,m) = (2 n1 m1, 2 n2 m2, 2 n3 m3, n2 m3 + n3 m2, n1 m3 + n3 m1, n1 m2 + n2 m1):
+ *   1/G(n,m) = w^T S w,  nu(n,m) = -(v(n)^T S v(m)) / (v(n)^T S v(n)).
+ *   ext [n,4] = G_min, G_max, nu_min, nu_max over all pairs; arg [n,4] int32 = their flat pair index d n_angles + k
+ *   (n_dirs n_angles <= 2^31 - 1), equal values resolved to the lowest index; maps [n,n_dirs,4]: optional, the same four
+ *   extremes over chi per direction.  Rows with flag bit 0: NaN and -1.
+ * matten_elastic_acoustic (predict.py:217-218: pymatgen's trans_v / long_v / debye_temperature take VRH averages; this is
+ *   the Christoffel equation per direction): Gamma_ik = C_ijkl n_j n_l from voigt [n,36] (the mean of its two triangles),
+ *   eigenvalues by cyclic Jacobi in registers, v_i = sqrt(lambda_i modulus_unit / density) ascending (m/s for density in
+ *   kg/m^3 and modulus_unit in Pa per unit of C).  A direction with an eigenvalue that is not positive and finite has three
+ *   NaN velocities and is counted in n_unstable [n].  vel [n,n_dirs,3]: optional.  ext [n,3] = v_slow_min (the lowest
+ *   branch's minimum over the directions), v_fast_max, sum_d sum_i v_i^-3 (lane-strided partial sums, xor butterfly, waves
+ *   in index order: bitwise reproducible; NaN with any unstable direction); arg [n,2] int32 = the direction indices of the
+ *   two extremes (NaN ignored; -1 if no finite value).  Rows with flag bit 0 or a density that is not positive and finite:
+ *   NaN and -1 (n_unstable too).
  * ------------------------------------------------------------------------------------------ */
 int matten_elastic_props(const void* c, int is_fp64, int layout, int64_t n, double* voigt, double* compliance,
                          double* props, int32_t* flags, matten_stream_t stream);
 int matten_elastic_directional(const double* compliance, const int32_t* flags, const double* dirs, int64_t n,
                                int64_t n_dirs, double* young, double* beta, double* ext, int32_t* arg,
                                matten_stream_t stream);
+int matten_elastic_pair(const double* compliance, const int32_t* flags, const double* dirs, const double* cos_sin,
+                        int64_t n, int64_t n_dirs, int64_t n_angles, double* maps, double* ext, int32_t* arg,
+                        matten_stream_t stream);
+int matten_elastic_acoustic(const double* voigt, const int32_t* flags, const double* density, const double* dirs, int64_t n,
+                            int64_t n_dirs, double modulus_unit, double* vel, double* ext, int32_t* arg, int32_t* n_unstable,
+                            matten_stream_t stream);
 
 
 /* ==========================================================================================

@@ -1,7 +1,10 @@
 // Derived elastic properties of predicted elasticity tensors (include/matten_hip.h, "Derived elastic properties").
 //   elastic_props_kernel       : Voigt matrix, compliance, the ten scalar moduli and the flags   reference predict.py:217-218
 //   elastic_directional_kernel : Young's modulus and linear compressibility over a direction set, with their extremes
-// The reference wraps every predicted tensor in pymatgen's ElasticTensor (one Python object per crystal); these two kernels
+//   elastic_pair_kernel        : shear modulus and Poisson's ratio over pairs of perpendicular directions, with their extremes
+//   elastic_acoustic_kernel    : the three acoustic phase velocities per direction (Christoffel equation), their extremes
+//                                and the sum of v^-3 of the Debye average
+// The reference wraps every predicted tensor in pymatgen's ElasticTensor (one Python object per crystal); these kernels
 // compute what its users read off that object.  All arithmetic is fp64; everything is held in registers with compile-time
 // indices, so no kernel here uses scratch memory (hipcc -Rpass-analysis=kernel-resource-usage: DESIGN.md).
 #include "common.h"
@@ -268,6 +271,237 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_directional_kernel(const 
     }
 }
 
+constexpr int EXT_NONE = 0x7fffffff;   // the index of an Ext that no candidate has replaced yet
+
+// the winner of the workgroup's four waves for NV (value, index) pairs -- minima at even, maxima at odd positions -- written
+// by lane q < NV to ext[q] / arg[q]; a pair that never met a comparable value (all NaN) becomes NaN and -1
+template <int NV>
+__device__ __forceinline__ void block_best(const Ext (&e)[NV], double* __restrict__ ext, int32_t* __restrict__ arg, int t) {
+    __shared__ double sh_v[DIR_THREADS / 64][NV];
+    __shared__ int sh_i[DIR_THREADS / 64][NV];
+    const int wave = t >> 6;
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) sh_v[wave][q] = e[q].v, sh_i[wave][q] = e[q].i;
+    }
+    __syncthreads();
+    if (t < NV) {
+        Ext a = {sh_v[0][t], sh_i[0][t]};
+#pragma unroll
+        for (int w = 1; w < DIR_THREADS / 64; ++w) {
+            const Ext o = {sh_v[w][t], sh_i[w][t]};
+            a = (t & 1) ? better<true>(a, o) : better<false>(a, o);
+        }
+        const bool none = a.i == EXT_NONE;
+        ext[t] = none ? __longlong_as_double(0x7ff8000000000000LL) : a.v;
+        arg[t] = none ? -1 : a.i;
+    }
+}
+
+// One workgroup per crystal, a lane per direction n in strides of DIR_THREADS; the lane walks the n_ang directions
+// m_k = cos(chi_k) e1 + sin(chi_k) e2 perpendicular to n itself, so the extremes over chi are lane-local.
+//   1/G(n,m) = w^T S w,  w = (2 n1 m1, 2 n2 m2, 2 n3 m3, n2 m3 + n3 m2, n1 m3 + n3 m1, n1 m2 + n2 m1)
+//   nu(n,m)  = -(v(n)^T S v(m)) / (v(n)^T S v(n))
+__global__ void __launch_bounds__(DIR_THREADS) elastic_pair_kernel(const double* __restrict__ compliance,
+                                                                   const int32_t* __restrict__ flags,
+                                                                   const double* __restrict__ dirs, int n_dirs,
+                                                                   const double* __restrict__ cos_sin, int n_ang,
+                                                                   double* __restrict__ maps, double* __restrict__ ext,
+                                                                   int32_t* __restrict__ arg) {
+    const int64_t b = blockIdx.x;
+    const int t = threadIdx.x;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    if (flags[b] & 1) {   // (uniform over the workgroup)
+        if (maps) {
+            for (int64_t i = t; i < (int64_t)n_dirs * 4; i += DIR_THREADS) maps[b * n_dirs * 4 + i] = nan;
+        }
+        if (t < 4) {
+            ext[b * 4 + t] = nan;
+            arg[b * 4 + t] = -1;
+        }
+        return;
+    }
+    const double* s = compliance + b * 36;
+    double S[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j) S[i][j] = S[j][i] = 0.5 * (s[i * 6 + j] + s[j * 6 + i]);
+    }
+
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    Ext best[4] = {{inf, EXT_NONE}, {-inf, EXT_NONE}, {inf, EXT_NONE}, {-inf, EXT_NONE}};   // G_min, G_max, nu_min, nu_max
+    for (int d = t; d < n_dirs; d += DIR_THREADS) {
+        const double n1 = dirs[d * 3 + 0], n2 = dirs[d * 3 + 1], n3 = dirs[d * 3 + 2];
+        const double v[6] = {n1 * n1, n2 * n2, n3 * n3, n2 * n3, n1 * n3, n1 * n2};
+        double Sv[6], q = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            double row = 0.0;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) row += S[i][j] * v[j];
+            Sv[i] = row;
+            q += v[i] * row;
+        }
+        // the branch-free orthonormal frame (e1, e2) of n
+        const double sg = n3 >= 0.0 ? 1.0 : -1.0;
+        const double fa = -1.0 / (sg + n3), fb = n1 * n2 * fa;
+        const double e1[3] = {1.0 + sg * n1 * n1 * fa, sg * fb, -sg * n1};
+        const double e2[3] = {fb, sg + n2 * n2 * fa, -n2};
+
+        Ext here[4] = {{inf, EXT_NONE}, {-inf, EXT_NONE}, {inf, EXT_NONE}, {-inf, EXT_NONE}};
+        const int base = d * n_ang;
+        for (int k = 0; k < n_ang; ++k) {
+            const double c = cos_sin[2 * (int64_t)k], sn = cos_sin[2 * (int64_t)k + 1];
+            const double m1 = c * e1[0] + sn * e2[0], m2 = c * e1[1] + sn * e2[1], m3 = c * e1[2] + sn * e2[2];
+            const double vm[6] = {m1 * m1, m2 * m2, m3 * m3, m2 * m3, m1 * m3, m1 * m2};
+            const double w[6] = {2.0 * n1 * m1, 2.0 * n2 * m2, 2.0 * n3 * m3, n2 * m3 + n3 * m2, n1 * m3 + n3 * m1,
+                                 n1 * m2 + n2 * m1};
+            double num = 0.0, h = 0.0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                double row = 0.0;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) row += S[i][j] * w[j];
+                h += w[i] * row;
+                num += Sv[i] * vm[i];
+            }
+            const Ext cg = {1.0 / h, base + k}, cn = {-num / q, base + k};
+            here[0] = better<false>(here[0], cg);
+            here[1] = better<true>(here[1], cg);
+            here[2] = better<false>(here[2], cn);
+            here[3] = better<true>(here[3], cn);
+        }
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            if (maps) maps[(b * n_dirs + d) * 4 + x] = here[x].i == EXT_NONE ? nan : here[x].v;
+            best[x] = (x & 1) ? better<true>(best[x], here[x]) : better<false>(best[x], here[x]);
+        }
+    }
+    best[0] = wave_best<false>(best[0]);
+    best[1] = wave_best<true>(best[1]);
+    best[2] = wave_best<false>(best[2]);
+    best[3] = wave_best<true>(best[3]);
+    block_best<4>(best, ext + b * 4, arg + b * 4, t);
+}
+
+// One cyclic-Jacobi rotation of a symmetric 3x3 matrix: annihilates a_pq; r is the third index.  Branch-free: a zero
+// a_pq (where theta is inf or 0/0) rotates by nothing.
+__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    double tn = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));   // (theta^2 = inf: 0)
+    tn = apq == 0.0 ? 0.0 : tn;
+    const double c = 1.0 / sqrt(tn * tn + 1.0), sn = tn * c, tau = sn / (1.0 + c);
+    const double h = tn * apq;
+    app -= h;
+    aqq += h;
+    apq = 0.0;
+    const double g = arp, f = arq;
+    arp = g - sn * (f + g * tau);
+    arq = f + sn * (g - f * tau);
+}
+
+// cyclic Jacobi converges quadratically: on the example data set, isotropic and cubic tensors the off-diagonal is below
+// 1e-21 max|C| after 4 sweeps (numpy fp64 run of this rotation); one more sweep is the margin
+constexpr int JACOBI_SWEEPS = 5;
+
+// One workgroup per crystal, a lane per direction in strides of DIR_THREADS: Gamma_ik = C_ijkl n_j n_l, its eigenvalues
+// by cyclic Jacobi in registers, v_i = sqrt(lambda_i unit / rho) ascending.
+__global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_kernel(const double* __restrict__ voigt,
+                                                                       const int32_t* __restrict__ flags,
+                                                                       const double* __restrict__ density,
+                                                                       const double* __restrict__ dirs, int n_dirs,
+                                                                       double modulus_unit, double* __restrict__ vel,
+                                                                       double* __restrict__ ext, int32_t* __restrict__ arg,
+                                                                       int32_t* __restrict__ n_unstable) {
+    const int64_t b = blockIdx.x;
+    const int t = threadIdx.x;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double rho = density[b];
+    if ((flags[b] & 1) || !(rho > 0.0) || !finite64(rho)) {   // (uniform over the workgroup)
+        if (vel) {
+            for (int64_t i = t; i < (int64_t)n_dirs * 3; i += DIR_THREADS) vel[b * n_dirs * 3 + i] = nan;
+        }
+        if (t < 3) ext[b * 3 + t] = nan;
+        if (t < 2) arg[b * 2 + t] = -1;
+        if (t == 0) n_unstable[b] = -1;
+        return;
+    }
+    const double* cp = voigt + b * 36;
+    double C[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j) C[i][j] = C[j][i] = 0.5 * (cp[i * 6 + j] + cp[j * 6 + i]);
+    }
+    constexpr int V[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}};   // Cartesian pair -> Voigt index
+    const double scale = modulus_unit / rho;
+
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    Ext best[2] = {{inf, EXT_NONE}, {-inf, EXT_NONE}};   // v_slow_min, v_fast_max
+    double sum = 0.0;
+    int bad = 0;
+    for (int d = t; d < n_dirs; d += DIR_THREADS) {
+        const double n[3] = {dirs[d * 3 + 0], dirs[d * 3 + 1], dirs[d * 3 + 2]};
+        double G[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int k = i; k < 3; ++k) {
+                double g = 0.0;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+#pragma unroll
+                    for (int l = 0; l < 3; ++l) g += C[V[i][j]][V[k][l]] * (n[j] * n[l]);
+                }
+                G[i][k] = g;
+            }
+        }
+        double a00 = G[0][0], a11 = G[1][1], a22 = G[2][2], a01 = G[0][1], a02 = G[0][2], a12 = G[1][2];
+#pragma unroll
+        for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+            jacobi_rotate(a00, a11, a01, a02, a12);   // (p, q, r) = (0, 1, 2)
+            jacobi_rotate(a00, a22, a02, a01, a12);   //             (0, 2, 1)
+            jacobi_rotate(a11, a22, a12, a01, a02);   //             (1, 2, 0)
+        }
+        const bool ok = a00 > 0.0 && a11 > 0.0 && a22 > 0.0 && finite64(a00) && finite64(a11) && finite64(a22);
+        const double lo01 = fmin(a00, a11), hi01 = fmax(a00, a11);
+        const double l0 = fmin(lo01, a22), top = fmax(lo01, a22);
+        const double l1 = fmin(hi01, top), l2 = fmax(hi01, top);
+        const double v0 = ok ? sqrt(l0 * scale) : nan, v1 = ok ? sqrt(l1 * scale) : nan, v2 = ok ? sqrt(l2 * scale) : nan;
+        if (vel) {
+            double* o = vel + (b * n_dirs + d) * 3;
+            o[0] = v0, o[1] = v1, o[2] = v2;
+        }
+        bad += ok ? 0 : 1;
+        sum += (1.0 / (v0 * v0 * v0) + 1.0 / (v1 * v1 * v1)) + 1.0 / (v2 * v2 * v2);
+        const Ext c0 = {v0, d}, c2 = {v2, d};
+        best[0] = better<false>(best[0], c0);   // (a NaN compares false: never taken)
+        best[1] = better<true>(best[1], c2);
+    }
+    best[0] = wave_best<false>(best[0]);
+    best[1] = wave_best<true>(best[1]);
+    // the sum in a fixed order: the lane's strided partial sum, an xor butterfly in the wave (a + b = b + a: every lane
+    // holds the same bits), the four waves in index order
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        sum += __shfl_xor(sum, off, 64);
+        bad += __shfl_xor(bad, off, 64);
+    }
+    __shared__ double sh_sum[DIR_THREADS / 64];
+    __shared__ int sh_bad[DIR_THREADS / 64];
+    if ((t & 63) == 0) sh_sum[t >> 6] = sum, sh_bad[t >> 6] = bad;
+    block_best<2>(best, ext + b * 3, arg + b * 2, t);   // (its barrier covers sh_sum / sh_bad as well)
+    if (t == 0) {
+        double total = sh_sum[0];
+        int n_bad = sh_bad[0];
+#pragma unroll
+        for (int w = 1; w < DIR_THREADS / 64; ++w) total += sh_sum[w], n_bad += sh_bad[w];
+        ext[b * 3 + 2] = total;
+        n_unstable[b] = n_bad;
+    }
+}
+
 }  // namespace
 
 extern "C" int matten_elastic_props(const void* c, int is_fp64, int layout, int64_t n, double* voigt, double* compliance,
@@ -298,6 +532,34 @@ extern "C" int matten_elastic_directional(const double* compliance, const int32_
     if (!compliance || !flags || !dirs || !ext || !arg) return MATTEN_EINVAL;
     elastic_directional_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(compliance, flags, dirs, (int)n_dirs, young, beta, ext,
                                                                         arg);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_elastic_pair(const double* compliance, const int32_t* flags, const double* dirs, const double* cos_sin,
+                                   int64_t n, int64_t n_dirs, int64_t n_angles, double* maps, double* ext, int32_t* arg,
+                                   matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || n > 0x7fffffff || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || n_angles < 1 || n_angles > 0x7fffffff ||
+        n_dirs * n_angles > 0x7fffffff)
+        return MATTEN_EINVAL;
+    if (n == 0) return MATTEN_OK;
+    if (!compliance || !flags || !dirs || !cos_sin || !ext || !arg) return MATTEN_EINVAL;
+    elastic_pair_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(compliance, flags, dirs, (int)n_dirs, cos_sin, (int)n_angles,
+                                                                 maps, ext, arg);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_elastic_acoustic(const double* voigt, const int32_t* flags, const double* density, const double* dirs,
+                                       int64_t n, int64_t n_dirs, double modulus_unit, double* vel, double* ext, int32_t* arg,
+                                       int32_t* n_unstable, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || n > 0x7fffffff || n_dirs < 1 || n_dirs > 0x7fffffff / 3) return MATTEN_EINVAL;
+    if (n == 0) return MATTEN_OK;
+    if (!voigt || !flags || !density || !dirs || !ext || !arg || !n_unstable) return MATTEN_EINVAL;
+    elastic_acoustic_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(voigt, flags, density, dirs, (int)n_dirs, modulus_unit, vel,
+                                                                     ext, arg, n_unstable);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }

@@ -5,11 +5,15 @@ The reference ends ``predict`` with ``predictions = [ElasticTensor(t) for t in p
 users read bulk and shear moduli, Young's modulus, Poisson's ratio, the anisotropy index, the compliance tensor and
 directional moduli off that pymatgen object, one Python object per crystal.  Here two kernels
 (``matten_elastic_props`` / ``matten_elastic_directional``, csrc/elastic.hip) compute them for a whole batch in fp64.
+Two more serve what depends on two directions or on the mass density: ``matten_elastic_pair`` (shear modulus and Poisson's
+ratio over pairs of perpendicular directions) and ``matten_elastic_acoustic`` (the Christoffel phase velocities per
+direction, their Debye average and, with a number density, the Debye temperature).
 
 Conventions (INTEGRATION.md, "Derived elastic properties"): Voigt order xx, yy, zz, yz, xz, xy as in pymatgen;
 ``C_IJ = C_ijkl`` without factors and ``compliance = inv(C_IJ)``, the engineering convention (the factors 2 and 4 live in
 the compliance); the input is symmetrised, never trusted.  Every value is in the units of the input tensor -- pymatgen's
-``y_mod`` alone is multiplied by 1e9 (GPa -> Pa); this module does not copy that.
+``y_mod`` alone is multiplied by 1e9 (GPa -> Pa); this module does not copy that.  The velocities (m/s) and the Debye
+temperature (K) alone are SI: ``density`` is kg/m^3, ``number_density`` atoms/m^3, ``modulus_unit`` Pa per unit of the input.
 """
 import numpy as np
 import torch
@@ -23,13 +27,23 @@ FLAG_SINGULAR, FLAG_NOT_POSITIVE_DEFINITE, FLAG_FAILED_STRUCTURE = 1, 2, 4
 # Voigt index -> Cartesian pair, pymatgen's order
 VOIGT_PAIRS = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))
 
+# exact SI constants (2019 redefinition): hbar = h / 2 pi [J s], k_B [J/K]
+HBAR = 6.62607015e-34 / (2.0 * np.pi)
+K_B = 1.380649e-23
+
 class ElasticProperties:
     """Batch of derived properties: ``voigt`` / ``compliance`` [B,6,6], one [B] tensor per name of ``PROP_NAMES``,
     ``flags`` [B] int32 (bit 0 singular or non-finite input: the row is NaN; bit 1 not positive definite; bit 2 the
     structure failed in ``predict``), ``is_stable`` / ``is_singular`` [B] bool.  With directions also ``directions`` [D,3],
     ``young_min`` / ``young_max`` / ``compressibility_min`` / ``compressibility_max`` [B] with their ``*_argmin`` /
     ``*_argmax`` direction indices (-1 on singular rows), and ``young`` / ``compressibility`` [B,D] when they were kept
-    (else None).  An unbatched input ([3,3,3,3] or [6,6]) gives the same without the leading dimension."""
+    (else None).  With ``angles`` = M also ``angles`` [M] (chi_k = pi k / M), ``shear_min`` / ``shear_max`` / ``poisson_min`` /
+    ``poisson_max`` [B] over all pairs (direction d, angle k), each with a ``*_direction`` and a ``*_angle`` index (-1 on
+    singular rows), and the per-direction extremes over chi ``shear_dir_min`` / ``shear_dir_max`` / ``poisson_dir_min`` /
+    ``poisson_dir_max`` [B,D] when kept.  With ``density`` also ``v_slow_min`` / ``v_fast_max`` [B] (m/s) with their
+    ``*_direction``, ``sum_inv_v3``, ``v_mean`` = (sum_inv_v3 / 3D)^(-1/3), ``acoustic_unstable_directions`` [B] int32 and
+    ``velocities`` [B,D,3] (ascending) when kept; with ``number_density`` also ``debye_temperature`` [B] (K).
+    An unbatched input ([3,3,3,3] or [6,6]) gives the same without the leading dimension."""
 
     def __init__(self, **fields):
         self._names = tuple(fields)
@@ -91,6 +105,58 @@ def check_directions(directions) -> np.ndarray:
     return n / np.linalg.norm(n, axis=1, keepdims=True)
 
 
+def angle_table(M: int) -> np.ndarray:
+    """[M,2] fp64 = (cos chi_k, sin chi_k), chi_k = pi k / M for k = 0..M-1: half a turn, m and -m count once.  Made with
+    numpy on the host and uploaded, so the kernel and a host reference use the same bits."""
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M < 1:
+        raise ValueError(f"angles: expected an int M >= 1, got {M!r}")
+    chi = np.pi * np.arange(int(M), dtype=np.float64) / int(M)
+    return np.stack([np.cos(chi), np.sin(chi)], axis=1)
+
+
+def split_pair_index(flat, M: int):
+    """flat pair index d M + k (a torch tensor or numpy array; -1 = none) -> (direction index d, angle index k), -1 kept"""
+    if isinstance(flat, torch.Tensor):
+        none = flat < 0
+        d = torch.div(flat, M, rounding_mode="floor")
+        return torch.where(none, flat, d), torch.where(none, flat, flat - d * M)
+    flat = np.asarray(flat)
+    return np.where(flat < 0, flat, flat // M), np.where(flat < 0, flat, flat % M)
+
+
+def _check_per_row(name: str, values, B: int, single: bool):
+    """``density`` / ``number_density``: a device tensor is taken as it is (the kernel answers a bad entry with NaN); a
+    host input is checked here, before anything is uploaded -> a tensor [B] (device input) or a numpy array [B] fp64"""
+    if isinstance(values, torch.Tensor) and values.is_cuda:
+        t = values.detach().reshape(-1).to(torch.float64)
+        if t.shape[0] != B:
+            raise ValueError(f"{name}: expected {B} value(s), one per tensor, got {t.shape[0]}")
+        return t
+    a = np.asarray(values.detach().numpy() if isinstance(values, torch.Tensor) else values, dtype=np.float64)
+    if a.ndim == 0 and (single or B == 1):
+        a = a.reshape(1)
+    if a.ndim != 1 or a.shape[0] != B:
+        raise ValueError(f"{name}: expected {B} value(s), one per tensor, got shape {a.shape}")
+    bad = ~(np.isfinite(a) & (a > 0.0))
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"{name}: expected finite positive values, got {a[i]} at index {i}")
+    return a
+
+
+def _check_extras(directions, angles, density, number_density):
+    """the argument combinations of the pair and acoustic properties (ValueError before anything else happens)"""
+    if angles is not None:
+        if isinstance(angles, bool) or not isinstance(angles, (int, np.integer)) or angles < 1:
+            raise ValueError(f"angles: expected an int M >= 1, got {angles!r}")
+        if directions is None:
+            raise ValueError("angles: the pairs (n, m) need a direction set, pass directions")
+    if density is not None and directions is None:
+        raise ValueError("density: the acoustic velocities need a direction set, pass directions")
+    if number_density is not None and density is None:
+        raise ValueError("number_density: the Debye temperature needs the sound velocities, pass density")
+
+
 _VOIGT_BASIS = {}
 
 
@@ -113,7 +179,8 @@ def _default_device() -> torch.device:
 
 
 def _as_rows(tensors):
-    """-> (rows [B,81] or [B,36] on the device, layout, unbatched?, failed [B] bool on the host or None)"""
+    """-> (rows [B,81] or [B,36] where the input is -- ``_upload`` makes the one copy of a host input once every host
+    check has passed --, layout, unbatched?, failed [B] bool on the host or None)"""
     failed = None
     if isinstance(tensors, (list, tuple)):
         if not tensors:
@@ -149,13 +216,19 @@ def _as_rows(tensors):
     else:
         raise ValueError(f"tensors: expected [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], got {shape}")
     rows = tensors.detach().reshape(-1, width)
+    return rows, layout, single, failed
+
+
+def _upload(rows):
     if not rows.is_cuda:
         rows = rows.to(_default_device())          # the one copy of a host input
-    return rows.contiguous(), layout, single, failed
+    return rows.contiguous()
 
 
-def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, failed=None) -> ElasticProperties:
-    """rows on the device -> ElasticProperties; ``dirs``: unit vectors out of ``check_directions`` (host) or None"""
+def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, failed=None, angles=None, density=None,
+               number_density=None, modulus_unit: float = 1e9) -> ElasticProperties:
+    """rows on the device -> ElasticProperties; ``dirs``: unit vectors out of ``check_directions`` (host) or None;
+    ``density`` / ``number_density``: out of ``_check_per_row`` or None"""
     voigt, compliance, props, flags = ops.elastic_props(rows, layout)
     if failed is not None and failed.any():
         flags |= torch.as_tensor(failed.astype(np.int32) * FLAG_FAILED_STRUCTURE, device=flags.device)
@@ -172,34 +245,74 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
                       young_min=ext[:, 0], young_max=ext[:, 1], young_argmin=arg[:, 0], young_argmax=arg[:, 1],
                       compressibility_min=ext[:, 2], compressibility_max=ext[:, 3],
                       compressibility_argmin=arg[:, 2], compressibility_argmax=arg[:, 3], directions=dirs)
+    if angles is not None:
+        M = int(angles)
+        table = angle_table(M)
+        maps, ext, arg = ops.elastic_pair(compliance, flags, dirs, torch.from_numpy(table).to(rows.device),
+                                          keep=keep_directional)
+        fields["angles"] = torch.from_numpy(np.pi * np.arange(M, dtype=np.float64) / M).to(rows.device)
+        for q, name in enumerate(("shear_min", "shear_max", "poisson_min", "poisson_max")):
+            fields[name] = ext[:, q]
+            fields[name + "_direction"], fields[name + "_angle"] = split_pair_index(arg[:, q], M)
+        for q, name in enumerate(("shear_dir_min", "shear_dir_max", "poisson_dir_min", "poisson_dir_max")):
+            fields[name] = None if maps is None else maps[:, :, q]
+    if density is not None:
+        rho = torch.as_tensor(density, dtype=torch.float64).to(rows.device)
+        vel, ext, arg, n_unstable = ops.elastic_acoustic(voigt, flags, rho, dirs, modulus_unit, keep=keep_directional)
+        fields.update(velocities=vel, v_slow_min=ext[:, 0], v_fast_max=ext[:, 1], v_slow_min_direction=arg[:, 0],
+                      v_fast_max_direction=arg[:, 1], sum_inv_v3=ext[:, 2],
+                      v_mean=(ext[:, 2] / (3.0 * dirs.shape[0])) ** (-1.0 / 3.0), acoustic_unstable_directions=n_unstable)
+        if number_density is not None:
+            n_at = torch.as_tensor(number_density, dtype=torch.float64).to(rows.device)
+            fields["debye_temperature"] = (HBAR / K_B) * (6.0 * np.pi ** 2 * n_at) ** (1.0 / 3.0) * fields["v_mean"]
     if single:
-        fields = {k: (v if v is None or k == "directions" else v[0]) for k, v in fields.items()}
+        fields = {k: (v if v is None or k in ("directions", "angles") else v[0]) for k, v in fields.items()}
     return ElasticProperties(**fields)
 
 
-def elastic_properties(tensors, directions=None, keep_directional: bool = False) -> ElasticProperties:
+def elastic_properties(tensors, directions=None, keep_directional: bool = False, angles=None, density=None,
+                       number_density=None, modulus_unit: float = 1e9) -> ElasticProperties:
     """``tensors``: a torch tensor or numpy array [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], fp32 or fp64, on the device or
     on the host (copied once), or a list of such tensors as ``predict`` returns (stacked; a ``None`` entry becomes a NaN
     row with flag bit 2).  ``directions``: an int D (``fibonacci_hemisphere(D)``) or an array [D,3] (validated and
     normalised on the host); with them the extremes of Young's modulus and of the linear compressibility over the
-    directions are returned, and the full [B,D] maps when ``keep_directional``.  The results stay on the device."""
+    directions are returned, and the full [B,D] maps when ``keep_directional``.  ``angles``: an int M >= 1 (needs
+    ``directions``): shear modulus G(n,m) and Poisson's ratio nu(n,m) over the D x M pairs of a direction n and the
+    perpendicular m at angle chi_k = pi k / M in n's frame, their extremes with a direction and an angle index each.
+    ``density``: [B] (a scalar for an unbatched input) in kg/m^3 (needs ``directions``): the three acoustic phase
+    velocities per direction in m/s, their extremes and the Debye average ``v_mean``; ``modulus_unit`` is Pa per unit of
+    the input (1e9: GPa).  ``number_density``: [B] atoms/m^3 (needs ``density``): ``debye_temperature`` in K.  A host
+    ``density`` / ``number_density`` is checked before anything is uploaded (ValueError naming the first bad index).
+    The results stay on the device."""
+    _check_extras(directions, angles, density, number_density)
     dirs = None if directions is None else check_directions(directions)      # (before anything is uploaded)
     rows, layout, single, failed = _as_rows(tensors)
-    return _from_rows(rows, layout, dirs, keep_directional, single, failed)
+    if density is not None:
+        density = _check_per_row("density", density, rows.shape[0], single)
+    if number_density is not None:
+        number_density = _check_per_row("number_density", number_density, rows.shape[0], single)
+    return _from_rows(_upload(rows), layout, dirs, keep_directional, single, failed, angles, density, number_density,
+                      modulus_unit)
 
 
 _VOIGT_Q = {}
 
 
 def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = False,
-                                   formula: str = "ijkl=jikl=klij") -> ElasticProperties:
+                                   formula: str = "ijkl=jikl=klij", angles=None, density=None, number_density=None,
+                                   modulus_unit: float = 1e9) -> ElasticProperties:
     """The same from the model's irreps rows ``x`` [B,21] (fp32, on the device): one ``dense_rows`` with ``voigt_basis``
     gives the Voigt matrices [B,36] directly -- no [B,81] Cartesian intermediate."""
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
         raise ValueError("x: expected a tensor [B,21] or [21]")
+    _check_extras(directions, angles, density, number_density)
     dirs = None if directions is None else check_directions(directions)
     single = x.dim() == 1
     x = x.detach().reshape(-1, x.shape[-1])
+    if density is not None:
+        density = _check_per_row("density", density, x.shape[0], single)
+    if number_density is not None:
+        number_density = _check_per_row("number_density", number_density, x.shape[0], single)
     V = voigt_basis(formula)
     if x.shape[1] != V.shape[0]:
         raise ValueError(f"x: expected {V.shape[0]} irreps components per row, got {x.shape[1]}")
@@ -209,4 +322,4 @@ def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = 
     if key not in _VOIGT_Q:
         _VOIGT_Q[key] = torch.tensor(V, dtype=torch.float32, device=x.device)
     rows = ops.dense_rows(x.to(torch.float32), _VOIGT_Q[key])
-    return _from_rows(rows, 1, dirs, keep_directional, single)
+    return _from_rows(rows, 1, dirs, keep_directional, single, None, angles, density, number_density, modulus_unit)

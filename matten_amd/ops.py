@@ -864,6 +864,52 @@ def elastic_directional(compliance, flags, dirs, keep: bool = False):
     return young, beta, ext, arg
 
 
+def elastic_pair(compliance, flags, dirs, cos_sin, keep: bool = False):
+    """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64, cos_sin [M,2] fp64 -> (maps [B,D,4] or
+    None, ext [B,4] = G_min, G_max, nu_min, nu_max, arg [B,4] int32 = flat pair indices d M + k) (matten_elastic_pair)"""
+    lib = _lib.load()
+    compliance = _need(compliance, torch.float64, "compliance")
+    flags = _need(flags, torch.int32, "flags")
+    dirs = _need(dirs, torch.float64, "dirs")
+    cos_sin = _need(cos_sin, torch.float64, "cos_sin")
+    B = flags.shape[0]
+    if (compliance.shape != (B, 6, 6) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1 or cos_sin.dim() != 2
+            or cos_sin.shape[1] != 2 or cos_sin.shape[0] < 1):
+        raise ValueError(f"expected compliance [B,6,6], flags [B], dirs [D>=1,3], cos_sin [M>=1,2]; got "
+                         f"{tuple(compliance.shape)}, {tuple(flags.shape)}, {tuple(dirs.shape)}, {tuple(cos_sin.shape)}")
+    D, M = dirs.shape[0], cos_sin.shape[0]
+    maps = torch.empty(B, D, 4, dtype=torch.float64, device=dirs.device) if keep else None
+    ext = torch.empty(B, 4, dtype=torch.float64, device=dirs.device)
+    arg = torch.empty(B, 4, dtype=torch.int32, device=dirs.device)
+    _lib.check(lib.matten_elastic_pair(_ptr(compliance), _ptr(flags), _ptr(dirs), _ptr(cos_sin), B, D, M, _ptr(maps), _ptr(ext),
+                                       _ptr(arg), _stream()), "matten_elastic_pair")
+    return maps, ext, arg
+
+
+def elastic_acoustic(voigt, flags, density, dirs, modulus_unit: float = 1e9, keep: bool = False):
+    """voigt [B,6,6] fp64, flags [B] int32, density [B] fp64 (kg/m^3), unit directions dirs [D,3] fp64, modulus_unit in Pa
+    per unit of voigt -> (vel [B,D,3] or None, ext [B,3] = v_slow_min, v_fast_max, sum of v^-3, arg [B,2] int32,
+    n_unstable [B] int32) (matten_elastic_acoustic)"""
+    lib = _lib.load()
+    voigt = _need(voigt, torch.float64, "voigt")
+    flags = _need(flags, torch.int32, "flags")
+    density = _need(density, torch.float64, "density")
+    dirs = _need(dirs, torch.float64, "dirs")
+    B = flags.shape[0]
+    if voigt.shape != (B, 6, 6) or density.shape != (B,) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
+        raise ValueError(f"expected voigt [B,6,6], flags [B], density [B], dirs [D>=1,3]; got {tuple(voigt.shape)}, "
+                         f"{tuple(flags.shape)}, {tuple(density.shape)}, {tuple(dirs.shape)}")
+    D = dirs.shape[0]
+    vel = torch.empty(B, D, 3, dtype=torch.float64, device=dirs.device) if keep else None
+    ext = torch.empty(B, 3, dtype=torch.float64, device=dirs.device)
+    arg = torch.empty(B, 2, dtype=torch.int32, device=dirs.device)
+    n_unstable = torch.empty(B, dtype=torch.int32, device=dirs.device)
+    _lib.check(lib.matten_elastic_acoustic(_ptr(voigt), _ptr(flags), _ptr(density), _ptr(dirs), B, D, float(modulus_unit),
+                                           _ptr(vel), _ptr(ext), _ptr(arg), _ptr(n_unstable), _stream()),
+               "matten_elastic_acoustic")
+    return vel, ext, arg, n_unstable
+
+
 # ---------------------------------------------------------------------------------------------------
 # adjoint operators (training step)
 # ---------------------------------------------------------------------------------------------------

@@ -547,7 +547,28 @@ def _predict_slabs(model, structures, r_cut, batch_size, tensor_target_name, ten
     return predictions, sorted(set(failed))
 
 
-def _properties_of_slabs(device_rows, n, failed, directions, single):
+def _structure_densities(structures) -> np.ndarray:
+    """``density="structure"``: kg/m^3 per structure, from a ``.density`` attribute (pymatgen: g/cm^3) or a dict's
+    ``"density"`` key (kg/m^3); ValueError listing the structures that carry none"""
+    out, missing = np.zeros(len(structures)), []
+    for i, s in enumerate(structures):
+        if isinstance(s, dict):
+            rho = s.get("density")
+        else:
+            rho = getattr(s, "density", None)
+            rho = None if rho is None else 1000.0 * float(rho)
+        if rho is None:
+            missing.append(i)
+        else:
+            out[i] = float(rho)
+    if missing:
+        raise ValueError(f'density="structure": no density on structures {missing} (a `.density` attribute in g/cm^3 or a '
+                         'dict key "density" in kg/m^3)')
+    return out
+
+
+def _properties_of_slabs(device_rows, n, failed, directions, single, angles=None, density=None, number_density=None,
+                         modulus_unit=1e9):
     """ElasticProperties of all n input structures from the slabs' device tensors: they never come back from the host.
     Structures without a prediction (``failed``) keep NaN rows and get flag bit 2."""
     from .elastic import _from_rows
@@ -561,7 +582,7 @@ def _properties_of_slabs(device_rows, n, failed, directions, single):
             rows[torch.as_tensor(keep, device=first.device)] = t.reshape(len(keep), 81)
     mask = np.zeros(n, dtype=bool)
     mask[list(failed)] = True
-    return _from_rows(rows, 0, directions, False, single, mask)
+    return _from_rows(rows, 0, directions, False, single, mask, angles, density, number_density, modulus_unit)
 
 
 def predict(
@@ -578,12 +599,20 @@ def predict(
     pbc=None,
     properties: bool = False,
     directions=None,
+    angles=None,
+    density=None,
+    number_density=None,
+    modulus_unit: float = 1e9,
 ):
     """See the module docstring.  ``model`` / ``config`` let a caller reuse an already loaded model.
     ``properties=True`` (elasticity tensors only: ``ValueError`` with ``is_atomic_tensor``) returns ``(tensors, props)``:
     the usual return value and an ``elastic.ElasticProperties`` with one row per input structure (bulk and shear moduli,
     Young's modulus, compliance, ...; with ``directions`` -- an int or an array [D,3] -- also the directional extremes),
     computed from the forwards' device buffers.  Rows of failed structures are NaN and carry flag bit 2.
+    ``angles`` (an int M), ``density`` (kg/m^3, one value per input structure, or ``"structure"``: read from each structure's
+    ``.density`` in g/cm^3 or a dict's ``"density"`` key in kg/m^3), ``number_density`` (atoms/m^3) and ``modulus_unit`` are
+    those of ``elastic.elastic_properties`` (shear modulus and Poisson's ratio over direction pairs, sound velocities, Debye
+    temperature); they need ``properties=True`` and are checked before any forward runs.
     ``batch_size`` (reference predict.py:155) is the memory knob it is there: consecutive batches are merged into one forward
     only while the merged batch stays within ``node_budget`` atoms (default MATTEN_PREDICT_NODE_BUDGET = 65536, ~2 GB) and
     only when batch_size is at least the reference's default of 200; ``node_budget=0`` never merges.  A merged forward
@@ -596,8 +625,24 @@ def predict(
     if properties and is_atomic_tensor:
         raise ValueError("properties=True derives elastic moduli from a rank-4 elasticity tensor per structure; "
                          "per-atom tensors (is_atomic_tensor=True) have none")
+    if not properties:
+        for name, value in (("angles", angles), ("density", density), ("number_density", number_density)):
+            if value is not None:
+                raise ValueError(f"{name} belongs to the derived properties: pass properties=True")
     single = not isinstance(structure, (list, tuple))
     structures = [structure] if single else list(structure)
+    if properties:
+        from .elastic import _check_extras, _check_per_row
+
+        _check_extras(directions, angles, density, number_density)
+        if isinstance(density, str):
+            if density != "structure":
+                raise ValueError(f'density: expected values in kg/m^3 or "structure", got {density!r}')
+            density = _structure_densities(structures)
+        if density is not None:
+            density = _check_per_row("density", density, len(structures), single)
+        if number_density is not None:
+            number_density = _check_per_row("number_density", number_density, len(structures), single)
 
     if model is None:
         model = get_pretrained_model(model_identifier, checkpoint,
@@ -634,7 +679,8 @@ def predict(
     if not predictions:
         raise RuntimeError("Cannot successfully convert any structures.")
     if properties:
-        props = _properties_of_slabs(device_rows, len(structures), failed, directions, single)
+        props = _properties_of_slabs(device_rows, len(structures), failed, directions, single, angles, density,
+                                     number_density, modulus_unit)
     if is_elasticity_tensor:
         try:
             from pymatgen.analysis.elasticity import ElasticTensor
