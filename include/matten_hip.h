@@ -405,6 +405,15 @@ int matten_dense_rows(const float* x, int64_t n_in, const float* q, int64_t n_ou
  *   homogeneous_poisson, universal_anisotropy (5 g_voigt/g_reuss + k_voigt/k_reuss - 6), pugh_ratio (k_vrh/g_vrh);
  *   flags [n] int32: bit 0 = singular or non-finite input, every output of the row is NaN; bit 1 = not positive definite
  *   (un-pivoted LDL^T; the values are still computed; also set on every row with bit 0).
+ * matten_elastic_props_bwd: the adjoint of matten_elastic_props, one crystal per thread, from what the forward wrote.
+ *   voigt, compliance [n,36], props [n,10], flags [n]: as matten_elastic_props returned them.  g_props [n,10], g_voigt
+ *   [n,36], g_compliance [n,36] (fp64): the upstream gradients; g_voigt and g_compliance may each be NULL (= zero).
+ *   g_c [n,81] (layout 0) or [n,36] (layout 1), fp32 (is_fp64 = 0) or fp64 (1): the gradient of the forward's input c, every
+ *   element written.  The scalars' gradients are folded into the Voigt and Reuss bounds, those onto the entries of C and S
+ *   that the forward summed; the inverse gives Cbar -= S^T Sbar S^T (Sbar a general 6x6); last the transpose of the
+ *   symmetrisation (layout 0: the 8-position mean, coinciding positions counted twice; layout 1: (Cbar + Cbar^T)/2).
+ *   A row with flag bit 0 gets zeros whatever the upstream gradients hold (NaN included); a row with bit 1 alone is
+ *   differentiated like any other.  No atomics, no cross-thread traffic: bitwise reproducible.
  * matten_elastic_directional: one workgroup per crystal over unit directions dirs [n_dirs,3] (fp64, n_dirs >= 1).  With
  *   v(n) = (n1^2, n2^2, n3^2, n2 n3, n1 n3, n1 n2): Young's modulus E(n) = 1 / (v^T S v), linear compressibility
  *   beta(n) = sum_I (S_I1 + S_I2 + S_I3) v_I, S = the mean of the two triangles of compliance [n,36].
@@ -434,6 +443,9 @@ int matten_dense_rows(const float* x, int64_t n_in, const float* q, int64_t n_ou
  * ------------------------------------------------------------------------------------------ */
 int matten_elastic_props(const void* c, int is_fp64, int layout, int64_t n, double* voigt, double* compliance,
                          double* props, int32_t* flags, matten_stream_t stream);
+int matten_elastic_props_bwd(const double* voigt, const double* compliance, const double* props, const int32_t* flags,
+                             const double* g_props, const double* g_voigt, const double* g_compliance, int is_fp64,
+                             int layout, int64_t n, void* g_c, matten_stream_t stream);
 int matten_elastic_directional(const double* compliance, const int32_t* flags, const double* dirs, int64_t n,
                                int64_t n_dirs, double* young, double* beta, double* ext, int32_t* arg,
                                matten_stream_t stream);

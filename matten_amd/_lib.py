@@ -107,6 +107,7 @@ SIGNATURES = {
     "matten_segment_minmax_bwd": (c_int, [P, c_int64, P, c_int64, P, P]),
     "matten_dense_rows": (c_int, [P, c_int64, P, c_int64, c_int64, P, P]),
     "matten_elastic_props": (c_int, [P, c_int, c_int, c_int64, P, P, P, P, P]),
+    "matten_elastic_props_bwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int64, P, P]),
     "matten_elastic_directional": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P]),
     "matten_elastic_pair": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P, P, P, P]),
     "matten_elastic_acoustic": (c_int, [P, P, P, P, c_int64, c_int64, ctypes.c_double, P, P, P, P, P]),

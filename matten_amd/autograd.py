@@ -419,6 +419,44 @@ class SegmentMinMaxFn(torch.autograd.Function):
         return ops.segment_minmax_bwd(g.contiguous(), arg, ctx.n), None, None
 
 
+class ElasticPropsFn(torch.autograd.Function):
+    """(voigt, compliance, props, flags) = matten_elastic_props(c) with its adjoint kernel (matten_elastic_props_bwd): the
+    backward works from the four outputs alone, so the input is not kept.  An output that nothing downstream used
+    reaches the kernel as a null pointer, not as a zero tensor; ``flags`` carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, c, layout):
+        voigt, compliance, props, flags = ops.elastic_props(c, layout)
+        ctx.layout, ctx.dtype = layout, c.dtype
+        ctx.save_for_backward(voigt, compliance, props, flags)
+        ctx.mark_non_differentiable(flags)
+        ctx.set_materialize_grads(False)
+        return voigt, compliance, props, flags
+
+    @staticmethod
+    def backward(ctx, g_voigt, g_compliance, g_props, _g_flags):
+        voigt, compliance, props, flags = ctx.saved_tensors
+        if g_props is None:
+            g_props = torch.zeros_like(props)
+        return ops.elastic_props_bwd(voigt, compliance, props, flags, g_props, g_voigt, g_compliance, ctx.layout,
+                                     ctx.dtype), None
+
+
+class DenseRowsFn(torch.autograd.Function):
+    """out = x @ q (matten_dense_rows) for a constant q [n_in, n_out]; the adjoint is the same kernel with q^T, which the
+    caller keeps next to q (``qt`` [n_out, n_in])."""
+
+    @staticmethod
+    def forward(ctx, x, q, qt):
+        ctx.save_for_backward(qt)
+        return ops.dense_rows(x, q)
+
+    @staticmethod
+    def backward(ctx, g):
+        (qt,) = ctx.saved_tensors
+        return ops.dense_rows(g.contiguous(), qt), None, None
+
+
 def needs_grad(*tensors: Optional[torch.Tensor]) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 

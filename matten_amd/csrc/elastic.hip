@@ -1,5 +1,6 @@
 // Derived elastic properties of predicted elasticity tensors (include/matten_hip.h, "Derived elastic properties").
 //   elastic_props_kernel       : Voigt matrix, compliance, the ten scalar moduli and the flags   reference predict.py:217-218
+//   elastic_props_bwd_kernel   : its adjoint (gradients of the scalars, the Voigt matrix and the compliance -> the input)
 //   elastic_directional_kernel : Young's modulus and linear compressibility over a direction set, with their extremes
 //   elastic_pair_kernel        : shear modulus and Poisson's ratio over pairs of perpendicular directions, with their extremes
 //   elastic_acoustic_kernel    : the three acoustic phase velocities per direction (Christoffel equation), their extremes
@@ -164,6 +165,114 @@ __global__ void __launch_bounds__(64) elastic_props_kernel(const T* __restrict__
 #pragma unroll
     for (int q = 0; q < 10; ++q) props[b * 10 + q] = ok ? P[q] : nan;
     flags[b] = (ok ? 0 : 1) | (pd ? 0 : 2);
+}
+
+// The adjoint of elastic_props_kernel, one crystal per thread, from what the forward wrote (voigt = the symmetrised C,
+// compliance = S, props, flags): upstream gradients of the ten scalars and, optionally, of voigt and compliance -> the
+// gradient of the input tensor.  The chain: scalars -> (K, G of the VRH means) -> the four Voigt / Reuss bounds -> the
+// entries of C and S the forward summed; S = C^-1 as a general 6x6 gives Cbar -= S^T Sbar S^T; the symmetrisation is
+// linear, its transpose spreads H = (Cbar + Cbar^T) / 2 over the positions it averaged.  Only S and one temporary
+// T = Sbar S^T stay live (Sbar is made a row at a time, Cbar an entry at a time).  The stored voigt enters no derivative
+// (every scalar is linear in C or a function of S and the stored scalars), so the entry checks it and the kernel does not
+// take it.  A row with flag bit 0 gets zeros by selects: its NaN never reaches the output.
+template <typename T, int LAYOUT>
+__global__ void __launch_bounds__(64) elastic_props_bwd_kernel(const double* __restrict__ compliance,
+                                                               const double* __restrict__ props,
+                                                               const int32_t* __restrict__ flags,
+                                                               const double* __restrict__ g_props,
+                                                               const double* __restrict__ g_voigt,
+                                                               const double* __restrict__ g_compliance, int64_t n,
+                                                               T* __restrict__ g_c) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    const bool bad = (flags[b] & 1) != 0;
+
+    // ---- the ten scalars' gradients folded into the four bounds, then into the sums the forward took of C and S
+    double P[10], gP[10];
+#pragma unroll
+    for (int q = 0; q < 10; ++q) {
+        P[q] = props[b * 10 + q];
+        gP[q] = g_props[b * 10 + q];
+    }
+    const double K = P[4], G = P[5], D = 3.0 * K + G, inv_d2 = 1.0 / (D * D);
+    const double k_bar = gP[4] + gP[6] * (9.0 * G * G * inv_d2) + gP[7] * (4.5 * G * inv_d2) + gP[9] / G;
+    const double g_bar = gP[5] + gP[6] * (27.0 * K * K * inv_d2) - gP[7] * (4.5 * K * inv_d2) - gP[9] * (K / (G * G));
+    const double kv_bar = gP[0] + 0.5 * k_bar + gP[8] / P[2];
+    const double gv_bar = gP[1] + 0.5 * g_bar + gP[8] * (5.0 / P[3]);
+    const double kr_bar = gP[2] + 0.5 * k_bar - gP[8] * (P[0] / (P[2] * P[2]));
+    const double gr_bar = gP[3] + 0.5 * g_bar - gP[8] * (5.0 * P[1] / (P[3] * P[3]));
+    const double kr2 = kr_bar * (P[2] * P[2]), gr2 = gr_bar * (P[3] * P[3]) / 15.0;
+    const double s_diag_bar = -kr2 - 4.0 * gr2, s_off_bar = -2.0 * kr2 + 4.0 * gr2, s_sh_bar = -3.0 * gr2;
+    const double c_diag_bar = kv_bar / 9.0 + gv_bar / 15.0, c_off_bar = 2.0 * kv_bar / 9.0 - gv_bar / 15.0,
+                 c_sh_bar = 3.0 * gv_bar / 15.0;
+
+    double S[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) S[i][j] = compliance[b * 36 + i * 6 + j];
+    }
+    // an absent upstream gradient is read from a valid row and replaced by zero with a select: no branch around the loads
+    const bool has_gs = g_compliance != nullptr, has_gv = g_voigt != nullptr;
+    const double* gs = (has_gs ? g_compliance : compliance) + b * 36;
+    const double* gv = (has_gv ? g_voigt : compliance) + b * 36;
+    // ---- pass 1: T = Sbar S^T, a row of Sbar at a time (the entries the forward read: diagonal 0..2, the three upper
+    // off-diagonals, diagonal 3..5)
+    double Tm[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double row[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            double v = has_gs ? gs[i * 6 + k] : 0.0;
+            if (i == k) v += i < 3 ? s_diag_bar : s_sh_bar;
+            if (i < k && k < 3) v += s_off_bar;
+            row[k] = v;
+        }
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) acc += row[k] * S[j][k];
+            Tm[i][j] = acc;
+        }
+    }
+    // ---- pass 2: Cbar = g_voigt + (the Voigt bounds' weights) - S^T T and H = (Cbar + Cbar^T) / 2, an entry at a time,
+    // each sent straight through the transpose of the symmetrisation.  Layout 0: the mean over the 8 equivalent
+    // positions, coinciding ones counted twice, gives a position (i,j,k,l) of the pair (I, J) the weight 1 / (n_I n_J)
+    // of H_IJ, n = 1 for a diagonal Cartesian pair (i == j) and 2 otherwise (positions that coincide are written twice
+    // with the same value).  Layout 1: H itself.
+    T* o = g_c + b * (LAYOUT == 0 ? 81 : 36);
+#pragma unroll
+    for (int I = 0; I < 6; ++I) {
+#pragma unroll
+        for (int J = I; J < 6; ++J) {
+            double m_ij = 0.0, m_ji = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                m_ij += S[k][I] * Tm[k][J];
+                m_ji += S[k][J] * Tm[k][I];
+            }
+            double c_ij = has_gv ? gv[I * 6 + J] : 0.0;
+            double c_ji = has_gv ? gv[J * 6 + I] : 0.0;
+            if (I == J) {
+                const double w = I < 3 ? c_diag_bar : c_sh_bar;
+                c_ij += w;
+                c_ji += w;
+            }
+            if (I < J && J < 3) c_ij += c_off_bar;
+            const double h0 = 0.5 * ((c_ij - m_ij) + (c_ji - m_ji));
+            const double h = bad ? 0.0 : h0;
+            if (LAYOUT == 0) {
+                const int i = VI[I], j = VJ[I], k = VI[J], l = VJ[J];
+                const T v = (T)((i == j ? 1.0 : 0.5) * (k == l ? 1.0 : 0.5) * h);
+                o[cart(i, j, k, l)] = v, o[cart(j, i, k, l)] = v, o[cart(i, j, l, k)] = v, o[cart(j, i, l, k)] = v;
+                o[cart(k, l, i, j)] = v, o[cart(k, l, j, i)] = v, o[cart(l, k, i, j)] = v, o[cart(l, k, j, i)] = v;
+            } else {
+                o[I * 6 + J] = o[J * 6 + I] = (T)h;
+            }
+        }
+    }
 }
 
 // (value, direction index) pairs ordered by value, equal values by the lower index: a total order, so the butterfly
@@ -519,6 +628,29 @@ extern "C" int matten_elastic_props(const void* c, int is_fp64, int layout, int6
         if (layout == 0) elastic_props_kernel<float, 0><<<grid, T, 0, stream>>>((const float*)c, n, voigt, compliance, props, flags);
         else elastic_props_kernel<float, 1><<<grid, T, 0, stream>>>((const float*)c, n, voigt, compliance, props, flags);
     }
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_elastic_props_bwd(const double* voigt, const double* compliance, const double* props, const int32_t* flags,
+                                        const double* g_props, const double* g_voigt, const double* g_compliance, int is_fp64,
+                                        int layout, int64_t n, void* g_c, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || (layout != 0 && layout != 1) || (is_fp64 != 0 && is_fp64 != 1)) return MATTEN_EINVAL;
+    if (n == 0) return MATTEN_OK;
+    if (!voigt || !compliance || !props || !flags || !g_props || !g_c) return MATTEN_EINVAL;
+    const int T = 64;
+    const unsigned grid = (unsigned)matten_cdiv(n, T);
+#define BWD_(TYPE, LAYOUT) \
+    elastic_props_bwd_kernel<TYPE, LAYOUT><<<grid, T, 0, stream>>>(compliance, props, flags, g_props, g_voigt, g_compliance, n, (TYPE*)g_c)
+    if (is_fp64) {
+        if (layout == 0) BWD_(double, 0);
+        else BWD_(double, 1);
+    } else {
+        if (layout == 0) BWD_(float, 0);
+        else BWD_(float, 1);
+    }
+#undef BWD_
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }

@@ -5,6 +5,10 @@ The reference ends ``predict`` with ``predictions = [ElasticTensor(t) for t in p
 users read bulk and shear moduli, Young's modulus, Poisson's ratio, the anisotropy index, the compliance tensor and
 directional moduli off that pymatgen object, one Python object per crystal.  Here two kernels
 (``matten_elastic_props`` / ``matten_elastic_directional``, csrc/elastic.hip) compute them for a whole batch in fp64.
+``elastic_properties`` detaches its input; ``elastic_moduli`` / ``elastic_moduli_from_irreps`` give the Voigt matrix, the
+compliance and the ten scalars attached to the autograd graph (``matten_elastic_props_bwd``), and ``ModuliLoss`` is the loss
+to fine-tune a tensor model against scalar moduli.  The directional, pair and acoustic quantities carry no gradient, there
+is no Lightning ``Task`` around the loss, and a host tensor is not differentiated.
 Two more serve what depends on two directions or on the mass density: ``matten_elastic_pair`` (shear modulus and Poisson's
 ratio over pairs of perpendicular directions) and ``matten_elastic_acoustic`` (the Christoffel phase velocities per
 direction, their Debye average and, with a number density, the Debye temperature).
@@ -62,7 +66,7 @@ class ElasticProperties:
 
     def to_dict(self) -> dict:
         """name -> numpy array on the host (None for directional maps that were not kept)"""
-        return {k: (None if getattr(self, k) is None else getattr(self, k).cpu().numpy()) for k in self._names}
+        return {k: (None if getattr(self, k) is None else getattr(self, k).detach().cpu().numpy()) for k in self._names}
 
     def __repr__(self):
         shape = tuple(self.flags.shape)
@@ -323,3 +327,126 @@ def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = 
         _VOIGT_Q[key] = torch.tensor(V, dtype=torch.float32, device=x.device)
     rows = ops.dense_rows(x.to(torch.float32), _VOIGT_Q[key])
     return _from_rows(rows, 1, dirs, keep_directional, single, None, angles, density, number_density, modulus_unit)
+
+
+# ---------------------------------------------------------------------------------------------------
+# differentiable: training on moduli
+# ---------------------------------------------------------------------------------------------------
+def _moduli_fields(rows, layout, single) -> ElasticProperties:
+    from .autograd import ElasticPropsFn
+
+    voigt, compliance, props, flags = ElasticPropsFn.apply(rows, layout)
+    fields = {"voigt": voigt, "compliance": compliance}
+    for q, name in enumerate(PROP_NAMES):
+        fields[name] = props[:, q]
+    fields["flags"] = flags
+    fields["is_stable"] = flags == 0
+    fields["is_singular"] = (flags & FLAG_SINGULAR) != 0
+    if single:
+        fields = {k: v[0] for k, v in fields.items()}
+    return ElasticProperties(**fields)
+
+
+def elastic_moduli(tensors) -> ElasticProperties:
+    """The differentiable ``elastic_properties``: ``tensors`` is a device tensor [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6],
+    fp32 or fp64; ``voigt``, ``compliance`` and the ten scalars of ``PROP_NAMES`` come back attached to its autograd graph
+    (``flags``, ``is_stable``, ``is_singular`` as in ``elastic_properties``).  A row with flag bit 0 is NaN and sends a zero
+    gradient back; an indefinite row is differentiated like any other.  No directional arguments: those quantities carry
+    no gradient."""
+    if not isinstance(tensors, torch.Tensor):
+        raise ValueError("tensors: elastic_moduli differentiates device tensors only; for arrays, lists and host tensors "
+                         "use elastic_properties (no gradient)")
+    if tensors.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"tensors: expected fp32 or fp64, got {tensors.dtype}")
+    shape = tuple(tensors.shape)
+    if shape[-4:] == (3, 3, 3, 3) and len(shape) in (4, 5):
+        layout, single, width = 0, len(shape) == 4, 81
+    elif shape[-2:] == (6, 6) and len(shape) in (2, 3):
+        layout, single, width = 1, len(shape) == 2, 36
+    else:
+        raise ValueError(f"tensors: expected [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], got {shape}")
+    if not tensors.is_cuda:
+        raise ValueError("tensors: elastic_moduli differentiates device tensors only; a host tensor goes through "
+                         "elastic_properties (no gradient)")
+    return _moduli_fields(tensors.reshape(-1, width), layout, single)
+
+
+_VOIGT_QT = {}
+
+
+def elastic_moduli_from_irreps(x, formula: str = "ijkl=jikl=klij") -> ElasticProperties:
+    """The differentiable ``elastic_properties_from_irreps``: ``x`` [B,21] (or [21]) fp32 on the device, usually the model's
+    output with its ``grad_fn``.  The forward is the same ``dense_rows`` with ``voigt_basis``; its adjoint is ``dense_rows``
+    with the transposed basis [36,21]."""
+    from .autograd import DenseRowsFn
+
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
+        raise ValueError("x: expected a tensor [B,21] or [21]")
+    V = voigt_basis(formula)
+    if x.shape[-1] != V.shape[0]:
+        raise ValueError(f"x: expected {V.shape[0]} irreps components per row, got {x.shape[-1]}")
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError("x: elastic_moduli_from_irreps differentiates fp32 device tensors only; a host tensor goes through "
+                         "elastic_properties_from_irreps (no gradient)")
+    single = x.dim() == 1
+    key = (formula, x.device)
+    if key not in _VOIGT_Q:
+        _VOIGT_Q[key] = torch.tensor(V, dtype=torch.float32, device=x.device)
+    if key not in _VOIGT_QT:
+        _VOIGT_QT[key] = _VOIGT_Q[key].t().contiguous()
+    rows = DenseRowsFn.apply(x.reshape(-1, x.shape[-1]), _VOIGT_Q[key], _VOIGT_QT[key])
+    return _moduli_fields(rows, 1, single)
+
+
+class ModuliLoss(torch.nn.Module):
+    """Loss on scalar moduli: ``forward(props, targets)`` with ``props`` an ``ElasticProperties`` (of ``elastic_moduli`` or
+    ``elastic_moduli_from_irreps``) and ``targets`` a dict name -> [B]; the mean of |difference| (``kind="l1"``) or of its
+    square (``"mse"``), weighted per name, over the entries whose row has flag bit 0 clear and whose target is finite.
+    Excluded entries are replaced with ``torch.where``, never multiplied away, so their NaN reaches neither the value nor
+    the gradient; a batch without a single entry gives a zero that is still attached to the graph."""
+
+    def __init__(self, names=("k_vrh", "g_vrh"), weights=None, kind: str = "l1"):
+        super().__init__()
+        names = (names,) if isinstance(names, str) else tuple(names)
+        if not names:
+            raise ValueError("names: at least one property is needed")
+        unknown = [n for n in names if n not in PROP_NAMES]
+        if unknown:
+            raise ValueError(f"names: {unknown} not in {PROP_NAMES}")
+        if len(set(names)) != len(names):
+            raise ValueError(f"names: repeated entry in {names}")
+        if kind not in ("l1", "mse"):
+            raise ValueError(f"kind: expected 'l1' or 'mse', got {kind!r}")
+        if weights is None:
+            weights = {n: 1.0 for n in names}
+        elif isinstance(weights, dict):
+            if set(weights) != set(names):
+                raise ValueError(f"weights: expected one weight for each of {names}, got {sorted(weights)}")
+        else:
+            weights = list(weights)
+            if len(weights) != len(names):
+                raise ValueError(f"weights: expected {len(names)} weights, got {len(weights)}")
+            weights = dict(zip(names, weights))
+        weights = {n: float(weights[n]) for n in names}
+        if not all(np.isfinite(w) and w >= 0.0 for w in weights.values()):
+            raise ValueError(f"weights: expected finite non-negative values, got {weights}")
+        self.names, self.weights, self.kind = names, weights, kind
+
+    def forward(self, props: ElasticProperties, targets: dict) -> torch.Tensor:
+        missing = [n for n in self.names if n not in targets]
+        if missing:
+            raise ValueError(f"targets: no entry for {missing}")
+        row_ok = (props.flags & FLAG_SINGULAR) == 0
+        total, count = None, None
+        for name in self.names:
+            value = getattr(props, name)
+            target = torch.as_tensor(targets[name], dtype=value.dtype, device=value.device)
+            if target.shape != value.shape:
+                raise ValueError(f"targets[{name!r}]: expected shape {tuple(value.shape)}, got {tuple(target.shape)}")
+            use = row_ok & torch.isfinite(target)
+            zero = torch.zeros_like(value)
+            diff = torch.where(use, value, zero) - torch.where(use, target, zero)
+            term = (diff.abs() if self.kind == "l1" else diff * diff).sum() * self.weights[name]
+            total = term if total is None else total + term
+            count = use.sum() if count is None else count + use.sum()
+        return total / count.clamp(min=1).to(total.dtype)

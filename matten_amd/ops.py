@@ -843,6 +843,37 @@ def elastic_props(c, layout: int):
     return voigt, compliance, props, flags
 
 
+def elastic_props_bwd(voigt, compliance, props, flags, g_props, g_voigt, g_compliance, layout: int, dtype):
+    """the adjoint of ``elastic_props``: its four outputs and the upstream gradients g_props [B,10], g_voigt [B,6,6] or
+    None, g_compliance [B,6,6] or None (fp64; None = zero) -> the gradient of c, [B,81] (layout 0) or [B,36] (layout 1) in
+    ``dtype`` (fp32 or fp64); rows with flag bit 0 are zero (matten_elastic_props_bwd)"""
+    lib = _lib.load()
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("dtype: expected fp32 or fp64")
+    if layout not in (0, 1):
+        raise ValueError(f"layout: expected 0 or 1, got {layout}")
+    voigt = _need(voigt, torch.float64, "voigt")
+    compliance = _need(compliance, torch.float64, "compliance")
+    props = _need(props, torch.float64, "props")
+    flags = _need(flags, torch.int32, "flags")
+    g_props = _need(g_props, torch.float64, "g_props")
+    g_voigt = None if g_voigt is None else _need(g_voigt, torch.float64, "g_voigt")
+    g_compliance = None if g_compliance is None else _need(g_compliance, torch.float64, "g_compliance")
+    B = flags.shape[0]
+    if (voigt.shape != (B, 6, 6) or compliance.shape != (B, 6, 6) or props.shape != (B, 10) or g_props.shape != (B, 10)
+            or (g_voigt is not None and g_voigt.shape != (B, 6, 6))
+            or (g_compliance is not None and g_compliance.shape != (B, 6, 6))):
+        raise ValueError(f"expected voigt / compliance / g_voigt / g_compliance [B,6,6], props / g_props [B,10], flags [B]; got "
+                         f"{tuple(voigt.shape)}, {tuple(compliance.shape)}, {tuple(props.shape)}, {tuple(flags.shape)}, "
+                         f"{tuple(g_props.shape)}, {None if g_voigt is None else tuple(g_voigt.shape)}, "
+                         f"{None if g_compliance is None else tuple(g_compliance.shape)}")
+    g_c = torch.empty(B, (81, 36)[layout], dtype=dtype, device=flags.device)
+    _lib.check(lib.matten_elastic_props_bwd(_ptr(voigt), _ptr(compliance), _ptr(props), _ptr(flags), _ptr(g_props),
+                                            _ptr(g_voigt), _ptr(g_compliance), int(dtype == torch.float64), layout, B,
+                                            _ptr(g_c), _stream()), "matten_elastic_props_bwd")
+    return g_c
+
+
 def elastic_directional(compliance, flags, dirs, keep: bool = False):
     """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64 -> (young [B,D] or None, beta [B,D] or
     None, ext [B,4] = E_min, E_max, beta_min, beta_max, arg [B,4] int32) (matten_elastic_directional)"""
