@@ -645,6 +645,24 @@ int matten_segment_reduce_bwd(const float* dy, int64_t dim, const int64_t* ptr, 
  *   atom); the caller scans them into offsets[n_atoms + 1] (exclusive, int64; matten_neighbor_summary with ptr in the
  *   place of pair_ptr gives the read-back); _fill writes edge_index[2,n_edges], edge_cell_shift[n_edges,3] and
  *   num_neigh[n_atoms] (optional).  No CSR is emitted here: matten_csr_build derives it.  n_atoms < 2^32.
+ * matten_neighbor_cells_grid / _bin / _scatter / _count / _fill (reference data/data.py:285-413, same edge contract, the
+ *   same canonical order and bit for bit the list of the rows entries): the rows search with a cell list in front, so
+ *   that a centre atom tests the atoms of at most 27 bins instead of its whole crystal.  The bins only prune which j
+ *   are looked at; whether an image is an edge is decided by the distance test all three routes share.
+ *   _grid (one block per crystal; bound from matten_graph_prep; pbc[B,3] / singular[B] as for matten_graph_prep_pbc,
+ *   NULL: every axis periodic / no singular cell) -> grid[B,8] int32 {bins along the three axes, 1 per open axis, 0, 0},
+ *   grid_f64[B,16] {per axis: the column of the completed inverse, origin, bin width; used on open axes}, n_bins[B]
+ *   int64.  Periodic axis k: nb = floor(1 / (bound_k (1 + 1e-6))) equal bins of frac - floor(frac), one bin when nb < 3.
+ *   Open axis: bins at least r_cut |inv[:, k]| (1 + 1e-6) wide from the crystal's smallest pos . inv[:, k], no wrap.
+ *   A crystal never gets more bins than it has atoms (the axis with the most bins is halved until that holds), so
+ *   the sum of n_bins is at most n_atoms + n_crystals.  The caller scans n_bins into bin_base[B+1] (exclusive).
+ *   _bin -> bin_of[n_atoms] (int32, bin within the crystal) and adds 1 per atom to bin_count[bin_base[B]] (int32,
+ *   zeroed by the caller); the caller scans bin_count into bin_start[bin_base[B] + 1] (exclusive, int32); _scatter ->
+ *   slot_atom[n_atoms] (int32: atom ids bin by bin, in no particular order inside a bin) and returns bin_count to zero.
+ *   _count / _fill: as the rows entries.  _fill ranks the (j, count) records of a row, which a wave keeps in LDS;
+ *   a row with more than matten_neighbor_cells_row_capacity() neighbouring atoms is walked as by the rows entry.
+ *   matten_neighbor_cells_max_axis_bins(): the most bins _grid lays along one axis before the cap at the atom count (the
+ *   host restatement data.graph.cell_grid_host clamps at the same number).  n_atoms < 2^31.
  * ========================================================================================== */
 int matten_graph_prep(const double* pos, const double* cell, const int64_t* ptr, int64_t n_crystals, double r_cut,
                       double* frac, double* bound, int64_t* batch, float* pos_f32, float* cell_f32,
@@ -659,6 +677,26 @@ int matten_neighbor_rows_fill(const double* pos, const double* cell, const int64
                               const double* frac, const double* bound, double r_cut, int64_t n_atoms,
                               const int64_t* offsets, int64_t n_edges, int64_t* edge_index, float* edge_cell_shift,
                               float* num_neigh, matten_stream_t stream);
+int matten_neighbor_cells_row_capacity(void);
+int matten_neighbor_cells_max_axis_bins(void);
+int matten_neighbor_cells_grid(const double* pos, const double* cell, const int64_t* ptr, const double* bound,
+                               const uint8_t* pbc, const int32_t* singular, int64_t n_crystals, double r_cut, int32_t* grid,
+                               double* grid_f64, int64_t* n_bins, matten_stream_t stream);
+int matten_neighbor_cells_bin(const double* pos, const double* frac, const int64_t* batch, const int32_t* grid,
+                              const double* grid_f64, const int64_t* bin_base, int64_t n_atoms, int32_t* bin_of,
+                              int32_t* bin_count, matten_stream_t stream);
+int matten_neighbor_cells_scatter(const int64_t* batch, const int64_t* bin_base, const int32_t* bin_of,
+                                  const int32_t* bin_start, int64_t n_atoms, int32_t* bin_count, int32_t* slot_atom,
+                                  matten_stream_t stream);
+int matten_neighbor_cells_count(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                                const double* frac, const double* bound, const int32_t* grid, const int64_t* bin_base,
+                                const int32_t* bin_of, const int32_t* bin_start, const int32_t* slot_atom, double r_cut,
+                                int64_t n_atoms, int32_t* counts, matten_stream_t stream);
+int matten_neighbor_cells_fill(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                               const double* frac, const double* bound, const int32_t* grid, const int64_t* bin_base,
+                               const int32_t* bin_of, const int32_t* bin_start, const int32_t* slot_atom, double r_cut,
+                               int64_t n_atoms, const int64_t* offsets, int64_t n_edges, int64_t* edge_index,
+                               float* edge_cell_shift, float* num_neigh, matten_stream_t stream);
 int matten_neighbor_count(const double* pos, const double* cell, const int64_t* ptr, const double* frac,
                           const double* bound, const int64_t* pair_ptr, double r_cut, int64_t n_crystals,
                           int64_t max_atoms, int32_t* counts, int32_t* counts_t, matten_stream_t stream);

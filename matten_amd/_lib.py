@@ -97,6 +97,13 @@ SIGNATURES = {
     "matten_graph_prep_pbc": (c_int, [P, P, P, P, c_int64, ctypes.c_double, P, P, P, P, P, P, P, P]),
     "matten_neighbor_rows_count": (c_int, [P, P, P, P, P, P, ctypes.c_double, c_int64, P, P]),
     "matten_neighbor_rows_fill": (c_int, [P, P, P, P, P, P, ctypes.c_double, c_int64, P, c_int64, P, P, P, P]),
+    "matten_neighbor_cells_row_capacity": (c_int, []),
+    "matten_neighbor_cells_max_axis_bins": (c_int, []),
+    "matten_neighbor_cells_grid": (c_int, [P, P, P, P, P, P, c_int64, ctypes.c_double, P, P, P, P]),
+    "matten_neighbor_cells_bin": (c_int, [P, P, P, P, P, P, c_int64, P, P, P]),
+    "matten_neighbor_cells_scatter": (c_int, [P, P, P, P, c_int64, P, P, P]),
+    "matten_neighbor_cells_count": (c_int, [P, P, P, P, P, P, P, P, P, P, P, ctypes.c_double, c_int64, P, P]),
+    "matten_neighbor_cells_fill": (c_int, [P, P, P, P, P, P, P, P, P, P, P, ctypes.c_double, c_int64, P, c_int64, P, P, P, P]),
     "matten_neighbor_count": (c_int, [P, P, P, P, P, P, ctypes.c_double, c_int64, c_int64, P, P, P]),
     "matten_neighbor_summary": (c_int, [P, P, c_int64, P, P]),
     "matten_neighbor_fill": (c_int, [P, P, P, P, P, P, ctypes.c_double, c_int64, c_int64, P, c_int64, P, P, P, P, c_int64,

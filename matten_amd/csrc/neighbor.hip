@@ -36,6 +36,20 @@
 // and call the same pair_walk.  The counting pass writes ONE count per atom; the fill pass recomputes the lane counts,
 // places a chunk's edges with a wave prefix sum plus a running base, and the edges of i come out j-ascending and
 // shift-lexicographic: the canonical order again, with O(N) bookkeeping.  No CSR is emitted on this route.
+//
+// Larger structures still (matten_neighbor_cells_*): the rows walk tests every atom of the crystal, O(n^2) arithmetic.
+// The cells kernels put a cell list in front of the same walk.  Every crystal gets a grid (cells_grid_kernel): along a
+// periodic axis floor(1 / (bound_k (1 + 1e-6))) equal bins of frac - floor(frac) -- an edge has |S_k + df_k| < bound_k,
+// so its atoms lie in the same or in adjacent bins modulo nb; below three bins the axis is one bin and is searched as
+// before, with several images per pair -- and along an open axis bins at least r_cut |inv[:, k]| (1 + 1e-6) wide over
+// the crystal's own extent of pos . inv[:, k] (completed cell), without wrap; never more bins than atoms.  Atoms are
+// counted per bin, the caller scans, atom ids are scattered bin by bin (vector atomics: the order inside a bin is
+// arbitrary).  One wave per centre atom then concatenates its at most 27 neighbouring bins and walks them 64
+// candidates at a time with the unchanged shift_range (unreduced frac difference) + pair_walk: the bins only prune
+// which j are looked at.  Candidates do not arrive in j order, so the fill pass keeps the (j, count) records of the
+// non-empty ones in LDS (CELLS_ROW_CAP per wave) and places a pair's edges behind the counts of the records with a
+// smaller j -- pair_walk emits a pair's images in shift order, so no edge is sorted.  A row with more records than
+// that takes rows_walk.  The list is bit for bit that of the other two routes, run to run.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -71,6 +85,36 @@ __device__ __forceinline__ void complete_two(const double* r0, double* r1, doubl
     unit_cross(r0[0], r0[1], r0[2], r1[0], r1[1], r1[2], r2[0], r2[1], r2[2]);
 }
 
+// The cell the inverse is taken of (header comment): every open-axis row of m is replaced by a unit vector orthogonal
+// to the periodic rows.  Shared by the prologue and by the grid of the cells route.
+__device__ __forceinline__ void complete_open_rows(double* m, bool p0, bool p1, bool p2) {
+    const int n_per = (int)p0 + (int)p1 + (int)p2;
+    if (n_per == 2) {   // the open row: the unit normal of the two periodic ones (cyclic order keeps the handedness)
+        const int o = !p0 ? 0 : (!p1 ? 1 : 2);
+        const double* u = m + 3 * ((o + 1) % 3);
+        const double* v = m + 3 * ((o + 2) % 3);
+        unit_cross(u[0], u[1], u[2], v[0], v[1], v[2], m[3 * o], m[3 * o + 1], m[3 * o + 2]);
+    } else if (n_per == 1) {
+        const int k = p0 ? 0 : (p1 ? 1 : 2);
+        complete_two(m + 3 * k, m + 3 * ((k + 1) % 3), m + 3 * ((k + 2) % 3));
+    } else if (n_per == 0) {
+        for (int k = 0; k < 9; ++k) m[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    }
+}
+
+// inv[3 r + k] = (m^-1)[r][k] in closed form, det = det m: frac_k = pos . inv[:, k]
+__device__ __forceinline__ void cell_inverse(const double* m, double* inv, double& det) {
+    const double ax = m[0], ay = m[1], az = m[2], bx = m[3], by = m[4], bz = m[5], cx = m[6], cy = m[7], cz = m[8];
+    // inv = [b x c, c x a, a x b] (as columns) / det
+    const double c0x = by * cz - bz * cy, c0y = bz * cx - bx * cz, c0z = bx * cy - by * cx;
+    const double c1x = cy * az - cz * ay, c1y = cz * ax - cx * az, c1z = cx * ay - cy * ax;
+    const double c2x = ay * bz - az * by, c2y = az * bx - ax * bz, c2z = ax * by - ay * bx;
+    det = (ax * c0x + ay * c0y) + az * c0z;
+    inv[0] = c0x / det, inv[3] = c0y / det, inv[6] = c0z / det;   // column 0
+    inv[1] = c1x / det, inv[4] = c1y / det, inv[7] = c1z / det;
+    inv[2] = c2x / det, inv[5] = c2y / det, inv[8] = c2z / det;
+}
+
 // PBC = false: matten_graph_prep (three periodic axes).  PBC = true: matten_graph_prep_pbc (header comment); the cell
 // that the model receives (cell_f32) is the caller's, the completed one serves the inverse and nothing else.
 template <bool PBC>
@@ -87,25 +131,10 @@ __global__ __launch_bounds__(64) void graph_prep_kernel(const double* __restrict
     bool p0 = true, p1 = true, p2 = true;
     if (PBC) {
         p0 = pbc[3 * b] != 0, p1 = pbc[3 * b + 1] != 0, p2 = pbc[3 * b + 2] != 0;
-        const int n_per = (int)p0 + (int)p1 + (int)p2;
-        if (n_per == 2) {   // the open row: the unit normal of the two periodic ones (cyclic order keeps the handedness)
-            const int o = !p0 ? 0 : (!p1 ? 1 : 2);
-            const double* u = m + 3 * ((o + 1) % 3);
-            const double* v = m + 3 * ((o + 2) % 3);
-            unit_cross(u[0], u[1], u[2], v[0], v[1], v[2], m[3 * o], m[3 * o + 1], m[3 * o + 2]);
-        } else if (n_per == 1) {
-            const int k = p0 ? 0 : (p1 ? 1 : 2);
-            complete_two(m + 3 * k, m + 3 * ((k + 1) % 3), m + 3 * ((k + 2) % 3));
-        } else if (n_per == 0) {
-            for (int k = 0; k < 9; ++k) m[k] = (k % 4 == 0) ? 1.0 : 0.0;
-        }
+        complete_open_rows(m, p0, p1, p2);
     }
-    const double ax = m[0], ay = m[1], az = m[2], bx = m[3], by = m[4], bz = m[5], cx = m[6], cy = m[7], cz = m[8];
-    // inv = [b x c, c x a, a x b] (as columns) / det
-    const double c0x = by * cz - bz * cy, c0y = bz * cx - bx * cz, c0z = bx * cy - by * cx;
-    const double c1x = cy * az - cz * ay, c1y = cz * ax - cx * az, c1z = cx * ay - cy * ax;
-    const double c2x = ay * bz - az * by, c2y = az * bx - ax * bz, c2z = ax * by - ay * bx;
-    const double det = (ax * c0x + ay * c0y) + az * c0z;
+    double inv[9], det;
+    cell_inverse(m, inv, det);
     if (PBC) {
         // |det| of the completed cell is the volume / area / length of the periodic sub-lattice: the periodic vectors
         // are dependent (or not finite) when it vanishes.  Such a crystal is searched as if open, so that the image
@@ -117,9 +146,9 @@ __global__ __launch_bounds__(64) void graph_prep_kernel(const double* __restrict
         }
         if (bad) p0 = p1 = p2 = false;
     }
-    const double i00 = c0x / det, i10 = c0y / det, i20 = c0z / det;   // column 0
-    const double i01 = c1x / det, i11 = c1y / det, i21 = c1z / det;
-    const double i02 = c2x / det, i12 = c2y / det, i22 = c2z / det;
+    const double i00 = inv[0], i10 = inv[3], i20 = inv[6];   // column 0
+    const double i01 = inv[1], i11 = inv[4], i21 = inv[7];
+    const double i02 = inv[2], i12 = inv[5], i22 = inv[8];
     if (threadIdx.x < 9) cell_f32[9 * b + threadIdx.x] = (float)cl[threadIdx.x];
     if (threadIdx.x == 0) {
         bound[3 * b] = p0 ? r_cut * sqrt((i00 * i00 + i10 * i10) + i20 * i20) : 0.0;
@@ -266,14 +295,12 @@ struct Rows {
     int64_t n_atoms;
 };
 
+// one wave, centre atom i (wave-uniform): every atom of i's crystal in j order.  The whole of the rows route, and the
+// walk the cells route falls back on for a row that outgrows its record buffer.
 template <bool FILL>
-__global__ __launch_bounds__(256) void neighbor_rows_kernel(Rows c, double r_cut, int32_t* __restrict__ counts,
-                                                            const int64_t* __restrict__ offsets,
-                                                            int64_t* __restrict__ edge_index, int64_t n_edges,
-                                                            float* __restrict__ shifts, float* __restrict__ num_neigh) {
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // wave-uniform
-    if (i >= c.n_atoms) return;
+__device__ __forceinline__ void rows_walk(const Rows& c, double r_cut, int64_t i, int lane, int32_t* __restrict__ counts,
+                                          const int64_t* __restrict__ offsets, int64_t* __restrict__ edge_index,
+                                          int64_t n_edges, float* __restrict__ shifts, float* __restrict__ num_neigh) {
     const int64_t b = c.batch[i];
     const int64_t lo = c.ptr[b], hi = c.ptr[b + 1];
     const double* cl = c.cell + 9 * b;
@@ -318,6 +345,274 @@ __global__ __launch_bounds__(256) void neighbor_rows_kernel(Rows c, double r_cut
     if (!FILL) {
         for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
         if (lane == 0) counts[i] = total;
+    }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void neighbor_rows_kernel(Rows c, double r_cut, int32_t* __restrict__ counts,
+                                                            const int64_t* __restrict__ offsets,
+                                                            int64_t* __restrict__ edge_index, int64_t n_edges,
+                                                            float* __restrict__ shifts, float* __restrict__ num_neigh) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // wave-uniform
+    if (i >= c.n_atoms) return;
+    rows_walk<FILL>(c, r_cut, i, lane, counts, offsets, edge_index, n_edges, shifts, num_neigh);
+}
+
+// ---- cells route: the rows walk over the atoms of the neighbouring bins only (header comment) ----
+#define CELLS_ROW_CAP 512        // (j, count) records a wave keeps in LDS: 4 KB per wave, 16 KB per block of four waves
+#define CELLS_MAX_NB (1 << 20)   // bins along one axis before the cap at the atom count
+
+struct Cells {
+    Rows r;
+    const int32_t* grid;        // [B,8] bins along each axis, then 1 where the axis is open (no wrap); two unused
+    const int64_t* bin_base;    // [B+1] first bin of each crystal
+    const int32_t* bin_of;      // [N] bin of each atom, numbered within its crystal, (c0 nb1 + c1) nb2 + c2
+    const int32_t* bin_start;   // [bin_base[B] + 1] first slot of each bin
+    const int32_t* slot_atom;   // [N] atom ids, bin by bin
+};
+
+// bins along a periodic axis: floor(1 / (bound (1 + 1e-6))).  Below three bins the axis collapses to one: with two,
+// c - 1 and c + 1 are the same bin and every candidate would be seen twice.  (A bound that is not finite: one bin.)
+__device__ __forceinline__ int periodic_bins(double bound) {
+    const double q = 1.0 / (bound * (1.0 + 1e-6));
+    return q >= 3.0 ? (q < (double)CELLS_MAX_NB ? (int)q : CELLS_MAX_NB) : 1;
+}
+
+// bin of the coordinate t, counted in bin widths from the grid's origin, clamped to the grid (NaN: bin 0)
+__device__ __forceinline__ int clamp_bin(double t, int nb) { return t >= 1.0 ? (t < (double)nb ? (int)t : nb - 1) : 0; }
+
+// One block per crystal: bins per axis, and for the open axes the coordinate they are laid along.  A periodic axis is
+// binned by frac - floor(frac) in nb equal bins; an open axis by u = pos . inv[:, k] of the completed cell, from the
+// smallest u of the crystal in bins at least r_cut |inv[:, k]| (1 + 1e-6) wide.  |d . inv[:, k]| < r_cut |inv[:, k]| for
+// every edge, so the two atoms of an edge lie in the same or in adjacent bins (modulo nb on a periodic axis).
+__global__ __launch_bounds__(256) void cells_grid_kernel(const double* __restrict__ pos, const double* __restrict__ cell,
+                                                         const int64_t* __restrict__ ptr, const double* __restrict__ bound,
+                                                         const uint8_t* __restrict__ pbc, const int32_t* __restrict__ singular,
+                                                         double r_cut, int32_t* __restrict__ grid, double* __restrict__ gridf,
+                                                         int64_t* __restrict__ n_bins) {
+    __shared__ double red[4][6];
+    const int64_t b = blockIdx.x;
+    double m[9];
+    for (int k = 0; k < 9; ++k) m[k] = cell[9 * b + k];
+    bool per[3] = {true, true, true};
+    if (pbc) per[0] = pbc[3 * b] != 0, per[1] = pbc[3 * b + 1] != 0, per[2] = pbc[3 * b + 2] != 0;
+    if (singular && singular[b]) per[0] = per[1] = per[2] = false;   // searched as if open, as the prologue says
+    const bool any_open = !(per[0] && per[1] && per[2]);
+    double inv[9], det;
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    const int64_t first = ptr[b], last = ptr[b + 1];
+    if (any_open) {   // (block-uniform)
+        complete_open_rows(m, per[0], per[1], per[2]);
+        cell_inverse(m, inv, det);
+        for (int64_t n = first + threadIdx.x; n < last; n += blockDim.x) {
+            const double x = pos[3 * n], y = pos[3 * n + 1], z = pos[3 * n + 2];
+            for (int k = 0; k < 3; ++k) {
+                const double u = (x * inv[k] + y * inv[3 + k]) + z * inv[6 + k];
+                lo[k] = fmin(lo[k], u), hi[k] = fmax(hi[k], u);
+            }
+        }
+        for (int k = 0; k < 3; ++k)
+            for (int off = 32; off > 0; off >>= 1) {
+                lo[k] = fmin(lo[k], __shfl_xor(lo[k], off, 64));
+                hi[k] = fmax(hi[k], __shfl_xor(hi[k], off, 64));
+            }
+        if ((threadIdx.x & 63) == 0)
+            for (int k = 0; k < 3; ++k) red[threadIdx.x >> 6][k] = lo[k], red[threadIdx.x >> 6][3 + k] = hi[k];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    int nb[3], raw[3];
+    double width[3] = {0.0, 0.0, 0.0}, origin[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < 3; ++k) {
+        if (per[k]) {
+            nb[k] = raw[k] = periodic_bins(bound[3 * b + k]);
+            continue;
+        }
+        for (int w = 0; w < 4; ++w) lo[k] = fmin(lo[k], red[w][k]), hi[k] = fmax(hi[k], red[w][3 + k]);
+        width[k] = r_cut * sqrt((inv[k] * inv[k] + inv[3 + k] * inv[3 + k]) + inv[6 + k] * inv[6 + k]) * (1.0 + 1e-6);
+        origin[k] = lo[k];
+        nb[k] = raw[k] = clamp_bin((hi[k] - lo[k]) / width[k], CELLS_MAX_NB - 1) + 1;   // (no atom, NaN: one bin)
+    }
+    // O(N) memory: no more bins than atoms.  The axis with the most bins is halved until that holds.
+    const int64_t cap = last - first > 1 ? last - first : 1;
+    while ((int64_t)nb[0] * nb[1] * nb[2] > cap) {
+        const int k = nb[0] >= nb[1] && nb[0] >= nb[2] ? 0 : (nb[1] >= nb[2] ? 1 : 2);
+        nb[k] = (nb[k] + 1) / 2;
+        if (per[k] && nb[k] < 3) nb[k] = 1;
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!per[k]) width[k] = width[k] * ((double)raw[k] / (double)nb[k]);   // the raw bins still cover the extent
+        grid[8 * b + k] = nb[k];
+        grid[8 * b + 3 + k] = per[k] ? 0 : 1;
+        double* gf = gridf + 16 * b + 5 * k;
+        gf[0] = per[k] ? 0.0 : inv[k], gf[1] = per[k] ? 0.0 : inv[3 + k], gf[2] = per[k] ? 0.0 : inv[6 + k];
+        gf[3] = origin[k], gf[4] = width[k];
+    }
+    grid[8 * b + 6] = grid[8 * b + 7] = 0;
+    gridf[16 * b + 15] = 0.0;
+    n_bins[b] = (int64_t)nb[0] * nb[1] * nb[2];
+}
+
+// SCATTER = false: the bin of every atom, and the number of atoms of every bin (vector atomics).  SCATTER = true, after
+// the caller's scan of those numbers: atom ids bin by bin; the order inside a bin is whatever the atomics produce (the
+// order of the edges is fixed later, by j), and bin_count is back at zero afterwards.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void cells_bin_kernel(const double* __restrict__ pos, const double* __restrict__ frac,
+                                                        const int64_t* __restrict__ batch, const int32_t* __restrict__ grid,
+                                                        const double* __restrict__ gridf, const int64_t* __restrict__ bin_base,
+                                                        int64_t n_atoms, int32_t* __restrict__ bin_of,
+                                                        int32_t* __restrict__ bin_count, const int32_t* __restrict__ bin_start,
+                                                        int32_t* __restrict__ slot_atom) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= n_atoms) return;
+    const int64_t b = batch[n];
+    if (SCATTER) {
+        const int64_t gb = bin_base[b] + bin_of[n];
+        const int left = atomicSub(&bin_count[gb], 1);
+        slot_atom[bin_start[gb] + left - 1] = (int32_t)n;
+        return;
+    }
+    const int32_t* g = grid + 8 * b;
+    int c[3];
+    for (int k = 0; k < 3; ++k) {
+        const double* gf = gridf + 16 * b + 5 * k;
+        double t = 0.0;
+        if (g[k] == 1) {
+        } else if (g[3 + k]) {
+            const double u = (pos[3 * n] * gf[0] + pos[3 * n + 1] * gf[1]) + pos[3 * n + 2] * gf[2];
+            t = (u - gf[3]) / gf[4];
+        } else {
+            const double f = frac[3 * n + k];
+            t = (f - floor(f)) * (double)g[k];
+        }
+        c[k] = clamp_bin(t, g[k]);
+    }
+    const int bin = (c[0] * g[1] + c[1]) * g[2] + c[2];   // (below the crystal's atom count)
+    bin_of[n] = bin;
+    atomicAdd(&bin_count[bin_base[b] + bin], 1);
+}
+
+// the bin at offset o (-1, 0, 1) from bin c along one axis; false where there is none (or it was counted already)
+__device__ __forceinline__ bool neighbour_bin(int c, int o, int nb, int open, int& q) {
+    q = c + o;
+    if (nb == 1) return o == 0;
+    if (open) return q >= 0 && q < nb;
+    q = q < 0 ? q + nb : (q >= nb ? q - nb : q);   // nb >= 3: three distinct bins
+    return true;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void neighbor_cells_kernel(Cells c, double r_cut, int32_t* __restrict__ counts,
+                                                             const int64_t* __restrict__ offsets,
+                                                             int64_t* __restrict__ edge_index, int64_t n_edges,
+                                                             float* __restrict__ shifts, float* __restrict__ num_neigh) {
+    __shared__ int2 rec_all[FILL ? 4 * CELLS_ROW_CAP : 1];
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // wave-uniform
+    if (i >= c.r.n_atoms) return;
+    const int64_t b = c.r.batch[i];
+    const int32_t* g = c.grid + 8 * b;
+    const int n0 = g[0], n1 = g[1], n2 = g[2];
+    const int bi = c.bin_of[i];
+    const int q0 = bi / (n1 * n2), q1 = (bi / n2) % n1, q2 = bi % n2;
+    // lanes 0..26: one neighbouring bin each, its first slot and its length; then the running sum of the lengths
+    int start = 0, len = 0;
+    if (lane < 27) {
+        int a0, a1, a2;
+        bool ok = neighbour_bin(q0, lane / 9 - 1, n0, g[3], a0);
+        ok = neighbour_bin(q1, (lane / 3) % 3 - 1, n1, g[4], a1) && ok;
+        ok = neighbour_bin(q2, lane % 3 - 1, n2, g[5], a2) && ok;
+        if (ok) {
+            const int64_t gb = c.bin_base[b] + ((int64_t)a0 * n1 + a1) * n2 + a2;
+            start = c.bin_start[gb];
+            len = c.bin_start[gb + 1] - start;
+        }
+    }
+    int incl = len;
+    for (int off = 1; off < 32; off <<= 1) {
+        const int v = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += v;
+    }
+    const int n_cand = __shfl(incl, 26, 64);
+
+    const double* cl = c.r.cell + 9 * b;
+    const double bx = c.r.bound[3 * b], by = c.r.bound[3 * b + 1], bz = c.r.bound[3 * b + 2];
+    const double fi[3] = {c.r.frac[3 * i], c.r.frac[3 * i + 1], c.r.frac[3 * i + 2]};
+    const double pi[3] = {c.r.pos[3 * i], c.r.pos[3 * i + 1], c.r.pos[3 * i + 2]};
+    int2* rec = rec_all + (FILL ? (threadIdx.x >> 6) * CELLS_ROW_CAP : 0);
+    int total = 0, n_rec = 0;
+    bool over = false;
+    for (int k0 = 0; k0 < n_cand; k0 += 64) {   // candidates k0 + lane of the concatenated bins; all lanes stay in
+        const int k = k0 + lane;
+        int slot = -1;
+        for (int r = 0; r < 27; ++r) {
+            const int e = __shfl(incl, r, 64), l = __shfl(len, r, 64), s0 = __shfl(start, r, 64);
+            if (k >= e - l && k < e) slot = s0 + (k - (e - l));
+        }
+        const bool live = slot >= 0;
+        const int64_t j = live ? c.slot_atom[slot] : 0;
+        int x0 = 0, x1 = -1, y0 = 0, y1 = -1, z0 = 0, z1 = -1;
+        double pj[3] = {0.0, 0.0, 0.0};
+        if (live) {
+            shift_range(bx, c.r.frac[3 * j] - fi[0], x0, x1);
+            shift_range(by, c.r.frac[3 * j + 1] - fi[1], y0, y1);
+            shift_range(bz, c.r.frac[3 * j + 2] - fi[2], z0, z1);
+            pj[0] = c.r.pos[3 * j], pj[1] = c.r.pos[3 * j + 1], pj[2] = c.r.pos[3 * j + 2];
+        }
+        const int cnt = pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, live && i == j, [](int, int, int) {});
+        if (!FILL) {
+            total += cnt;
+            continue;
+        }
+        const unsigned long long hit = __ballot(cnt > 0);
+        const int n_hit = __popcll(hit);
+        if (n_rec + n_hit > CELLS_ROW_CAP) {   // (wave-uniform)
+            over = true;
+            break;
+        }
+        if (cnt > 0) rec[n_rec + __popcll(hit & ((1ull << lane) - 1ull))] = make_int2((int)j, cnt);
+        n_rec += n_hit;
+    }
+    if (!FILL) {
+        for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
+        if (lane == 0) counts[i] = total;
+        return;
+    }
+    if (over) {   // a row longer than the record buffer: the j-ordered walk over the whole crystal
+        rows_walk<true>(c.r, r_cut, i, lane, nullptr, offsets, edge_index, n_edges, shifts, num_neigh);
+        return;
+    }
+    if (num_neigh && lane == 0) num_neigh[i] = (float)(offsets[i + 1] - offsets[i]);
+    // the records are visible to the wave: LDS is in order per wave, the fences keep the compiler from moving the reads
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // pair_walk emits a pair's images in shift order, so a pair's first edge sits behind the edges of the row's pairs
+    // with a smaller j: rank the records, no edge is sorted
+    const int64_t base = offsets[i];
+    for (int r = lane; r < n_rec; r += 64) {
+        const int2 me = rec[r];
+        int before = 0;
+        for (int q = 0; q < n_rec; ++q) {
+            const int2 o = rec[q];
+            before += o.x < me.x ? o.y : 0;
+        }
+        const int64_t j = me.x;
+        int x0, x1, y0, y1, z0, z1;
+        shift_range(bx, c.r.frac[3 * j] - fi[0], x0, x1);
+        shift_range(by, c.r.frac[3 * j + 1] - fi[1], y0, y1);
+        shift_range(bz, c.r.frac[3 * j + 2] - fi[2], z0, z1);
+        const double pj[3] = {c.r.pos[3 * j], c.r.pos[3 * j + 1], c.r.pos[3 * j + 2]};
+        int64_t out = base + before;
+        pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [&](int sx, int sy, int sz) {
+            edge_index[out] = i;
+            edge_index[n_edges + out] = j;
+            shifts[3 * out] = (float)sx;
+            shifts[3 * out + 1] = (float)sy;
+            shifts[3 * out + 2] = (float)sz;
+            ++out;
+        });
     }
 }
 
@@ -428,6 +723,92 @@ extern "C" int matten_neighbor_rows_fill(const double* pos, const double* cell, 
     Rows c{pos, cell, ptr, batch, frac, bound, n_atoms};
     neighbor_rows_kernel<true><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, nullptr, offsets, edge_index,
                                                                                     n_edges, edge_cell_shift, num_neigh);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_neighbor_cells_row_capacity(void) { return CELLS_ROW_CAP; }
+extern "C" int matten_neighbor_cells_max_axis_bins(void) { return CELLS_MAX_NB; }
+
+extern "C" int matten_neighbor_cells_grid(const double* pos, const double* cell, const int64_t* ptr, const double* bound,
+                                          const uint8_t* pbc, const int32_t* singular, int64_t n_crystals, double r_cut,
+                                          int32_t* grid, double* grid_f64, int64_t* n_bins, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_crystals < 0 || !(r_cut > 0.0) || n_crystals >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
+    if (n_crystals == 0) return MATTEN_OK;
+    if (!pos || !cell || !ptr || !bound || !grid || !grid_f64 || !n_bins) return MATTEN_EINVAL;
+    cells_grid_kernel<<<(unsigned)n_crystals, 256, 0, stream>>>(pos, cell, ptr, bound, pbc, singular, r_cut, grid, grid_f64,
+                                                                n_bins);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+// the cells route numbers atoms and bins in int32
+static int cells_args_ok(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch, const double* frac,
+                         const double* bound, double r_cut, int64_t n_atoms, const int32_t* grid, const int64_t* bin_base,
+                         const int32_t* bin_of, const int32_t* bin_start, const int32_t* slot_atom) {
+    if (!rows_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms) || n_atoms >= ((int64_t)1 << 31)) return 0;
+    return n_atoms == 0 || (grid && bin_base && bin_of && bin_start && slot_atom);
+}
+
+extern "C" int matten_neighbor_cells_bin(const double* pos, const double* frac, const int64_t* batch, const int32_t* grid,
+                                         const double* grid_f64, const int64_t* bin_base, int64_t n_atoms, int32_t* bin_of,
+                                         int32_t* bin_count, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_atoms < 0 || n_atoms >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
+    if (n_atoms == 0) return MATTEN_OK;
+    if (!pos || !frac || !batch || !grid || !grid_f64 || !bin_base || !bin_of || !bin_count) return MATTEN_EINVAL;
+    cells_bin_kernel<false><<<(unsigned)matten_cdiv(n_atoms, 256), 256, 0, stream>>>(pos, frac, batch, grid, grid_f64, bin_base,
+                                                                                   n_atoms, bin_of, bin_count, nullptr, nullptr);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_neighbor_cells_scatter(const int64_t* batch, const int64_t* bin_base, const int32_t* bin_of,
+                                             const int32_t* bin_start, int64_t n_atoms, int32_t* bin_count,
+                                             int32_t* slot_atom, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_atoms < 0 || n_atoms >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
+    if (n_atoms == 0) return MATTEN_OK;
+    if (!batch || !bin_base || !bin_of || !bin_start || !bin_count || !slot_atom) return MATTEN_EINVAL;
+    cells_bin_kernel<true><<<(unsigned)matten_cdiv(n_atoms, 256), 256, 0, stream>>>(
+        nullptr, nullptr, batch, nullptr, nullptr, bin_base, n_atoms, const_cast<int32_t*>(bin_of), bin_count, bin_start, slot_atom);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_neighbor_cells_count(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                                           const double* frac, const double* bound, const int32_t* grid,
+                                           const int64_t* bin_base, const int32_t* bin_of, const int32_t* bin_start,
+                                           const int32_t* slot_atom, double r_cut, int64_t n_atoms, int32_t* counts,
+                                           matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!cells_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms, grid, bin_base, bin_of, bin_start, slot_atom))
+        return MATTEN_EINVAL;
+    if (n_atoms == 0) return MATTEN_OK;
+    if (!counts) return MATTEN_EINVAL;
+    Cells c{Rows{pos, cell, ptr, batch, frac, bound, n_atoms}, grid, bin_base, bin_of, bin_start, slot_atom};
+    neighbor_cells_kernel<false><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, counts, nullptr, nullptr, 0,
+                                                                                      nullptr, nullptr);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_neighbor_cells_fill(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                                          const double* frac, const double* bound, const int32_t* grid,
+                                          const int64_t* bin_base, const int32_t* bin_of, const int32_t* bin_start,
+                                          const int32_t* slot_atom, double r_cut, int64_t n_atoms, const int64_t* offsets,
+                                          int64_t n_edges, int64_t* edge_index, float* edge_cell_shift, float* num_neigh,
+                                          matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!cells_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms, grid, bin_base, bin_of, bin_start, slot_atom) ||
+        n_edges < 0)
+        return MATTEN_EINVAL;
+    if (n_atoms == 0) return MATTEN_OK;
+    if (!offsets || (n_edges > 0 && (!edge_index || !edge_cell_shift))) return MATTEN_EINVAL;
+    Cells c{Rows{pos, cell, ptr, batch, frac, bound, n_atoms}, grid, bin_base, bin_of, bin_start, slot_atom};
+    neighbor_cells_kernel<true><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, nullptr, offsets, edge_index,
+                                                                                     n_edges, edge_cell_shift, num_neigh);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }

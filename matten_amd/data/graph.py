@@ -216,6 +216,77 @@ def rows_min_atoms() -> int:
     return int(os.environ.get("MATTEN_NEIGHBOR_ROWS_MIN_ATOMS", "2048"))
 
 
+def cells_min_atoms() -> int:
+    """Size of the largest structure of a batch from which the rows search gets a cell list in front
+    (matten_neighbor_cells_*: a centre atom tests the atoms of at most 27 bins instead of its whole structure).
+    The default is measured (docs/LAB_NOTES.md, "Graph builder: the cell list"; tools/pbc_graph_bench.py --route, one
+    structure per batch at 5 A, rows ms -> cells ms on one MI355X): the cell list costs five more launches and two scans,
+    so at 2048 atoms it loses (fcc ball 0.30 -> 0.33, periodic supercell 0.22 -> 0.30); at 4096 it wins on both (0.53 ->
+    0.33, 0.34 -> 0.28), by 2-3x at 8000, 7-17x at 32 000 and 27-62x at 100 000 (127 -> 2.0 ms).  4096 is the smallest
+    power of two from which the cells build is not slower on either generator.  Where rows exceed the 512 records of the
+    fill pass (14 A cutoff, ~500 edges per atom) the fallback makes the cells build 1.3x slower than rows at 8000 atoms
+    and 1.3x faster at 32 000.
+    Read per call; the route is taken when the largest structure has at least max(rows_min_atoms(), cells_min_atoms())
+    atoms (``search_route``), so a huge MATTEN_NEIGHBOR_CELLS_MIN_ATOMS switches it off and
+    MATTEN_NEIGHBOR_ROWS_MIN_ATOMS=1 alone still means the rows route."""
+    return int(os.environ.get("MATTEN_NEIGHBOR_CELLS_MIN_ATOMS", "4096"))
+
+
+def search_route(max_atoms: int) -> str:
+    """The search kernels the device builder takes for a batch whose largest structure has ``max_atoms`` atoms:
+    "pair" (one thread per ordered atom pair, emits the CSR), "rows" (one wave per centre atom, O(N) memory) or "cells"
+    (rows behind a cell list, O(N) arithmetic too).  All three yield the same list bit for bit."""
+    if max_atoms < rows_min_atoms():
+        return "pair"
+    return "cells" if max_atoms >= cells_min_atoms() else "rows"
+
+
+CELLS_MAX_NB = 1 << 20   # bins along one axis before the cap at the atom count: matten_neighbor_cells_max_axis_bins()
+                         # (tests/test_cells_host.py holds the two equal)
+
+
+def cell_grid_host(pos: np.ndarray, cell: np.ndarray, pbc, r_cut: float) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (nb [3], bin_of_atom [n]): the grid of the cells route for one structure, restated in numpy; the bin of an atom
+    is (c0 nb[1] + c1) nb[2] + c2 with c_k its index along axis k.
+    Periodic axis k: nb_k = floor(1 / (bound_k (1 + 1e-6))) with bound_k = r_cut |inv[:, k]|, equal bins of
+    frac - floor(frac); below three bins the axis collapses to one (with two, c - 1 and c + 1 are the same bin).
+    Open axis: u = pos . inv[:, k] of the completed cell, bins r_cut |inv[:, k]| (1 + 1e-6) wide from the smallest u, no
+    wrap.  |d . inv[:, k]| < r_cut |inv[:, k]| for every edge, so its two atoms lie in the same or in adjacent bins.
+    The axis with the most bins is halved until the structure has no more bins than atoms."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    pbc = normalize_pbc(pbc)
+    cell = np.zeros((3, 3)) if cell is None else np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    inv = np.linalg.inv(complete_cell(cell, pbc))
+    n = len(pos)
+    u = pos @ inv
+    nb, raw, width, origin = [1] * 3, [1] * 3, [0.0] * 3, [0.0] * 3
+    for k in range(3):
+        b = float(r_cut) * float(np.linalg.norm(inv[:, k]))
+        if pbc[k]:
+            q = 1.0 / (b * (1.0 + 1e-6))
+            nb[k] = raw[k] = min(int(q), CELLS_MAX_NB) if q >= 3.0 else 1
+        else:
+            width[k] = b * (1.0 + 1e-6)
+            origin[k] = float(u[:, k].min()) if n else 0.0
+            q = (float(u[:, k].max()) - origin[k]) / width[k] if n else 0.0
+            nb[k] = raw[k] = (min(int(q), CELLS_MAX_NB - 2) if q >= 1.0 else 0) + 1
+    while nb[0] * nb[1] * nb[2] > max(n, 1):
+        k = int(np.argmax(nb))   # (the first of equals)
+        nb[k] = (nb[k] + 1) // 2
+        if pbc[k] and nb[k] < 3:
+            nb[k] = 1
+    bins = np.zeros((n, 3), dtype=np.int64)
+    for k in range(3):
+        if nb[k] == 1:
+            continue
+        if pbc[k]:
+            t = (u[:, k] - np.floor(u[:, k])) * nb[k]
+        else:
+            t = (u[:, k] - origin[k]) / (width[k] * (raw[k] / nb[k]))
+        bins[:, k] = np.clip(np.floor(t).astype(np.int64), 0, nb[k] - 1)
+    return np.asarray(nb, dtype=np.int64), (bins[:, 0] * nb[1] + bins[:, 1]) * nb[2] + bins[:, 2]
+
+
 def batch_graphs_gpu(structures: Sequence, r_cut: float, device="cuda", y: Optional[Dict[str, torch.Tensor]] = None,
                      ) -> Dict[str, torch.Tensor]:
     """Crystals -> collated batch, with the neighbour search on the GPU (matten_neighbor_count/_fill).
@@ -248,7 +319,8 @@ def batch_graphs_gpu_soa(pos: np.ndarray, cell: np.ndarray, Z: np.ndarray, ptr: 
 
     ``pbc``: [B,3] bools (None: every axis of every crystal periodic); a crystal whose periodic vectors are linearly
     dependent raises ``SingularCells``.  A batch whose largest structure has ``rows_min_atoms()`` atoms or more is
-    searched without per-pair bookkeeping and carries no CSR keys (the forward builds the CSR itself)."""
+    searched without per-pair bookkeeping (``search_route``: the rows or the cells kernels) and carries no CSR keys (the
+    forward builds the CSR itself)."""
     from .. import ops
 
     pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
@@ -300,7 +372,8 @@ def batch_graphs_gpu_soa(pos: np.ndarray, cell: np.ndarray, Z: np.ndarray, ptr: 
     dev = torch.device(device)
     pos_d = torch.from_numpy(pos).to(dev)
     cell_d = torch.from_numpy(cell.reshape(-1, 9)).to(dev)
-    rows = n_crystals > 0 and int(sizes.max()) >= rows_min_atoms()
+    route = search_route(int(sizes.max())) if n_crystals > 0 else "pair"
+    rows = route != "pair"
     if pbc is None and not rows:   # the common path: crystals of ordinary size
         pair_ptr = np.zeros(n_crystals + 1, dtype=np.int64)
         np.cumsum(sizes * sizes, out=pair_ptr[1:])
@@ -333,8 +406,13 @@ def batch_graphs_gpu_soa(pos: np.ndarray, cell: np.ndarray, Z: np.ndarray, ptr: 
                                                                                    summary[2:])
         if rows:
             csr = None
-            edge_index, shifts, num_neigh, first, min_edges, host = ops.neighbor_list_rows(
-                pos_d, cell_d, ptr_d, batch_d, frac_d, bound_d, r_cut, summary)
+            if route == "cells":
+                edge_index, shifts, num_neigh, first, min_edges, host = ops.neighbor_list_cells(
+                    pos_d, cell_d, ptr_d, batch_d, frac_d, bound_d, r_cut, summary,
+                    pbc=None if pbc is None else pbc_d, singular=singular)
+            else:
+                edge_index, shifts, num_neigh, first, min_edges, host = ops.neighbor_list_rows(
+                    pos_d, cell_d, ptr_d, batch_d, frac_d, bound_d, r_cut, summary)
             seg = ptr_d
         else:
             edge_index, shifts, num_neigh, first, min_edges, csr, host = ops.neighbor_list_flagged(

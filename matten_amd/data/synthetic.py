@@ -6,8 +6,9 @@ neighbour shells fall inside the 5 A cutoff (18 neighbours/atom, 1152 edges), Ga
 sigma = 0.02 A, species i.i.d. from ten fcc metals.  Seeded with numpy default_rng(20250711).
 
 Open and partly periodic inputs (seeded too): ``molecules`` (random clusters with a minimum distance, no lattice),
-``fcc_slabs`` (periodic in x and y, open along z) and ``fcc_cluster`` (a ball cut from the fcc lattice, for the large
-cases of the pair-free neighbour search).
+``fcc_slabs`` (periodic in x and y, open along z), ``fcc_cluster`` (a ball cut from the fcc lattice) and
+``fcc_supercell`` (nx x ny x nz conventional cells, optionally sheared: the periodic counterpart) for the large cases of
+the pair-free neighbour search.
 """
 from typing import Dict, List
 
@@ -117,3 +118,23 @@ def fcc_cluster(n_atoms: int, seed: int = OPEN_SEED + 2, a: float = 4.05) -> Dic
     pos = sites[np.sort(order)] + rng.normal(0.0, 0.02, size=(n_atoms, 3))
     return {"cart_coords": pos, "atomic_numbers": rng.choice(FCC_METALS, size=n_atoms).astype(np.int64),
             "pbc": (False, False, False)}
+
+
+def fcc_supercell(nx: int, ny: int, nz: int, a: float = 4.05, seed: int = OPEN_SEED + 3, jitter: float = 0.02,
+                  shear=None) -> Dict[str, np.ndarray]:
+    """nx x ny x nz conventional fcc cells (4 nx ny nz atoms), jittered by `jitter` A: one periodic structure, the same
+    dict as ``fcc_cluster`` plus ``lattice``.  ``shear``: a [3,3] strictly upper-triangular perturbation E of the cell,
+    lattice = diag(nx, ny, nz) a (1 + E), applied to the atoms too (a triclinic cell with the same fractional sites)."""
+    rng = np.random.default_rng(seed)
+    corners = np.stack(np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij"), -1).reshape(-1, 1, 3)
+    basis = 0.5 * np.array([[0.0, 0, 0], [0, 1, 1], [1, 0, 1], [1, 1, 0]])
+    pos = (corners + basis).reshape(-1, 3) * a
+    lattice = np.diag([nx * a, ny * a, nz * a]).astype(np.float64)
+    if shear is not None:
+        strain = np.eye(3) + np.triu(np.asarray(shear, dtype=np.float64).reshape(3, 3), 1)
+        pos, lattice = pos @ strain, lattice @ strain
+    n = len(pos)
+    if jitter:
+        pos = pos + rng.normal(0.0, jitter, size=(n, 3))
+    return {"lattice": lattice, "cart_coords": pos, "atomic_numbers": rng.choice(FCC_METALS, size=n).astype(np.int64),
+            "pbc": (True, True, True)}

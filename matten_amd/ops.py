@@ -1376,3 +1376,77 @@ def neighbor_list_rows(pos64, cell64, ptr, batch, frac, bound, r_cut: float, sum
                                                  float(r_cut), N, _ptr(offsets), E, _ptr(edge_index), _ptr(shifts),
                                                  _ptr(num_neigh), _stream()), "matten_neighbor_rows_fill")
     return edge_index, shifts, num_neigh, offsets, int(min_edges), host
+
+
+def neighbor_cells_row_capacity() -> int:
+    """neighbouring atoms of a centre atom that the cells route's fill pass ranks in LDS; a longer row is walked as on the
+    rows route (matten_neighbor_cells_row_capacity)"""
+    return int(_lib.load().matten_neighbor_cells_row_capacity())
+
+
+def neighbor_list_cells(pos64, cell64, ptr, batch, frac, bound, r_cut: float, summary: torch.Tensor = None, pbc=None,
+                        singular=None):
+    """neighbor_list_rows with a cell list in front (matten_neighbor_cells_grid / _bin / _scatter / _count / _fill): a
+    centre atom tests the atoms of at most 27 bins instead of its whole structure, which makes the search linear in the
+    number of atoms.  The same arguments, the same results bit for bit and the same one read-back as neighbor_list_rows;
+    pbc [B,3] uint8 and singular [B] i32 are ops.graph_prep_pbc's (None: every axis periodic).  Scratch is O(N): about
+    65 bytes per atom."""
+    lib = _lib.load()
+    pos64 = _need(pos64, torch.float64, "pos")
+    cell64 = _need(cell64, torch.float64, "cell")
+    ptr = _need(ptr, torch.int64, "ptr")
+    batch = _need(batch, torch.int64, "batch")
+    frac = _need(frac, torch.float64, "frac")
+    bound = _need(bound, torch.float64, "bound")
+    if pbc is not None:
+        pbc = _need(pbc, torch.uint8, "pbc")
+    if singular is not None:
+        singular = _need(singular, torch.int32, "singular")
+    B, N, dev = ptr.shape[0] - 1, pos64.shape[0], pos64.device
+    if (pbc is not None and pbc.numel() != 3 * B) or (singular is not None and singular.numel() != B):
+        raise ValueError("pbc must hold [B,3] flags, singular [B]")
+    grid = torch.empty(B, 8, dtype=torch.int32, device=dev)
+    grid_f = torch.empty(B, 16, dtype=torch.float64, device=dev)
+    bin_base = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    n_bins = torch.empty(B, dtype=torch.int64, device=dev)
+    with _timed("neighbor_cells_bin"):
+        _lib.check(lib.matten_neighbor_cells_grid(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(bound), _ptr(pbc), _ptr(singular),
+                                                  B, float(r_cut), _ptr(grid), _ptr(grid_f), _ptr(n_bins), _stream()),
+                   "matten_neighbor_cells_grid")
+        torch.cumsum(n_bins, 0, out=bin_base[1:])
+        # a structure has at most as many bins as atoms (one when it is empty): N + B bounds their number without a read-back
+        bin_count = torch.zeros(N + B, dtype=torch.int32, device=dev)
+        bin_start = torch.zeros(N + B + 1, dtype=torch.int32, device=dev)
+        bin_of = torch.empty(N, dtype=torch.int32, device=dev)
+        slot_atom = torch.empty(N, dtype=torch.int32, device=dev)
+        _lib.check(lib.matten_neighbor_cells_bin(_ptr(pos64), _ptr(frac), _ptr(batch), _ptr(grid), _ptr(grid_f), _ptr(bin_base),
+                                                 N, _ptr(bin_of), _ptr(bin_count), _stream()), "matten_neighbor_cells_bin")
+        torch.cumsum(bin_count, 0, dtype=torch.int32, out=bin_start[1:])
+        _lib.check(lib.matten_neighbor_cells_scatter(_ptr(batch), _ptr(bin_base), _ptr(bin_of), _ptr(bin_start), N,
+                                                     _ptr(bin_count), _ptr(slot_atom), _stream()),
+                   "matten_neighbor_cells_scatter")
+    del bin_count, n_bins, grid_f
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    with _timed("neighbor_cells_count"):
+        _lib.check(lib.matten_neighbor_cells_count(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound),
+                                                   _ptr(grid), _ptr(bin_base), _ptr(bin_of), _ptr(bin_start), _ptr(slot_atom),
+                                                   float(r_cut), N, _ptr(counts), _stream()), "matten_neighbor_cells_count")
+    offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    if summary is None:
+        summary = torch.zeros(3, dtype=torch.int64, device=dev)
+    if N:
+        _lib.check(lib.matten_neighbor_summary(_ptr(offsets), _ptr(ptr), B, _ptr(summary), _stream()), "matten_neighbor_summary")
+        host = summary.tolist()   # the one host sync of graph construction
+    else:
+        host = [0, 0, 0]
+    E, min_edges = host[0], host[1]
+    edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
+    shifts = torch.empty(E, 3, dtype=torch.float32, device=dev)
+    num_neigh = torch.empty(N, dtype=torch.float32, device=dev)
+    with _timed("neighbor_cells_fill"):
+        _lib.check(lib.matten_neighbor_cells_fill(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound),
+                                                  _ptr(grid), _ptr(bin_base), _ptr(bin_of), _ptr(bin_start), _ptr(slot_atom),
+                                                  float(r_cut), N, _ptr(offsets), E, _ptr(edge_index), _ptr(shifts),
+                                                  _ptr(num_neigh), _stream()), "matten_neighbor_cells_fill")
+    return edge_index, shifts, num_neigh, offsets, int(min_edges), host
