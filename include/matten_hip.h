@@ -440,6 +440,22 @@ int matten_dense_rows(const float* x, int64_t n_in, const float* q, int64_t n_ou
  *   in index order: bitwise reproducible; NaN with any unstable direction); arg [n,2] int32 = the direction indices of the
  *   two extremes (NaN ignored; -1 if no finite value).  Rows with flag bit 0 or a density that is not positive and finite:
  *   NaN and -1 (n_unstable too).
+ * matten_elastic_directional_bwd: the adjoint of matten_elastic_directional, the same launch shape.  compliance, flags, dirs
+ *   as the forward took them (nothing else is kept: E(n) is made again).  g_young, g_beta [n,n_dirs]: the maps' upstream
+ *   gradients; g_ext [n,4]: those of E_min, E_max, beta_min, beta_max, each sent to the direction arg [n,4] recorded by the
+ *   forward (a subgradient where values tie; an index outside 0..n_dirs-1, the forward's -1 included, adds nothing).  Each
+ *   of g_young, g_beta, g_ext may be NULL (= zero); g_ext needs arg.  g_compliance [n,36], every entry written:
+ *   (H + H^T)/2 with H = sum_d (-gE_d E_d^2 v_d v_d^T + gbeta_d v_d e^T), e = (1,1,1,0,0,0).  Rows with flag bit 0: zeros.
+ * matten_elastic_acoustic_bwd: the adjoint of matten_elastic_acoustic, the same launch shape.  The cyclic Jacobi is run again
+ *   with the rotations accumulated into eigenvectors u_k; with s = modulus_unit / density and v_k = sqrt(lambda_k s),
+ *   w_k = (g_vel_k + [d = arg_0, k = 0] g_ext_0 + [d = arg_1, k = 2] g_ext_1 - 3 g_ext_2 v_k^-4) s / (2 v_k),
+ *   Gbar = sum_k w_k u_k u_k^T, Hc[V(i,j)][V(k,l)] += Gbar_ik n_j n_l over the directions, g_voigt [n,36] = (Hc + Hc^T)/2,
+ *   every entry written.  g_vel [n,n_dirs,3] and g_ext [n,3] (v_slow_min, v_fast_max, sum of v^-3) may each be NULL (= zero);
+ *   g_ext needs arg [n,2].  Rows with flag bit 0 or a density that is not positive and finite: zeros; a direction the
+ *   forward marked unstable contributes nothing.  Exactly degenerate modes: per-mode gradients (g_vel, the extremes) take
+ *   the orthonormal basis Jacobi left (finite; the derivative is undefined there), the sum's gradient does not depend on it.
+ *   Both adjoints: excluded rows and directions are replaced by selects, so a NaN in an upstream gradient there does not
+ *   reach the output; lane-strided partial sums, xor butterfly, waves in index order, no atomics: bitwise reproducible.
  * ------------------------------------------------------------------------------------------ */
 int matten_elastic_props(const void* c, int is_fp64, int layout, int64_t n, double* voigt, double* compliance,
                          double* props, int32_t* flags, matten_stream_t stream);
@@ -455,6 +471,12 @@ int matten_elastic_pair(const double* compliance, const int32_t* flags, const do
 int matten_elastic_acoustic(const double* voigt, const int32_t* flags, const double* density, const double* dirs, int64_t n,
                             int64_t n_dirs, double modulus_unit, double* vel, double* ext, int32_t* arg, int32_t* n_unstable,
                             matten_stream_t stream);
+int matten_elastic_directional_bwd(const double* compliance, const int32_t* flags, const double* dirs, int64_t n,
+                                   int64_t n_dirs, const double* g_young, const double* g_beta, const double* g_ext,
+                                   const int32_t* arg, double* g_compliance, matten_stream_t stream);
+int matten_elastic_acoustic_bwd(const double* voigt, const int32_t* flags, const double* density, const double* dirs,
+                                int64_t n, int64_t n_dirs, double modulus_unit, const double* g_vel, const double* g_ext,
+                                const int32_t* arg, double* g_voigt, matten_stream_t stream);
 
 
 /* ==========================================================================================

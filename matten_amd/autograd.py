@@ -442,6 +442,47 @@ class ElasticPropsFn(torch.autograd.Function):
                                      ctx.dtype), None
 
 
+class ElasticDirectionalFn(torch.autograd.Function):
+    """(young, beta, ext, arg) = matten_elastic_directional(compliance) with its adjoint kernel
+    (matten_elastic_directional_bwd), which works from the compliance and the recorded direction indices alone.  Only the
+    compliance receives a gradient; ``arg`` carries none; an output that nothing downstream used reaches the kernel as a
+    null pointer."""
+
+    @staticmethod
+    def forward(ctx, compliance, flags, dirs, keep):
+        young, beta, ext, arg = ops.elastic_directional(compliance, flags, dirs, keep=keep)
+        ctx.save_for_backward(compliance, flags, dirs, arg)
+        ctx.mark_non_differentiable(arg)
+        ctx.set_materialize_grads(False)
+        return young, beta, ext, arg
+
+    @staticmethod
+    def backward(ctx, g_young, g_beta, g_ext, _g_arg):
+        compliance, flags, dirs, arg = ctx.saved_tensors
+        return ops.elastic_directional_bwd(compliance, flags, dirs, g_young, g_beta, g_ext, arg), None, None, None
+
+
+class ElasticAcousticFn(torch.autograd.Function):
+    """(vel, ext, arg, n_unstable) = matten_elastic_acoustic(voigt) with its adjoint kernel (matten_elastic_acoustic_bwd),
+    which runs the Jacobi sweeps again with eigenvectors.  Only the Voigt matrix receives a gradient (not the density,
+    not the directions); ``arg`` and ``n_unstable`` carry none."""
+
+    @staticmethod
+    def forward(ctx, voigt, flags, density, dirs, modulus_unit, keep):
+        vel, ext, arg, n_unstable = ops.elastic_acoustic(voigt, flags, density, dirs, modulus_unit, keep=keep)
+        ctx.modulus_unit = modulus_unit
+        ctx.save_for_backward(voigt, flags, density, dirs, arg)
+        ctx.mark_non_differentiable(arg, n_unstable)
+        ctx.set_materialize_grads(False)
+        return vel, ext, arg, n_unstable
+
+    @staticmethod
+    def backward(ctx, g_vel, g_ext, _g_arg, _g_unstable):
+        voigt, flags, density, dirs, arg = ctx.saved_tensors
+        return (ops.elastic_acoustic_bwd(voigt, flags, density, dirs, ctx.modulus_unit, g_vel, g_ext, arg), None, None, None,
+                None, None)
+
+
 class DenseRowsFn(torch.autograd.Function):
     """out = x @ q (matten_dense_rows) for a constant q [n_in, n_out]; the adjoint is the same kernel with q^T, which the
     caller keeps next to q (``qt`` [n_out, n_in])."""

@@ -5,6 +5,8 @@
 //   elastic_pair_kernel        : shear modulus and Poisson's ratio over pairs of perpendicular directions, with their extremes
 //   elastic_acoustic_kernel    : the three acoustic phase velocities per direction (Christoffel equation), their extremes
 //                                and the sum of v^-3 of the Debye average
+//   elastic_directional_bwd_kernel, elastic_acoustic_bwd_kernel : the adjoints of those two (gradients of the maps, the
+//                                extremes and the sum of v^-3 -> the compliance / the Voigt matrix)
 // The reference wraps every predicted tensor in pymatgen's ElasticTensor (one Python object per crystal); these kernels
 // compute what its users read off that object.  All arithmetic is fp64; everything is held in registers with compile-time
 // indices, so no kernel here uses scratch memory (hipcc -Rpass-analysis=kernel-resource-usage: DESIGN.md).
@@ -611,6 +613,263 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_kernel(const dou
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// the adjoints of the directional and the acoustic kernel (training on directional moduli, sound velocities and the
+// Debye temperature): the same launch shape as their forwards, lane-strided partial sums of the gradient's distinct
+// entries, combined in a fixed order
+// ---------------------------------------------------------------------------------------------------
+
+// position of (i, j), i <= j, in the row-major upper triangle of a symmetric 6x6 matrix (21 entries)
+__device__ __forceinline__ constexpr int tri6(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }
+
+// The workgroup's sum of NV lane-partial values in a fixed order: an xor butterfly in the wave (a + b = b + a: every
+// lane holds the same bits), then the four waves in index order through LDS.  total[NV] lives in LDS and is complete
+// for every thread on return.  No atomics: bitwise reproducible.
+template <int NV>
+__device__ __forceinline__ void block_sum(double (&a)[NV], double* __restrict__ total, int t) {
+    __shared__ double sh[DIR_THREADS / 64][NV];
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) a[q] += __shfl_xor(a[q], off, 64);
+    }
+    const int wave = t >> 6;
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) sh[wave][q] = a[q];
+    }
+    __syncthreads();
+    if (t < NV) {
+        double s = sh[0][t];
+#pragma unroll
+        for (int w = 1; w < DIR_THREADS / 64; ++w) s += sh[w][t];
+        total[t] = s;
+    }
+    __syncthreads();
+}
+
+// The adjoint of elastic_directional_kernel, one workgroup per crystal, a lane per direction in strides of DIR_THREADS.
+// Nothing but the compliance is kept, so E(n) is made again per direction (the forward's expression: the same bits).
+// With e = (1,1,1,0,0,0):  H = sum_d ( -gE_d E_d^2 v_d v_d^T + gbeta_d v_d e^T ),  g_compliance = (H + H^T) / 2.
+// gE_d = the map's gradient plus the extremes' at the directions the forward recorded (a subgradient where values tie),
+// gbeta_d likewise.  A lane accumulates the 21 distinct entries of the symmetric part and the 6 of sum_d gbeta_d v_d.
+// Absent upstream gradients are skipped by workgroup-uniform branches; a row with flag bit 0 gets zeros, a direction
+// whose E is not finite contributes nothing -- by a select, so a NaN from above does not reach the output.
+__global__ void __launch_bounds__(DIR_THREADS) elastic_directional_bwd_kernel(
+    const double* __restrict__ compliance, const int32_t* __restrict__ flags, const double* __restrict__ dirs, int n_dirs,
+    const double* __restrict__ g_young, const double* __restrict__ g_beta, const double* __restrict__ g_ext,
+    const int32_t* __restrict__ arg, double* __restrict__ g_compliance) {
+    const int64_t b = blockIdx.x;
+    const int t = threadIdx.x;
+    double* out = g_compliance + b * 36;
+    if (flags[b] & 1) {   // (uniform over the workgroup)
+        if (t < 36) out[t] = 0.0;
+        return;
+    }
+    const double* s = compliance + b * 36;
+    double S[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j) S[i][j] = S[j][i] = 0.5 * (s[i * 6 + j] + s[j * 6 + i]);
+    }
+    int at[4] = {-1, -1, -1, -1};            // E_min, E_max, beta_min, beta_max: where, and their upstream gradients
+    double gx[4] = {0.0, 0.0, 0.0, 0.0};
+    if (g_ext) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) at[q] = arg[b * 4 + q], gx[q] = g_ext[b * 4 + q];
+    }
+
+    double acc[27];
+#pragma unroll
+    for (int q = 0; q < 27; ++q) acc[q] = 0.0;
+    for (int d = t; d < n_dirs; d += DIR_THREADS) {
+        const double n1 = dirs[d * 3 + 0], n2 = dirs[d * 3 + 1], n3 = dirs[d * 3 + 2];
+        const double v[6] = {n1 * n1, n2 * n2, n3 * n3, n2 * n3, n1 * n3, n1 * n2};
+        double q = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            double row = 0.0;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) row += S[i][j] * v[j];
+            q += v[i] * row;
+        }
+        const double E = 1.0 / q;
+        double gE = 0.0, gb = 0.0;
+        if (g_young) gE = g_young[b * n_dirs + d];
+        if (g_beta) gb = g_beta[b * n_dirs + d];
+        gE += d == at[0] ? gx[0] : 0.0;
+        gE += d == at[1] ? gx[1] : 0.0;
+        gb += d == at[2] ? gx[2] : 0.0;
+        gb += d == at[3] ? gx[3] : 0.0;
+        const double a0 = -gE * (E * E);
+        const double a = finite64(E) ? a0 : 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+#pragma unroll
+            for (int j = i; j < 6; ++j) acc[tri6(i, j)] += a * (v[i] * v[j]);
+            acc[21 + i] += gb * v[i];
+        }
+    }
+    __shared__ double total[27];
+    block_sum<27>(acc, total, t);
+    if (t < 36) {
+        const int i = t / 6, j = t - 6 * i;
+        const double sym = total[i <= j ? tri6(i, j) : tri6(j, i)];
+        const double h_ij = sym + (j < 3 ? total[21 + i] : 0.0), h_ji = sym + (i < 3 ? total[21 + j] : 0.0);
+        out[t] = 0.5 * (h_ij + h_ji);
+    }
+}
+
+// jacobi_rotate with the rotation accumulated into the eigenvectors: the same arithmetic on the matrix (so the eigenvalues
+// are the forward's, bit for bit), then columns p and q of U turned by the same (sn, tau)
+__device__ __forceinline__ void jacobi_rotate_vec(double& app, double& aqq, double& apq, double& arp, double& arq, double& u0p,
+                                                  double& u0q, double& u1p, double& u1q, double& u2p, double& u2q) {
+    const double theta = (aqq - app) / (2.0 * apq);
+    double tn = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));   // (theta^2 = inf: 0)
+    tn = apq == 0.0 ? 0.0 : tn;
+    const double c = 1.0 / sqrt(tn * tn + 1.0), sn = tn * c, tau = sn / (1.0 + c);
+    const double h = tn * apq;
+    app -= h;
+    aqq += h;
+    apq = 0.0;
+    const double g = arp, f = arq;
+    arp = g - sn * (f + g * tau);
+    arq = f + sn * (g - f * tau);
+    const double g0 = u0p, f0 = u0q, g1 = u1p, f1 = u1q, g2 = u2p, f2 = u2q;
+    u0p = g0 - sn * (f0 + g0 * tau);
+    u0q = f0 + sn * (g0 - f0 * tau);
+    u1p = g1 - sn * (f1 + g1 * tau);
+    u1q = f1 + sn * (g1 - f1 * tau);
+    u2p = g2 - sn * (f2 + g2 * tau);
+    u2q = f2 + sn * (g2 - f2 * tau);
+}
+
+// one comparator of the sorting network: (value, eigenvector column) pairs exchanged by selects where lp > lq
+__device__ __forceinline__ void sort_pair(double& lp, double& lq, double& u0p, double& u0q, double& u1p, double& u1q,
+                                          double& u2p, double& u2q) {
+    const bool sw = lp > lq;
+    const double a = lp, b = lq, a0 = u0p, b0 = u0q, a1 = u1p, b1 = u1q, a2 = u2p, b2 = u2q;
+    lp = sw ? b : a, lq = sw ? a : b;
+    u0p = sw ? b0 : a0, u0q = sw ? a0 : b0;
+    u1p = sw ? b1 : a1, u1q = sw ? a1 : b1;
+    u2p = sw ? b2 : a2, u2q = sw ? a2 : b2;
+}
+
+// The adjoint of elastic_acoustic_kernel, one workgroup per crystal, a lane per direction in strides of DIR_THREADS.
+// Gamma and its Jacobi sweeps are run again with the eigenvectors u_k; with s = modulus_unit / rho, v_k = sqrt(lambda_k s):
+//   w_k = (g_vel_k + [slowest here] g_ext_0 + [fastest here] g_ext_1 - 3 g_ext_2 v_k^-4) s / (2 v_k),
+//   Gbar = sum_k w_k u_k u_k^T,   Hc[V[i][j]][V[k][l]] += Gbar_ik n_j n_l  (symmetric: 21 distinct entries per lane),
+//   g_voigt = (Hc + Hc^T) / 2 = Hc.
+// Exactly degenerate modes: the per-mode terms take whatever orthonormal basis Jacobi left (finite, basis-dependent as
+// the derivative itself is undefined); the sum_inv_v3 term weights the modes by one function of lambda and is
+// basis-independent.  A row with flag bit 0 or a density that is not positive and finite gets zeros; a direction the
+// forward marked unstable contributes nothing -- by a select on its whole contribution.
+__global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_bwd_kernel(
+    const double* __restrict__ voigt, const int32_t* __restrict__ flags, const double* __restrict__ density,
+    const double* __restrict__ dirs, int n_dirs, double modulus_unit, const double* __restrict__ g_vel,
+    const double* __restrict__ g_ext, const int32_t* __restrict__ arg, double* __restrict__ g_voigt) {
+    const int64_t b = blockIdx.x;
+    const int t = threadIdx.x;
+    double* out = g_voigt + b * 36;
+    const double rho = density[b];
+    if ((flags[b] & 1) || !(rho > 0.0) || !finite64(rho)) {   // (uniform over the workgroup)
+        if (t < 36) out[t] = 0.0;
+        return;
+    }
+    const double* cp = voigt + b * 36;
+    double C[6][6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j) C[i][j] = C[j][i] = 0.5 * (cp[i * 6 + j] + cp[j * 6 + i]);
+    }
+    constexpr int V[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}};   // Cartesian pair -> Voigt index
+    const double scale = modulus_unit / rho;
+    int at_slow = -1, at_fast = -1;
+    double gx_slow = 0.0, gx_fast = 0.0, gx_sum = 0.0;
+    if (g_ext) {
+        at_slow = arg[b * 2 + 0], at_fast = arg[b * 2 + 1];
+        gx_slow = g_ext[b * 3 + 0], gx_fast = g_ext[b * 3 + 1], gx_sum = g_ext[b * 3 + 2];
+    }
+
+    double acc[21];
+#pragma unroll
+    for (int q = 0; q < 21; ++q) acc[q] = 0.0;
+    for (int d = t; d < n_dirs; d += DIR_THREADS) {
+        const double n[3] = {dirs[d * 3 + 0], dirs[d * 3 + 1], dirs[d * 3 + 2]};
+        double G[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int k = i; k < 3; ++k) {
+                double g = 0.0;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+#pragma unroll
+                    for (int l = 0; l < 3; ++l) g += C[V[i][j]][V[k][l]] * (n[j] * n[l]);
+                }
+                G[i][k] = g;
+            }
+        }
+        double a00 = G[0][0], a11 = G[1][1], a22 = G[2][2], a01 = G[0][1], a02 = G[0][2], a12 = G[1][2];
+        double u00 = 1.0, u01 = 0.0, u02 = 0.0, u10 = 0.0, u11 = 1.0, u12 = 0.0, u20 = 0.0, u21 = 0.0, u22 = 1.0;
+#pragma unroll
+        for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+            jacobi_rotate_vec(a00, a11, a01, a02, a12, u00, u01, u10, u11, u20, u21);   // (p, q, r) = (0, 1, 2)
+            jacobi_rotate_vec(a00, a22, a02, a01, a12, u00, u02, u10, u12, u20, u22);   //             (0, 2, 1)
+            jacobi_rotate_vec(a11, a22, a12, a01, a02, u01, u02, u11, u12, u21, u22);   //             (1, 2, 0)
+        }
+        const bool ok = a00 > 0.0 && a11 > 0.0 && a22 > 0.0 && finite64(a00) && finite64(a11) && finite64(a22);
+        sort_pair(a00, a11, u00, u01, u10, u11, u20, u21);
+        sort_pair(a11, a22, u01, u02, u11, u12, u21, u22);
+        sort_pair(a00, a11, u00, u01, u10, u11, u20, u21);
+        const double lam[3] = {a00, a11, a22};
+        const double U[3][3] = {{u00, u01, u02}, {u10, u11, u12}, {u20, u21, u22}};   // column k = u_k
+        double w[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double vk = sqrt(lam[k] * scale), v2 = vk * vk;
+            double g = 0.0;
+            if (g_vel) g = g_vel[(b * n_dirs + d) * 3 + k];
+            if (k == 0) g += d == at_slow ? gx_slow : 0.0;
+            if (k == 2) g += d == at_fast ? gx_fast : 0.0;
+            w[k] = (g - 3.0 * gx_sum / (v2 * v2)) * (scale / (2.0 * vk));
+        }
+        double Gb[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int k = i; k < 3; ++k)
+                Gb[i][k] = Gb[k][i] = (w[0] * (U[i][0] * U[k][0]) + w[1] * (U[i][1] * U[k][1])) + w[2] * (U[i][2] * U[k][2]);
+        }
+        double h[21];
+#pragma unroll
+        for (int q = 0; q < 21; ++q) h[q] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+#pragma unroll
+                    for (int l = 0; l < 3; ++l) {
+                        if (V[i][j] <= V[k][l]) h[tri6(V[i][j], V[k][l])] += Gb[i][k] * (n[j] * n[l]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 21; ++q) acc[q] += ok ? h[q] : 0.0;
+    }
+    __shared__ double total[21];
+    block_sum<21>(acc, total, t);
+    if (t < 36) {
+        const int i = t / 6, j = t - 6 * i;
+        out[t] = total[i <= j ? tri6(i, j) : tri6(j, i)];   // Hc is symmetric: (Hc + Hc^T) / 2 is Hc itself
+    }
+}
+
 }  // namespace
 
 extern "C" int matten_elastic_props(const void* c, int is_fp64, int layout, int64_t n, double* voigt, double* compliance,
@@ -692,6 +951,32 @@ extern "C" int matten_elastic_acoustic(const double* voigt, const int32_t* flags
     if (!voigt || !flags || !density || !dirs || !ext || !arg || !n_unstable) return MATTEN_EINVAL;
     elastic_acoustic_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(voigt, flags, density, dirs, (int)n_dirs, modulus_unit, vel,
                                                                      ext, arg, n_unstable);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_elastic_directional_bwd(const double* compliance, const int32_t* flags, const double* dirs, int64_t n,
+                                              int64_t n_dirs, const double* g_young, const double* g_beta, const double* g_ext,
+                                              const int32_t* arg, double* g_compliance, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || n > 0x7fffffff || (g_ext && !arg)) return MATTEN_EINVAL;
+    if (n == 0) return MATTEN_OK;
+    if (!compliance || !flags || !dirs || !g_compliance) return MATTEN_EINVAL;
+    elastic_directional_bwd_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(compliance, flags, dirs, (int)n_dirs, g_young, g_beta,
+                                                                            g_ext, arg, g_compliance);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_elastic_acoustic_bwd(const double* voigt, const int32_t* flags, const double* density, const double* dirs,
+                                           int64_t n, int64_t n_dirs, double modulus_unit, const double* g_vel,
+                                           const double* g_ext, const int32_t* arg, double* g_voigt, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || n > 0x7fffffff || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || (g_ext && !arg)) return MATTEN_EINVAL;
+    if (n == 0) return MATTEN_OK;
+    if (!voigt || !flags || !density || !dirs || !g_voigt) return MATTEN_EINVAL;
+    elastic_acoustic_bwd_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(voigt, flags, density, dirs, (int)n_dirs, modulus_unit,
+                                                                         g_vel, g_ext, arg, g_voigt);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }

@@ -7,8 +7,12 @@ directional moduli off that pymatgen object, one Python object per crystal.  Her
 (``matten_elastic_props`` / ``matten_elastic_directional``, csrc/elastic.hip) compute them for a whole batch in fp64.
 ``elastic_properties`` detaches its input; ``elastic_moduli`` / ``elastic_moduli_from_irreps`` give the Voigt matrix, the
 compliance and the ten scalars attached to the autograd graph (``matten_elastic_props_bwd``), and ``ModuliLoss`` is the loss
-to fine-tune a tensor model against scalar moduli.  The directional, pair and acoustic quantities carry no gradient, there
-is no Lightning ``Task`` around the loss, and a host tensor is not differentiated.
+to fine-tune a tensor model against scalar moduli.  With ``directions`` / ``density`` / ``number_density`` they attach the
+directional Young's modulus and compressibility, the Christoffel velocities, their extremes, the Debye average and the
+Debye temperature as well (``matten_elastic_directional_bwd`` / ``matten_elastic_acoustic_bwd``), and ``ModuliLoss`` takes
+those names: training on ultrasonic, calorimetric and indentation data.  The pair quantities (shear modulus and Poisson's
+ratio over direction pairs) carry no gradient, neither do directions and densities, there is no Lightning ``Task`` around
+the loss, and a host tensor is not differentiated.
 Two more serve what depends on two directions or on the mass density: ``matten_elastic_pair`` (shear modulus and Poisson's
 ratio over pairs of perpendicular directions) and ``matten_elastic_acoustic`` (the Christoffel phase velocities per
 direction, their Debye average and, with a number density, the Debye temperature).
@@ -26,6 +30,11 @@ from . import o3, ops
 
 PROP_NAMES = ("k_voigt", "g_voigt", "k_reuss", "g_reuss", "k_vrh", "g_vrh", "y_mod", "homogeneous_poisson",
               "universal_anisotropy", "pugh_ratio")
+# the [B] directional and acoustic quantities that ``elastic_moduli`` attaches to the graph and ``ModuliLoss`` accepts, with
+# the argument of ``elastic_moduli`` that produces each
+DIRECTIONAL_NAMES = {"young_min": "directions", "young_max": "directions", "compressibility_min": "directions",
+                     "compressibility_max": "directions", "v_slow_min": "density", "v_fast_max": "density",
+                     "v_mean": "density", "debye_temperature": "number_density"}
 FLAG_SINGULAR, FLAG_NOT_POSITIVE_DEFINITE, FLAG_FAILED_STRUCTURE = 1, 2, 4
 
 # Voigt index -> Cartesian pair, pymatgen's order
@@ -229,6 +238,26 @@ def _upload(rows):
     return rows.contiguous()
 
 
+def _directional_fields(young, beta, ext, arg, dirs) -> dict:
+    """the outputs of the directional kernel under their field names"""
+    return dict(young=young, compressibility=beta,
+                young_min=ext[:, 0], young_max=ext[:, 1], young_argmin=arg[:, 0], young_argmax=arg[:, 1],
+                compressibility_min=ext[:, 2], compressibility_max=ext[:, 3],
+                compressibility_argmin=arg[:, 2], compressibility_argmax=arg[:, 3], directions=dirs)
+
+
+def _acoustic_fields(vel, ext, arg, n_unstable, n_dirs: int, number_density) -> dict:
+    """the outputs of the acoustic kernel under their field names, with the Debye average and temperature (torch
+    expressions on the sum of v^-3)"""
+    fields = dict(velocities=vel, v_slow_min=ext[:, 0], v_fast_max=ext[:, 1], v_slow_min_direction=arg[:, 0],
+                  v_fast_max_direction=arg[:, 1], sum_inv_v3=ext[:, 2],
+                  v_mean=(ext[:, 2] / (3.0 * n_dirs)) ** (-1.0 / 3.0), acoustic_unstable_directions=n_unstable)
+    if number_density is not None:
+        n_at = torch.as_tensor(number_density, dtype=torch.float64).to(ext.device)
+        fields["debye_temperature"] = (HBAR / K_B) * (6.0 * np.pi ** 2 * n_at) ** (1.0 / 3.0) * fields["v_mean"]
+    return fields
+
+
 def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, failed=None, angles=None, density=None,
                number_density=None, modulus_unit: float = 1e9) -> ElasticProperties:
     """rows on the device -> ElasticProperties; ``dirs``: unit vectors out of ``check_directions`` (host) or None;
@@ -244,11 +273,7 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
     fields["is_singular"] = (flags & FLAG_SINGULAR) != 0
     if dirs is not None:
         dirs = torch.from_numpy(np.ascontiguousarray(dirs)).to(rows.device)
-        young, beta, ext, arg = ops.elastic_directional(compliance, flags, dirs, keep=keep_directional)
-        fields.update(young=young, compressibility=beta,
-                      young_min=ext[:, 0], young_max=ext[:, 1], young_argmin=arg[:, 0], young_argmax=arg[:, 1],
-                      compressibility_min=ext[:, 2], compressibility_max=ext[:, 3],
-                      compressibility_argmin=arg[:, 2], compressibility_argmax=arg[:, 3], directions=dirs)
+        fields.update(_directional_fields(*ops.elastic_directional(compliance, flags, dirs, keep=keep_directional), dirs))
     if angles is not None:
         M = int(angles)
         table = angle_table(M)
@@ -262,13 +287,8 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
             fields[name] = None if maps is None else maps[:, :, q]
     if density is not None:
         rho = torch.as_tensor(density, dtype=torch.float64).to(rows.device)
-        vel, ext, arg, n_unstable = ops.elastic_acoustic(voigt, flags, rho, dirs, modulus_unit, keep=keep_directional)
-        fields.update(velocities=vel, v_slow_min=ext[:, 0], v_fast_max=ext[:, 1], v_slow_min_direction=arg[:, 0],
-                      v_fast_max_direction=arg[:, 1], sum_inv_v3=ext[:, 2],
-                      v_mean=(ext[:, 2] / (3.0 * dirs.shape[0])) ** (-1.0 / 3.0), acoustic_unstable_directions=n_unstable)
-        if number_density is not None:
-            n_at = torch.as_tensor(number_density, dtype=torch.float64).to(rows.device)
-            fields["debye_temperature"] = (HBAR / K_B) * (6.0 * np.pi ** 2 * n_at) ** (1.0 / 3.0) * fields["v_mean"]
+        fields.update(_acoustic_fields(*ops.elastic_acoustic(voigt, flags, rho, dirs, modulus_unit, keep=keep_directional),
+                                       dirs.shape[0], number_density))
     if single:
         fields = {k: (v if v is None or k in ("directions", "angles") else v[0]) for k, v in fields.items()}
     return ElasticProperties(**fields)
@@ -332,8 +352,10 @@ def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = 
 # ---------------------------------------------------------------------------------------------------
 # differentiable: training on moduli
 # ---------------------------------------------------------------------------------------------------
-def _moduli_fields(rows, layout, single) -> ElasticProperties:
-    from .autograd import ElasticPropsFn
+def _moduli_fields(rows, layout, single, dirs=None, keep_directional=False, density=None, number_density=None,
+                   modulus_unit: float = 1e9) -> ElasticProperties:
+    """``_from_rows`` attached to the autograd graph (no pair quantities): the same kernels, so the same bits"""
+    from .autograd import ElasticAcousticFn, ElasticDirectionalFn, ElasticPropsFn
 
     voigt, compliance, props, flags = ElasticPropsFn.apply(rows, layout)
     fields = {"voigt": voigt, "compliance": compliance}
@@ -342,17 +364,45 @@ def _moduli_fields(rows, layout, single) -> ElasticProperties:
     fields["flags"] = flags
     fields["is_stable"] = flags == 0
     fields["is_singular"] = (flags & FLAG_SINGULAR) != 0
+    if dirs is not None:
+        dirs = torch.from_numpy(np.ascontiguousarray(dirs)).to(rows.device)
+        fields.update(_directional_fields(*ElasticDirectionalFn.apply(compliance, flags, dirs, bool(keep_directional)), dirs))
+    if density is not None:
+        rho = torch.as_tensor(density, dtype=torch.float64).to(rows.device)
+        fields.update(_acoustic_fields(*ElasticAcousticFn.apply(voigt, flags, rho, dirs, float(modulus_unit),
+                                                                bool(keep_directional)), dirs.shape[0], number_density))
     if single:
-        fields = {k: v[0] for k, v in fields.items()}
+        fields = {k: (v if v is None or k == "directions" else v[0]) for k, v in fields.items()}
     return ElasticProperties(**fields)
 
 
-def elastic_moduli(tensors) -> ElasticProperties:
+def _check_moduli_extras(directions, angles, density, number_density, B: int, single: bool):
+    """the directional arguments of ``elastic_moduli*``, validated as ``elastic_properties`` does, before anything touches
+    the device -> (dirs, density, number_density)"""
+    if angles is not None:
+        raise ValueError("angles: the pair quantities carry no gradient (shear modulus and Poisson's ratio over direction "
+                         "pairs); use elastic_properties for them")
+    _check_extras(directions, None, density, number_density)
+    dirs = None if directions is None else check_directions(directions)
+    if density is not None:
+        density = _check_per_row("density", density, B, single)
+    if number_density is not None:
+        number_density = _check_per_row("number_density", number_density, B, single)
+    return dirs, density, number_density
+
+
+def elastic_moduli(tensors, directions=None, keep_directional: bool = False, density=None, number_density=None,
+                   modulus_unit: float = 1e9, angles=None) -> ElasticProperties:
     """The differentiable ``elastic_properties``: ``tensors`` is a device tensor [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6],
     fp32 or fp64; ``voigt``, ``compliance`` and the ten scalars of ``PROP_NAMES`` come back attached to its autograd graph
     (``flags``, ``is_stable``, ``is_singular`` as in ``elastic_properties``).  A row with flag bit 0 is NaN and sends a zero
-    gradient back; an indefinite row is differentiated like any other.  No directional arguments: those quantities carry
-    no gradient."""
+    gradient back; an indefinite row is differentiated like any other.  ``directions``, ``keep_directional``, ``density``,
+    ``number_density`` and ``modulus_unit`` are those of ``elastic_properties`` (same validation, same values bit for
+    bit); with them ``young_min`` / ``young_max``, ``compressibility_min`` / ``compressibility_max``, ``v_slow_min``,
+    ``v_fast_max``, ``sum_inv_v3``, ``v_mean``, ``debye_temperature`` and, when kept, the maps ``young`` / ``compressibility``
+    / ``velocities`` are attached too (``DIRECTIONAL_NAMES``); an extreme's gradient is that of the direction where it was
+    found, an acoustically unstable direction contributes nothing.  The directions and densities receive no gradient.
+    ``angles`` is refused: the pair quantities carry no gradient."""
     if not isinstance(tensors, torch.Tensor):
         raise ValueError("tensors: elastic_moduli differentiates device tensors only; for arrays, lists and host tensors "
                          "use elastic_properties (no gradient)")
@@ -365,19 +415,23 @@ def elastic_moduli(tensors) -> ElasticProperties:
         layout, single, width = 1, len(shape) == 2, 36
     else:
         raise ValueError(f"tensors: expected [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], got {shape}")
+    B = 1 if single else shape[0]
+    dirs, density, number_density = _check_moduli_extras(directions, angles, density, number_density, B, single)
     if not tensors.is_cuda:
         raise ValueError("tensors: elastic_moduli differentiates device tensors only; a host tensor goes through "
                          "elastic_properties (no gradient)")
-    return _moduli_fields(tensors.reshape(-1, width), layout, single)
+    return _moduli_fields(tensors.reshape(-1, width), layout, single, dirs, keep_directional, density, number_density,
+                          modulus_unit)
 
 
 _VOIGT_QT = {}
 
 
-def elastic_moduli_from_irreps(x, formula: str = "ijkl=jikl=klij") -> ElasticProperties:
+def elastic_moduli_from_irreps(x, formula: str = "ijkl=jikl=klij", directions=None, keep_directional: bool = False,
+                               density=None, number_density=None, modulus_unit: float = 1e9, angles=None) -> ElasticProperties:
     """The differentiable ``elastic_properties_from_irreps``: ``x`` [B,21] (or [21]) fp32 on the device, usually the model's
     output with its ``grad_fn``.  The forward is the same ``dense_rows`` with ``voigt_basis``; its adjoint is ``dense_rows``
-    with the transposed basis [36,21]."""
+    with the transposed basis [36,21].  The directional arguments are those of ``elastic_moduli``."""
     from .autograd import DenseRowsFn
 
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
@@ -385,23 +439,28 @@ def elastic_moduli_from_irreps(x, formula: str = "ijkl=jikl=klij") -> ElasticPro
     V = voigt_basis(formula)
     if x.shape[-1] != V.shape[0]:
         raise ValueError(f"x: expected {V.shape[0]} irreps components per row, got {x.shape[-1]}")
+    single = x.dim() == 1
+    dirs, density, number_density = _check_moduli_extras(directions, angles, density, number_density,
+                                                         1 if single else x.shape[0], single)
     if not x.is_cuda or x.dtype != torch.float32:
         raise ValueError("x: elastic_moduli_from_irreps differentiates fp32 device tensors only; a host tensor goes through "
                          "elastic_properties_from_irreps (no gradient)")
-    single = x.dim() == 1
     key = (formula, x.device)
     if key not in _VOIGT_Q:
         _VOIGT_Q[key] = torch.tensor(V, dtype=torch.float32, device=x.device)
     if key not in _VOIGT_QT:
         _VOIGT_QT[key] = _VOIGT_Q[key].t().contiguous()
     rows = DenseRowsFn.apply(x.reshape(-1, x.shape[-1]), _VOIGT_Q[key], _VOIGT_QT[key])
-    return _moduli_fields(rows, 1, single)
+    return _moduli_fields(rows, 1, single, dirs, keep_directional, density, number_density, modulus_unit)
 
 
 class ModuliLoss(torch.nn.Module):
     """Loss on scalar moduli: ``forward(props, targets)`` with ``props`` an ``ElasticProperties`` (of ``elastic_moduli`` or
     ``elastic_moduli_from_irreps``) and ``targets`` a dict name -> [B]; the mean of |difference| (``kind="l1"``) or of its
     square (``"mse"``), weighted per name, over the entries whose row has flag bit 0 clear and whose target is finite.
+    ``names`` come from ``PROP_NAMES`` and ``DIRECTIONAL_NAMES`` (directional extremes, sound velocities, the Debye
+    temperature: ``props`` must have been made with the directional arguments); an entry of the latter whose value is not
+    finite (a row with acoustically unstable directions, say) is excluded as well.
     Excluded entries are replaced with ``torch.where``, never multiplied away, so their NaN reaches neither the value nor
     the gradient; a batch without a single entry gives a zero that is still attached to the graph."""
 
@@ -410,9 +469,9 @@ class ModuliLoss(torch.nn.Module):
         names = (names,) if isinstance(names, str) else tuple(names)
         if not names:
             raise ValueError("names: at least one property is needed")
-        unknown = [n for n in names if n not in PROP_NAMES]
+        unknown = [n for n in names if n not in PROP_NAMES and n not in DIRECTIONAL_NAMES]
         if unknown:
-            raise ValueError(f"names: {unknown} not in {PROP_NAMES}")
+            raise ValueError(f"names: {unknown} not in {PROP_NAMES + tuple(DIRECTIONAL_NAMES)}")
         if len(set(names)) != len(names):
             raise ValueError(f"names: repeated entry in {names}")
         if kind not in ("l1", "mse"):
@@ -439,11 +498,16 @@ class ModuliLoss(torch.nn.Module):
         row_ok = (props.flags & FLAG_SINGULAR) == 0
         total, count = None, None
         for name in self.names:
-            value = getattr(props, name)
+            value = getattr(props, name, None)
+            if value is None:
+                raise ValueError(f"props: no {name!r}; pass {DIRECTIONAL_NAMES[name]} to elastic_moduli / "
+                                 f"elastic_moduli_from_irreps")
             target = torch.as_tensor(targets[name], dtype=value.dtype, device=value.device)
             if target.shape != value.shape:
                 raise ValueError(f"targets[{name!r}]: expected shape {tuple(value.shape)}, got {tuple(target.shape)}")
             use = row_ok & torch.isfinite(target)
+            if name in DIRECTIONAL_NAMES:      # e.g. a row with acoustically unstable directions, a bad density
+                use = use & torch.isfinite(value.detach())
             zero = torch.zeros_like(value)
             diff = torch.where(use, value, zero) - torch.where(use, target, zero)
             term = (diff.abs() if self.kind == "l1" else diff * diff).sum() * self.weights[name]

@@ -941,6 +941,79 @@ def elastic_acoustic(voigt, flags, density, dirs, modulus_unit: float = 1e9, kee
     return vel, ext, arg, n_unstable
 
 
+def _opt_grad(g, shape, name: str):
+    """an optional fp64 upstream gradient: None stays None (a null pointer for the kernel)"""
+    if g is None:
+        return None
+    g = _need(g, torch.float64, name)
+    if g.shape != shape:
+        raise ValueError(f"{name}: expected {tuple(shape)}, got {tuple(g.shape)}")
+    return g
+
+
+def elastic_directional_bwd(compliance, flags, dirs, g_young=None, g_beta=None, g_ext=None, arg=None) -> torch.Tensor:
+    """the adjoint of ``elastic_directional``: its inputs, the upstream gradients g_young / g_beta [B,D] and g_ext [B,4] (fp64;
+    None = zero) and the forward's arg [B,4] int32 (needed with g_ext) -> the gradient of compliance [B,6,6]; rows with
+    flag bit 0 are zero (matten_elastic_directional_bwd)"""
+    lib = _lib.load()
+    compliance = _need(compliance, torch.float64, "compliance")
+    flags = _need(flags, torch.int32, "flags")
+    dirs = _need(dirs, torch.float64, "dirs")
+    B = flags.shape[0]
+    if compliance.shape != (B, 6, 6) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
+        raise ValueError(f"expected compliance [B,6,6], flags [B], dirs [D>=1,3]; got {tuple(compliance.shape)}, "
+                         f"{tuple(flags.shape)}, {tuple(dirs.shape)}")
+    D = dirs.shape[0]
+    g_young = _opt_grad(g_young, (B, D), "g_young")
+    g_beta = _opt_grad(g_beta, (B, D), "g_beta")
+    g_ext = _opt_grad(g_ext, (B, 4), "g_ext")
+    if g_ext is not None:
+        if arg is None:
+            raise ValueError("arg: the extremes' gradient g_ext needs the direction indices the forward returned")
+        arg = _need(arg, torch.int32, "arg")
+        if arg.shape != (B, 4):
+            raise ValueError(f"arg: expected {(B, 4)}, got {tuple(arg.shape)}")
+    else:
+        arg = None
+    g_compliance = torch.empty(B, 6, 6, dtype=torch.float64, device=dirs.device)
+    _lib.check(lib.matten_elastic_directional_bwd(_ptr(compliance), _ptr(flags), _ptr(dirs), B, D, _ptr(g_young), _ptr(g_beta),
+                                                  _ptr(g_ext), _ptr(arg), _ptr(g_compliance), _stream()),
+               "matten_elastic_directional_bwd")
+    return g_compliance
+
+
+def elastic_acoustic_bwd(voigt, flags, density, dirs, modulus_unit: float = 1e9, g_vel=None, g_ext=None, arg=None) -> torch.Tensor:
+    """the adjoint of ``elastic_acoustic``: its inputs, the upstream gradients g_vel [B,D,3] and g_ext [B,3] (v_slow_min,
+    v_fast_max, sum of v^-3; fp64; None = zero) and the forward's arg [B,2] int32 (needed with g_ext) -> the gradient of
+    voigt [B,6,6]; rows with flag bit 0 or a bad density are zero, unstable directions add nothing
+    (matten_elastic_acoustic_bwd)"""
+    lib = _lib.load()
+    voigt = _need(voigt, torch.float64, "voigt")
+    flags = _need(flags, torch.int32, "flags")
+    density = _need(density, torch.float64, "density")
+    dirs = _need(dirs, torch.float64, "dirs")
+    B = flags.shape[0]
+    if voigt.shape != (B, 6, 6) or density.shape != (B,) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
+        raise ValueError(f"expected voigt [B,6,6], flags [B], density [B], dirs [D>=1,3]; got {tuple(voigt.shape)}, "
+                         f"{tuple(flags.shape)}, {tuple(density.shape)}, {tuple(dirs.shape)}")
+    D = dirs.shape[0]
+    g_vel = _opt_grad(g_vel, (B, D, 3), "g_vel")
+    g_ext = _opt_grad(g_ext, (B, 3), "g_ext")
+    if g_ext is not None:
+        if arg is None:
+            raise ValueError("arg: the extremes' gradient g_ext needs the direction indices the forward returned")
+        arg = _need(arg, torch.int32, "arg")
+        if arg.shape != (B, 2):
+            raise ValueError(f"arg: expected {(B, 2)}, got {tuple(arg.shape)}")
+    else:
+        arg = None
+    g_voigt = torch.empty(B, 6, 6, dtype=torch.float64, device=dirs.device)
+    _lib.check(lib.matten_elastic_acoustic_bwd(_ptr(voigt), _ptr(flags), _ptr(density), _ptr(dirs), B, D, float(modulus_unit),
+                                               _ptr(g_vel), _ptr(g_ext), _ptr(arg), _ptr(g_voigt), _stream()),
+               "matten_elastic_acoustic_bwd")
+    return g_voigt
+
+
 # ---------------------------------------------------------------------------------------------------
 # adjoint operators (training step)
 # ---------------------------------------------------------------------------------------------------
