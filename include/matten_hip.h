@@ -456,6 +456,28 @@ int matten_dense_rows(const float* x, int64_t n_in, const float* q, int64_t n_ou
  *   the orthonormal basis Jacobi left (finite; the derivative is undefined there), the sum's gradient does not depend on it.
  *   Both adjoints: excluded rows and directions are replaced by selects, so a NaN in an upstream gradient there does not
  *   reach the output; lane-strided partial sums, xor butterfly, waves in index order, no atomics: bitwise reproducible.
+ * matten_elastic_refine (predict.py:217-218: the extremes pymatgen's users read are as good as their grid; ELATE polishes its
+ *   grid's winners in the same way): the extremes of matten_elastic_directional and matten_elastic_pair refined off the grid,
+ *   one thread per item = q n + b (extreme-major), q = 0..3 E_min, E_max, beta_min, beta_max from ext_dir / arg_dir [n,4],
+ *   q = 4..7 G_min, G_max, nu_min, nu_max from ext_pair / arg_pair [n,4] (only with n_angles >= 1; n_angles = 0: four
+ *   extremes, cos_sin / ext_pair / arg_pair are not read and may be NULL).  dirs [n_dirs,3] and cos_sin [n_angles,2] are the
+ *   tables the two kernels took; the start pair is n = dirs[d], m = cos(chi_k) e1 + sin(chi_k) e2 in the frame above (k = 0
+ *   for E and beta).  E, G, nu: F(w) = +-f(R(w) n, R(w) m), R(w) the rotation by |w| about w, is maximised by a damped Newton
+ *   iteration: the gradient at w = 0 is n x dF/dn + m x dF/dm (analytic), the Hessian the symmetric part of that gradient's
+ *   central differences over rotations by +-2^-14 rad about the three axes, diagonalised by cyclic Jacobi; every eigenvalue
+ *   is clamped to min(lambda, -1e-3 max|lambda|), the step capped at 0.3 rad and accepted only if the value strictly
+ *   improves, else damped (doubling, from 1e-3 max|lambda|, 30 tries) and tried again; (n, m) are made orthonormal again
+ *   after every step.  It stops when |gradient| <= tol |f| (nu: tol max(|f|, 1)), after max_iter accepted steps, or when no
+ *   damped step improves the value any more (stationary to fp64: converged if |gradient| <= max(tol, 1e-7) |f|).
+ *   beta(n) = n^T B n, B_ij = sum_k S_ijkk: the extreme eigenvalues of B with their eigenvectors (cyclic Jacobi), no
+ *   iteration.  A result that rounding left behind the grid's value gives way to the grid's value and pair.
+ *   Outputs, all extreme-major with Q = 4 or 8: value [Q,n]; vec_n, vec_m [Q,n,3] unit and perpendicular (m of E and beta
+ *   is some perpendicular without meaning; the overall sign of either is unspecified); iterations [Q,n] int32 accepted
+ *   steps; status [Q,n] int32: 0 converged, 1 iteration cap reached (the value is still no worse than the grid's: every
+ *   accepted step improves), 2 not refined (flag bit 1: E and nu have poles; grid value and grid pair copied, 0
+ *   iterations), -1 flag bit 0 or no grid winner (NaN).  The result is the stationary point of the basin the grid's
+ *   winner lies in.  No atomics, no cross-lane traffic, nothing read back: bitwise reproducible, each row independent of the
+ *   others, capturable.  tol > 0 finite, max_iter >= 0.
  * ------------------------------------------------------------------------------------------ */
 int matten_elastic_props(const void* c, int is_fp64, int layout, int64_t n, double* voigt, double* compliance,
                          double* props, int32_t* flags, matten_stream_t stream);
@@ -477,6 +499,10 @@ int matten_elastic_directional_bwd(const double* compliance, const int32_t* flag
 int matten_elastic_acoustic_bwd(const double* voigt, const int32_t* flags, const double* density, const double* dirs,
                                 int64_t n, int64_t n_dirs, double modulus_unit, const double* g_vel, const double* g_ext,
                                 const int32_t* arg, double* g_voigt, matten_stream_t stream);
+int matten_elastic_refine(const double* compliance, const int32_t* flags, const double* dirs, const double* cos_sin,
+                          const double* ext_dir, const int32_t* arg_dir, const double* ext_pair, const int32_t* arg_pair,
+                          int64_t n, int64_t n_dirs, int64_t n_angles, double tol, int64_t max_iter, double* value,
+                          double* vec_n, double* vec_m, int32_t* status, int32_t* iterations, matten_stream_t stream);
 
 
 /* ==========================================================================================

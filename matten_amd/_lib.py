@@ -120,6 +120,8 @@ SIGNATURES = {
     "matten_elastic_acoustic": (c_int, [P, P, P, P, c_int64, c_int64, ctypes.c_double, P, P, P, P, P]),
     "matten_elastic_directional_bwd": (c_int, [P, P, P, c_int64, c_int64, P, P, P, P, P, P]),
     "matten_elastic_acoustic_bwd": (c_int, [P, P, P, P, c_int64, c_int64, ctypes.c_double, P, P, P, P, P]),
+    "matten_elastic_refine": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, ctypes.c_double, c_int64, P, P, P, P, P,
+                                      P]),
 }
 
 _lib = None

@@ -870,6 +870,275 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_bwd_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// refinement of the grid's extremes (elastic_properties(refine=True)): the winners of the directional and the pair kernel
+// polished off the grid.  matten_amd/elastic.py:refine_extremes_host is the same iteration in numpy.
+// ---------------------------------------------------------------------------------------------------
+struct V3 {
+    double x, y, z;
+};
+__device__ __forceinline__ V3 cross3(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ double dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 add3(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3 scale3(double c, V3 a) { return {c * a.x, c * a.y, c * a.z}; }
+
+__device__ __forceinline__ void matvec6(const double (&S)[6][6], const double (&x)[6], double (&y)[6]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double row = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) row += S[i][j] * x[j];
+        y[i] = row;
+    }
+}
+__device__ __forceinline__ double dot6(const double (&a)[6], const double (&b)[6]) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s += a[i] * b[i];
+    return s;
+}
+// A(a) x with the symmetric A(a) = [[2 a0, a5, a4], [a5, 2 a1, a3], [a4, a3, 2 a2]]: a . v(n) = n^T A(a) n / 2 and
+// a . w(n,m) = n^T A(a) m, so A(a) x is the derivative of either
+__device__ __forceinline__ V3 sym_apply(const double (&a)[6], V3 x) {
+    return {2.0 * a[0] * x.x + a[5] * x.y + a[4] * x.z, a[5] * x.x + 2.0 * a[1] * x.y + a[3] * x.z,
+            a[4] * x.x + a[3] * x.y + 2.0 * a[2] * x.z};
+}
+
+// kind 0: E(n), 1: G(n,m), 2: nu(n,m) (the definitions above elastic_pair_kernel) with df/dn and df/dm, n and m taken as
+// independent vectors
+__device__ __forceinline__ void refine_eval(int kind, const double (&S)[6][6], V3 n, V3 m, double& f, V3& dn, V3& dm) {
+    if (kind == 1) {
+        const double w[6] = {2.0 * n.x * m.x, 2.0 * n.y * m.y, 2.0 * n.z * m.z, n.y * m.z + n.z * m.y, n.x * m.z + n.z * m.x,
+                             n.x * m.y + n.y * m.x};
+        double Sw[6];
+        matvec6(S, w, Sw);
+        f = 1.0 / dot6(w, Sw);
+        const double c = -2.0 * f * f;
+        dn = scale3(c, sym_apply(Sw, m));
+        dm = scale3(c, sym_apply(Sw, n));
+        return;
+    }
+    const double v[6] = {n.x * n.x, n.y * n.y, n.z * n.z, n.y * n.z, n.x * n.z, n.x * n.y};
+    double Sv[6];
+    matvec6(S, v, Sv);
+    const double q = dot6(v, Sv);
+    if (kind == 0) {
+        f = 1.0 / q;
+        dn = scale3(-2.0 * f * f, sym_apply(Sv, n));
+        dm = {0.0, 0.0, 0.0};
+        return;
+    }
+    const double vm[6] = {m.x * m.x, m.y * m.y, m.z * m.z, m.y * m.z, m.x * m.z, m.x * m.y};
+    double Svm[6];
+    matvec6(S, vm, Svm);
+    const double p = dot6(Sv, vm);
+    f = -p / q;
+    dn = add3(scale3(-1.0 / q, sym_apply(Svm, n)), scale3(2.0 * p / (q * q), sym_apply(Sv, n)));
+    dm = scale3(-1.0 / q, sym_apply(Sv, m));
+}
+
+// F = sign f at the pair and its gradient over rotations of the pair, n x dF/dn + m x dF/dm
+__device__ __forceinline__ void refine_grad(int kind, double sign, const double (&S)[6][6], V3 n, V3 m, double& F, V3& g) {
+    double f;
+    V3 dn, dm;
+    refine_eval(kind, S, n, m, f, dn, dm);
+    F = sign * f;
+    g = scale3(sign, add3(cross3(n, dn), cross3(m, dm)));
+}
+
+// R(w) x = x + a (w x x) + b (w x (w x x)), a = sin|w| / |w|, b = (1 - cos|w|) / |w|^2 (Rodrigues)
+__device__ __forceinline__ void rot_coeff(V3 w, double& a, double& b) {
+    const double t2 = dot3(w, w), t = sqrt(t2), sh = sin(0.5 * t);
+    const bool tiny = t2 < 1e-16;
+    a = tiny ? 1.0 : sin(t) / t;
+    b = tiny ? 0.5 : 2.0 * sh * sh / t2;
+}
+__device__ __forceinline__ V3 rot_apply(V3 w, double a, double b, V3 x) {
+    const V3 wx = cross3(w, x);
+    return add3(x, add3(scale3(a, wx), scale3(b, cross3(w, wx))));
+}
+__device__ __forceinline__ void orthonormal(V3& n, V3& m) {
+    n = scale3(1.0 / sqrt(dot3(n, n)), n);
+    m = add3(m, scale3(-dot3(m, n), n));
+    m = scale3(1.0 / sqrt(dot3(m, m)), m);
+}
+// a column of the gradient's central differences: the rotation e (|e| = h, coefficients a, b) and its opposite
+__device__ __forceinline__ V3 refine_fd(int kind, double sign, const double (&S)[6][6], V3 n, V3 m, V3 e, double a, double b,
+                                        double inv_2h) {
+    const V3 o = {-e.x, -e.y, -e.z};
+    double F;
+    V3 gp, gm;
+    refine_grad(kind, sign, S, rot_apply(e, a, b, n), rot_apply(e, a, b, m), F, gp);
+    refine_grad(kind, sign, S, rot_apply(o, a, b, n), rot_apply(o, a, b, m), F, gm);
+    return {(gp.x - gm.x) * inv_2h, (gp.y - gm.y) * inv_2h, (gp.z - gm.z) * inv_2h};
+}
+
+// the iteration's constants (elastic.py holds the same, with the reasons)
+constexpr double REFINE_FD_STEP = 6.103515625e-05;   // 2^-14 rad
+constexpr double REFINE_MAX_STEP = 0.3;
+constexpr double REFINE_CLAMP = 1e-3;
+constexpr double REFINE_STALL_TOL = 1e-7;
+constexpr int REFINE_DAMP_TRIES = 30;
+constexpr int REFINE_THREADS = 64;
+
+// One thread per (extreme q, crystal b), item = q n + b: a wave works on one kind of extreme (but for the one that holds a
+// boundary).  q = 0..3: E_min, E_max, beta_min, beta_max from the directional kernel's ext / arg; 4..7: G_min, G_max,
+// nu_min, nu_max from the pair kernel's.  The start pair is the winner's n with m = cos(chi_k) e1 + sin(chi_k) e2 in the
+// pair kernel's frame (k = 0 for E and beta).  E, G, nu: F(w) = +-f(R(w) n, R(w) m) is maximised by a damped Newton
+// iteration -- the analytic gradient at w = 0, the Hessian as the symmetric part of that gradient's central differences
+// over rotations about the three axes, diagonalised by cyclic Jacobi, every eigenvalue clamped to the ascent side
+// (min(lambda, -1e-3 max|lambda|), so directions the function does not depend on -- m for E, chi for G at a cubic [100] --
+// and an isotropic tensor are harmless), the step capped at 0.3 rad, accepted only if the value strictly improves, else
+// damped and tried again; the pair is made orthonormal again after every step.  beta = n^T B n: the extreme eigenvalues
+// of B with their eigenvectors, no iteration.  No atomics, no cross-lane traffic, nothing read back: a row's result does
+// not depend on the other rows and is bitwise reproducible.
+__global__ void __launch_bounds__(REFINE_THREADS) elastic_refine_kernel(
+    const double* __restrict__ compliance, const int32_t* __restrict__ flags, const double* __restrict__ dirs, int n_dirs,
+    const double* __restrict__ cos_sin, int n_ang, const double* __restrict__ ext_dir, const int32_t* __restrict__ arg_dir,
+    const double* __restrict__ ext_pair, const int32_t* __restrict__ arg_pair, int64_t n, int n_q, double tol, int max_iter,
+    double* __restrict__ value, double* __restrict__ vec_n, double* __restrict__ vec_m, int32_t* __restrict__ status,
+    int32_t* __restrict__ iterations) {
+    const int64_t item = (int64_t)blockIdx.x * REFINE_THREADS + threadIdx.x;
+    if (item >= n * n_q) return;
+    const int q = (int)(item / n);
+    const int64_t b = item - (int64_t)q * n;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const bool pairq = q >= 4;
+    const int fl = flags[b];
+    const double grid = pairq ? ext_pair[b * 4 + (q - 4)] : ext_dir[b * 4 + q];
+    const int at = pairq ? arg_pair[b * 4 + (q - 4)] : arg_dir[b * 4 + q];
+    const int64_t n_start = pairq ? (int64_t)n_dirs * n_ang : (int64_t)n_dirs;
+
+    double val = nan;
+    V3 n_out = {nan, nan, nan}, m_out = {nan, nan, nan};
+    int st = -1, it = 0;
+    if (!(fl & 1) && at >= 0 && at < n_start) {   // (an index outside the tables is never followed)
+        const int d = pairq ? at / n_ang : at, k = pairq ? at - d * n_ang : 0;
+        const V3 n0 = {dirs[d * 3 + 0], dirs[d * 3 + 1], dirs[d * 3 + 2]};
+        // the pair kernel's frame and its m, expression for expression
+        const double sg = n0.z >= 0.0 ? 1.0 : -1.0;
+        const double fa = -1.0 / (sg + n0.z), fb = n0.x * n0.y * fa;
+        const double e1[3] = {1.0 + sg * n0.x * n0.x * fa, sg * fb, -sg * n0.x};
+        const double e2[3] = {fb, sg + n0.y * n0.y * fa, -n0.y};
+        const double c = pairq ? cos_sin[2 * (int64_t)k] : 1.0, sn = pairq ? cos_sin[2 * (int64_t)k + 1] : 0.0;
+        const V3 m0 = {c * e1[0] + sn * e2[0], c * e1[1] + sn * e2[1], c * e1[2] + sn * e2[2]};
+        const double sign = (q & 1) ? 1.0 : -1.0;
+
+        const double* s = compliance + b * 36;
+        double S[6][6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+#pragma unroll
+            for (int j = i; j < 6; ++j) S[i][j] = S[j][i] = 0.5 * (s[i * 6 + j] + s[j * 6 + i]);
+        }
+
+        V3 nn = n0, mm = m0;
+        if (fl & 2) {   // not positive definite: E and nu have poles, nothing is followed
+            val = grid;
+            st = 2;
+        } else if (q == 2 || q == 3) {
+            double r[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) r[i] = S[i][0] + S[i][1] + S[i][2];
+            double a00 = r[0], a11 = r[1], a22 = r[2], a01 = 0.5 * r[5], a02 = 0.5 * r[4], a12 = 0.5 * r[3];
+            double u00 = 1.0, u01 = 0.0, u02 = 0.0, u10 = 0.0, u11 = 1.0, u12 = 0.0, u20 = 0.0, u21 = 0.0, u22 = 1.0;
+#pragma unroll
+            for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+                jacobi_rotate_vec(a00, a11, a01, a02, a12, u00, u01, u10, u11, u20, u21);   // (p, q, r) = (0, 1, 2)
+                jacobi_rotate_vec(a00, a22, a02, a01, a12, u00, u02, u10, u12, u20, u22);   //             (0, 2, 1)
+                jacobi_rotate_vec(a11, a22, a12, a01, a02, u01, u02, u11, u12, u21, u22);   //             (1, 2, 0)
+            }
+            sort_pair(a00, a11, u00, u01, u10, u11, u20, u21);
+            sort_pair(a11, a22, u01, u02, u11, u12, u21, u22);
+            sort_pair(a00, a11, u00, u01, u10, u11, u20, u21);
+            const bool top = q == 3;
+            val = top ? a22 : a00;
+            nn = top ? V3{u02, u12, u22} : V3{u00, u10, u20};
+            mm = {u01, u11, u21};
+            st = 0;
+        } else {
+            const int kind = q < 2 ? 0 : (q < 6 ? 1 : 2);
+            double ah, bh;
+            rot_coeff({REFINE_FD_STEP, 0.0, 0.0}, ah, bh);
+            const double inv_2h = 1.0 / (2.0 * REFINE_FD_STEP);
+            for (;;) {
+                double F0;
+                V3 g;
+                refine_grad(kind, sign, S, nn, mm, F0, g);
+                val = sign * F0;
+                if (!finite64(F0)) {
+                    val = grid;
+                    st = 2;
+                    break;
+                }
+                const double scale = kind == 2 ? fmax(fabs(F0), 1.0) : fabs(F0);
+                const double gnorm = sqrt(dot3(g, g));
+                if (gnorm <= tol * scale) {
+                    st = 0;
+                    break;
+                }
+                if (it >= max_iter) {
+                    st = 1;
+                    break;
+                }
+                const V3 d0 = refine_fd(kind, sign, S, nn, mm, {REFINE_FD_STEP, 0.0, 0.0}, ah, bh, inv_2h);
+                const V3 d1 = refine_fd(kind, sign, S, nn, mm, {0.0, REFINE_FD_STEP, 0.0}, ah, bh, inv_2h);
+                const V3 d2 = refine_fd(kind, sign, S, nn, mm, {0.0, 0.0, REFINE_FD_STEP}, ah, bh, inv_2h);
+                // H_ij = (D_ij + D_ji) / 2, D_ij = d g_i / d w_j (column j = d_j)
+                double a00 = d0.x, a11 = d1.y, a22 = d2.z, a01 = 0.5 * (d1.x + d0.y), a02 = 0.5 * (d2.x + d0.z),
+                       a12 = 0.5 * (d2.y + d1.z);
+                double u00 = 1.0, u01 = 0.0, u02 = 0.0, u10 = 0.0, u11 = 1.0, u12 = 0.0, u20 = 0.0, u21 = 0.0, u22 = 1.0;
+#pragma unroll
+                for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+                    jacobi_rotate_vec(a00, a11, a01, a02, a12, u00, u01, u10, u11, u20, u21);
+                    jacobi_rotate_vec(a00, a22, a02, a01, a12, u00, u02, u10, u12, u20, u22);
+                    jacobi_rotate_vec(a11, a22, a12, a01, a02, u01, u02, u11, u12, u21, u22);
+                }
+                const double dl = REFINE_CLAMP * fmax(fabs(a00), fmax(fabs(a11), fabs(a22))) + 1e-300;
+                const double l0 = fmin(a00, -dl), l1 = fmin(a11, -dl), l2 = fmin(a22, -dl);
+                const double ug0 = u00 * g.x + u10 * g.y + u20 * g.z, ug1 = u01 * g.x + u11 * g.y + u21 * g.z,
+                             ug2 = u02 * g.x + u12 * g.y + u22 * g.z;
+                double damp = 0.0;
+                bool moved = false;
+                for (int tries = 0; tries < REFINE_DAMP_TRIES; ++tries) {
+                    const double c0 = -ug0 / (l0 - damp), c1 = -ug1 / (l1 - damp), c2 = -ug2 / (l2 - damp);
+                    V3 step = {u00 * c0 + u01 * c1 + u02 * c2, u10 * c0 + u11 * c1 + u12 * c2, u20 * c0 + u21 * c1 + u22 * c2};
+                    const double len = sqrt(dot3(step, step));
+                    step = len > REFINE_MAX_STEP ? scale3(REFINE_MAX_STEP / len, step) : step;
+                    double ra, rb;
+                    rot_coeff(step, ra, rb);
+                    V3 n1 = rot_apply(step, ra, rb, nn), m1 = rot_apply(step, ra, rb, mm);
+                    orthonormal(n1, m1);
+                    double f1;
+                    V3 unused_n, unused_m;
+                    refine_eval(kind, S, n1, m1, f1, unused_n, unused_m);
+                    if (sign * f1 > F0) {
+                        nn = n1, mm = m1, moved = true;
+                        break;
+                    }
+                    damp = fmax(2.0 * damp, dl);
+                }
+                if (!moved) {   // no step improves the value any more: stationary to fp64
+                    st = gnorm <= fmax(tol, REFINE_STALL_TOL) * scale ? 0 : 1;
+                    break;
+                }
+                ++it;
+            }
+        }
+        // rounding alone can leave the result behind the grid's (a constant beta, an isotropic E); a NaN fails the
+        // comparison too: the grid's value and pair then
+        const bool keep = sign * val >= sign * grid;
+        val = keep ? val : grid;
+        n_out = keep ? nn : n0;
+        m_out = keep ? mm : m0;
+    }
+    value[item] = val;
+    vec_n[item * 3 + 0] = n_out.x, vec_n[item * 3 + 1] = n_out.y, vec_n[item * 3 + 2] = n_out.z;
+    vec_m[item * 3 + 0] = m_out.x, vec_m[item * 3 + 1] = m_out.y, vec_m[item * 3 + 2] = m_out.z;
+    status[item] = st;
+    iterations[item] = it;
+}
+
 }  // namespace
 
 extern "C" int matten_elastic_props(const void* c, int is_fp64, int layout, int64_t n, double* voigt, double* compliance,
@@ -977,6 +1246,27 @@ extern "C" int matten_elastic_acoustic_bwd(const double* voigt, const int32_t* f
     if (!voigt || !flags || !density || !dirs || !g_voigt) return MATTEN_EINVAL;
     elastic_acoustic_bwd_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(voigt, flags, density, dirs, (int)n_dirs, modulus_unit,
                                                                          g_vel, g_ext, arg, g_voigt);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_elastic_refine(const double* compliance, const int32_t* flags, const double* dirs, const double* cos_sin,
+                                     const double* ext_dir, const int32_t* arg_dir, const double* ext_pair,
+                                     const int32_t* arg_pair, int64_t n, int64_t n_dirs, int64_t n_angles, double tol,
+                                     int64_t max_iter, double* value, double* vec_n, double* vec_m, int32_t* status,
+                                     int32_t* iterations, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || n > 0x7fffffff / 8 || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || n_angles < 0 || n_angles > 0x7fffffff ||
+        n_dirs * n_angles > 0x7fffffff || !(tol > 0.0) || !(tol <= 1.7976931348623157e308) || max_iter < 0 || max_iter > 0x7fffffff)
+        return MATTEN_EINVAL;
+    if (n == 0) return MATTEN_OK;
+    if (!compliance || !flags || !dirs || !ext_dir || !arg_dir || !value || !vec_n || !vec_m || !status || !iterations)
+        return MATTEN_EINVAL;
+    if (n_angles > 0 && (!cos_sin || !ext_pair || !arg_pair)) return MATTEN_EINVAL;
+    const int n_q = n_angles > 0 ? 8 : 4;
+    elastic_refine_kernel<<<(unsigned)matten_cdiv(n * n_q, REFINE_THREADS), REFINE_THREADS, 0, stream>>>(
+        compliance, flags, dirs, (int)n_dirs, cos_sin, (int)n_angles, ext_dir, arg_dir, ext_pair, arg_pair, n, n_q, tol,
+        (int)max_iter, value, vec_n, vec_m, status, iterations);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }

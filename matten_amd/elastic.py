@@ -22,6 +22,11 @@ Conventions ("Derived elastic properties"): Voigt order xx, yy, 
 the compliance); the input is symmetrised, never trusted.  Every value is in the units of the input tensor -- pymatgen's
 ``y_mod`` alone is multiplied by 1e9 (GPa -> Pa); this module does not copy that.  The velocities (m/s) and the Debye
 temperature (K) alone are SI: ``density`` is kg/m^3, ``number_density`` atoms/m^3, ``modulus_unit`` Pa per unit of the input.
+
+``refine=True`` polishes the grid's directional extremes off the grid (``matten_elastic_refine``: a damped Newton iteration
+over rotations of the pair (n, m) from each grid winner, the compressibility by a 3x3 eigen-decomposition);
+``refine_extremes_host`` states the algorithm in numpy.  ``elastic_moduli*`` do not take it: the refined extremes carry no
+gradient.
 """
 import numpy as np
 import torch
@@ -56,6 +61,10 @@ class ElasticProperties:
     ``poisson_dir_max`` [B,D] when kept.  With ``density`` also ``v_slow_min`` / ``v_fast_max`` [B] (m/s) with their
     ``*_direction``, ``sum_inv_v3``, ``v_mean`` = (sum_inv_v3 / 3D)^(-1/3), ``acoustic_unstable_directions`` [B] int32 and
     ``velocities`` [B,D,3] (ascending) when kept; with ``number_density`` also ``debye_temperature`` [B] (K).
+    With ``refine`` also, for every X of ``young_min`` / ``young_max`` / ``compressibility_min`` / ``compressibility_max`` and
+    (with ``angles``) ``shear_min`` / ``shear_max`` / ``poisson_min`` / ``poisson_max``: ``X_refined`` [B], the extreme off the
+    grid, ``X_refined_n`` [B,3] and (pair quantities) ``X_refined_m`` [B,3] where it is taken, ``X_refined_status`` [B] int32
+    (0 converged, 1 iteration cap, 2 not refined, -1 singular row) and ``X_refined_iterations`` [B] int32.
     An unbatched input ([3,3,3,3] or [6,6]) gives the same without the leading dimension."""
 
     def __init__(self, **fields):
@@ -135,6 +144,258 @@ def split_pair_index(flat, M: int):
         return torch.where(none, flat, d), torch.where(none, flat, flat - d * M)
     flat = np.asarray(flat)
     return np.where(flat < 0, flat, flat // M), np.where(flat < 0, flat, flat % M)
+
+
+# ---------------------------------------------------------------------------------------------------
+# refinement of the directional extremes off the grid (``refine=True``; matten_elastic_refine, csrc/elastic.hip)
+# ---------------------------------------------------------------------------------------------------
+# the refined extremes, in the order of the kernel's items (item = q B + b): the four of the directional kernel's ``ext``,
+# then the four of the pair kernel's
+REFINE_NAMES = ("young_min", "young_max", "compressibility_min", "compressibility_max", "shear_min", "shear_max",
+                "poisson_min", "poisson_max")
+REFINE_CONVERGED, REFINE_ITERATION_CAP, REFINE_NOT_REFINED, REFINE_SINGULAR = 0, 1, 2, -1
+# constants of the iteration, the same in the kernel: the rotation angle of the central differences that give the Hessian
+# from the analytic gradient (truncation h^2 ~ 4e-9, rounding eps / h ~ 4e-12 of the Hessian: Newton stays superlinear), the
+# step cap in rad, the eigenvalue clamp relative to the largest magnitude, the damped retries of one step, and the
+# gradient below which a step that can no longer improve the value counts as converged (an improvement g^2 / 2H under
+# eps |f| cannot be seen in fp64, which is |g| <~ sqrt(2 eps) |f| ~ 2e-8 |f|; 1e-7 leaves a factor 5)
+REFINE_FD_STEP = 2.0 ** -14
+REFINE_MAX_STEP = 0.3
+REFINE_CLAMP = 1e-3
+REFINE_DAMP_TRIES = 30
+REFINE_STALL_TOL = 1e-7
+
+
+def _check_refine(refine, directions, refine_tol, refine_max_iter):
+    """the arguments of the refinement (ValueError before anything else happens)"""
+    if not refine:
+        return
+    if directions is None:
+        raise ValueError("refine: the refinement starts at the winners of a direction set, pass directions")
+    if not (isinstance(refine_tol, (float, int, np.floating, np.integer)) and not isinstance(refine_tol, bool)
+            and np.isfinite(refine_tol) and refine_tol > 0.0):
+        raise ValueError(f"refine_tol: expected a finite positive number, got {refine_tol!r}")
+    if (isinstance(refine_max_iter, bool) or not isinstance(refine_max_iter, (int, np.integer)) or refine_max_iter < 0
+            or refine_max_iter > 0x7fffffff):
+        raise ValueError(f"refine_max_iter: expected an int >= 0, got {refine_max_iter!r}")
+
+
+def _v6(n):
+    return np.array([n[0] * n[0], n[1] * n[1], n[2] * n[2], n[1] * n[2], n[0] * n[2], n[0] * n[1]])
+
+
+def _w6(n, m):
+    return np.array([2.0 * n[0] * m[0], 2.0 * n[1] * m[1], 2.0 * n[2] * m[2], n[1] * m[2] + n[2] * m[1],
+                     n[0] * m[2] + n[2] * m[0], n[0] * m[1] + n[1] * m[0]])
+
+
+def _a3(a, x):
+    """A(a) x with the symmetric A(a) = [[2 a0, a5, a4], [a5, 2 a1, a3], [a4, a3, 2 a2]]: a . v(n) = n^T A(a) n / 2 and
+    a . w(n,m) = n^T A(a) m, so A(a) x is the derivative of either"""
+    return np.array([2.0 * a[0] * x[0] + a[5] * x[1] + a[4] * x[2], a[5] * x[0] + 2.0 * a[1] * x[1] + a[3] * x[2],
+                     a[4] * x[0] + a[3] * x[1] + 2.0 * a[2] * x[2]])
+
+
+def pair_frame(n):
+    """the branch-free orthonormal frame (e1, e2) of a unit vector n, as in the pair kernel"""
+    sg = 1.0 if n[2] >= 0.0 else -1.0
+    fa = -1.0 / (sg + n[2])
+    fb = n[0] * n[1] * fa
+    return (np.array([1.0 + sg * n[0] * n[0] * fa, sg * fb, -sg * n[0]]), np.array([fb, sg + n[1] * n[1] * fa, -n[1]]))
+
+
+def _refine_eval(kind: int, S, n, m):
+    """kind 0: E(n), 1: G(n,m), 2: nu(n,m) -> (f, df/dn, df/dm), n and m taken as independent vectors"""
+    if kind == 1:
+        w = _w6(n, m)
+        Sw = S @ w
+        f = 1.0 / (w @ Sw)
+        c = -2.0 * f * f
+        return f, c * _a3(Sw, m), c * _a3(Sw, n)
+    v = _v6(n)
+    Sv = S @ v
+    q = v @ Sv
+    if kind == 0:
+        f = 1.0 / q
+        return f, (-2.0 * f * f) * _a3(Sv, n), np.zeros(3)
+    vm = _v6(m)
+    p = Sv @ vm
+    return -p / q, -_a3(S @ vm, n) / q + (2.0 * p / (q * q)) * _a3(Sv, n), -_a3(Sv, m) / q
+
+
+def _rotate(w, x):
+    """R(w) x, the rotation by |w| about w (Rodrigues)"""
+    t2 = w @ w
+    if t2 < 1e-16:
+        a, b = 1.0, 0.5
+    else:
+        t = np.sqrt(t2)
+        sh = np.sin(0.5 * t)
+        a, b = np.sin(t) / t, 2.0 * sh * sh / t2
+    wx = np.cross(w, x)
+    return x + a * wx + b * np.cross(w, wx)
+
+
+def _orthonormal(n, m):
+    n = n / np.sqrt(n @ n)
+    m = m - (m @ n) * n
+    return n, m / np.sqrt(m @ m)
+
+
+def _refine_one(kind: int, sign: float, S, n, m, tol: float, max_iter: int):
+    """one extreme of E, G or nu (``sign`` +1: maximum, -1: minimum) from the start pair (n, m) -> (value, n, m, status,
+    accepted steps).  F(w) = sign f(R(w) n, R(w) m) is maximised: the gradient at w = 0 is n x dF/dn + m x dF/dm; the
+    Hessian is the symmetric part of that gradient's central differences over rotations by +-h about the three axes (the
+    antisymmetric part is the chart's, not the function's); its eigenvalues are clamped to the ascent side, min(lambda,
+    -1e-3 max|lambda|), the step is capped at 0.3 rad and taken only if the value strictly improves, else damped and tried
+    again.  A step that no damping can make improve ends the iteration: the value is then stationary to fp64."""
+    def grad(n_, m_):
+        f, dn, dm = _refine_eval(kind, S, n_, m_)
+        return sign * f, sign * (np.cross(n_, dn) + np.cross(m_, dm))
+
+    h = REFINE_FD_STEP
+    it = 0
+    while True:
+        F0, g = grad(n, m)
+        if not np.isfinite(F0):
+            return sign * F0, n, m, REFINE_NOT_REFINED, it
+        scale = max(abs(F0), 1.0) if kind == 2 else abs(F0)
+        gnorm = np.sqrt(g @ g)
+        if gnorm <= tol * scale:
+            return sign * F0, n, m, REFINE_CONVERGED, it
+        if it >= max_iter:
+            return sign * F0, n, m, REFINE_ITERATION_CAP, it
+        D = np.empty((3, 3))
+        for j in range(3):
+            e = np.zeros(3)
+            e[j] = h
+            D[:, j] = (grad(_rotate(e, n), _rotate(e, m))[1] - grad(_rotate(-e, n), _rotate(-e, m))[1]) / (2.0 * h)
+        ev, U = np.linalg.eigh(0.5 * (D + D.T))
+        dl = REFINE_CLAMP * np.abs(ev).max() + 1e-300
+        ug = U.T @ g
+        damp, moved = 0.0, False
+        for _ in range(REFINE_DAMP_TRIES):
+            step = U @ (-ug / (np.minimum(ev, -dl) - damp))
+            length = np.sqrt(step @ step)
+            if length > REFINE_MAX_STEP:
+                step = step * (REFINE_MAX_STEP / length)
+            n1, m1 = _orthonormal(_rotate(step, n), _rotate(step, m))
+            F1 = sign * _refine_eval(kind, S, n1, m1)[0]
+            if F1 > F0:
+                n, m, moved = n1, m1, True
+                break
+            damp = max(2.0 * damp, dl)
+        if not moved:
+            ok = gnorm <= max(tol, REFINE_STALL_TOL) * scale
+            return sign * F0, n, m, REFINE_CONVERGED if ok else REFINE_ITERATION_CAP, it
+        it += 1
+
+
+def compressibility_matrix(S):
+    """B_ij = sum_k S_ijkk as a symmetric 3x3 matrix from the 6x6 compliance: beta(n) = n^T B n"""
+    r = S[:, 0] + S[:, 1] + S[:, 2]
+    return np.array([[r[0], 0.5 * r[5], 0.5 * r[4]], [0.5 * r[5], r[1], 0.5 * r[3]], [0.5 * r[4], 0.5 * r[3], r[2]]])
+
+
+def _grid_winners(S, dirs, table):
+    """the grid pass of the directional and the pair kernel in numpy: name -> (value, direction index, angle index); equal
+    values go to the lowest (flat) index, NaN is never taken, (nan, -1, -1) if nothing compares"""
+    V = np.stack([dirs[:, 0] ** 2, dirs[:, 1] ** 2, dirs[:, 2] ** 2, dirs[:, 1] * dirs[:, 2], dirs[:, 0] * dirs[:, 2],
+                  dirs[:, 0] * dirs[:, 1]], axis=1)
+    SV = V @ S
+    q = np.einsum("di,di->d", V, SV)
+    with np.errstate(all="ignore"):
+        maps = {"young": (1.0 / q)[:, None], "compressibility": (V @ (S[:, 0] + S[:, 1] + S[:, 2]))[:, None]}
+        if table is not None:
+            E12 = [pair_frame(n) for n in dirs]
+            e1, e2 = np.array([e[0] for e in E12]), np.array([e[1] for e in E12])
+            m = table[None, :, 0, None] * e1[:, None, :] + table[None, :, 1, None] * e2[:, None, :]      # [D,M,3]
+            n = dirs[:, None, :]
+            W = np.stack([2.0 * n[..., 0] * m[..., 0], 2.0 * n[..., 1] * m[..., 1], 2.0 * n[..., 2] * m[..., 2],
+                          n[..., 1] * m[..., 2] + n[..., 2] * m[..., 1], n[..., 0] * m[..., 2] + n[..., 2] * m[..., 0],
+                          n[..., 0] * m[..., 1] + n[..., 1] * m[..., 0]], axis=-1)
+            VM = np.stack([m[..., 0] ** 2, m[..., 1] ** 2, m[..., 2] ** 2, m[..., 1] * m[..., 2], m[..., 0] * m[..., 2],
+                           m[..., 0] * m[..., 1]], axis=-1)
+            maps["shear"] = 1.0 / np.einsum("dki,ij,dkj->dk", W, S, W)
+            maps["poisson"] = -np.einsum("di,dki->dk", SV, VM) / q[:, None]
+    out = {}
+    for name, f in maps.items():
+        for side, fill, pick in (("min", np.inf, np.argmin), ("max", -np.inf, np.argmax)):
+            flat = f.reshape(-1)
+            if np.isnan(flat).all():
+                out[f"{name}_{side}"] = (np.nan, -1, -1)
+                continue
+            i = int(pick(np.where(np.isnan(flat), fill, flat)))
+            out[f"{name}_{side}"] = (flat[i], i // f.shape[1], i % f.shape[1])
+    return out
+
+
+def refine_extremes_host(compliance, directions, angles=None, tol: float = 1e-9, max_iter: int = 32, flags=None) -> dict:
+    """The refinement of ``refine=True`` restated in numpy fp64 -- the documented algorithm, which the kernel follows step
+    for step.  ``compliance`` [B,6,6] or [6,6] (engineering convention, the mean of its two triangles is used),
+    ``directions`` / ``angles`` as in ``elastic_properties``, ``flags`` [B] as ``matten_elastic_props`` sets them (None: bit
+    0 for a non-finite row, bit 1 for one that is not positive definite).  -> name -> dict(value [B], n [B,3], m [B,3],
+    status [B], iterations [B], grid_value [B], grid_direction [B], grid_angle [B]) for the names of ``REFINE_NAMES`` (the
+    first four without ``angles``).
+
+    Per extreme: the grid pass picks the winner (d, k) as the kernels do, the start pair is n = directions[d],
+    m = cos(chi_k) e1 + sin(chi_k) e2 in ``pair_frame(n)``, and ``_refine_one`` polishes it; the result is the stationary
+    point of the basin the winner lies in.  The compressibility's extremes are the extreme eigenvalues of
+    ``compressibility_matrix`` with their eigenvectors, no iteration.  A result that rounding left behind the grid value
+    gives way to the grid's value and pair.  Status: 0 converged, 1 iteration cap reached (the value is still no worse
+    than the grid's), 2 not refined (flag bit 1: grid value and pair copied), -1 flag bit 0 (NaN)."""
+    S_all = np.asarray(compliance, dtype=np.float64)
+    single = S_all.ndim == 2
+    S_all = S_all.reshape(-1, 6, 6)
+    S_all = 0.5 * (S_all + S_all.transpose(0, 2, 1))
+    B = S_all.shape[0]
+    dirs = check_directions(directions)
+    table = None if angles is None else angle_table(angles)
+    if flags is None:
+        flags = np.zeros(B, dtype=np.int32)
+        for b in range(B):
+            if not np.isfinite(S_all[b]).all():
+                flags[b] = FLAG_SINGULAR | FLAG_NOT_POSITIVE_DEFINITE
+            elif not (np.linalg.eigvalsh(S_all[b]) > 0.0).all():
+                flags[b] = FLAG_NOT_POSITIVE_DEFINITE
+    flags = np.asarray(flags).reshape(-1)
+    names = REFINE_NAMES if table is not None else REFINE_NAMES[:4]
+    out = {name: dict(value=np.full(B, np.nan), n=np.full((B, 3), np.nan), m=np.full((B, 3), np.nan),
+                      status=np.full(B, REFINE_SINGULAR, dtype=np.int32), iterations=np.zeros(B, dtype=np.int32),
+                      grid_value=np.full(B, np.nan), grid_direction=np.full(B, -1, dtype=np.int64),
+                      grid_angle=np.full(B, -1, dtype=np.int64)) for name in names}
+    for b in range(B):
+        if flags[b] & FLAG_SINGULAR:
+            continue
+        S = S_all[b]
+        winners = _grid_winners(S, dirs, table)
+        for name in names:
+            o = out[name]
+            grid, d, k = winners[name]
+            o["grid_value"][b], o["grid_direction"][b], o["grid_angle"][b] = grid, d, k
+            if d < 0:
+                continue
+            n0 = dirs[d]
+            e1, e2 = pair_frame(n0)
+            m0 = e1 if table is None or name.startswith(("young", "compressibility")) else table[k, 0] * e1 + table[k, 1] * e2
+            sign = 1.0 if name.endswith("_max") else -1.0
+            if flags[b] & FLAG_NOT_POSITIVE_DEFINITE:
+                value, n, m, status, it = grid, n0, m0, REFINE_NOT_REFINED, 0
+            elif name.startswith("compressibility"):
+                ev, U = np.linalg.eigh(compressibility_matrix(S))
+                i = 2 if sign > 0 else 0
+                value, n, m, status, it = ev[i], U[:, i], U[:, 1], REFINE_CONVERGED, 0
+            else:
+                kind = 0 if name.startswith("young") else 1 if name.startswith("shear") else 2
+                value, n, m, status, it = _refine_one(kind, sign, S, n0, m0, float(tol), int(max_iter))
+                if status == REFINE_NOT_REFINED:
+                    value = grid
+            if not sign * value >= sign * grid:       # (rounding alone can leave it behind; also a NaN)
+                value, n, m = grid, n0, m0
+            o["value"][b], o["n"][b], o["m"][b], o["status"][b], o["iterations"][b] = value, n, m, status, it
+    if single:
+        out = {name: {k: v[0] for k, v in o.items()} for name, o in out.items()}
+    return out
 
 
 def _check_per_row(name: str, values, B: int, single: bool):
@@ -259,9 +520,10 @@ def _acoustic_fields(vel, ext, arg, n_unstable, n_dirs: int, number_density) -> 
 
 
 def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, failed=None, angles=None, density=None,
-               number_density=None, modulus_unit: float = 1e9) -> ElasticProperties:
+               number_density=None, modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
+               refine_max_iter: int = 32) -> ElasticProperties:
     """rows on the device -> ElasticProperties; ``dirs``: unit vectors out of ``check_directions`` (host) or None;
-    ``density`` / ``number_density``: out of ``_check_per_row`` or None"""
+    ``density`` / ``number_density``: out of ``_check_per_row`` or None; ``refine*``: checked by ``_check_refine``"""
     voigt, compliance, props, flags = ops.elastic_props(rows, layout)
     if failed is not None and failed.any():
         flags |= torch.as_tensor(failed.astype(np.int32) * FLAG_FAILED_STRUCTURE, device=flags.device)
@@ -273,18 +535,28 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
     fields["is_singular"] = (flags & FLAG_SINGULAR) != 0
     if dirs is not None:
         dirs = torch.from_numpy(np.ascontiguousarray(dirs)).to(rows.device)
-        fields.update(_directional_fields(*ops.elastic_directional(compliance, flags, dirs, keep=keep_directional), dirs))
+        young, beta, ext_dir, arg_dir = ops.elastic_directional(compliance, flags, dirs, keep=keep_directional)
+        fields.update(_directional_fields(young, beta, ext_dir, arg_dir, dirs))
+    table = ext = arg = None
     if angles is not None:
         M = int(angles)
-        table = angle_table(M)
-        maps, ext, arg = ops.elastic_pair(compliance, flags, dirs, torch.from_numpy(table).to(rows.device),
-                                          keep=keep_directional)
+        table = torch.from_numpy(angle_table(M)).to(rows.device)
+        maps, ext, arg = ops.elastic_pair(compliance, flags, dirs, table, keep=keep_directional)
         fields["angles"] = torch.from_numpy(np.pi * np.arange(M, dtype=np.float64) / M).to(rows.device)
         for q, name in enumerate(("shear_min", "shear_max", "poisson_min", "poisson_max")):
             fields[name] = ext[:, q]
             fields[name + "_direction"], fields[name + "_angle"] = split_pair_index(arg[:, q], M)
         for q, name in enumerate(("shear_dir_min", "shear_dir_max", "poisson_dir_min", "poisson_dir_max")):
             fields[name] = None if maps is None else maps[:, :, q]
+    if refine:      # (one launch on the winners just written; nothing comes back to the host)
+        value, vec_n, vec_m, status, iterations = ops.elastic_refine(compliance, flags, dirs, ext_dir, arg_dir, table, ext, arg,
+                                                                     refine_tol, refine_max_iter)
+        for q in range(value.shape[0]):
+            name = REFINE_NAMES[q] + "_refined"
+            fields[name], fields[name + "_n"] = value[q], vec_n[q]
+            if q >= 4:
+                fields[name + "_m"] = vec_m[q]
+            fields[name + "_status"], fields[name + "_iterations"] = status[q], iterations[q]
     if density is not None:
         rho = torch.as_tensor(density, dtype=torch.float64).to(rows.device)
         fields.update(_acoustic_fields(*ops.elastic_acoustic(voigt, flags, rho, dirs, modulus_unit, keep=keep_directional),
@@ -295,7 +567,8 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
 
 
 def elastic_properties(tensors, directions=None, keep_directional: bool = False, angles=None, density=None,
-                       number_density=None, modulus_unit: float = 1e9) -> ElasticProperties:
+                       number_density=None, modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
+                       refine_max_iter: int = 32) -> ElasticProperties:
     """``tensors``: a torch tensor or numpy array [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], fp32 or fp64, on the device or
     on the host (copied once), or a list of such tensors as ``predict`` returns (stacked; a ``None`` entry becomes a NaN
     row with flag bit 2).  ``directions``: an int D (``fibonacci_hemisphere(D)``) or an array [D,3] (validated and
@@ -307,8 +580,17 @@ def elastic_properties(tensors, directions=None, keep_directional: bool = False,
     velocities per direction in m/s, their extremes and the Debye average ``v_mean``; ``modulus_unit`` is Pa per unit of
     the input (1e9: GPa).  ``number_density``: [B] atoms/m^3 (needs ``density``): ``debye_temperature`` in K.  A host
     ``density`` / ``number_density`` is checked before anything is uploaded (ValueError naming the first bad index).
+    ``refine`` (needs ``directions``): every grid winner -- ``young_*``, ``compressibility_*`` and, with ``angles``,
+    ``shear_*`` / ``poisson_*`` -- is polished off the grid on the device (``refine_extremes_host`` is the algorithm): for each
+    such name X the fields ``X_refined`` [B], ``X_refined_n`` [B,3] (unit), ``X_refined_m`` [B,3] (pair quantities only; unit,
+    perpendicular to n), ``X_refined_status`` [B] int32 (0 converged, 1 iteration cap, 2 not refined: the row is not positive
+    definite and keeps the grid's value and pair, -1 singular row: NaN) and ``X_refined_iterations`` [B] int32 come beside
+    the grid fields, which stay as they are.  ``refine_tol`` is the relative gradient residual at which the iteration stops,
+    ``refine_max_iter`` its cap.  The refined extreme is the stationary point of the basin the grid winner lies in: on a
+    coarse grid that need not be the global extreme.  The sign of n and of m is unspecified (all four functions are even).
     The results stay on the device."""
     _check_extras(directions, angles, density, number_density)
+    _check_refine(refine, directions, refine_tol, refine_max_iter)
     dirs = None if directions is None else check_directions(directions)      # (before anything is uploaded)
     rows, layout, single, failed = _as_rows(tensors)
     if density is not None:
@@ -316,7 +598,7 @@ def elastic_properties(tensors, directions=None, keep_directional: bool = False,
     if number_density is not None:
         number_density = _check_per_row("number_density", number_density, rows.shape[0], single)
     return _from_rows(_upload(rows), layout, dirs, keep_directional, single, failed, angles, density, number_density,
-                      modulus_unit)
+                      modulus_unit, refine, refine_tol, refine_max_iter)
 
 
 _VOIGT_Q = {}
@@ -324,12 +606,14 @@ _VOIGT_Q = {}
 
 def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = False,
                                    formula: str = "ijkl=jikl=klij", angles=None, density=None, number_density=None,
-                                   modulus_unit: float = 1e9) -> ElasticProperties:
+                                   modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
+                                   refine_max_iter: int = 32) -> ElasticProperties:
     """The same from the model's irreps rows ``x`` [B,21] (fp32, on the device): one ``dense_rows`` with ``voigt_basis``
     gives the Voigt matrices [B,36] directly -- no [B,81] Cartesian intermediate."""
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
         raise ValueError("x: expected a tensor [B,21] or [21]")
     _check_extras(directions, angles, density, number_density)
+    _check_refine(refine, directions, refine_tol, refine_max_iter)
     dirs = None if directions is None else check_directions(directions)
     single = x.dim() == 1
     x = x.detach().reshape(-1, x.shape[-1])
@@ -346,7 +630,8 @@ def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = 
     if key not in _VOIGT_Q:
         _VOIGT_Q[key] = torch.tensor(V, dtype=torch.float32, device=x.device)
     rows = ops.dense_rows(x.to(torch.float32), _VOIGT_Q[key])
-    return _from_rows(rows, 1, dirs, keep_directional, single, None, angles, density, number_density, modulus_unit)
+    return _from_rows(rows, 1, dirs, keep_directional, single, None, angles, density, number_density, modulus_unit, refine,
+                      refine_tol, refine_max_iter)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -941,6 +941,49 @@ def elastic_acoustic(voigt, flags, density, dirs, modulus_unit: float = 1e9, kee
     return vel, ext, arg, n_unstable
 
 
+def elastic_refine(compliance, flags, dirs, ext_dir, arg_dir, cos_sin=None, ext_pair=None, arg_pair=None, tol: float = 1e-9,
+                   max_iter: int = 32):
+    """the extremes of ``elastic_directional`` (ext_dir / arg_dir [B,4]) and, with cos_sin [M,2] and ext_pair / arg_pair
+    [B,4], of ``elastic_pair`` refined off the grid -> (value [Q,B], n [Q,B,3], m [Q,B,3], status [Q,B] int32, iterations
+    [Q,B] int32), Q = 4 (E_min, E_max, beta_min, beta_max) or 8 (then G_min, G_max, nu_min, nu_max)
+    (matten_elastic_refine)"""
+    lib = _lib.load()
+    compliance = _need(compliance, torch.float64, "compliance")
+    flags = _need(flags, torch.int32, "flags")
+    dirs = _need(dirs, torch.float64, "dirs")
+    ext_dir = _need(ext_dir, torch.float64, "ext_dir")
+    arg_dir = _need(arg_dir, torch.int32, "arg_dir")
+    B = flags.shape[0]
+    if (compliance.shape != (B, 6, 6) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1 or ext_dir.shape != (B, 4)
+            or arg_dir.shape != (B, 4)):
+        raise ValueError(f"expected compliance [B,6,6], flags [B], dirs [D>=1,3], ext_dir / arg_dir [B,4]; got "
+                         f"{tuple(compliance.shape)}, {tuple(flags.shape)}, {tuple(dirs.shape)}, {tuple(ext_dir.shape)}, "
+                         f"{tuple(arg_dir.shape)}")
+    pair = (cos_sin is not None, ext_pair is not None, arg_pair is not None)
+    if any(pair) != all(pair):
+        raise ValueError("cos_sin, ext_pair and arg_pair go together: all three or none")
+    M = 0
+    if all(pair):
+        cos_sin = _need(cos_sin, torch.float64, "cos_sin")
+        ext_pair = _need(ext_pair, torch.float64, "ext_pair")
+        arg_pair = _need(arg_pair, torch.int32, "arg_pair")
+        if cos_sin.dim() != 2 or cos_sin.shape[1] != 2 or cos_sin.shape[0] < 1 or ext_pair.shape != (B, 4) or arg_pair.shape != (B, 4):
+            raise ValueError(f"expected cos_sin [M>=1,2], ext_pair / arg_pair [B,4]; got {tuple(cos_sin.shape)}, "
+                             f"{tuple(ext_pair.shape)}, {tuple(arg_pair.shape)}")
+        M = cos_sin.shape[0]
+    D, Q = dirs.shape[0], 8 if M else 4
+    value = torch.empty(Q, B, dtype=torch.float64, device=dirs.device)
+    vec_n = torch.empty(Q, B, 3, dtype=torch.float64, device=dirs.device)
+    vec_m = torch.empty(Q, B, 3, dtype=torch.float64, device=dirs.device)
+    status = torch.empty(Q, B, dtype=torch.int32, device=dirs.device)
+    iterations = torch.empty(Q, B, dtype=torch.int32, device=dirs.device)
+    _lib.check(lib.matten_elastic_refine(_ptr(compliance), _ptr(flags), _ptr(dirs), _ptr(cos_sin), _ptr(ext_dir), _ptr(arg_dir),
+                                         _ptr(ext_pair), _ptr(arg_pair), B, D, M, float(tol), int(max_iter), _ptr(value),
+                                         _ptr(vec_n), _ptr(vec_m), _ptr(status), _ptr(iterations), _stream()),
+               "matten_elastic_refine")
+    return value, vec_n, vec_m, status, iterations
+
+
 def _opt_grad(g, shape, name: str):
     """an optional fp64 upstream gradient: None stays None (a null pointer for the kernel)"""
     if g is None:

@@ -568,7 +568,7 @@ def _structure_densities(structures) -> np.ndarray:
 
 
 def _properties_of_slabs(device_rows, n, failed, directions, single, angles=None, density=None, number_density=None,
-                         modulus_unit=1e9):
+                         modulus_unit=1e9, refine=False, refine_tol=1e-9, refine_max_iter=32):
     """ElasticProperties of all n input structures from the slabs' device tensors: they never come back from the host.
     Structures without a prediction (``failed``) keep NaN rows and get flag bit 2."""
     from .elastic import _from_rows
@@ -582,7 +582,8 @@ def _properties_of_slabs(device_rows, n, failed, directions, single, angles=None
             rows[torch.as_tensor(keep, device=first.device)] = t.reshape(len(keep), 81)
     mask = np.zeros(n, dtype=bool)
     mask[list(failed)] = True
-    return _from_rows(rows, 0, directions, False, single, mask, angles, density, number_density, modulus_unit)
+    return _from_rows(rows, 0, directions, False, single, mask, angles, density, number_density, modulus_unit, refine,
+                      refine_tol, refine_max_iter)
 
 
 def predict(
@@ -603,6 +604,9 @@ def predict(
     density=None,
     number_density=None,
     modulus_unit: float = 1e9,
+    refine: bool = False,
+    refine_tol: float = 1e-9,
+    refine_max_iter: int = 32,
 ):
     """See the module docstring.  ``model`` / ``config`` let a caller reuse an already loaded model.
     ``properties=True`` (elasticity tensors only: ``ValueError`` with ``is_atomic_tensor``) returns ``(tensors, props)``:
@@ -612,7 +616,8 @@ def predict(
     ``angles`` (an int M), ``density`` (kg/m^3, one value per input structure, or ``"structure"``: read from each structure's
     ``.density`` in g/cm^3 or a dict's ``"density"`` key in kg/m^3), ``number_density`` (atoms/m^3) and ``modulus_unit`` are
     those of ``elastic.elastic_properties`` (shear modulus and Poisson's ratio over direction pairs, sound velocities, Debye
-    temperature); they need ``properties=True`` and are checked before any forward runs.
+    temperature); they need ``properties=True`` and are checked before any forward runs.  So are ``refine``, ``refine_tol``
+    and ``refine_max_iter``: the directional extremes polished off the grid (the ``*_refined*`` fields; needs ``directions``).
     ``batch_size`` (reference predict.py:155) is the memory knob it is there: consecutive batches are merged into one forward
     only while the merged batch stays within ``node_budget`` atoms (default MATTEN_PREDICT_NODE_BUDGET = 65536, ~2 GB) and
     only when batch_size is at least the reference's default of 200; ``node_budget=0`` never merges.  A merged forward
@@ -629,12 +634,15 @@ def predict(
         for name, value in (("angles", angles), ("density", density), ("number_density", number_density)):
             if value is not None:
                 raise ValueError(f"{name} belongs to the derived properties: pass properties=True")
+        if refine:
+            raise ValueError("refine belongs to the derived properties: pass properties=True")
     single = not isinstance(structure, (list, tuple))
     structures = [structure] if single else list(structure)
     if properties:
-        from .elastic import _check_extras, _check_per_row
+        from .elastic import _check_extras, _check_per_row, _check_refine
 
         _check_extras(directions, angles, density, number_density)
+        _check_refine(refine, directions, refine_tol, refine_max_iter)
         if isinstance(density, str):
             if density != "structure":
                 raise ValueError(f'density: expected values in kg/m^3 or "structure", got {density!r}')
@@ -680,7 +688,7 @@ def predict(
         raise RuntimeError("Cannot successfully convert any structures.")
     if properties:
         props = _properties_of_slabs(device_rows, len(structures), failed, directions, single, angles, density,
-                                     number_density, modulus_unit)
+                                     number_density, modulus_unit, refine, refine_tol, refine_max_iter)
     if is_elasticity_tensor:
         try:
             from pymatgen.analysis.elasticity import ElasticTensor
