@@ -288,6 +288,8 @@ class PointConvWithActivation(ModuleIrreps, torch.nn.Module):
         bn_idx, mean_idx = meta & 0xFFFF, (meta >> 16) & 0xFFFF
         scale = (w / torch.sqrt(rv + self.norm.n.eps))[bn_idx]
         has_mean = mean_idx != 0xFFFF
+        if b.numel() == 0:   # an activated row without 0e channels (gated irreps and odd scalars only): nothing is centred
+            return scale.contiguous(), torch.zeros_like(scale)
         mi = torch.where(has_mean, mean_idx, torch.zeros_like(mean_idx))
         shift = torch.where(has_mean, b[mi] - rm[mi] * scale, torch.zeros_like(scale))
         return scale.contiguous(), shift.contiguous()

@@ -692,6 +692,7 @@ def test_agg_linear_plan_reproduces_lin2_on_the_host():
     the oracle's FullyConnectedTensorProduct(agg_mul_ir, one_hot(species)): every channel of every path lands in exactly
     one slot, pad slots are never read as data, wide irreps split into table rows add up, the fragment layout matches the
     kernel's operand indexing."""
+    import agg_linear_cases as alc
     from common import PAPER
     from matten_amd import plan as mplan
     from matten_amd.model_factory.tfn_scalar_tensor import create_model
@@ -705,53 +706,20 @@ def test_agg_linear_plan_reproduces_lin2_on_the_host():
         uvu, lp = conv.tp.plan, conv.lin2.plan
         ap = mplan.plan_agg_linear(uvu, S, lp.irreps_out)
         assert ap is not None and ap.ld % 32 == 0 and ap.n_chunks * 16 <= ap.ld
+        lay = alc.Layer("paper layer", S, uvu, ap, lp.irreps_out, None, None)
         N = 5
         agg = rng.standard_normal((N, uvu.d_mid)).astype(np.float64)          # reference layout: per path [u][k]
         species = rng.integers(0, S, N)
         w = rng.standard_normal(lp.weight_numel)
-        # --- what tp_fused's epilogue does with the new entries: out_off[c] + u + k * t_off[c] ---
-        row = np.full((N, ap.ld), np.nan)                                      # NaN: a slot that is read must have been written
-        ent = ap.entries
-        written = np.zeros(ap.ld, dtype=int)
-        for e in range(len(ent)):
-            mul = int(uvu.group_entry_mul[e])    # channels of the record OWN block (merged entries: 2 + 2 over two records)
-            for c, pi in uvu.group_entry_paths[e].items():
-                pth = uvu.paths[pi]
-                d3 = 2 * pth.l3 + 1
-                o, ks = int(ent[e][20 + c]), int(ent[e][8 + c])
-                for u in range(mul):
-                    for k in range(d3):
-                        row[:, o + u + k * ks] = agg[:, pth.out_off + (uvu.group_entry_u0[e] + u) * d3 + k]
-                        written[o + u + k * ks] += 1
+        # --- what tp_fused's epilogue does with the new entries: out_off[c] + u + k * t_off[c] (NaN where nobody writes:
+        # a slot that is read must have been written) ---
+        row, written = alc.scatter_rows(lay, agg)
         assert written.max() == 1 and written.sum() == uvu.d_mid               # a bijection onto the used slots
-        # --- what agg_linear does: blocks -> chunks -> MFMA steps with A[t][mt][g][c][s] ---
+        # --- what agg_linear does: blocks -> chunks -> MFMA steps with A[t][mt][g][c][s] (alc.emulate asserts the tables'
+        # invariants and that no read slot is NaN) ---
         wtab = np.where(ap.gather >= 0, w[np.clip(ap.gather, 0, None)] * ap.scale[None, :], 0.0)
-        out = np.zeros((N, ap.d_out))
-        seen_chunks = 0
-        for (chunk, info, t0, _) in ap.blocks.tolist():
-            n, k, ii = info & 255, (info >> 12) & 255, (info >> 20) & 4095
-            c0, T, K, packed, a_off, out_off, mo, k0 = ap.io_table[ii].tolist()
-            d3, n_mt, cw, kk = packed & 255, (packed >> 8) & 255, (packed >> 16) & 255, (packed >> 24) & 255
-            assert mo * kk <= mplan.AGG_STAGE_W and n_mt <= mplan.AGG_MAX_MT and 1 <= n <= mplan.AGG_BLOCK
-            assert k0 <= k < k0 + kk <= d3   # the row's component range (a wide irrep is cut by component: no chunk read twice)
-            assert chunk == c0 + k * T + t0
-            for i in range(n):
-                t = t0 + i
-                seen_chunks += 1
-                for g in range(4):
-                    for s_ in range(4):
-                        slot = 16 * t + 4 * g + s_
-                        if slot >= K:
-                            continue                                           # masked by the kernel (select, not multiply)
-                        b = row[:, 16 * (chunk + i) + 4 * g + s_]
-                        assert not np.isnan(b).any()
-                        for mt in range(n_mt):
-                            for c in range(min(cw, 16)):
-                                v = 16 * mt + c
-                                if v >= mo:
-                                    continue
-                                a_idx = a_off + ((((t * n_mt + mt) * 4 + g) * cw + c) * 4 + s_)
-                                out[:, out_off + v * d3 + k] += wtab[species, a_idx] * b
+        out, stores = alc.emulate(ap, row, wtab, species)
+        assert (stores == 1).all()
         ref = ro3.FullyConnectedTensorProduct(str(uvu.irreps_out), f"{S}x0e", str(lp.irreps_out)).double()
         with torch.no_grad():
             ref.weight.copy_(torch.as_tensor(w))
