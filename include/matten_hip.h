@@ -531,6 +531,32 @@ int matten_tp_backward(const float* x, int64_t d_in, const void* w_edge, int64_t
 int matten_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const float* step,
                      float lr, float beta1, float beta2, float eps, float weight_decay, matten_stream_t stream);
 
+/* The same step with its controls on the device: global 2-norm clipping of grads, a guard that skips a step whose gradient
+ * is not finite, coupled (Adam) or decoupled (AdamW) weight decay, an exponential moving average of the parameters and a
+ * learning rate read from device memory.  Enqueues at most three kernels on `stream` (sum of squares -> control -> update)
+ * and nothing else: no read-back, no memset node, no second stream, so the call captures into a hipGraph and a replay
+ * uses whatever ctl[0] holds at that moment.  All device state is the caller's:
+ *   ctl      fp32 [8]   [0] learning rate (input)  [1] norm of grads at the last step  [2] scale applied to them
+ *                       (both outputs; [1] is NaN when neither clipping nor the guard asked for the norm); rest zero
+ *   counters int32 [2]  [0] steps skipped so far  [1] 1 if the last step was skipped, else 0
+ *   step     fp32 [1]   number of steps taken; THIS call advances it (by 0 for a skipped step) -- unlike matten_adam_step
+ *   workspace           matten_adam_ctl_workspace_bytes(n) bytes, 8-byte aligned: one fp64 partial per workgroup of the
+ *                       norm pass.  The number of workgroups depends on n alone and every sum runs in a fixed order in
+ *                       fp64 without atomics: the norm has the same bits on every device and in every run.
+ * max_norm > 0: scale = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); 0: no clipping.  guard != 0: a
+ * non-finite sum of squares skips the step -- params, exp_avg, exp_avg_sq, ema and step keep their bits, counters[0] += 1.
+ * Without the guard a non-finite norm makes scale, and so the parameters, NaN (as under torch).  With g' = scale * g:
+ * decoupled == 0: g' += weight_decay * p, then matten_adam_step's rule; != 0: p *= 1 - lr * weight_decay first
+ * (torch.optim.AdamW).  ema != NULL: ema = ema_decay * ema + (1 - ema_decay) * p_new in the same pass.
+ * MATTEN_EINVAL: n < 0, beta1 / beta2 / ema_decay outside [0, 1), eps < 0, max_norm < 0 (or any of them NaN); for n > 0 a
+ * NULL pointer other than ema, a flat buffer (ema included) off a 16-byte boundary, workspace_bytes below the query.
+ * n == 0: MATTEN_OK, no pointer is looked at. */
+size_t matten_adam_ctl_workspace_bytes(int64_t n);
+int matten_adam_step_ctl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema /* or NULL */,
+                         int64_t n, float* step, float* ctl, int32_t* counters, void* workspace, size_t workspace_bytes,
+                         float max_norm, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                         int decoupled, int guard, matten_stream_t stream);
+
 /* the same adjoint with the literal-coefficient coupling code of the forward kernels (cg_gen.h): a thread owns (edge,
  * channel of one input block) and walks the block's paths; one atomic per (edge, channel, component) into dx.
  *   blocks[n_blocks,4] int32 {x_off, mul, l1, first path | n_paths << 16}; paths[n_paths,4] {l1*25+l2*5+l3, w_off, out_off, 0};

@@ -79,6 +79,9 @@ SIGNATURES = {
     "matten_tp_backward_lit_wfree": (c_int, [P, c_int64, P, P, P, P, c_int64, P, P, P, c_int64, c_int64, P, c_int64, P, c_int64, c_float,
                                              P, c_int64, P, P, c_int64, c_int, c_int64, P, P, P, c_int64, c_int, c_int, P]),
     "matten_adam_step": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_float, P]),
+    "matten_adam_ctl_workspace_bytes": (c_size_t, [c_int64]),
+    "matten_adam_step_ctl": (c_int, [P, P, P, P, P, c_int64, P, P, P, P, c_size_t, c_float, c_float, c_float, c_float, c_float,
+                                     c_float, c_int, c_int, P]),
     "matten_species_linear_wgrad": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, c_int64, P, c_int64, c_int64, P, P, P]),
     "matten_gate_bwd": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, P, P]),
     "matten_bn_scratch_floats": (c_int64, [c_int64, c_int64]),
@@ -141,6 +144,13 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} not found: the HIP extension is not built. matten_amd has no CPU fallback; "
             "run `make -C matten_amd/csrc` (needs hipcc, --offload-arch=gfx950)."
         )
+    # One HIP runtime per process.  A torch wheel may ship its own runtime (torch/lib/libamdhip64.so) and ask for it under
+    # another name than this library's DT_NEEDED entry (libamdhip64.so.N, found in the ROCm installation).  If this library
+    # comes first, torch's copy is mapped as a SECOND runtime beside it, and a kernel registered with one runtime cannot be
+    # launched on a stream of the other: every launch fails (MATTEN_ELAUNCH).  With torch loaded first its runtime carries
+    # the SONAME this library asks for, and the loader hands it the same one.
+    import torch  # noqa: F401
+
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         try:

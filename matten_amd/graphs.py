@@ -139,6 +139,8 @@ class GraphedTrainStep:
         _copy_batch(self._static, batch, "step")
         if target.data_ptr() != self._target.data_ptr():
             self._target.copy_(target, non_blocking=True)
+        if hasattr(self.optimizer, "sync_hyperparameters"):
+            self.optimizer.sync_hyperparameters()   # a scheduler's new learning rate reaches the device before the replay
         self.graph.replay()
         bump_weights_epoch()   # the replayed optimiser step (and BatchNorm's running statistics) moved no _version counter
         if validate:

@@ -12,9 +12,10 @@ import torch
 
 class Trainer:
     def __init__(self, max_epochs: int = 1, limit_train_batches: Optional[int] = None, accelerator: str = "gpu",
-                 devices: int = 1, **ignored):
+                 devices: int = 1, gradient_clip_val: Optional[float] = None, **ignored):
         self.max_epochs, self.limit_train_batches = max_epochs, limit_train_batches
-        self.history = []
+        self.gradient_clip_val = gradient_clip_val   # Lightning's name: the global 2-norm the gradients are clipped to
+        self.history, self.optimizers = [], []
 
     def fit(self, model, datamodule=None, train_dataloaders=None, val_dataloaders=None):
         train = train_dataloaders if train_dataloaders is not None else datamodule.train_dataloader()
@@ -22,6 +23,15 @@ class Trainer:
         cfg = model.configure_optimizers()
         optimizer = cfg["optimizer"] if isinstance(cfg, dict) else cfg
         scheduler = cfg.get("lr_scheduler") if isinstance(cfg, dict) else None
+        self.optimizers = [optimizer]   # Lightning's name
+        clip_params = None
+        if self.gradient_clip_val is not None:
+            from ..optim import FlatAdam
+
+            if isinstance(optimizer, FlatAdam):
+                optimizer.set_max_grad_norm(self.gradient_clip_val)   # clipped inside its own step, on the device
+            else:
+                clip_params = [p for g in optimizer.param_groups for p in g["params"]]
         for epoch in range(self.max_epochs):
             model.train()
             for i, batch in enumerate(train):
@@ -30,6 +40,8 @@ class Trainer:
                 loss = model.training_step(batch, i)["loss"]
                 optimizer.zero_grad(set_to_none=True)
                 loss.backward()
+                if clip_params is not None:
+                    torch.nn.utils.clip_grad_norm_(clip_params, self.gradient_clip_val)
                 optimizer.step()
             model.on_training_epoch_end()
             if val is not None:

@@ -88,7 +88,9 @@ class DataParallelStep:
     whole batch whatever the shard sizes.  Returns the global loss (a device tensor, identical on every rank).
 
     The optimiser is matten_amd.optim.FlatAdam (one flat gradient buffer = one collective) or any torch optimiser (the
-    gradients are flattened into a scratch buffer for the exchange and copied back)."""
+    gradients are flattened into a scratch buffer for the exchange and copied back).  FlatAdam's ``max_grad_norm`` and
+    ``skip_nonfinite`` need nothing here: the norm is taken inside ``optimizer.step()``, after the all-reduce, over gradients
+    that are identical on every rank -- so every rank clips by the same global norm and skips the same steps."""
 
     def __init__(self, model, optimizer, loss_fn, group=None, task_name: str = "elastic_tensor_full"):
         self.model, self.optimizer, self.loss_fn, self.group, self.task_name = model, optimizer, loss_fn, group, task_name
