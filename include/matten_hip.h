@@ -782,6 +782,50 @@ int matten_neighbor_fill(const double* pos, const double* cell, const int64_t* p
                          float* edge_cell_shift, float* num_neigh, const int64_t* offsets_t, int64_t n_atoms,
                          int32_t* rowptr, int32_t* src_sorted, int32_t* perm, matten_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Batch assembly from a device-resident training set (replaces PyG's collate at reference data/dataset.py:150-152,
+ * which concatenates the picked crystals on the host for every batch of every epoch).
+ *
+ * A batch is a disjoint union with node and edge ranges in crystal order, so each of its arrays is the concatenation of
+ * the picked crystals' rows, some with an offset added.  matten_batch_gather moves every array of a batch in ONE launch.
+ *   table[5][n_crystals + 1] (int32, device), one column per picked crystal in batch order: destination node start,
+ *     destination edge start, source node start, source edge start, source crystal.  The closing column holds
+ *     (n_nodes, n_edges, 0, 0, 0).  The host derives it from its copies of the store's running sums.
+ *   streams[n_streams][MATTEN_BATCH_STREAM_WORDS] (int64, HOST memory, read before the call returns): per array
+ *     {source pointer, destination pointer, element size (4 or 8), elements per row, class, operation}.
+ *     class: whose rows these are (MATTEN_BATCH_NODE / _EDGE / _CRYSTAL).  Operation:
+ *       RAW         the row copied as is, any class, any width (16-, 8- or 4-byte accesses as alignment allows)
+ *       ADD32_NODE  int32 per edge + the crystal's destination node start      (source / destination ids in sorted order)
+ *       ADD32_EDGE  int32 per edge + the crystal's destination edge start      (the two CSR permutations)
+ *       ADD64_NODE  int64 per edge + the crystal's destination node start      (one row of edge_index)
+ *       ROWPTR32    int32 per node + the destination edge start; the destination holds n_nodes + 1 entries, the last
+ *                   one is set to n_edges                                      (the row pointers of the two CSRs)
+ *       BATCH64     int64 per node: the crystal's position in the batch; no source
+ *       PTR64       int64 per crystal: its destination node start; n_crystals + 1 entries, the last n_nodes; no source
+ *   Sources hold the store's rows (crystal-relative ids); destinations hold n_nodes / n_edges / n_crystals rows.
+ * MATTEN_EINVAL: a negative size, sizes of 2^31 or more, more than MATTEN_BATCH_MAX_STREAMS streams, a NULL table,
+ * streams array, destination or (where the operation reads one) source, an element size other than 4 or 8, a row of no
+ * elements, an unknown class or operation, an operation outside its class or element size, a pointer off its element size.
+ * Up to matten_batch_gather_lds_rows() - 1 crystals the two destination running sums are searched in LDS, above that
+ * in global memory.  No workspace, no atomics, no synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+#define MATTEN_BATCH_MAX_STREAMS 32
+#define MATTEN_BATCH_STREAM_WORDS 6
+#define MATTEN_BATCH_NODE 0
+#define MATTEN_BATCH_EDGE 1
+#define MATTEN_BATCH_CRYSTAL 2
+#define MATTEN_BATCH_OP_RAW 0
+#define MATTEN_BATCH_OP_ADD32_NODE 1
+#define MATTEN_BATCH_OP_ADD32_EDGE 2
+#define MATTEN_BATCH_OP_ADD64_NODE 3
+#define MATTEN_BATCH_OP_ROWPTR32 4
+#define MATTEN_BATCH_OP_BATCH64 5
+#define MATTEN_BATCH_OP_PTR64 6
+int matten_batch_gather_lds_rows(void);
+int matten_batch_gather_max_streams(void);
+int matten_batch_gather(const int64_t* streams, int64_t n_streams, const int32_t* table, int64_t n_crystals,
+                        int64_t n_nodes, int64_t n_edges, matten_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,176 @@
+// matten_batch_gather: a training batch assembled on the device from a device-resident set of crystals.
+//
+// A batch is a disjoint union with node (and edge) ranges in crystal order, so every array of the batch is the
+// concatenation of the picked crystals' own rows, some with an offset added: node ids gain the crystal's first node of
+// the batch, edge ids (the CSR permutations and row pointers, stored crystal-relative) its first edge.  One launch moves
+// everything: the item space is nodes | edges | crystals | one closing item, one thread per item, and a thread walks the
+// streams of its class.  The crystal of an item is found by binary search over the destination running sums, which are
+// staged in LDS when the batch has at most BATCH_LDS_ROWS - 1 crystals and read from global memory (L2) otherwise.
+// No atomics, no workspace, no synchronisation.
+#include "common.h"
+
+constexpr int BATCH_THREADS = 256;
+constexpr int BATCH_LDS_ROWS = 1024;   // B + 1 up to this: both running sums in LDS (8 KB)
+
+extern "C" int matten_batch_gather_lds_rows(void) { return BATCH_LDS_ROWS; }
+extern "C" int matten_batch_gather_max_streams(void) { return MATTEN_BATCH_MAX_STREAMS; }
+
+struct BatchStream {
+    const char* src;
+    char* dst;
+    int32_t row_bytes;
+    int16_t cls;   // MATTEN_BATCH_NODE / _EDGE / _CRYSTAL
+    int8_t op;     // MATTEN_BATCH_OP_*
+    int8_t vec;    // bytes per load / store of a raw row: 4, 8 or 16
+};
+
+struct BatchArgs {
+    BatchStream s[MATTEN_BATCH_MAX_STREAMS];
+    int n_streams;
+};
+
+// the last row r of a[0 .. n) with a[r] <= v (a is non-decreasing, a[0] = 0 <= v): crystals without rows are skipped
+__device__ __forceinline__ int batch_find(const int32_t* a, int n, int v) {
+    int lo = 0, hi = n;   // a[lo] <= v < a[hi] (a[n] = +inf)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void batch_copy_row(char* __restrict__ d, const char* __restrict__ s, int bytes, int vec) {
+    if (vec == 16) {
+        for (int o = 0; o < bytes; o += 16) *reinterpret_cast<uint4*>(d + o) = *reinterpret_cast<const uint4*>(s + o);
+    } else if (vec == 8) {
+        for (int o = 0; o < bytes; o += 8) *reinterpret_cast<uint2*>(d + o) = *reinterpret_cast<const uint2*>(s + o);
+    } else {
+        for (int o = 0; o < bytes; o += 4) *reinterpret_cast<uint32_t*>(d + o) = *reinterpret_cast<const uint32_t*>(s + o);
+    }
+}
+
+// table[5][n_crystals + 1] (int32): destination node start, destination edge start, source node start, source edge
+// start, source crystal; the closing column holds (n_nodes, n_edges, 0, 0, 0)
+template <bool LDS>
+__global__ __launch_bounds__(BATCH_THREADS) void batch_gather_kernel(const BatchArgs args, const int32_t* __restrict__ table,
+                                                                      int n_crystals, int n_nodes, int n_edges) {
+    __shared__ int32_t sh[LDS ? 2 * BATCH_LDS_ROWS : 1];
+    const int rows = n_crystals + 1;
+    if (LDS) {
+        for (int k = threadIdx.x; k < 2 * rows; k += BATCH_THREADS) sh[k] = table[k];   // (the two sums are adjacent)
+        __syncthreads();
+    }
+    const int64_t item = (int64_t)blockIdx.x * BATCH_THREADS + threadIdx.x;
+    const int64_t total = (int64_t)n_nodes + n_edges + n_crystals + 1;
+    if (item >= total) return;
+
+    const int32_t* node_sum = LDS ? sh : table;   // destination running sums: [rows] each
+    const int32_t* edge_sum = LDS ? sh + rows : table + rows;
+    int cls, c, local;   // class, crystal of the batch, row inside the crystal
+    int64_t dst_row;
+    if (item < n_nodes) {
+        cls = MATTEN_BATCH_NODE;
+        dst_row = item;
+        c = batch_find(node_sum, rows, (int)item);
+        local = (int)item - node_sum[c];
+    } else if (item < (int64_t)n_nodes + n_edges) {
+        cls = MATTEN_BATCH_EDGE;
+        dst_row = item - n_nodes;
+        c = batch_find(edge_sum, rows, (int)dst_row);
+        local = (int)dst_row - edge_sum[c];
+    } else {
+        cls = MATTEN_BATCH_CRYSTAL;
+        dst_row = item - n_nodes - n_edges;   // == n_crystals: the closing item
+        c = (int)dst_row;
+        local = 0;
+    }
+    const int node0 = node_sum[c], edge0 = edge_sum[c];
+    if (c == n_crystals) {
+        // closing entries: rowptr[N] = E (both CSRs), ptr[B] = N
+        for (int k = 0; k < args.n_streams; ++k) {
+            const BatchStream& st = args.s[k];
+            if (st.op == MATTEN_BATCH_OP_ROWPTR32) reinterpret_cast<int32_t*>(st.dst)[n_nodes] = n_edges;
+            else if (st.op == MATTEN_BATCH_OP_PTR64) reinterpret_cast<int64_t*>(st.dst)[n_crystals] = n_nodes;
+        }
+        return;
+    }
+    const int64_t src_row = cls == MATTEN_BATCH_NODE   ? (int64_t)table[2 * rows + c] + local
+                            : cls == MATTEN_BATCH_EDGE ? (int64_t)table[3 * rows + c] + local
+                                                       : (int64_t)table[4 * rows + c];
+    for (int k = 0; k < args.n_streams; ++k) {
+        const BatchStream& st = args.s[k];
+        if (st.cls != cls) continue;
+        switch (st.op) {
+        case MATTEN_BATCH_OP_RAW:
+            batch_copy_row(st.dst + dst_row * st.row_bytes, st.src + src_row * st.row_bytes, st.row_bytes, st.vec);
+            break;
+        case MATTEN_BATCH_OP_ADD32_NODE:
+            reinterpret_cast<int32_t*>(st.dst)[dst_row] = reinterpret_cast<const int32_t*>(st.src)[src_row] + node0;
+            break;
+        case MATTEN_BATCH_OP_ADD32_EDGE:
+        case MATTEN_BATCH_OP_ROWPTR32:
+            reinterpret_cast<int32_t*>(st.dst)[dst_row] = reinterpret_cast<const int32_t*>(st.src)[src_row] + edge0;
+            break;
+        case MATTEN_BATCH_OP_ADD64_NODE:
+            reinterpret_cast<int64_t*>(st.dst)[dst_row] = reinterpret_cast<const int64_t*>(st.src)[src_row] + node0;
+            break;
+        case MATTEN_BATCH_OP_BATCH64:
+            reinterpret_cast<int64_t*>(st.dst)[dst_row] = c;
+            break;
+        case MATTEN_BATCH_OP_PTR64:
+            reinterpret_cast<int64_t*>(st.dst)[dst_row] = node0;
+            break;
+        }
+    }
+}
+
+extern "C" int matten_batch_gather(const int64_t* streams, int64_t n_streams, const int32_t* table, int64_t n_crystals,
+                                   int64_t n_nodes, int64_t n_edges, matten_stream_t stream_) {
+    if (n_streams < 0 || n_streams > MATTEN_BATCH_MAX_STREAMS || n_crystals < 0 || n_nodes < 0 || n_edges < 0)
+        return MATTEN_EINVAL;
+    if (n_nodes >= ((int64_t)1 << 31) || n_edges >= ((int64_t)1 << 31) || n_crystals >= ((int64_t)1 << 31) - 1)
+        return MATTEN_EINVAL;
+    if ((n_streams > 0 && !streams) || !table) return MATTEN_EINVAL;
+    BatchArgs args;
+    args.n_streams = (int)n_streams;
+    for (int k = 0; k < (int)n_streams; ++k) {
+        const int64_t* d = streams + (int64_t)k * MATTEN_BATCH_STREAM_WORDS;
+        const int64_t src = d[0], dst = d[1], elem = d[2], row_elems = d[3], cls = d[4], op = d[5];
+        if (elem != 4 && elem != 8) return MATTEN_EINVAL;
+        if (row_elems <= 0 || row_elems >= ((int64_t)1 << 28)) return MATTEN_EINVAL;   // (a row stays below 2^31 bytes)
+        if (cls != MATTEN_BATCH_NODE && cls != MATTEN_BATCH_EDGE && cls != MATTEN_BATCH_CRYSTAL) return MATTEN_EINVAL;
+        if (op < MATTEN_BATCH_OP_RAW || op > MATTEN_BATCH_OP_PTR64) return MATTEN_EINVAL;
+        const bool fills = op == MATTEN_BATCH_OP_BATCH64 || op == MATTEN_BATCH_OP_PTR64;
+        if (!dst || (!fills && !src)) return MATTEN_EINVAL;
+        // the offset forms are one element per row of a fixed width, each in its own class
+        const int64_t want_elem = op == MATTEN_BATCH_OP_RAW ? elem
+                                  : (op == MATTEN_BATCH_OP_ADD64_NODE || fills) ? 8 : 4;
+        if (elem != want_elem || (op != MATTEN_BATCH_OP_RAW && row_elems != 1)) return MATTEN_EINVAL;
+        const int64_t want_cls = op == MATTEN_BATCH_OP_RAW ? cls
+                                 : (op == MATTEN_BATCH_OP_ROWPTR32 || op == MATTEN_BATCH_OP_BATCH64) ? MATTEN_BATCH_NODE
+                                 : op == MATTEN_BATCH_OP_PTR64 ? MATTEN_BATCH_CRYSTAL : MATTEN_BATCH_EDGE;
+        if (cls != want_cls) return MATTEN_EINVAL;
+        if ((src | dst) % elem) return MATTEN_EINVAL;
+        BatchStream& st = args.s[k];
+        st.src = (const char*)(uintptr_t)src;
+        st.dst = (char*)(uintptr_t)dst;
+        st.row_bytes = (int32_t)(row_elems * elem);
+        st.cls = (int16_t)cls;
+        st.op = (int8_t)op;
+        const int64_t align = src | dst | st.row_bytes;   // every row of the stream starts on a multiple of `vec`
+        st.vec = (int8_t)(align % 16 == 0 ? 16 : align % 8 == 0 ? 8 : 4);
+    }
+    const int64_t total = n_nodes + n_edges + n_crystals + 1;
+    const int64_t blocks = matten_cdiv(total, BATCH_THREADS);
+    if (blocks >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_crystals + 1 <= BATCH_LDS_ROWS)
+        batch_gather_kernel<true><<<(unsigned)blocks, BATCH_THREADS, 0, stream>>>(args, table, (int)n_crystals, (int)n_nodes,
+                                                                                (int)n_edges);
+    else
+        batch_gather_kernel<false><<<(unsigned)blocks, BATCH_THREADS, 0, stream>>>(args, table, (int)n_crystals, (int)n_nodes,
+                                                                                 (int)n_edges);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}

@@ -36,6 +36,12 @@ TOTAL_ENERGY = "total_energy"
 AMD_PERM = "_amd_perm"            # [E] i32  sorted position -> original edge id
 AMD_ROWPTR = "_amd_rowptr"        # [N+1] i32
 AMD_SRC = "_amd_src_sorted"       # [E] i32
+AMD_DST = "_amd_dst_sorted"       # [E] i32  destination ids in sorted order (training: the tensor-product adjoint)
+# the sorted edges grouped by source node (training: the order in which dL/dx is summed).  A batch of
+# data.store.DeviceGraphStore carries this CSR as two TENSORS, so that a captured step refreshes it on replay;
+# nn/_nequip.ensure_training_edge_tensors forms the tuple "_amd_out_csr" = (ptr, perm) the adjoint reads
+AMD_OUT_PTR = "_amd_out_ptr"      # [N+1] i32
+AMD_OUT_PERM = "_amd_out_perm"    # [E] i32  position in source order -> sorted edge id
 AMD_GEOM = "_amd_geom_sorted"     # [E,4] f32 (vx,vy,vz,|v|)
 AMD_SH = "_amd_sh_sorted"         # [E,(lmax+1)^2] f32
 AMD_SPECIES = "_amd_species_order"  # (order[N] i32 nodes sorted by species, seg[S+1] i32)

@@ -38,6 +38,29 @@ class _Loader:
             yield collate([self.graphs[i] for i in order[lo:lo + self.batch_size]], device=self.device)
 
 
+class _DeviceLoader:
+    """``_Loader`` over a device-resident store (``matten_amd.data.store.DeviceGraphStore``): the same ``batch_size`` /
+    ``shuffle`` / ``seed`` semantics -- the same generator and the same ``randperm`` per epoch, so it visits the same
+    crystals in the same order, the short last batch included -- with every batch gathered on the device."""
+
+    def __init__(self, store, batch_size: int = 1, shuffle: bool = False, seed: int = 0, training: bool = True, **ignored):
+        self.store, self.batch_size, self.shuffle, self.training = store, int(batch_size), bool(shuffle), bool(training)
+        self._gen = torch.Generator().manual_seed(seed)
+
+    def __len__(self) -> int:
+        return -(-len(self.store) // self.batch_size)
+
+    def batch_indices(self) -> List[List[int]]:
+        """the crystal ids of every batch of the NEXT epoch (draws that epoch's permutation, like one pass of iteration)"""
+        n = len(self.store)
+        order = torch.randperm(n, generator=self._gen).tolist() if self.shuffle else list(range(n))
+        return [order[lo:lo + self.batch_size] for lo in range(0, n, self.batch_size)]
+
+    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
+        for idx in self.batch_indices():
+            yield self.store.batch(idx, training=self.training)
+
+
 class TensorDataModule:
     def __init__(
         self,
@@ -56,6 +79,7 @@ class TensorDataModule:
         loader_kwargs: Optional[Dict[str, Any]] = None,
         device=None,
         pbc=None,
+        device_resident: bool = False,
         **unsupported,
     ):
         bad = {k: v for k, v in unsupported.items() if v not in (None, False, [], {})
@@ -71,7 +95,13 @@ class TensorDataModule:
         self.loader_kwargs = dict(loader_kwargs or {})
         self.device = device
         self.pbc = pbc   # a bool or one per axis, applied to every structure; None: each record's own (Molecule: open)
+        # device_resident: the sets are uploaded once in setup() (one DeviceGraphStore per distinct file) and the loaders
+        # gather their batches on the device; the batches are those of the default loaders, plus their CSR keys
+        self.device_resident = bool(device_resident)
+        if self.device_resident and device is None:
+            raise ValueError("device_resident=True needs `device`: the store lives on one GPU")
         self._data: Dict[str, List[Dict[str, torch.Tensor]]] = {}
+        self._stores: Dict[str, Any] = {}
 
     # Lightning's DataModule protocol
     def prepare_data(self):
@@ -99,18 +129,32 @@ class TensorDataModule:
             if fn not in cache:
                 cache[fn] = self._load(fn)
             self._data[mode] = cache[fn]
+        if self.device_resident:
+            from ..data.store import DeviceGraphStore
+
+            stores: Dict[str, Any] = {}
+            for mode, fn in self.files.items():
+                if fn not in stores:
+                    stores[fn] = DeviceGraphStore.from_graphs(cache[fn], self.device)
+                self._stores[mode] = stores[fn]
 
     @property
     def train_data(self):
         return self._data["train"]
 
     def train_dataloader(self):
+        if self.device_resident:
+            return _DeviceLoader(self._stores["train"], training=True, **self.loader_kwargs)
         return _Loader(self._data["train"], device=self.device, **self.loader_kwargs)
 
     def val_dataloader(self):
+        if self.device_resident:
+            return _DeviceLoader(self._stores["val"], training=False, **dict(self.loader_kwargs, shuffle=False))
         return _Loader(self._data["val"], device=self.device, **dict(self.loader_kwargs, shuffle=False))
 
     def test_dataloader(self):
+        if self.device_resident:
+            return _DeviceLoader(self._stores["test"], training=False, **dict(self.loader_kwargs, shuffle=False))
         return _Loader(self._data["test"], device=self.device, **dict(self.loader_kwargs, shuffle=False))
 
     # reference dataset/structure_scalar_tensor.py:640-666

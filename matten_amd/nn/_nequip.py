@@ -81,6 +81,9 @@ def ensure_training_edge_tensors(data: DataKey.Type) -> DataKey.Type:
         pairs = torch.stack([src, src])
         out_perm, out_ptr, _, _ = ops.csr_build(pairs, int(data[DataKey.POSITIONS].shape[0]))
         data["_amd_out_csr"] = (out_ptr, out_perm)
+    elif "_amd_out_csr" not in data and DataKey.AMD_OUT_PTR in data and DataKey.AMD_OUT_PERM in data:
+        # a batch of data.store.DeviceGraphStore: everything above came with it, the source-keyed CSR as two tensors
+        data["_amd_out_csr"] = (data[DataKey.AMD_OUT_PTR], data[DataKey.AMD_OUT_PERM])
     return data
 
 
