@@ -629,6 +629,21 @@ int matten_bn_train_bwd(const float* x, const float* dy, int64_t dim, int64_t n_
                         float eps, float* A, float* B, float* dx, float* dweight, float* dbias, float* scratch,
                         matten_stream_t stream);
 /* dweight [n_chan] = A rsqrt(nu + eps), dbias [number of 0e channels] = B of the 0e channels (both or neither, may be NULL) */
+/* Padded batches: the statistics, the running-average update and the adjoint's two reductions over the rows
+ * [0, *n_valid) only, divided by *n_valid.  n_valid is a DEVICE word the kernels read (the host never does, so the call
+ * captures and a replay sees the refreshed count); n_rows, the padded count, sizes the launches, the scratch and the
+ * choice between the one-launch and the two-stage reductions.  Rows >= *n_valid get y from the valid rows' statistics
+ * and dx = 0 exactly; nothing else depends on their contents.  *n_valid == n_rows gives the bits of the entries above.
+ * *n_valid is clamped to [0, n_rows]; with no valid row mean and nu are zero and the running averages stay as they are.
+ * MATTEN_EINVAL: as above, and a NULL n_valid. */
+int matten_bn_train_fwd_valid(const float* x, int64_t dim, int64_t n_rows, const int32_t* col2chan, const int32_t* chan,
+                              int64_t n_chan, const float* weight, const float* bias, float eps, float* mean, float* nu,
+                              float* y, float* running_mean, float* running_var, float momentum, float* scratch,
+                              const int64_t* n_valid, matten_stream_t stream);
+int matten_bn_train_bwd_valid(const float* x, const float* dy, int64_t dim, int64_t n_rows, const int32_t* col2chan,
+                              const int32_t* chan, int64_t n_chan, const float* mean, const float* nu, const float* weight,
+                              float eps, float* A, float* B, float* dx, float* dweight, float* dbias, float* scratch,
+                              const int64_t* n_valid, matten_stream_t stream);
 
 /* e3nn NormActivation as the reference configures it (nn/utils.py:142-150: nonlinearity_type "norm"; normalize = True,
  * epsilon = 1e-8, bias = False): every channel c (chan[c] = {column offset, 2l+1, is_0e, mean index}, as for
@@ -825,6 +840,35 @@ int matten_batch_gather_lds_rows(void);
 int matten_batch_gather_max_streams(void);
 int matten_batch_gather(const int64_t* streams, int64_t n_streams, const int32_t* table, int64_t n_crystals,
                         int64_t n_nodes, int64_t n_edges, matten_stream_t stream);
+
+/* The same batch grown to FIXED sizes, so that a captured training step can replay it: behind the v_crystals picked
+ * crystals (v_nodes nodes, v_edges edges, written exactly as matten_batch_gather writes them) the launch synthesises
+ * K = n_crystals - v_crystals >= 1 padding crystals from closed forms (no source rows, no search, no second launch).
+ *   Padding crystal 0 owns P = n_nodes - v_nodes - (K - 1) >= 1 nodes and all n_edges - v_edges padding edges; padding
+ *   crystals 1 .. K-1 own one node and no edge.  Node j of padding crystal 0 owns the padding edges
+ *   [floor(j Ep / P), floor((j + 1) Ep / P)), each a self-image edge j -> j, so the padding edges are destination-sorted:
+ *   ADD32_EDGE streams get the identity there, ADD32_NODE / ADD64_NODE the owning node, ROWPTR32 the closed-form bounds,
+ *   BATCH64 / PTR64 follow the layout.
+ *   streams[n_streams][MATTEN_BATCH_PAD_STREAM_WORDS]: the six words of matten_batch_gather, then the fill of a RAW
+ *   stream's padding rows and the fill's element (low four bytes for 4-byte elements):
+ *       PAD_ZERO    zeros                         PAD_CONST   every element = value   (atomic_numbers)
+ *       PAD_FIRST   (value, 0, 0, ...)            (edge_cell_shift = (1, 0, 0))
+ *       PAD_DIAG3   value on the diagonal of a 3 x 3 row (cell = pad_length * I; 9 elements)
+ *       PAD_DEGREE  one float per node: the number of padding edges it owns (num_neigh)
+ *   table[5][n_crystals + 1]: the destination running sums cover the padding crystals; the closing column holds
+ *   (n_nodes, n_edges, v_nodes, v_edges, v_crystals).  n_valid[3] (int64, device) receives its last three entries.
+ * MATTEN_EINVAL: as matten_batch_gather, and n_crystals <= v_crystals, n_edges < v_edges,
+ * n_nodes < v_nodes + (n_crystals - v_crystals), a NULL n_valid, an unknown fill, a fill on a stream that is not RAW,
+ * PAD_DEGREE off a one-float node stream, PAD_DIAG3 off a 9-element row.  Plain stores only: no atomics, no workspace. */
+#define MATTEN_BATCH_PAD_STREAM_WORDS 8
+#define MATTEN_BATCH_PAD_ZERO 0
+#define MATTEN_BATCH_PAD_CONST 1
+#define MATTEN_BATCH_PAD_FIRST 2
+#define MATTEN_BATCH_PAD_DIAG3 3
+#define MATTEN_BATCH_PAD_DEGREE 4
+int matten_batch_gather_padded(const int64_t* streams, int64_t n_streams, const int32_t* table, int64_t n_crystals,
+                               int64_t n_nodes, int64_t n_edges, int64_t v_crystals, int64_t v_nodes, int64_t v_edges,
+                               int64_t* n_valid, matten_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,8 @@ SIGNATURES = {
     "matten_bn_scratch_floats": (c_int64, [c_int64, c_int64]),
     "matten_bn_train_fwd": (c_int, [P, c_int64, c_int64, P, P, c_int64, P, P, c_float, P, P, P, P, P, c_float, P, P]),
     "matten_bn_train_bwd": (c_int, [P, P, c_int64, c_int64, P, P, c_int64, P, P, P, c_float, P, P, P, P, P, P, P]),
+    "matten_bn_train_fwd_valid": (c_int, [P, c_int64, c_int64, P, P, c_int64, P, P, c_float, P, P, P, P, P, c_float, P, P, P]),
+    "matten_bn_train_bwd_valid": (c_int, [P, P, c_int64, c_int64, P, P, c_int64, P, P, P, c_float, P, P, P, P, P, P, P, P]),
     "matten_norm_act": (c_int, [P, c_int64, c_int64, P, c_int64, c_int, c_float, P, P, P, P, c_float, P, P]),
     "matten_norm_act_bwd": (c_int, [P, P, c_int64, c_int64, P, c_int64, c_int, c_float, P, P]),
     "matten_bn_eval_bwd_scratch_floats": (c_int64, [c_int64, c_int64]),
@@ -128,6 +130,7 @@ SIGNATURES = {
     "matten_batch_gather_lds_rows": (c_int, []),
     "matten_batch_gather_max_streams": (c_int, []),
     "matten_batch_gather": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P]),
+    "matten_batch_gather_padded": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, P, P]),
 }
 
 _lib = None

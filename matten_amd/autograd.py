@@ -351,24 +351,27 @@ class NormActBnEvalFn(torch.autograd.Function):
 
 class BatchNormTrainFn(torch.autograd.Function):
     """e3nn BatchNorm with batch statistics; the running averages are updated in place by the statistics kernel
-    (running = (1 - momentum) running + momentum batch), so the step needs no small library launches for them."""
+    (running = (1 - momentum) running + momentum batch), so the step needs no small library launches for them.
+    n_valid (optional): the device word of a padded batch (``_amd_n_valid``); the statistics, the running averages and
+    the adjoint's reductions then run over the rows in front of it only."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, bn):
+    def forward(ctx, x, weight, bias, bn, n_valid=None):
         dev = x.device
         y, mean, nu = ops.bn_train_fwd(x, bn._tables.get("col2chan", dev), bn._tables.get("chan", dev), weight, bias,
-                                       bn.eps, bn.running_mean, bn.running_var, bn.momentum)
+                                       bn.eps, bn.running_mean, bn.running_var, bn.momentum, n_valid=n_valid)
         ctx.bn = bn
-        ctx.save_for_backward(x, weight, mean, nu)
+        ctx.save_for_backward(x, weight, mean, nu, n_valid)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x, weight, mean, nu = ctx.saved_tensors
+        x, weight, mean, nu, n_valid = ctx.saved_tensors
         bn, dev = ctx.bn, g.device
         dx, dweight, dbias = ops.bn_train_bwd(x, g.contiguous(), bn._tables.get("col2chan", dev),
-                                              bn._tables.get("chan", dev), mean, nu, weight, bn.eps, bn.bias.numel())
-        return dx, dweight, dbias, None
+                                              bn._tables.get("chan", dev), mean, nu, weight, bn.eps, bn.bias.numel(),
+                                              n_valid=n_valid)
+        return dx, dweight, dbias, None, None
 
 
 class InstanceNormFn(torch.autograd.Function):

@@ -473,15 +473,25 @@ __global__ void norm_act_bwd_kernel(const float* __restrict__ x, const float* __
 // ------------------------------------------------------------------------------------------------
 // Segmented form (instance / graph normalisation, reference nn/utils.py:448-588: one set of statistics per crystal):
 // seg_ptr[B+1] != NULL, grid.y = B, rows [seg_ptr[b], seg_ptr[b+1]) -> mean / nu [B, C]; seg_ptr == NULL: the whole batch.
+// Valid-rows form (padded batches, matten_bn_train_fwd_valid / _bwd_valid): n_valid != NULL is a DEVICE word, the
+// reductions run over rows [0, *n_valid) and divide by it; the rows behind are padding.  The launch shapes and the
+// route follow the padded row count, which a captured step keeps; *n_valid == n_rows gives the bits of n_valid == NULL.
+__device__ __forceinline__ int64_t bn_valid_rows(const int64_t* __restrict__ n_valid, int64_t n_rows) {
+    if (!n_valid) return n_rows;
+    const int64_t v = *n_valid;
+    return v < 0 ? 0 : v > n_rows ? n_rows : v;
+}
+
 __global__ void bn_stats_kernel(const float* __restrict__ x, int dim, int64_t n_rows_all, const int4* __restrict__ chan,
                                 float* __restrict__ mean, float* __restrict__ nu, const int64_t* __restrict__ seg_ptr,
-                                float* __restrict__ running_mean, float* __restrict__ running_var, float momentum) {
+                                float* __restrict__ running_mean, float* __restrict__ running_var, float momentum,
+                                const int64_t* __restrict__ n_valid) {
     __shared__ float red[256];
     const int c = blockIdx.x;
     const int4 ch = chan[c];
     const int d = ch.y;
     const int64_t r0 = seg_ptr ? seg_ptr[blockIdx.y] : 0;
-    const int64_t n_rows = seg_ptr ? seg_ptr[blockIdx.y + 1] - r0 : n_rows_all;
+    const int64_t n_rows = seg_ptr ? seg_ptr[blockIdx.y + 1] - r0 : bn_valid_rows(n_valid, n_rows_all);
     x += r0 * dim;
     mean += (int64_t)blockIdx.y * gridDim.x;
     nu += (int64_t)blockIdx.y * gridDim.x;
@@ -561,10 +571,15 @@ constexpr int BN_RB = 16;             // rows per block
 constexpr int BN_COLS_MIN_ROWS = 2048;   // below: the one-launch kernels
 __global__ __launch_bounds__(256) void bn_stats_cols_kernel(const float* __restrict__ x, int dim, int64_t n_rows,
                                                             const int32_t* __restrict__ col2chan,
-                                                            const int4* __restrict__ chan, float2* __restrict__ part) {
+                                                            const int4* __restrict__ chan, float2* __restrict__ part,
+                                                            const int64_t* __restrict__ n_valid) {
     const int64_t r0 = (int64_t)blockIdx.x * BN_RB;
-    const int nr = (int)min((int64_t)BN_RB, n_rows - r0);
+    const int nr = (int)min((int64_t)BN_RB, bn_valid_rows(n_valid, n_rows) - r0);
     for (int col = threadIdx.x; col < dim; col += blockDim.x) {
+        if (nr <= 0) {   // a block of padding rows only: an empty record (bn_stats_finish_kernel merges a count of 0)
+            part[(int64_t)blockIdx.x * dim + col] = make_float2(0.0f, 0.0f);
+            continue;
+        }
         float v[BN_RB];
 #pragma unroll
         for (int r = 0; r < BN_RB; ++r) v[r] = r < nr ? x[(r0 + r) * dim + col] : 0.0f;
@@ -599,15 +614,21 @@ __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const float2* __re
                                                               int n_blocks, const int4* __restrict__ chan,
                                                               float* __restrict__ mean, float* __restrict__ nu,
                                                               float* __restrict__ running_mean,
-                                                              float* __restrict__ running_var, float momentum) {
+                                                              float* __restrict__ running_var, float momentum,
+                                                              const int64_t* __restrict__ n_valid) {
     __shared__ float rn[256], rm[256], rq[256];
     const int c = blockIdx.x, t = threadIdx.x;
     const int4 ch = chan[c];
+    n_rows = bn_valid_rows(n_valid, n_rows);
+    if (n_rows <= 0) {   // no valid row (as bn_stats_kernel): zero statistics, the running averages stay
+        if (t == 0) mean[c] = 0.0f, nu[c] = 0.0f;
+        return;
+    }
     float n = 0.0f, m = 0.0f, q = 0.0f;
     if (ch.z) {   // one column: thread t merges blocks t, t + 256, ... in order
         for (int b = t; b < n_blocks; b += 256) {
             const float2 p = part[(int64_t)b * dim + ch.x];
-            bn_merge(n, m, q, (float)min((int64_t)BN_RB, n_rows - (int64_t)b * BN_RB), p.x, p.y);
+            bn_merge(n, m, q, (float)max((int64_t)0, min((int64_t)BN_RB, n_rows - (int64_t)b * BN_RB)), p.x, p.y);
         }
     } else {
         const int items = n_blocks * ch.y;
@@ -640,9 +661,10 @@ __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const float2* __re
 // adjoint reductions, same two stages: part[block, column] = (sum dy (x - mean), sum dy) over the block's rows
 __global__ __launch_bounds__(256) void bn_bwd_cols_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           int dim, int64_t n_rows, const int32_t* __restrict__ col2chan,
-                                                          const float* __restrict__ mean, float2* __restrict__ part) {
+                                                          const float* __restrict__ mean, float2* __restrict__ part,
+                                                          const int64_t* __restrict__ n_valid) {
     const int64_t r0 = (int64_t)blockIdx.x * BN_RB;
-    const int nr = (int)min((int64_t)BN_RB, n_rows - r0);
+    const int nr = (int)min((int64_t)BN_RB, bn_valid_rows(n_valid, n_rows) - r0);   // (<= 0: padding rows only, zeros)
     for (int col = threadIdx.x; col < dim; col += blockDim.x) {
         const float mu = mean[col2chan[col]];
         float xv[BN_RB], g[BN_RB];
@@ -714,10 +736,11 @@ __global__ void bn_bwd_reduce_kernel(const float* __restrict__ x, const float* _
                                      const int4* __restrict__ chan, const float* __restrict__ mean,
                                      float* __restrict__ A, float* __restrict__ B, const int64_t* __restrict__ seg_ptr,
                                      const float* __restrict__ nu, float eps, float* __restrict__ dweight,
-                                     float* __restrict__ dbias) {
+                                     float* __restrict__ dbias, const int64_t* __restrict__ n_valid) {
     __shared__ float ra[256], rb[256];
     const int c = blockIdx.x;
     const int4 ch = chan[c];
+    n_rows = bn_valid_rows(n_valid, n_rows);
     if (seg_ptr) {   // segment blockIdx.y (see bn_stats_kernel)
         const int64_t r0 = seg_ptr[blockIdx.y];
         n_rows = seg_ptr[blockIdx.y + 1] - r0;
@@ -783,14 +806,19 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __
                                     const float* __restrict__ weight, const float* __restrict__ A,
                                     const float* __restrict__ B, float eps, float* __restrict__ dx,
                                     const int64_t* __restrict__ seg_of_row, const int64_t* __restrict__ seg_ptr,
-                                    int n_chan) {
+                                    int n_chan, const int64_t* __restrict__ n_valid) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n_rows * dim) return;
+    const int64_t valid = bn_valid_rows(n_valid, n_rows);
+    if (idx >= valid * dim) {   // a padding row: outside the statistics, so nothing flows back into it
+        dx[idx] = 0.0f;
+        return;
+    }
     const int col = (int)(idx % dim);
     const int c = col2chan[col];
     const int4 ch = chan[c];
     int64_t sc = c;
-    float rows = (float)n_rows;
+    float rows = (float)valid;
     if (seg_of_row) {
         const int64_t b = seg_of_row[idx / dim];
         sc = b * n_chan + c;
@@ -946,10 +974,12 @@ extern "C" int64_t matten_bn_scratch_floats(int64_t n_rows, int64_t dim) {
     return n_rows >= BN_COLS_MIN_ROWS ? 2 * matten_cdiv(n_rows, BN_RB) * dim : 0;
 }
 
-extern "C" int matten_bn_train_fwd(const float* x, int64_t dim, int64_t n_rows, const int32_t* col2chan,
-                                   const int32_t* chan, int64_t n_chan, const float* weight, const float* bias,
-                                   float eps, float* mean, float* nu, float* y, float* running_mean,
-                                   float* running_var, float momentum, float* scratch, matten_stream_t stream_) {
+// n_valid == NULL: every row counts (matten_bn_train_fwd); else a device word read by the kernels (.._valid)
+static int bn_train_fwd_launch(const float* x, int64_t dim, int64_t n_rows, const int32_t* col2chan,
+                               const int32_t* chan, int64_t n_chan, const float* weight, const float* bias,
+                               float eps, float* mean, float* nu, float* y, float* running_mean,
+                               float* running_var, float momentum, float* scratch, const int64_t* n_valid,
+                               matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_rows <= 0 || dim <= 0 || n_chan <= 0) return MATTEN_EINVAL;
     if (!x || !col2chan || !chan || !weight || !bias || !mean || !nu || !y) return MATTEN_EINVAL;
@@ -959,22 +989,41 @@ extern "C" int matten_bn_train_fwd(const float* x, int64_t dim, int64_t n_rows, 
         const int64_t n_blocks = matten_cdiv(n_rows, BN_RB);
         if (n_blocks >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
         bn_stats_cols_kernel<<<(unsigned)n_blocks, 256, 0, stream>>>(x, (int)dim, n_rows, col2chan, (const int4*)chan,
-                                                                     (float2*)scratch);
+                                                                     (float2*)scratch, n_valid);
         MATTEN_LAUNCH_CHECK();
         bn_stats_finish_kernel<<<(unsigned)n_chan, 256, 0, stream>>>((const float2*)scratch, (int)dim, n_rows,
                                                                      (int)n_blocks, (const int4*)chan, mean, nu,
-                                                                     running_mean, running_var, momentum);
+                                                                     running_mean, running_var, momentum, n_valid);
     } else {
         bn_stats_kernel<<<(unsigned)n_chan, 256, 0, stream>>>(x, (int)dim, n_rows, (const int4*)chan, mean, nu, nullptr,
-                                                              running_mean, running_var, momentum);
+                                                              running_mean, running_var, momentum, n_valid);
     }
     MATTEN_LAUNCH_CHECK();
     const int T = 256;
+    // (padding rows get y from the valid rows' statistics: finite)
     bn_apply_kernel<<<(unsigned)matten_cdiv(n_rows * dim, T), T, 0, stream>>>(x, (int)dim, n_rows, col2chan,
                                                                               (const int4*)chan, mean, nu, weight, bias,
                                                                               eps, y, nullptr, (int)n_chan);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
+}
+
+extern "C" int matten_bn_train_fwd(const float* x, int64_t dim, int64_t n_rows, const int32_t* col2chan,
+                                   const int32_t* chan, int64_t n_chan, const float* weight, const float* bias,
+                                   float eps, float* mean, float* nu, float* y, float* running_mean,
+                                   float* running_var, float momentum, float* scratch, matten_stream_t stream_) {
+    return bn_train_fwd_launch(x, dim, n_rows, col2chan, chan, n_chan, weight, bias, eps, mean, nu, y, running_mean,
+                               running_var, momentum, scratch, nullptr, stream_);
+}
+
+extern "C" int matten_bn_train_fwd_valid(const float* x, int64_t dim, int64_t n_rows, const int32_t* col2chan,
+                                         const int32_t* chan, int64_t n_chan, const float* weight, const float* bias,
+                                         float eps, float* mean, float* nu, float* y, float* running_mean,
+                                         float* running_var, float momentum, float* scratch, const int64_t* n_valid,
+                                         matten_stream_t stream_) {
+    if (!n_valid) return MATTEN_EINVAL;
+    return bn_train_fwd_launch(x, dim, n_rows, col2chan, chan, n_chan, weight, bias, eps, mean, nu, y, running_mean,
+                               running_var, momentum, scratch, n_valid, stream_);
 }
 
 // Instance (graph) normalisation, reference nn/utils.py:448-588: the statistics of matten_bn_train_fwd per crystal.
@@ -989,7 +1038,7 @@ extern "C" int matten_instance_norm_fwd(const float* x, int64_t dim, int64_t n_r
     if (!seg_ptr || !col2chan || !chan || !weight || !bias || !mean || !nu) return MATTEN_EINVAL;
     if (n_rows > 0 && (!x || !y || !seg_of_row)) return MATTEN_EINVAL;
     bn_stats_kernel<<<dim3((unsigned)n_chan, (unsigned)n_seg), 256, 0, stream>>>(x, (int)dim, n_rows, (const int4*)chan, mean,
-                                                                                  nu, seg_ptr, nullptr, nullptr, 0.0f);
+                                                                                  nu, seg_ptr, nullptr, nullptr, 0.0f, nullptr);
     MATTEN_LAUNCH_CHECK();
     if (n_rows == 0) return MATTEN_OK;
     const int T = 256;
@@ -1012,20 +1061,21 @@ extern "C" int matten_instance_norm_bwd(const float* x, const float* dy, int64_t
         return MATTEN_EINVAL;
     bn_bwd_reduce_kernel<<<dim3((unsigned)n_chan, (unsigned)n_seg), 256, 0, stream>>>(x, dy, (int)dim, n_rows,
                                                                                        (const int4*)chan, mean, A, B, seg_ptr,
-                                                                                       nullptr, 0.0f, nullptr, nullptr);
+                                                                                       nullptr, 0.0f, nullptr, nullptr, nullptr);
     MATTEN_LAUNCH_CHECK();
     const int T = 256;
     bn_bwd_apply_kernel<<<(unsigned)matten_cdiv(n_rows * dim, T), T, 0, stream>>>(
         x, dy, (int)dim, n_rows, col2chan, (const int4*)chan, mean, nu, weight, A, B, eps, dx, seg_of_row, seg_ptr,
-        (int)n_chan);
+        (int)n_chan, nullptr);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }
 
-extern "C" int matten_bn_train_bwd(const float* x, const float* dy, int64_t dim, int64_t n_rows,
-                                   const int32_t* col2chan, const int32_t* chan, int64_t n_chan, const float* mean,
-                                   const float* nu, const float* weight, float eps, float* A, float* B, float* dx,
-                                   float* dweight, float* dbias, float* scratch, matten_stream_t stream_) {
+static int bn_train_bwd_launch(const float* x, const float* dy, int64_t dim, int64_t n_rows,
+                               const int32_t* col2chan, const int32_t* chan, int64_t n_chan, const float* mean,
+                               const float* nu, const float* weight, float eps, float* A, float* B, float* dx,
+                               float* dweight, float* dbias, float* scratch, const int64_t* n_valid,
+                               matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_rows <= 0 || dim <= 0 || n_chan <= 0) return MATTEN_EINVAL;
     if (!x || !dy || !col2chan || !chan || !mean || !nu || !weight || !A || !B || !dx) return MATTEN_EINVAL;
@@ -1035,20 +1085,40 @@ extern "C" int matten_bn_train_bwd(const float* x, const float* dy, int64_t dim,
         const int64_t n_blocks = matten_cdiv(n_rows, BN_RB);
         if (n_blocks >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
         bn_bwd_cols_kernel<<<(unsigned)n_blocks, 256, 0, stream>>>(x, dy, (int)dim, n_rows, col2chan, mean,
-                                                                   (float2*)scratch);
+                                                                   (float2*)scratch, n_valid);
         MATTEN_LAUNCH_CHECK();
         bn_bwd_finish_kernel<<<(unsigned)n_chan, 256, 0, stream>>>((const float2*)scratch, (int)dim, (int)n_blocks,
                                                                    (const int4*)chan, A, B, nu, eps, dweight, dbias);
     } else {
         bn_bwd_reduce_kernel<<<(unsigned)n_chan, 256, 0, stream>>>(x, dy, (int)dim, n_rows, (const int4*)chan, mean, A, B,
-                                                                   nullptr, nu, eps, dweight, dbias);
+                                                                   nullptr, nu, eps, dweight, dbias, n_valid);
     }
     MATTEN_LAUNCH_CHECK();
     const int T = 256;
     bn_bwd_apply_kernel<<<(unsigned)matten_cdiv(n_rows * dim, T), T, 0, stream>>>(
-        x, dy, (int)dim, n_rows, col2chan, (const int4*)chan, mean, nu, weight, A, B, eps, dx, nullptr, nullptr, (int)n_chan);
+        x, dy, (int)dim, n_rows, col2chan, (const int4*)chan, mean, nu, weight, A, B, eps, dx, nullptr, nullptr, (int)n_chan,
+        n_valid);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
+}
+
+extern "C" int matten_bn_train_bwd(const float* x, const float* dy, int64_t dim, int64_t n_rows,
+                                   const int32_t* col2chan, const int32_t* chan, int64_t n_chan, const float* mean,
+                                   const float* nu, const float* weight, float eps, float* A, float* B, float* dx,
+                                   float* dweight, float* dbias, float* scratch, matten_stream_t stream_) {
+    return bn_train_bwd_launch(x, dy, dim, n_rows, col2chan, chan, n_chan, mean, nu, weight, eps, A, B, dx, dweight, dbias,
+                               scratch, nullptr, stream_);
+}
+
+// dx of the rows behind *n_valid is exactly zero, whatever dy holds there
+extern "C" int matten_bn_train_bwd_valid(const float* x, const float* dy, int64_t dim, int64_t n_rows,
+                                         const int32_t* col2chan, const int32_t* chan, int64_t n_chan, const float* mean,
+                                         const float* nu, const float* weight, float eps, float* A, float* B, float* dx,
+                                         float* dweight, float* dbias, float* scratch, const int64_t* n_valid,
+                                         matten_stream_t stream_) {
+    if (!n_valid) return MATTEN_EINVAL;
+    return bn_train_bwd_launch(x, dy, dim, n_rows, col2chan, chan, n_chan, mean, nu, weight, eps, A, B, dx, dweight, dbias,
+                               scratch, n_valid, stream_);
 }
 
 extern "C" int matten_segment_reduce_bwd(const float* dy, int64_t dim, const int64_t* ptr, int64_t n_segments, int mean,

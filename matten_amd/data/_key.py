@@ -42,6 +42,9 @@ AMD_DST = "_amd_dst_sorted"       # [E] i32  destination ids in sorted order (tr
 # nn/_nequip.ensure_training_edge_tensors forms the tuple "_amd_out_csr" = (ptr, perm) the adjoint reads
 AMD_OUT_PTR = "_amd_out_ptr"      # [N+1] i32
 AMD_OUT_PERM = "_amd_out_perm"    # [E] i32  position in source order -> sorted edge id
+# a padded batch (data.store.DeviceGraphStore.batch(pad_to=...)): how much of it is real.  A tensor, so that a captured
+# step refreshes it on replay; training-mode BatchNorm reads its first word on the device
+AMD_N_VALID = "_amd_n_valid"      # [3] i64  valid nodes, edges, crystals
 AMD_GEOM = "_amd_geom_sorted"     # [E,4] f32 (vx,vy,vz,|v|)
 AMD_SH = "_amd_sh_sorted"         # [E,(lmax+1)^2] f32
 AMD_SPECIES = "_amd_species_order"  # (order[N] i32 nodes sorted by species, seg[S+1] i32)

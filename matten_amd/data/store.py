@@ -25,6 +25,9 @@ from . import _key as DataKey
 NODE, EDGE, CRYSTAL = 0, 1, 2   # MATTEN_BATCH_NODE / _EDGE / _CRYSTAL (include/matten_hip.h)
 OP_RAW, OP_ADD32_NODE, OP_ADD32_EDGE, OP_ADD64_NODE, OP_ROWPTR32, OP_BATCH64, OP_PTR64 = range(7)
 STREAM_WORDS = 6
+# matten_batch_gather_padded: two more words per stream, the fill of a RAW stream's padding rows and the fill's element
+PAD_STREAM_WORDS = 8
+PAD_ZERO, PAD_CONST, PAD_FIRST, PAD_DIAG3, PAD_DEGREE = range(5)
 
 # key -> (class, dtype, shape of one crystal's tensor with n atoms / e edges written as "n" / "e")
 CORE_KEYS = {
@@ -129,6 +132,116 @@ class GraphStoreHost:
         table[2, :b], table[3, :b], table[4, :b] = self.node_ptr[idx], self.edge_ptr[idx], idx
         return table, n_out, e_out
 
+    # ---- padded batches: fixed sizes (N_b, E_b, B_b), so that a captured training step can replay them ----------------
+    #
+    # Behind the B picked crystals (N nodes, E edges, exactly the unpadded batch) come K = B_b - B >= 1 padding crystals.
+    # Padding crystal 0 owns P = N_b - N - (K - 1) >= 1 nodes and all E_b - E padding edges; padding crystals 1 .. K-1 own
+    # one node and no edge (the short last batch of an epoch).  Node j of padding crystal 0 owns the padding edges
+    # [floor(j (E_b - E) / P), floor((j + 1) (E_b - E) / P)), each a self-image edge j -> j with cell shift (1, 0, 0) in the
+    # cell pad_length * I: its length is pad_length > 0 (a zero-length edge is 0/0 in the harmonics), no padding crystal
+    # is empty (mean pooling), and the padding edges are destination-sorted as they stand.
+    def plan_padded(self, idx, pad_to) -> Tuple[np.ndarray, int, int]:
+        """-> (table int32 [5, B_b + 1], N, E) for matten_batch_gather_padded: the destination running sums cover the
+        padding crystals, the source rows of the padding columns are 0, the closing column is (N_b, E_b, N, E, B).
+        ValueError unless B_b > B, E_b >= E and N_b >= N + (B_b - B)."""
+        real, n, e = self.plan(idx)
+        b = real.shape[1] - 1
+        try:
+            n_b, e_b, b_b = (int(v) for v in pad_to)
+        except (TypeError, ValueError):
+            raise ValueError(f"pad_to = {pad_to!r}: expected (nodes, edges, crystals)") from None
+        k = b_b - b
+        if k < 1:
+            raise ValueError(f"pad_to asks for {b_b} crystals, the batch holds {b}: at least one padding crystal is needed")
+        if e_b < e:
+            raise ValueError(f"pad_to asks for {e_b} edges, the batch holds {e}")
+        if n_b < n + k:
+            raise ValueError(f"pad_to asks for {n_b} nodes, the batch holds {n} and its {k} padding crystals need one each")
+        if n_b >= 2 ** 31 or e_b >= 2 ** 31:
+            raise ValueError(f"a batch of {n_b} atoms and {e_b} edges: both must stay below 2^31")
+        p = n_b - n - (k - 1)
+        table = np.zeros((5, b_b + 1), dtype=np.int32)
+        table[:, :b] = real[:, :b]
+        table[0, b] = n
+        table[0, b + 1:b_b] = n + p + np.arange(k - 1)
+        table[1, b] = e
+        table[1, b + 1:b_b] = e_b
+        table[:, b_b] = (n_b, e_b, n, e, b)
+        return table, n, e
+
+    def pad_values(self, pad_species=None, pad_length: float = 2.0) -> Tuple[int, float]:
+        """(species, length) of the padding atoms and edges, checked: the species must be one of the store's (default: its
+        smallest atomic number), so that the model's species table holds it; the length must be positive"""
+        species = np.unique(self.flat[DataKey.ATOMIC_NUMBERS].numpy())
+        z = int(species[0]) if pad_species is None else int(pad_species)
+        if z not in species.tolist():
+            raise ValueError(f"pad_species {z} is none of the store's species {species.tolist()}")
+        length = float(pad_length)
+        if not (length > 0.0 and np.isfinite(length)):
+            raise ValueError(f"pad_length {pad_length}: a padding edge needs a positive length")
+        return z, length
+
+    def padded_reference(self, idx, pad_to, pad_species=None, pad_length: float = 2.0,
+                         training: bool = True) -> Dict[str, torch.Tensor]:
+        """The padded batch restated on the host, key for key what ``DeviceGraphStore.batch(idx, pad_to=...)`` returns: the
+        definition the kernel is tested against."""
+        table, n, e = self.plan_padded(idx, pad_to)
+        z, length = self.pad_values(pad_species, pad_length)
+        b_b = table.shape[1] - 1
+        n_b, e_b, b = int(table[0, -1]), int(table[1, -1]), int(table[4, -1])
+        k, ep = b_b - b, e_b - e
+        p = n_b - n - (k - 1)
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        # padding node j of crystal 0 owns the edges [lo[j], lo[j + 1]) (python integers: exact)
+        lo = np.array([j * ep // p for j in range(p + 1)], dtype=np.int64)
+        owner = n + np.repeat(np.arange(p, dtype=np.int64), np.diff(lo))            # per padding edge
+        degree = np.concatenate([np.diff(lo), np.zeros(k - 1, dtype=np.int64)])      # per padding node
+        rows = {NODE: n_b - n, EDGE: ep, CRYSTAL: k}
+        out: Dict[str, torch.Tensor] = {}
+        for key in self.keys:
+            flat, cls = self.flat[key], self.classes[key]
+            ptr = self.node_ptr if cls == NODE else self.edge_ptr if cls == EDGE else np.arange(self.n + 1)
+            if key == DataKey.EDGE_INDEX:
+                real = torch.cat([flat[:, ptr[i]:ptr[i + 1]] + int(table[0, c]) for c, i in enumerate(idx)], dim=1)
+                out[key] = torch.cat([real, torch.from_numpy(np.stack([owner, owner]))], dim=1)
+                continue
+            per = 3 if key == DataKey.CELL else 1   # (a crystal's cell is three rows)
+            real = torch.cat([flat[per * ptr[i]:per * ptr[i + 1]] for i in idx], dim=0)
+            pad = torch.zeros((per * rows[cls],) + tuple(flat.shape[1:]), dtype=flat.dtype)
+            if key == DataKey.CELL:
+                pad = (length * torch.eye(3, dtype=flat.dtype)).repeat(k, 1)
+            elif key == DataKey.EDGE_CELL_SHIFT:
+                pad[:, 0] = 1.0
+            elif key == DataKey.ATOMIC_NUMBERS:
+                pad[:] = z
+            elif key == DataKey.NUM_NEIGH:
+                pad = torch.from_numpy(degree).to(flat.dtype)
+            out[key] = torch.cat([real, pad], dim=0)
+        sizes = np.diff(table[0].astype(np.int64))   # nodes per crystal, the padding ones included
+        out[DataKey.BATCH] = torch.from_numpy(np.repeat(np.arange(b_b, dtype=np.int64), sizes))
+        out[DataKey.PTR] = torch.from_numpy(table[0].astype(np.int64))
+        # the real part's CSR by a stable sort, the padding part by its closed form
+        src, dst = (out[DataKey.EDGE_INDEX][r, :e].numpy() for r in (0, 1))
+        perm = np.argsort(dst, kind="stable")
+        src_s, dst_s = src[perm], dst[perm]
+        out_perm = np.argsort(src_s, kind="stable")
+        pad_ids = np.arange(e, e_b, dtype=np.int64)
+        pad_ptr = np.concatenate([e + lo[:p], np.full(k, e_b, dtype=np.int64)])   # padding nodes, then the closing entry
+
+        def rowptr(ids):
+            return np.concatenate([np.searchsorted(ids, np.arange(n), side="left"), pad_ptr])
+
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.int32))
+        out[DataKey.AMD_PERM] = i32(np.concatenate([perm, pad_ids]))
+        out[DataKey.AMD_ROWPTR] = i32(rowptr(dst_s))
+        out[DataKey.AMD_SRC] = i32(np.concatenate([src_s, owner]))
+        if training:
+            out[DataKey.AMD_DST] = i32(np.concatenate([dst_s, owner]))
+            out[DataKey.AMD_OUT_PTR] = i32(rowptr(src_s[out_perm]))
+            out[DataKey.AMD_OUT_PERM] = i32(np.concatenate([out_perm, pad_ids]))
+        out[DataKey.AMD_N_VALID] = torch.tensor([n, e, b], dtype=torch.int64)
+        return out
+
 
 class DeviceGraphStore:
     """The whole set on one device.  ``batch(idx)`` returns what ``collate([graphs[i] for i in idx], device)`` returns,
@@ -213,25 +326,43 @@ class DeviceGraphStore:
         own = (self._perm, self._src, self._dst, self._out_perm, self._rowptr, self._out_ptr)
         return sum(t.numel() * t.element_size() for t in (*self._dev.values(), *own))
 
-    def batch(self, idx, training: bool = True) -> Dict[str, torch.Tensor]:
+    def batch(self, idx, training: bool = True, pad_to=None, pad_species=None,
+              pad_length: float = 2.0) -> Dict[str, torch.Tensor]:
+        """pad_to = (N_b, E_b, B_b): the batch grown to exactly these sizes by padding crystals the same launch writes
+        (layout: GraphStoreHost.plan_padded; the definition: GraphStoreHost.padded_reference), plus the tensor key
+        ``_amd_n_valid`` = (N, E, B).  pad_to=None: the batch as it is."""
         from .. import _lib
         from ..ops import _stream
 
-        table, n_out, e_out = self.host.plan(idx)
+        padded = pad_to is not None
+        if padded:
+            table, n_real, e_real = self.host.plan_padded(idx, pad_to)
+            z, length = self.host.pad_values(pad_species, pad_length)
+            n_out, e_out = int(table[0, -1]), int(table[1, -1])
+            # (CORE_KEYS pins these dtypes, checked per graph by GraphStoreHost: edge_cell_shift, cell and num_neigh are
+            # float32, atomic_numbers int64 -- the fills below are elements of those widths)
+            bits = lambda v: int(np.float32(v).view(np.int32))
+            fills = {DataKey.EDGE_CELL_SHIFT: (PAD_FIRST, bits(1.0)), DataKey.CELL: (PAD_DIAG3, bits(length)),
+                     DataKey.NUM_NEIGH: (PAD_DEGREE, 0), DataKey.ATOMIC_NUMBERS: (PAD_CONST, z)}
+        else:
+            table, n_out, e_out = self.host.plan(idx)
         b = table.shape[1] - 1
         dev = self.device
         rows = (n_out, e_out, b)
         out: Dict[str, torch.Tensor] = {}
         streams: List[Tuple[int, ...]] = []
+        stream_keys: List[str] = []   # the key of every stream (a padded batch fills its padding rows by key)
         for k, src, dtype, row, cls, op in self._public:
             if k == DataKey.EDGE_INDEX:
                 dst = torch.empty((2, e_out), dtype=dtype, device=dev)
                 stride = 8 * src.shape[1]
                 streams.append((src.data_ptr(), dst.data_ptr(), 8, 1, cls, op))
                 streams.append((src.data_ptr() + stride, dst.data_ptr() + 8 * e_out, 8, 1, cls, op))
+                stream_keys += [k, k]
             elif k == DataKey.CELL:
                 dst = torch.empty((3 * b, 3), dtype=dtype, device=dev)
                 streams.append((src.data_ptr(), dst.data_ptr(), 4, 9, cls, op))
+                stream_keys.append(k)
             else:
                 dst = torch.empty((rows[cls],) + row, dtype=dtype, device=dev)
                 n_elem = 1
@@ -241,16 +372,33 @@ class DeviceGraphStore:
                     out[k] = dst
                     continue
                 streams.append((src.data_ptr(), dst.data_ptr(), src.element_size(), n_elem, cls, op))
+                stream_keys.append(k)
             out[k] = dst
         out[DataKey.BATCH] = torch.empty(n_out, dtype=torch.int64, device=dev)
         out[DataKey.PTR] = torch.empty(b + 1, dtype=torch.int64, device=dev)
         streams.append((0, out[DataKey.BATCH].data_ptr(), 8, 1, NODE, OP_BATCH64))
         streams.append((0, out[DataKey.PTR].data_ptr(), 8, 1, CRYSTAL, OP_PTR64))
+        stream_keys += [DataKey.BATCH, DataKey.PTR]
         for k, src, cls, op in (self._csr + self._train if training else self._csr):
             dst = torch.empty((n_out + 1) if op == OP_ROWPTR32 else e_out, dtype=torch.int32, device=dev)
             streams.append((src.data_ptr(), dst.data_ptr(), 4, 1, cls, op))
+            stream_keys.append(k)
             out[k] = dst
         tab = torch.from_numpy(table).to(dev)   # the one host-to-device copy of a batch
+        if padded:
+            out[DataKey.AMD_N_VALID] = n_valid = torch.empty(3, dtype=torch.int64, device=dev)
+            # (the fill of every RAW stream follows its key; the streams above were appended in key order)
+            desc = np.zeros((len(streams), PAD_STREAM_WORDS), dtype=np.int64)
+            desc[:, :STREAM_WORDS] = np.asarray(streams, dtype=np.int64)
+            for row, key in enumerate(stream_keys):
+                desc[row, STREAM_WORDS:] = fills.get(key, (PAD_ZERO, 0))
+            b_real = int(table[4, -1])
+            for lo in range(0, len(streams), self._max_streams):
+                part = np.ascontiguousarray(desc[lo:lo + self._max_streams])
+                _lib.check(self._lib.matten_batch_gather_padded(part.ctypes.data, part.shape[0], tab.data_ptr(), b, n_out,
+                                                                e_out, b_real, n_real, e_real, n_valid.data_ptr(),
+                                                                _stream()), "matten_batch_gather_padded")
+            return out
         desc = np.asarray(streams, dtype=np.int64)
         for lo in range(0, len(streams), self._max_streams):   # (one launch up to 32 streams: 17 extra keys)
             part = np.ascontiguousarray(desc[lo:lo + self._max_streams])

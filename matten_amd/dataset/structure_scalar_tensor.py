@@ -41,11 +41,23 @@ class _Loader:
 class _DeviceLoader:
     """``_Loader`` over a device-resident store (``matten_amd.data.store.DeviceGraphStore``): the same ``batch_size`` /
     ``shuffle`` / ``seed`` semantics -- the same generator and the same ``randperm`` per epoch, so it visits the same
-    crystals in the same order, the short last batch included -- with every batch gathered on the device."""
+    crystals in the same order, the short last batch included -- with every batch gathered on the device.
 
-    def __init__(self, store, batch_size: int = 1, shuffle: bool = False, seed: int = 0, training: bool = True, **ignored):
+    ``pad=(node_quantum, edge_quantum)``: every batch is padded (``DeviceGraphStore.batch(pad_to=...)``) to
+    ``batch_size + 1`` crystals, to the next multiple of `node_quantum` nodes that holds its atoms and one per padding
+    crystal, and to the next multiple of `edge_quantum` edges, so that an epoch has a few batch shapes only
+    (``matten_amd.graphs.BucketedTrainStep``).  The crystals and their order do not change.  Off by default."""
+
+    def __init__(self, store, batch_size: int = 1, shuffle: bool = False, seed: int = 0, training: bool = True,
+                 pad=None, pad_species=None, pad_length: float = 2.0, **ignored):
         self.store, self.batch_size, self.shuffle, self.training = store, int(batch_size), bool(shuffle), bool(training)
         self._gen = torch.Generator().manual_seed(seed)
+        self.pad = None
+        if pad is not None:
+            self.pad = tuple(int(q) for q in pad)
+            if len(self.pad) != 2 or min(self.pad) < 1:
+                raise ValueError(f"pad = {pad!r}: expected (node_quantum, edge_quantum), both at least 1")
+        self.pad_species, self.pad_length = pad_species, pad_length
 
     def __len__(self) -> int:
         return -(-len(self.store) // self.batch_size)
@@ -56,9 +68,23 @@ class _DeviceLoader:
         order = torch.randperm(n, generator=self._gen).tolist() if self.shuffle else list(range(n))
         return [order[lo:lo + self.batch_size] for lo in range(0, n, self.batch_size)]
 
+    def padded_sizes(self, idx) -> tuple:
+        """(N_b, E_b, B_b) of the batch `idx` under ``pad``: B_b = batch_size + 1, N_b the next multiple of the node quantum
+        from N + (B_b - B) (the atoms and one node per padding crystal), E_b the next multiple of the edge quantum from E"""
+        host = getattr(self.store, "host", self.store)
+        _, n, e = host.plan(idx)
+        qn, qe = self.pad
+        b_b = self.batch_size + 1
+        need = n + (b_b - len(idx))
+        return qn * -(-need // qn), qe * -(-e // qe), b_b
+
     def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
         for idx in self.batch_indices():
-            yield self.store.batch(idx, training=self.training)
+            if self.pad is None:
+                yield self.store.batch(idx, training=self.training)
+            else:
+                yield self.store.batch(idx, training=self.training, pad_to=self.padded_sizes(idx),
+                                       pad_species=self.pad_species, pad_length=self.pad_length)
 
 
 class TensorDataModule:
@@ -100,6 +126,9 @@ class TensorDataModule:
         self.device_resident = bool(device_resident)
         if self.device_resident and device is None:
             raise ValueError("device_resident=True needs `device`: the store lives on one GPU")
+        if self.loader_kwargs.get("pad") is not None and not self.device_resident:
+            raise ValueError("loader_kwargs['pad'] pads batches in the device loader's gather: it needs device_resident=True "
+                             "(the host loader does not pad)")
         self._data: Dict[str, List[Dict[str, torch.Tensor]]] = {}
         self._stores: Dict[str, Any] = {}
 
@@ -147,14 +176,21 @@ class TensorDataModule:
             return _DeviceLoader(self._stores["train"], training=True, **self.loader_kwargs)
         return _Loader(self._data["train"], device=self.device, **self.loader_kwargs)
 
+    def _eval_kwargs(self) -> Dict[str, Any]:
+        """validation and test batches are never padded (`pad` serves the captured training step)"""
+        kw = dict(self.loader_kwargs, shuffle=False)
+        for k in ("pad", "pad_species", "pad_length"):
+            kw.pop(k, None)
+        return kw
+
     def val_dataloader(self):
         if self.device_resident:
-            return _DeviceLoader(self._stores["val"], training=False, **dict(self.loader_kwargs, shuffle=False))
+            return _DeviceLoader(self._stores["val"], training=False, **self._eval_kwargs())
         return _Loader(self._data["val"], device=self.device, **dict(self.loader_kwargs, shuffle=False))
 
     def test_dataloader(self):
         if self.device_resident:
-            return _DeviceLoader(self._stores["test"], training=False, **dict(self.loader_kwargs, shuffle=False))
+            return _DeviceLoader(self._stores["test"], training=False, **self._eval_kwargs())
         return _Loader(self._data["test"], device=self.device, **dict(self.loader_kwargs, shuffle=False))
 
     # reference dataset/structure_scalar_tensor.py:640-666

@@ -6,8 +6,8 @@ a step is ~350 kernel launches for under 3 ms of kernel time: the host cannot is
 (``torch.cuda.CUDAGraph`` = hipStreamBeginCapture / hipGraphLaunch on ROCm), a step is one launch.  The kernels of
 ``libmatten_hip.so`` take their stream as an argument and never synchronise, so they capture as they are.
 
-Constraints (checked): every tensor of the batch keeps its shape and dtype between steps (pad or bucket batches
-upstream), the optimiser is capturable (``torch.optim.Adam(..., capturable=True)``), and the one host synchronisation
+Constraints (checked): every tensor of the batch keeps its shape and dtype between steps (``BucketedTrainStep`` below
+keeps one captured step per shape of the padded device loader's batches), the optimiser is capturable (``torch.optim.Adam(..., capturable=True)``), and the one host synchronisation
 of the forward -- the species / edge_index range check of ``SpeciesEmbedding`` -- is done once, eagerly, before the
 capture and switched off inside it.  Replayed batches are therefore trusted by default (the kernels clamp bad ids:
 memory-safe, but the result of a malformed batch is meaningless); pass ``validate=True`` to ``step`` / ``__call__`` to
@@ -75,6 +75,48 @@ def _copy_batch(static: Dict, batch: Dict, what: str) -> None:
             s.copy_(v, non_blocking=True)
 
 
+def _apply_loss(loss_fn: Callable, preds, target, batch):
+    """loss_fn(preds, target), or loss_fn(preds, target, batch) for a loss that reads the batch (padded_mean_loss:
+    ``wants_batch``) -- inside a captured step `batch` holds the captured buffers, which every replay refreshes"""
+    if getattr(loss_fn, "wants_batch", False):
+        return loss_fn(preds, target, batch)
+    return loss_fn(preds, target)
+
+
+def padded_mean_loss(fn: Callable, key: str = None) -> Callable:
+    """The mean of a per-element loss over the REAL crystals of a padded batch (``DeviceGraphStore.batch(pad_to=...)``).
+
+    ``fn(prediction, target)`` returns the loss per element, [B_b, ...] (``lambda p, t: (p - t) ** 2`` for squared error);
+    `key` picks the prediction out of the model's dict.  The returned ``loss(preds, target, batch)`` keeps the rows of
+    the first ``batch["_amd_n_valid"][2]`` crystals (``torch.where`` on ``arange(B_b) < n_valid[2]``: whatever a padding row
+    holds, NaN included, is replaced and gets a zero gradient) and divides their sum by the number of real elements.  The
+    count stays on the device: no host read, so the loss captures, and a replay follows the refreshed count."""
+
+    def loss(preds, target, batch):
+        if "_amd_n_valid" not in batch:
+            raise ValueError("padded_mean_loss needs a padded batch (DeviceGraphStore.batch(pad_to=...) or "
+                             "_DeviceLoader(pad=...)): this batch has no '_amd_n_valid'")
+        n_real = batch["_amd_n_valid"][2]
+        per = fn(preds[key] if key is not None else preds, target)
+        rows = per.shape[0]
+        keep = (torch.arange(rows, device=per.device) < n_real).view((rows,) + (1,) * (per.dim() - 1))
+        kept = torch.where(keep, per, torch.zeros((), dtype=per.dtype, device=per.device))
+        return kept.sum() / (n_real * (per.numel() // max(rows, 1))).to(per.dtype)
+
+    loss.wants_batch = True
+    return loss
+
+
+def _train_step(model, optimizer, loss_fn: Callable, batch, target, task_name: str):
+    """one optimisation step as it is captured, and as it runs eagerly: forward, loss, backward, optimiser"""
+    preds, _ = model(dict(batch), task_name=task_name)
+    loss = _apply_loss(loss_fn, preds, target, batch)
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    optimizer.step()
+    return loss
+
+
 class GraphedTrainStep:
     def __init__(self, model, optimizer, loss_fn: Callable, batch: Dict[str, torch.Tensor], target: torch.Tensor,
                  warmup: int = 3, task_name: str = "elastic_tensor_full"):
@@ -125,12 +167,7 @@ class GraphedTrainStep:
                 m.check_species = f
 
     def _eager_step(self):
-        preds, _ = self.model(dict(self._static), task_name=self.task_name)
-        loss = self.loss_fn(preds, self._target)
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
-        return loss
+        return _train_step(self.model, self.optimizer, self.loss_fn, self._static, self._target, self.task_name)
 
     def step(self, batch: Dict[str, torch.Tensor], target: torch.Tensor, validate: bool = False) -> torch.Tensor:
         """copy the batch into the captured buffers (shapes must match) and replay; returns the captured loss tensor.
@@ -146,6 +183,48 @@ class GraphedTrainStep:
         if validate:
             _raise_for_flags(self._embeds, self._static)
         return self._loss
+
+
+class BucketedTrainStep:
+    """Training steps over batches of a FEW shapes, each shape captured once: the padded device loader
+    (``_DeviceLoader(..., pad=(node_quantum, edge_quantum))``) rounds every batch up to a bucket (N_b, E_b, B_b), and
+    ``step`` replays the ``GraphedTrainStep`` of the batch's bucket, capturing it on first sight.  Beyond `max_graphs`
+    distinct buckets (a captured step keeps its own activations) the step runs eagerly.  The captured steps share the
+    model and the optimiser, so their parameters, running statistics and optimiser state are one trajectory.
+
+    ``captures`` / ``replays`` / ``eager_steps`` count what each call of ``step`` did (a capturing call replays its new
+    graph once and counts as a capture)."""
+
+    def __init__(self, model, optimizer, loss_fn: Callable, max_graphs: int = 8, warmup: int = 2,
+                 task_name: str = "elastic_tensor_full"):
+        self.model, self.optimizer, self.loss_fn, self.task_name = model, optimizer, loss_fn, task_name
+        self.max_graphs, self.warmup = int(max_graphs), int(warmup)
+        self.graphs: Dict[tuple, GraphedTrainStep] = {}
+        self.captures = self.replays = self.eager_steps = 0
+
+    @staticmethod
+    def bucket(batch: Dict[str, torch.Tensor]) -> tuple:
+        return (int(batch["pos"].shape[0]), int(batch["edge_index"].shape[1]), int(batch["ptr"].shape[0]) - 1)
+
+    def step(self, batch: Dict[str, torch.Tensor], target: torch.Tensor, validate: bool = False) -> torch.Tensor:
+        """one optimisation step on `batch`; returns the loss tensor (a captured step's is overwritten by its next replay).
+        `validate` is GraphedTrainStep.step's and concerns replays only: an overflow step is an ordinary eager step, whose
+        forward runs the range checks itself and raises before the parameters move."""
+        key = self.bucket(batch)
+        graphed = self.graphs.get(key)
+        if graphed is None and len(self.graphs) >= self.max_graphs:
+            self.eager_steps += 1
+            if hasattr(self.optimizer, "sync_hyperparameters"):
+                self.optimizer.sync_hyperparameters()   # (as before a replay)
+            return _train_step(self.model, self.optimizer, self.loss_fn, batch, target, self.task_name)
+        if graphed is None:
+            # (refuses what cannot be captured; the warm-up steps are undone, so the replay below is this batch's one step)
+            graphed = self.graphs[key] = GraphedTrainStep(self.model, self.optimizer, self.loss_fn, batch, target,
+                                                          warmup=self.warmup, task_name=self.task_name)
+            self.captures += 1
+        else:
+            self.replays += 1
+        return graphed.step(batch, target, validate=validate)
 
 
 class GraphedForward:

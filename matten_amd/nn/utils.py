@@ -413,6 +413,12 @@ class UVUTensorProduct(torch.nn.Module):
         )
 
 
+def _n_valid(data):
+    """a padded batch's device word (data.store.DeviceGraphStore.batch(pad_to=...)): BatchNorm's batch statistics are the
+    one place where crystals meet, and they skip the padding rows behind it"""
+    return data.get(DataKey.AMD_N_VALID) if data is not None else None
+
+
 class ActivationLayer(torch.nn.Module):
     def __init__(
         self,
@@ -464,7 +470,7 @@ class ActivationLayer(torch.nn.Module):
                 return norm.n(y, data)
             if bn is None:
                 return y
-            return bn.forward_train(y)
+            return bn.forward_train(y, _n_valid(data))
         return ops.norm_act(x, self._tables.get("chan", dev), self.plan.act_code, self.plan.epsilon,
                             *((bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps) if bn is not None else ()))
 
@@ -482,7 +488,7 @@ class ActivationLayer(torch.nn.Module):
             # training: Gate, then BatchNorm with batch statistics (and the running-average update)
             y = _ag.GateFn.apply(x, self) if x.requires_grad else ops.gate_bn(
                 x, self._tables.get("meta", dev), self._tables.get("act_cst", dev))
-            return bn.forward_train(y)
+            return bn.forward_train(y, _n_valid(data))
         if bn is not None and _ag.needs_grad(x, bn.weight, bn.bias):
             # frozen statistics under autograd (fine-tuning with BatchNorm in eval mode, gradients of an eval-mode model)
             return _ag.GateBnEvalFn.apply(x, bn.weight, bn.bias, self, bn)
@@ -512,9 +518,11 @@ class _IrrepBatchNorm(torch.nn.Module):
         self._tables = DeviceTables(chan=chan, col2chan=col2chan,
                                     scalar_chan=np.nonzero(chan[:, 2])[0].astype(np.int64))
 
-    def forward_train(self, x: Tensor) -> Tensor:
+    def forward_train(self, x: Tensor, n_valid: Tensor = None) -> Tensor:
         # e3nn: running = (1 - momentum) * running + momentum * batch -- done by the statistics kernel itself
-        return _ag.BatchNormTrainFn.apply(x, self.weight, self.bias, self)
+        if n_valid is None:
+            return _ag.BatchNormTrainFn.apply(x, self.weight, self.bias, self)
+        return _ag.BatchNormTrainFn.apply(x, self.weight, self.bias, self, n_valid)   # a padded batch: its valid rows
 
     def train(self, mode: bool = True):
         """frozen statistics (model.freeze_batchnorm): a later ``model.train()`` leaves this module in eval mode"""

@@ -1198,8 +1198,19 @@ def _bn_scratch(lib, x):
     return torch.empty(n, dtype=torch.float32, device=x.device) if n > 0 else None
 
 
-def bn_train_fwd(x, col2chan, chan, weight, bias, eps: float, running_mean=None, running_var=None, momentum: float = 0.0):
-    """batch statistics -> (y, mean, nu); running_mean / running_var (optional) are updated in place by the same launch"""
+def _bn_n_valid(n_valid, x):
+    """the device word of the valid-rows entries: int64, on x's device, never read by the host"""
+    if n_valid.dtype != torch.int64 or n_valid.device != x.device or n_valid.numel() < 1 or not n_valid.is_contiguous():
+        raise ValueError(f"n_valid must be a contiguous int64 tensor on {x.device}, got {n_valid.dtype} {tuple(n_valid.shape)} "
+                         f"on {n_valid.device}")
+    return n_valid
+
+
+def bn_train_fwd(x, col2chan, chan, weight, bias, eps: float, running_mean=None, running_var=None, momentum: float = 0.0,
+                 n_valid=None):
+    """batch statistics -> (y, mean, nu); running_mean / running_var (optional) are updated in place by the same launch.
+    n_valid (optional, int64 on the device; its first element is read by the kernels): the statistics run over the rows
+    [0, n_valid) only (a padded batch, matten_bn_train_fwd_valid)"""
     lib = _lib.load()
     x = _need(x, torch.float32, "x")
     C = chan.shape[0]
@@ -1210,10 +1221,17 @@ def bn_train_fwd(x, col2chan, chan, weight, bias, eps: float, running_mean=None,
         running_mean = _need(running_mean, torch.float32, "running_mean")
         running_var = _need(running_var, torch.float32, "running_var")
     scratch = _bn_scratch(lib, x)
-    _lib.check(lib.matten_bn_train_fwd(_ptr(x), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C, _ptr(weight),
-                                       _ptr(bias), eps, _ptr(mean), _ptr(nu), _ptr(y), _ptr(running_mean),
-                                       _ptr(running_var), float(momentum), _ptr(scratch), _stream()),
-               "matten_bn_train_fwd")
+    if n_valid is None:
+        _lib.check(lib.matten_bn_train_fwd(_ptr(x), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C, _ptr(weight),
+                                           _ptr(bias), eps, _ptr(mean), _ptr(nu), _ptr(y), _ptr(running_mean),
+                                           _ptr(running_var), float(momentum), _ptr(scratch), _stream()),
+                   "matten_bn_train_fwd")
+    else:
+        _lib.check(lib.matten_bn_train_fwd_valid(_ptr(x), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C, _ptr(weight),
+                                                 _ptr(bias), eps, _ptr(mean), _ptr(nu), _ptr(y), _ptr(running_mean),
+                                                 _ptr(running_var), float(momentum), _ptr(scratch),
+                                                 _ptr(_bn_n_valid(n_valid, x)), _stream()),
+                   "matten_bn_train_fwd_valid")
     if running_var is not None:
         bump_weights_epoch()   # the running statistics were updated through raw pointers (caches of the folded BatchNorm)
     return y, mean, nu
@@ -1316,8 +1334,9 @@ def instance_norm_bwd(x, dy, seg_ptr, seg_of_row, col2chan, chan, mean, nu, weig
     return dx, A, Bs
 
 
-def bn_train_bwd(x, dy, col2chan, chan, mean, nu, weight, eps: float, n_bias: int):
-    """-> (dx, dweight [C], dbias [n_bias]): the parameter gradients come out of the reduction kernel itself"""
+def bn_train_bwd(x, dy, col2chan, chan, mean, nu, weight, eps: float, n_bias: int, n_valid=None):
+    """-> (dx, dweight [C], dbias [n_bias]): the parameter gradients come out of the reduction kernel itself.
+    n_valid as in bn_train_fwd: the reductions over the valid rows, dx of the rows behind them exactly zero"""
     lib = _lib.load()
     dy = _need(dy, torch.float32, "dy")
     C = chan.shape[0]
@@ -1327,10 +1346,17 @@ def bn_train_bwd(x, dy, col2chan, chan, mean, nu, weight, eps: float, n_bias: in
     dbias = torch.empty(n_bias, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
     scratch = _bn_scratch(lib, x)
-    _lib.check(lib.matten_bn_train_bwd(_ptr(x), _ptr(dy), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C,
-                                       _ptr(mean), _ptr(nu), _ptr(weight), eps, _ptr(A), _ptr(B), _ptr(dx), _ptr(dweight),
-                                       _ptr(dbias), _ptr(scratch), _stream()),
-               "matten_bn_train_bwd")
+    if n_valid is None:
+        _lib.check(lib.matten_bn_train_bwd(_ptr(x), _ptr(dy), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C,
+                                           _ptr(mean), _ptr(nu), _ptr(weight), eps, _ptr(A), _ptr(B), _ptr(dx), _ptr(dweight),
+                                           _ptr(dbias), _ptr(scratch), _stream()),
+                   "matten_bn_train_bwd")
+    else:
+        _lib.check(lib.matten_bn_train_bwd_valid(_ptr(x), _ptr(dy), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C,
+                                                 _ptr(mean), _ptr(nu), _ptr(weight), eps, _ptr(A), _ptr(B), _ptr(dx),
+                                                 _ptr(dweight), _ptr(dbias), _ptr(scratch), _ptr(_bn_n_valid(n_valid, x)),
+                                                 _stream()),
+                   "matten_bn_train_bwd_valid")
     return dx, dweight, dbias
 
 
