@@ -806,8 +806,9 @@ int matten_neighbor_fill(const double* pos, const double* cell, const int64_t* p
  *   table[5][n_crystals + 1] (int32, device), one column per picked crystal in batch order: destination node start,
  *     destination edge start, source node start, source edge start, source crystal.  The closing column holds
  *     (n_nodes, n_edges, 0, 0, 0).  The host derives it from its copies of the store's running sums.
- *   streams[n_streams][MATTEN_BATCH_STREAM_WORDS] (int64, HOST memory, read before the call returns): per array
- *     {source pointer, destination pointer, element size (4 or 8), elements per row, class, operation}.
+ *   streams[n_streams][words] (int64, HOST memory, read before the call returns), words = MATTEN_BATCH_STREAM_WORDS
+ *     here and MATTEN_BATCH_PAD_STREAM_WORDS for matten_batch_gather_padded, which reads the same six words first: per
+ *     array {source pointer, destination pointer, element size (4 or 8), elements per row, class, operation}.
  *     class: whose rows these are (MATTEN_BATCH_NODE / _EDGE / _CRYSTAL).  Operation:
  *       RAW         the row copied as is, any class, any width (16-, 8- or 4-byte accesses as alignment allows)
  *       ADD32_NODE  int32 per edge + the crystal's destination node start      (source / destination ids in sorted order)
@@ -841,25 +842,28 @@ int matten_batch_gather_max_streams(void);
 int matten_batch_gather(const int64_t* streams, int64_t n_streams, const int32_t* table, int64_t n_crystals,
                         int64_t n_nodes, int64_t n_edges, matten_stream_t stream);
 
-/* The same batch grown to FIXED sizes, so that a captured training step can replay it: behind the v_crystals picked
- * crystals (v_nodes nodes, v_edges edges, written exactly as matten_batch_gather writes them) the launch synthesises
- * K = n_crystals - v_crystals >= 1 padding crystals from closed forms (no source rows, no search, no second launch).
+/* The same batch grown to FIXED sizes, so that a captured training step can replay it: the same kernel, which behind
+ * the v_crystals picked crystals (v_nodes nodes, v_edges edges, written as matten_batch_gather writes them: that entry is
+ * this one without padding crystals) synthesises K = n_crystals - v_crystals >= 1 padding crystals from closed forms (no
+ * source rows, no search, no second launch).
  *   Padding crystal 0 owns P = n_nodes - v_nodes - (K - 1) >= 1 nodes and all n_edges - v_edges padding edges; padding
  *   crystals 1 .. K-1 own one node and no edge.  Node j of padding crystal 0 owns the padding edges
  *   [floor(j Ep / P), floor((j + 1) Ep / P)), each a self-image edge j -> j, so the padding edges are destination-sorted:
  *   ADD32_EDGE streams get the identity there, ADD32_NODE / ADD64_NODE the owning node, ROWPTR32 the closed-form bounds,
  *   BATCH64 / PTR64 follow the layout.
- *   streams[n_streams][MATTEN_BATCH_PAD_STREAM_WORDS]: the six words of matten_batch_gather, then the fill of a RAW
- *   stream's padding rows and the fill's element (low four bytes for 4-byte elements):
+ *   streams: words, classes and operations as above; words 7 and 8 are the fill of a RAW stream's padding rows and the
+ *   fill's element (low four bytes for 4-byte elements):
  *       PAD_ZERO    zeros                         PAD_CONST   every element = value   (atomic_numbers)
  *       PAD_FIRST   (value, 0, 0, ...)            (edge_cell_shift = (1, 0, 0))
  *       PAD_DIAG3   value on the diagonal of a 3 x 3 row (cell = pad_length * I; 9 elements)
  *       PAD_DEGREE  one float per node: the number of padding edges it owns (num_neigh)
  *   table[5][n_crystals + 1]: the destination running sums cover the padding crystals; the closing column holds
- *   (n_nodes, n_edges, v_nodes, v_edges, v_crystals).  n_valid[3] (int64, device) receives its last three entries.
- * MATTEN_EINVAL: as matten_batch_gather, and n_crystals <= v_crystals, n_edges < v_edges,
- * n_nodes < v_nodes + (n_crystals - v_crystals), a NULL n_valid, an unknown fill, a fill on a stream that is not RAW,
- * PAD_DEGREE off a one-float node stream, PAD_DIAG3 off a 9-element row.  Plain stores only: no atomics, no workspace. */
+ *   (n_nodes, n_edges, v_nodes, v_edges, v_crystals).  n_valid[3] (int64, device) receives its last three entries: the
+ *   kernel copies them from the table, not from the arguments.
+ * MATTEN_EINVAL: whatever matten_batch_gather refuses (one decoder reads the records of both), and
+ * n_crystals <= v_crystals, n_edges < v_edges, n_nodes < v_nodes + (n_crystals - v_crystals), a negative valid size, a
+ * NULL n_valid, an unknown fill, a fill on a stream that is not RAW, PAD_DEGREE off a one-float node stream, PAD_DIAG3
+ * off a 9-element row.  Plain stores only: no atomics, no workspace. */
 #define MATTEN_BATCH_PAD_STREAM_WORDS 8
 #define MATTEN_BATCH_PAD_ZERO 0
 #define MATTEN_BATCH_PAD_CONST 1

@@ -350,19 +350,16 @@ class DeviceGraphStore:
         dev = self.device
         rows = (n_out, e_out, b)
         out: Dict[str, torch.Tensor] = {}
-        streams: List[Tuple[int, ...]] = []
-        stream_keys: List[str] = []   # the key of every stream (a padded batch fills its padding rows by key)
+        streams: List[Tuple[str, Tuple[int, ...]]] = []   # (key, the six words of the stream)
         for k, src, dtype, row, cls, op in self._public:
             if k == DataKey.EDGE_INDEX:
                 dst = torch.empty((2, e_out), dtype=dtype, device=dev)
                 stride = 8 * src.shape[1]
-                streams.append((src.data_ptr(), dst.data_ptr(), 8, 1, cls, op))
-                streams.append((src.data_ptr() + stride, dst.data_ptr() + 8 * e_out, 8, 1, cls, op))
-                stream_keys += [k, k]
+                streams.append((k, (src.data_ptr(), dst.data_ptr(), 8, 1, cls, op)))
+                streams.append((k, (src.data_ptr() + stride, dst.data_ptr() + 8 * e_out, 8, 1, cls, op)))
             elif k == DataKey.CELL:
                 dst = torch.empty((3 * b, 3), dtype=dtype, device=dev)
-                streams.append((src.data_ptr(), dst.data_ptr(), 4, 9, cls, op))
-                stream_keys.append(k)
+                streams.append((k, (src.data_ptr(), dst.data_ptr(), 4, 9, cls, op)))
             else:
                 dst = torch.empty((rows[cls],) + row, dtype=dtype, device=dev)
                 n_elem = 1
@@ -371,37 +368,30 @@ class DeviceGraphStore:
                 if n_elem == 0:
                     out[k] = dst
                     continue
-                streams.append((src.data_ptr(), dst.data_ptr(), src.element_size(), n_elem, cls, op))
-                stream_keys.append(k)
+                streams.append((k, (src.data_ptr(), dst.data_ptr(), src.element_size(), n_elem, cls, op)))
             out[k] = dst
         out[DataKey.BATCH] = torch.empty(n_out, dtype=torch.int64, device=dev)
         out[DataKey.PTR] = torch.empty(b + 1, dtype=torch.int64, device=dev)
-        streams.append((0, out[DataKey.BATCH].data_ptr(), 8, 1, NODE, OP_BATCH64))
-        streams.append((0, out[DataKey.PTR].data_ptr(), 8, 1, CRYSTAL, OP_PTR64))
-        stream_keys += [DataKey.BATCH, DataKey.PTR]
+        streams.append((DataKey.BATCH, (0, out[DataKey.BATCH].data_ptr(), 8, 1, NODE, OP_BATCH64)))
+        streams.append((DataKey.PTR, (0, out[DataKey.PTR].data_ptr(), 8, 1, CRYSTAL, OP_PTR64)))
         for k, src, cls, op in (self._csr + self._train if training else self._csr):
             dst = torch.empty((n_out + 1) if op == OP_ROWPTR32 else e_out, dtype=torch.int32, device=dev)
-            streams.append((src.data_ptr(), dst.data_ptr(), 4, 1, cls, op))
-            stream_keys.append(k)
+            streams.append((k, (src.data_ptr(), dst.data_ptr(), 4, 1, cls, op)))
             out[k] = dst
         tab = torch.from_numpy(table).to(dev)   # the one host-to-device copy of a batch
-        if padded:
+        if padded:   # two more words per stream: the fill that follows its key
+            desc = np.array([words + fills.get(k, (PAD_ZERO, 0)) for k, words in streams], dtype=np.int64)
             out[DataKey.AMD_N_VALID] = n_valid = torch.empty(3, dtype=torch.int64, device=dev)
-            # (the fill of every RAW stream follows its key; the streams above were appended in key order)
-            desc = np.zeros((len(streams), PAD_STREAM_WORDS), dtype=np.int64)
-            desc[:, :STREAM_WORDS] = np.asarray(streams, dtype=np.int64)
-            for row, key in enumerate(stream_keys):
-                desc[row, STREAM_WORDS:] = fills.get(key, (PAD_ZERO, 0))
             b_real = int(table[4, -1])
-            for lo in range(0, len(streams), self._max_streams):
-                part = np.ascontiguousarray(desc[lo:lo + self._max_streams])
+        else:
+            desc = np.array([words for _, words in streams], dtype=np.int64)
+        for lo in range(0, len(streams), self._max_streams):   # (one launch up to 32 streams: 17 extra keys)
+            part = np.ascontiguousarray(desc[lo:lo + self._max_streams])
+            if padded:
                 _lib.check(self._lib.matten_batch_gather_padded(part.ctypes.data, part.shape[0], tab.data_ptr(), b, n_out,
                                                                 e_out, b_real, n_real, e_real, n_valid.data_ptr(),
                                                                 _stream()), "matten_batch_gather_padded")
-            return out
-        desc = np.asarray(streams, dtype=np.int64)
-        for lo in range(0, len(streams), self._max_streams):   # (one launch up to 32 streams: 17 extra keys)
-            part = np.ascontiguousarray(desc[lo:lo + self._max_streams])
-            _lib.check(self._lib.matten_batch_gather(part.ctypes.data, part.shape[0], tab.data_ptr(), b, n_out, e_out,
-                                                     _stream()), "matten_batch_gather")
+            else:
+                _lib.check(self._lib.matten_batch_gather(part.ctypes.data, part.shape[0], tab.data_ptr(), b, n_out, e_out,
+                                                         _stream()), "matten_batch_gather")
         return out

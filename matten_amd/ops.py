@@ -1221,17 +1221,13 @@ def bn_train_fwd(x, col2chan, chan, weight, bias, eps: float, running_mean=None,
         running_mean = _need(running_mean, torch.float32, "running_mean")
         running_var = _need(running_var, torch.float32, "running_var")
     scratch = _bn_scratch(lib, x)
-    if n_valid is None:
-        _lib.check(lib.matten_bn_train_fwd(_ptr(x), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C, _ptr(weight),
-                                           _ptr(bias), eps, _ptr(mean), _ptr(nu), _ptr(y), _ptr(running_mean),
-                                           _ptr(running_var), float(momentum), _ptr(scratch), _stream()),
-                   "matten_bn_train_fwd")
-    else:
-        _lib.check(lib.matten_bn_train_fwd_valid(_ptr(x), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C, _ptr(weight),
-                                                 _ptr(bias), eps, _ptr(mean), _ptr(nu), _ptr(y), _ptr(running_mean),
-                                                 _ptr(running_var), float(momentum), _ptr(scratch),
-                                                 _ptr(_bn_n_valid(n_valid, x)), _stream()),
-                   "matten_bn_train_fwd_valid")
+    args = [_ptr(x), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C, _ptr(weight), _ptr(bias), eps, _ptr(mean), _ptr(nu),
+            _ptr(y), _ptr(running_mean), _ptr(running_var), float(momentum), _ptr(scratch)]
+    name = "matten_bn_train_fwd"
+    if n_valid is not None:
+        args.append(_ptr(_bn_n_valid(n_valid, x)))
+        name += "_valid"
+    _lib.check(getattr(lib, name)(*args, _stream()), name)
     if running_var is not None:
         bump_weights_epoch()   # the running statistics were updated through raw pointers (caches of the folded BatchNorm)
     return y, mean, nu
@@ -1346,17 +1342,13 @@ def bn_train_bwd(x, dy, col2chan, chan, mean, nu, weight, eps: float, n_bias: in
     dbias = torch.empty(n_bias, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
     scratch = _bn_scratch(lib, x)
-    if n_valid is None:
-        _lib.check(lib.matten_bn_train_bwd(_ptr(x), _ptr(dy), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C,
-                                           _ptr(mean), _ptr(nu), _ptr(weight), eps, _ptr(A), _ptr(B), _ptr(dx), _ptr(dweight),
-                                           _ptr(dbias), _ptr(scratch), _stream()),
-                   "matten_bn_train_bwd")
-    else:
-        _lib.check(lib.matten_bn_train_bwd_valid(_ptr(x), _ptr(dy), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C,
-                                                 _ptr(mean), _ptr(nu), _ptr(weight), eps, _ptr(A), _ptr(B), _ptr(dx),
-                                                 _ptr(dweight), _ptr(dbias), _ptr(scratch), _ptr(_bn_n_valid(n_valid, x)),
-                                                 _stream()),
-                   "matten_bn_train_bwd_valid")
+    args = [_ptr(x), _ptr(dy), x.shape[1], x.shape[0], _ptr(col2chan), _ptr(chan), C, _ptr(mean), _ptr(nu), _ptr(weight), eps,
+            _ptr(A), _ptr(B), _ptr(dx), _ptr(dweight), _ptr(dbias), _ptr(scratch)]
+    name = "matten_bn_train_bwd"
+    if n_valid is not None:
+        args.append(_ptr(_bn_n_valid(n_valid, x)))
+        name += "_valid"
+    _lib.check(getattr(lib, name)(*args, _stream()), name)
     return dx, dweight, dbias
 
 

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from common import LMAX2, build_pair
-from store_cases import TARGET, golden_graphs, store_graphs
+from store_cases import TARGET, golden_graphs, many_key_graphs, store_graphs, streams_needed
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -75,18 +75,21 @@ def _sizes(store, idx):
     return n, e
 
 
-def test_gather_16_crystals_to_the_next_bucket(store):
-    idx = list(range(40, 56))
-    n, e = _sizes(store, idx)
-    got = _check_padded(store, idx, (_round_up(n + 1, 64), _round_up(e, 1024), 17))
-    assert got["_amd_n_valid"].tolist() == [n, e, 16]
-    # the first B crystals are bit for bit the unpadded batch
-    plain = store.batch(idx)
+def _same_as_plain(got, plain, e):
+    """the first B crystals of the padded batch `got` are bit for bit the unpadded batch `plain` of e edges"""
     for k, v in plain.items():
         part = got[k][:, :e] if k == "edge_index" else got[k][:v.shape[0]]
         if k in ("_amd_rowptr", "_amd_out_ptr", "ptr"):
             part, v = part[:-1], v[:-1]   # (the closing entry of the unpadded batch is the first padding row's start)
         assert torch.equal(part, v), k
+
+
+def test_gather_16_crystals_to_the_next_bucket(store):
+    idx = list(range(40, 56))
+    n, e = _sizes(store, idx)
+    got = _check_padded(store, idx, (_round_up(n + 1, 64), _round_up(e, 1024), 17))
+    assert got["_amd_n_valid"].tolist() == [n, e, 16]
+    _same_as_plain(got, store.batch(idx), e)
 
 
 def test_gather_without_padding_edges(store):
@@ -126,7 +129,10 @@ def test_gather_table_beyond_lds(store):
     for b, k in ((cap - 2, 1), (cap + 76, 2)):   # B_b + 1 == cap: the last table in LDS; B_b + 1 > cap
         idx = torch.randint(0, 100, (b,), generator=g).tolist()
         n, e = _sizes(store, idx)
-        _check_padded(store, idx, (_round_up(n + k, 64), _round_up(e, 1024), b + k))
+        got = _check_padded(store, idx, (_round_up(n + k, 64), _round_up(e, 1024), b + k))
+    # above the cap too, the real rows are bit for bit the unpadded batch (as test_gather_16_crystals_to_the_next_bucket)
+    assert b + k + 1 > cap
+    _same_as_plain(got, store.batch(idx), e)
 
 
 def test_gather_extra_keys():
@@ -148,6 +154,27 @@ def test_gather_extra_keys():
     assert not got["crystal_pair"][6:].any() and not got[TARGET][6:].any()
     assert not got["node_tensor"][n:].any() and not got["edge_tag"][e:].any()
     assert got["crystal_pair"][:6].abs().min() > 0
+
+
+def test_gather_more_streams_than_one_launch_takes():
+    """18 extra keys: a training batch is 34 streams, two launches of the padded entry; every extra key zero on its
+    padding rows, n_valid written"""
+    from matten.data.store import CRYSTAL, EDGE, NODE, DeviceGraphStore
+    from matten_amd import _lib
+
+    s = DeviceGraphStore.from_graphs(many_key_graphs(), DEV)
+    cap = _lib.load().matten_batch_gather_max_streams()
+    assert cap < streams_needed(s.host) <= 2 * cap
+    idx = [13, 0, 12, 14, 5, 5]
+    n, e = _sizes(s, idx)
+    got = _check_padded(s, idx, (n + 5, e + 11, len(idx) + 2))
+    assert got["_amd_n_valid"].tolist() == [n, e, len(idx)]
+    first_pad = {NODE: n, EDGE: e, CRYSTAL: len(idx)}
+    extra = [k for k in s.host.keys if "_extra" in k]
+    assert len(extra) == 18
+    for k in extra:
+        real, pad = got[k][:first_pad[s.host.classes[k]]], got[k][first_pad[s.host.classes[k]]:]
+        assert pad.shape[0] > 0 and not pad.any() and bool((real != 0).all()), k
 
 
 # ----------------------------------------------------------------------------------------------------------------------

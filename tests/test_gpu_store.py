@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from common import LMAX2
-from store_cases import GOLDEN, N100, TARGET, data_module, golden_graphs, index_lists, store_graphs
+from store_cases import (GOLDEN, N100, TARGET, data_module, golden_graphs, index_lists, many_key_graphs, store_graphs,
+                         streams_needed)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -115,6 +116,20 @@ def test_extra_keys():
     for idx in ([14], [13, 0, 12, 14, 5, 5], list(range(14, -1, -1))):
         got = _check(s, graphs, idx)
         assert got[TARGET].shape == (len(idx), 21) and got["node_tensor"].shape[1:] == (9,) and got["edge_tag"].dtype == torch.int64
+
+
+def test_more_streams_than_one_launch_takes():
+    """18 extra keys: a training batch is 34 streams, two launches; the last streams, a row pointer with its closing
+    entry among them, go with the second"""
+    from matten.data.store import DeviceGraphStore
+    from matten_amd import _lib
+
+    graphs = many_key_graphs()
+    s = DeviceGraphStore.from_graphs(graphs, DEV)
+    cap = _lib.load().matten_batch_gather_max_streams()
+    assert cap < streams_needed(s.host) <= 2 * cap
+    for idx in ([14], [13, 0, 12, 14, 5, 5]):
+        _check(s, graphs, idx)
 
 
 def _species_hparams(graphs):

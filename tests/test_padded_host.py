@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from store_cases import golden_graphs
+from store_cases import golden_graphs, refused_streams
 
 CSR_KEYS = ("_amd_perm", "_amd_rowptr", "_amd_src_sorted")
 TRAIN_KEYS = ("_amd_dst_sorted", "_amd_out_ptr", "_amd_out_perm")
@@ -247,3 +247,29 @@ def test_new_symbols_and_abi():
     f = lib.matten_bn_train_fwd_valid(p, 4, 8, p, p, 1, p, p, 1e-5, p, p, p, None, None, 0.1, None, None, None)
     b = lib.matten_bn_train_bwd_valid(p, p, 4, 8, p, p, 1, p, p, p, 1e-5, p, p, p, None, None, None, None, None)
     assert f == -1 and b == -1
+
+
+def test_both_gather_entries_refuse_the_same_streams():
+    """one decoder behind both entries: every six-word record matten_batch_gather refuses (the rows of
+    test_store_host.py::test_batch_gather_argument_errors), extended by the fill (PAD_ZERO, 0), is refused by
+    matten_batch_gather_padded too, before any launch"""
+    from matten_amd import _lib
+    from matten_amd.data import store
+
+    lib = _lib.load()
+    buf = np.zeros(64, dtype=np.int64)
+    p = buf.ctypes.data
+    bad = refused_streams(p)
+    assert len(bad) >= 22
+
+    def plain(streams):
+        d = np.asarray(streams, dtype=np.int64).reshape(-1, store.STREAM_WORDS)
+        return lib.matten_batch_gather(d.ctypes.data, len(d), p, 1, 1, 1, None)
+
+    def padded(streams):   # (the sizes of test_new_symbols_and_abi: a good record passes every check with them)
+        d = np.asarray([tuple(s) + (store.PAD_ZERO, 0) for s in streams], dtype=np.int64).reshape(-1, store.PAD_STREAM_WORDS)
+        return lib.matten_batch_gather_padded(d.ctypes.data, len(d), p, 3, 10, 10, 2, 8, 8, p, None)
+
+    for streams in bad:
+        assert plain(streams) == -1, streams
+        assert padded(streams) == -1, streams
