@@ -7,9 +7,12 @@
 //                                and the sum of v^-3 of the Debye average
 //   elastic_directional_bwd_kernel, elastic_acoustic_bwd_kernel : the adjoints of those two (gradients of the maps, the
 //                                extremes and the sum of v^-3 -> the compliance / the Voigt matrix)
+//   elastic_refine_kernel      : the extremes of the directional and the pair kernel polished off the grid
 // The reference wraps every predicted tensor in pymatgen's ElasticTensor (one Python object per crystal); these kernels
 // compute what its users read off that object.  All arithmetic is fp64; everything is held in registers with compile-time
-// indices, so no kernel here uses scratch memory (hipcc -Rpass-analysis=kernel-resource-usage: DESIGN.md).
+// indices, so no kernel here uses scratch memory (hipcc -Rpass-analysis=kernel-resource-usage: DESIGN.md).  Every formula
+// that a forward, its adjoint and the refinement share is one helper here: "the same bits" between them is one piece of
+// code, not two kept in step.
 #include "common.h"
 
 namespace {
@@ -21,6 +24,64 @@ __device__ constexpr int VJ[6] = {0, 1, 2, 2, 2, 1};
 __device__ __forceinline__ constexpr int cart(int i, int j, int k, int l) { return ((i * 3 + j) * 3 + k) * 3 + l; }
 
 __device__ __forceinline__ bool finite64(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN
+
+struct V3 {
+    double x, y, z;
+};
+__device__ __forceinline__ V3 load_dir(const double* __restrict__ dirs, int d) {
+    return {dirs[d * 3 + 0], dirs[d * 3 + 1], dirs[d * 3 + 2]};
+}
+
+// a [36] Voigt matrix as the mean of its two triangles: the input is never trusted to be symmetric (the two triangles of
+// the elimination's result agree to rounding only)
+template <typename T>
+__device__ __forceinline__ void load_sym6(const T* __restrict__ p, double (&M)[6][6]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j) M[i][j] = M[j][i] = 0.5 * ((double)p[i * 6 + j] + (double)p[j * 6 + i]);
+    }
+}
+__device__ __forceinline__ void matvec6(const double (&S)[6][6], const double (&x)[6], double (&y)[6]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double row = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) row += S[i][j] * x[j];
+        y[i] = row;
+    }
+}
+__device__ __forceinline__ double dot6(const double (&a)[6], const double (&b)[6]) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s += a[i] * b[i];
+    return s;
+}
+// v(n): 1 / E(n) = v^T S v, beta(n) = r . v with the compressibility's row sums r
+__device__ __forceinline__ void voigt_dyad(V3 n, double (&v)[6]) {
+    v[0] = n.x * n.x, v[1] = n.y * n.y, v[2] = n.z * n.z, v[3] = n.y * n.z, v[4] = n.x * n.z, v[5] = n.x * n.y;
+}
+// w(n,m): 1 / G(n,m) = w^T S w.  The fma of a b + c d is spelled out, here and in frame_dir: left to the compiler, which of
+// the two products is rounded before the sum depends on where the expression is inlined, and the pair kernel and the
+// refinement, which starts from the pair kernel's winner, must form the same m and the same w.
+__device__ __forceinline__ void voigt_pair(V3 n, V3 m, double (&w)[6]) {
+    w[0] = 2.0 * n.x * m.x, w[1] = 2.0 * n.y * m.y, w[2] = 2.0 * n.z * m.z;
+    w[3] = fma(n.y, m.z, n.z * m.y), w[4] = fma(n.x, m.z, n.z * m.x), w[5] = fma(n.x, m.y, n.y * m.x);
+}
+__device__ __forceinline__ void compress_rows(const double (&S)[6][6], double (&r)[6]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) r[i] = S[i][0] + S[i][1] + S[i][2];
+}
+// the branch-free orthonormal frame (e1, e2) of a unit vector n, and the direction at the angle (c, s) = (cos, sin) in it
+__device__ __forceinline__ void pair_frame(V3 n, V3& e1, V3& e2) {
+    const double sg = n.z >= 0.0 ? 1.0 : -1.0;
+    const double fa = -1.0 / (sg + n.z), fb = n.x * n.y * fa;
+    e1 = {1.0 + sg * n.x * n.x * fa, sg * fb, -sg * n.x};
+    e2 = {fb, sg + n.y * n.y * fa, -n.y};
+}
+__device__ __forceinline__ V3 frame_dir(double c, double s, V3 e1, V3 e2) {
+    return {fma(c, e1.x, s * e2.x), fma(c, e1.y, s * e2.y), fma(c, e1.z, s * e2.z)};
+}
 
 // One crystal per thread.  LAYOUT 0: c [n, 81] Cartesian, 1: c [n, 36] Voigt.
 template <typename T, int LAYOUT>
@@ -49,12 +110,7 @@ __global__ void __launch_bounds__(64) elastic_props_kernel(const T* __restrict__
             }
         }
     } else {
-        const T* p = c + b * 36;
-#pragma unroll
-        for (int I = 0; I < 6; ++I) {
-#pragma unroll
-            for (int J = I; J < 6; ++J) C[I][J] = C[J][I] = 0.5 * ((double)p[I * 6 + J] + (double)p[J * 6 + I]);
-        }
+        load_sym6(c + b * 36, C);
     }
     bool ok = true;
 #pragma unroll
@@ -301,6 +357,36 @@ __device__ __forceinline__ Ext wave_best(Ext a) {
 }
 
 constexpr int DIR_THREADS = 256;
+constexpr int EXT_NONE = 0x7fffffff;   // the index of an Ext that no candidate has replaced yet
+
+// the workgroup's winner of NV lane-local (value, index) pairs -- minima at even, maxima at odd positions -- written by lane
+// q < NV to ext[q] / arg[q]: in the wave first, then across the four waves through LDS.  A pair that never met a comparable
+// value (all NaN) becomes NaN and -1 with NONE_IS_NAN; without, it is written as it stands (+-inf and EXT_NONE: what the
+// directional kernel has written since its first version)
+template <int NV, bool NONE_IS_NAN>
+__device__ __forceinline__ void block_best(Ext (&e)[NV], double* __restrict__ ext, int32_t* __restrict__ arg, int t) {
+    __shared__ double sh_v[DIR_THREADS / 64][NV];
+    __shared__ int sh_i[DIR_THREADS / 64][NV];
+#pragma unroll
+    for (int q = 0; q < NV; ++q) e[q] = (q & 1) ? wave_best<true>(e[q]) : wave_best<false>(e[q]);
+    const int wave = t >> 6;
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) sh_v[wave][q] = e[q].v, sh_i[wave][q] = e[q].i;
+    }
+    __syncthreads();
+    if (t < NV) {
+        Ext a = {sh_v[0][t], sh_i[0][t]};
+#pragma unroll
+        for (int w = 1; w < DIR_THREADS / 64; ++w) {
+            const Ext o = {sh_v[w][t], sh_i[w][t]};
+            a = (t & 1) ? better<true>(a, o) : better<false>(a, o);
+        }
+        const bool none = NONE_IS_NAN && a.i == EXT_NONE;
+        ext[t] = none ? __longlong_as_double(0x7ff8000000000000LL) : a.v;
+        arg[t] = none ? -1 : a.i;
+    }
+}
 
 // One workgroup per crystal, a lane per direction in strides of DIR_THREADS.
 __global__ void __launch_bounds__(DIR_THREADS) elastic_directional_kernel(const double* __restrict__ compliance,
@@ -322,91 +408,26 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_directional_kernel(const 
         }
         return;
     }
-    // the 21 distinct entries (the two triangles of the elimination's result agree to rounding: their mean), and the
-    // row sums of the compressibility
-    const double* s = compliance + b * 36;
     double S[6][6], r[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = i; j < 6; ++j) S[i][j] = S[j][i] = 0.5 * (s[i * 6 + j] + s[j * 6 + i]);
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) r[i] = S[i][0] + S[i][1] + S[i][2];
+    load_sym6(compliance + b * 36, S);
+    compress_rows(S, r);
 
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
-    Ext e_min = {inf, 0x7fffffff}, e_max = {-inf, 0x7fffffff}, b_min = {inf, 0x7fffffff}, b_max = {-inf, 0x7fffffff};
+    Ext best[4] = {{inf, EXT_NONE}, {-inf, EXT_NONE}, {inf, EXT_NONE}, {-inf, EXT_NONE}};   // E_min, E_max, beta_min, beta_max
     for (int d = t; d < n_dirs; d += DIR_THREADS) {
-        const double n1 = dirs[d * 3 + 0], n2 = dirs[d * 3 + 1], n3 = dirs[d * 3 + 2];
-        const double v[6] = {n1 * n1, n2 * n2, n3 * n3, n2 * n3, n1 * n3, n1 * n2};
-        double q = 0.0, bt = 0.0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double row = 0.0;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) row += S[i][j] * v[j];
-            q += v[i] * row;
-            bt += r[i] * v[i];
-        }
-        const double E = 1.0 / q;
+        double v[6], Sv[6];
+        voigt_dyad(load_dir(dirs, d), v);
+        matvec6(S, v, Sv);
+        const double E = 1.0 / dot6(v, Sv), bt = dot6(r, v);
         if (young) young[b * n_dirs + d] = E;
         if (beta) beta[b * n_dirs + d] = bt;
         const Ext ce = {E, d}, cb = {bt, d};
-        e_min = better<false>(e_min, ce);
-        e_max = better<true>(e_max, ce);
-        b_min = better<false>(b_min, cb);
-        b_max = better<true>(b_max, cb);
+        best[0] = better<false>(best[0], ce);
+        best[1] = better<true>(best[1], ce);
+        best[2] = better<false>(best[2], cb);
+        best[3] = better<true>(best[3], cb);
     }
-    // in the wave first, then across the four waves through LDS
-    e_min = wave_best<false>(e_min);
-    e_max = wave_best<true>(e_max);
-    b_min = wave_best<false>(b_min);
-    b_max = wave_best<true>(b_max);
-    __shared__ double sh_v[DIR_THREADS / 64][4];
-    __shared__ int sh_i[DIR_THREADS / 64][4];
-    const int wave = t >> 6;
-    if ((t & 63) == 0) {
-        sh_v[wave][0] = e_min.v, sh_v[wave][1] = e_max.v, sh_v[wave][2] = b_min.v, sh_v[wave][3] = b_max.v;
-        sh_i[wave][0] = e_min.i, sh_i[wave][1] = e_max.i, sh_i[wave][2] = b_min.i, sh_i[wave][3] = b_max.i;
-    }
-    __syncthreads();
-    if (t < 4) {
-        Ext a = {sh_v[0][t], sh_i[0][t]};
-#pragma unroll
-        for (int w = 1; w < DIR_THREADS / 64; ++w) {
-            const Ext o = {sh_v[w][t], sh_i[w][t]};
-            a = (t & 1) ? better<true>(a, o) : better<false>(a, o);
-        }
-        ext[b * 4 + t] = a.v;
-        arg[b * 4 + t] = a.i;
-    }
-}
-
-constexpr int EXT_NONE = 0x7fffffff;   // the index of an Ext that no candidate has replaced yet
-
-// the winner of the workgroup's four waves for NV (value, index) pairs -- minima at even, maxima at odd positions -- written
-// by lane q < NV to ext[q] / arg[q]; a pair that never met a comparable value (all NaN) becomes NaN and -1
-template <int NV>
-__device__ __forceinline__ void block_best(const Ext (&e)[NV], double* __restrict__ ext, int32_t* __restrict__ arg, int t) {
-    __shared__ double sh_v[DIR_THREADS / 64][NV];
-    __shared__ int sh_i[DIR_THREADS / 64][NV];
-    const int wave = t >> 6;
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) sh_v[wave][q] = e[q].v, sh_i[wave][q] = e[q].i;
-    }
-    __syncthreads();
-    if (t < NV) {
-        Ext a = {sh_v[0][t], sh_i[0][t]};
-#pragma unroll
-        for (int w = 1; w < DIR_THREADS / 64; ++w) {
-            const Ext o = {sh_v[w][t], sh_i[w][t]};
-            a = (t & 1) ? better<true>(a, o) : better<false>(a, o);
-        }
-        const bool none = a.i == EXT_NONE;
-        ext[t] = none ? __longlong_as_double(0x7ff8000000000000LL) : a.v;
-        arg[t] = none ? -1 : a.i;
-    }
+    block_best<4, false>(best, ext + b * 4, arg + b * 4, t);
 }
 
 // One workgroup per crystal, a lane per direction n in strides of DIR_THREADS; the lane walks the n_ang directions
@@ -432,51 +453,29 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_pair_kernel(const double*
         }
         return;
     }
-    const double* s = compliance + b * 36;
     double S[6][6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = i; j < 6; ++j) S[i][j] = S[j][i] = 0.5 * (s[i * 6 + j] + s[j * 6 + i]);
-    }
+    load_sym6(compliance + b * 36, S);
 
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
     Ext best[4] = {{inf, EXT_NONE}, {-inf, EXT_NONE}, {inf, EXT_NONE}, {-inf, EXT_NONE}};   // G_min, G_max, nu_min, nu_max
     for (int d = t; d < n_dirs; d += DIR_THREADS) {
-        const double n1 = dirs[d * 3 + 0], n2 = dirs[d * 3 + 1], n3 = dirs[d * 3 + 2];
-        const double v[6] = {n1 * n1, n2 * n2, n3 * n3, n2 * n3, n1 * n3, n1 * n2};
-        double Sv[6], q = 0.0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double row = 0.0;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) row += S[i][j] * v[j];
-            Sv[i] = row;
-            q += v[i] * row;
-        }
-        // the branch-free orthonormal frame (e1, e2) of n
-        const double sg = n3 >= 0.0 ? 1.0 : -1.0;
-        const double fa = -1.0 / (sg + n3), fb = n1 * n2 * fa;
-        const double e1[3] = {1.0 + sg * n1 * n1 * fa, sg * fb, -sg * n1};
-        const double e2[3] = {fb, sg + n2 * n2 * fa, -n2};
+        const V3 n = load_dir(dirs, d);
+        double v[6], Sv[6];
+        voigt_dyad(n, v);
+        matvec6(S, v, Sv);
+        const double q = dot6(v, Sv);
+        V3 e1, e2;
+        pair_frame(n, e1, e2);
 
         Ext here[4] = {{inf, EXT_NONE}, {-inf, EXT_NONE}, {inf, EXT_NONE}, {-inf, EXT_NONE}};
         const int base = d * n_ang;
         for (int k = 0; k < n_ang; ++k) {
-            const double c = cos_sin[2 * (int64_t)k], sn = cos_sin[2 * (int64_t)k + 1];
-            const double m1 = c * e1[0] + sn * e2[0], m2 = c * e1[1] + sn * e2[1], m3 = c * e1[2] + sn * e2[2];
-            const double vm[6] = {m1 * m1, m2 * m2, m3 * m3, m2 * m3, m1 * m3, m1 * m2};
-            const double w[6] = {2.0 * n1 * m1, 2.0 * n2 * m2, 2.0 * n3 * m3, n2 * m3 + n3 * m2, n1 * m3 + n3 * m1,
-                                 n1 * m2 + n2 * m1};
-            double num = 0.0, h = 0.0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                double row = 0.0;
-#pragma unroll
-                for (int j = 0; j < 6; ++j) row += S[i][j] * w[j];
-                h += w[i] * row;
-                num += Sv[i] * vm[i];
-            }
+            const V3 m = frame_dir(cos_sin[2 * (int64_t)k], cos_sin[2 * (int64_t)k + 1], e1, e2);
+            double vm[6], w[6], Sw[6];
+            voigt_dyad(m, vm);
+            voigt_pair(n, m, w);
+            matvec6(S, w, Sw);
+            const double h = dot6(w, Sw), num = dot6(Sv, vm);
             const Ext cg = {1.0 / h, base + k}, cn = {-num / q, base + k};
             here[0] = better<false>(here[0], cg);
             here[1] = better<true>(here[1], cg);
@@ -489,32 +488,104 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_pair_kernel(const double*
             best[x] = (x & 1) ? better<true>(best[x], here[x]) : better<false>(best[x], here[x]);
         }
     }
-    best[0] = wave_best<false>(best[0]);
-    best[1] = wave_best<true>(best[1]);
-    best[2] = wave_best<false>(best[2]);
-    best[3] = wave_best<true>(best[3]);
-    block_best<4>(best, ext + b * 4, arg + b * 4, t);
+    block_best<4, true>(best, ext + b * 4, arg + b * 4, t);
 }
 
+// Gamma_ik = C_ijkl n_j n_l, its upper triangle
+__device__ constexpr int VOIGT_OF[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}};   // Cartesian pair -> Voigt index
+__device__ __forceinline__ void christoffel(const double (&C)[6][6], const double (&n)[3], double (&G)[3][3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int k = i; k < 3; ++k) {
+            double g = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+#pragma unroll
+                for (int l = 0; l < 3; ++l) g += C[VOIGT_OF[i][j]][VOIGT_OF[k][l]] * (n[j] * n[l]);
+            }
+            G[i][k] = g;
+        }
+    }
+}
+
+// a pair (g, f) of row or column entries p, q turned by the rotation (sn, tau)
+__device__ __forceinline__ void jacobi_turn(double sn, double tau, double& g, double& f) {
+    const double g0 = g, f0 = f;
+    g = g0 - sn * (f0 + g0 * tau);
+    f = f0 + sn * (g0 - f0 * tau);
+}
 // One cyclic-Jacobi rotation of a symmetric 3x3 matrix: annihilates a_pq; r is the third index.  Branch-free: a zero
-// a_pq (where theta is inf or 0/0) rotates by nothing.
-__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
+// a_pq (where theta is inf or 0/0) rotates by nothing.  Hands back (sn, tau) for the eigenvectors.
+__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& sn,
+                                              double& tau) {
     const double theta = (aqq - app) / (2.0 * apq);
     double tn = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));   // (theta^2 = inf: 0)
     tn = apq == 0.0 ? 0.0 : tn;
-    const double c = 1.0 / sqrt(tn * tn + 1.0), sn = tn * c, tau = sn / (1.0 + c);
+    const double c = 1.0 / sqrt(tn * tn + 1.0);
+    sn = tn * c, tau = sn / (1.0 + c);
     const double h = tn * apq;
     app -= h;
     aqq += h;
     apq = 0.0;
-    const double g = arp, f = arq;
-    arp = g - sn * (f + g * tau);
-    arq = f + sn * (g - f * tau);
+    jacobi_turn(sn, tau, arp, arq);
 }
 
 // cyclic Jacobi converges quadratically: on the example data set, isotropic and cubic tensors the off-diagonal is below
 // 1e-21 max|C| after 4 sweeps (numpy fp64 run of this rotation); one more sweep is the margin
 constexpr int JACOBI_SWEEPS = 5;
+
+// The eigenvalues of the symmetric A (its upper triangle is read and destroyed) in lam, unsorted, by JACOBI_SWEEPS cyclic
+// sweeps; with VEC the eigenvectors in the columns of U, which is not touched otherwise.  The arithmetic on the matrix does
+// not depend on VEC: an adjoint that asks for the vectors gets the forward's eigenvalues, bit for bit.
+template <bool VEC, int P, int Q>
+__device__ __forceinline__ void jacobi_step(double (&A)[3][3], double (&U)[3][3]) {
+    constexpr int R = 3 - P - Q;
+    double sn, tau;
+    jacobi_rotate(A[P][P], A[Q][Q], A[P][Q], A[R < P ? R : P][R < P ? P : R], A[R < Q ? R : Q][R < Q ? Q : R], sn, tau);
+    if (VEC) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) jacobi_turn(sn, tau, U[i][P], U[i][Q]);
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void sym3_eig(double (&A)[3][3], double (&lam)[3], double (&U)[3][3]) {
+    if (VEC) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) U[i][j] = i == j ? 1.0 : 0.0;
+        }
+    }
+#pragma unroll
+    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+        jacobi_step<VEC, 0, 1>(A, U);
+        jacobi_step<VEC, 0, 2>(A, U);
+        jacobi_step<VEC, 1, 2>(A, U);
+    }
+    lam[0] = A[0][0], lam[1] = A[1][1], lam[2] = A[2][2];
+}
+// a direction is acoustically stable where all three eigenvalues of Gamma are positive and finite (false for NaN)
+__device__ __forceinline__ bool stable3(const double (&lam)[3]) {
+    return lam[0] > 0.0 && lam[1] > 0.0 && lam[2] > 0.0 && finite64(lam[0]) && finite64(lam[1]) && finite64(lam[2]);
+}
+// (eigenvalue, eigenvector column) pairs in ascending order: a network of three comparators, exchanged by selects
+template <int P, int Q>
+__device__ __forceinline__ void sort_pair(double (&lam)[3], double (&U)[3][3]) {
+    const bool sw = lam[P] > lam[Q];
+    const double a = lam[P], b = lam[Q];
+    lam[P] = sw ? b : a, lam[Q] = sw ? a : b;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double x = U[i][P], y = U[i][Q];
+        U[i][P] = sw ? y : x, U[i][Q] = sw ? x : y;
+    }
+}
+__device__ __forceinline__ void sort3(double (&lam)[3], double (&U)[3][3]) {
+    sort_pair<0, 1>(lam, U);
+    sort_pair<1, 2>(lam, U);
+    sort_pair<0, 1>(lam, U);
+}
 
 // One workgroup per crystal, a lane per direction in strides of DIR_THREADS: Gamma_ik = C_ijkl n_j n_l, its eigenvalues
 // by cyclic Jacobi in registers, v_i = sqrt(lambda_i unit / rho) ascending.
@@ -538,14 +609,8 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_kernel(const dou
         if (t == 0) n_unstable[b] = -1;
         return;
     }
-    const double* cp = voigt + b * 36;
     double C[6][6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = i; j < 6; ++j) C[i][j] = C[j][i] = 0.5 * (cp[i * 6 + j] + cp[j * 6 + i]);
-    }
-    constexpr int V[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}};   // Cartesian pair -> Voigt index
+    load_sym6(voigt + b * 36, C);
     const double scale = modulus_unit / rho;
 
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
@@ -554,30 +619,12 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_kernel(const dou
     int bad = 0;
     for (int d = t; d < n_dirs; d += DIR_THREADS) {
         const double n[3] = {dirs[d * 3 + 0], dirs[d * 3 + 1], dirs[d * 3 + 2]};
-        double G[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int k = i; k < 3; ++k) {
-                double g = 0.0;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-#pragma unroll
-                    for (int l = 0; l < 3; ++l) g += C[V[i][j]][V[k][l]] * (n[j] * n[l]);
-                }
-                G[i][k] = g;
-            }
-        }
-        double a00 = G[0][0], a11 = G[1][1], a22 = G[2][2], a01 = G[0][1], a02 = G[0][2], a12 = G[1][2];
-#pragma unroll
-        for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-            jacobi_rotate(a00, a11, a01, a02, a12);   // (p, q, r) = (0, 1, 2)
-            jacobi_rotate(a00, a22, a02, a01, a12);   //             (0, 2, 1)
-            jacobi_rotate(a11, a22, a12, a01, a02);   //             (1, 2, 0)
-        }
-        const bool ok = a00 > 0.0 && a11 > 0.0 && a22 > 0.0 && finite64(a00) && finite64(a11) && finite64(a22);
-        const double lo01 = fmin(a00, a11), hi01 = fmax(a00, a11);
-        const double l0 = fmin(lo01, a22), top = fmax(lo01, a22);
+        double G[3][3], lam[3], U[3][3];
+        christoffel(C, n, G);
+        sym3_eig<false>(G, lam, U);
+        const bool ok = stable3(lam);
+        const double lo01 = fmin(lam[0], lam[1]), hi01 = fmax(lam[0], lam[1]);
+        const double l0 = fmin(lo01, lam[2]), top = fmax(lo01, lam[2]);
         const double l1 = fmin(hi01, top), l2 = fmax(hi01, top);
         const double v0 = ok ? sqrt(l0 * scale) : nan, v1 = ok ? sqrt(l1 * scale) : nan, v2 = ok ? sqrt(l2 * scale) : nan;
         if (vel) {
@@ -590,8 +637,6 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_kernel(const dou
         best[0] = better<false>(best[0], c0);   // (a NaN compares false: never taken)
         best[1] = better<true>(best[1], c2);
     }
-    best[0] = wave_best<false>(best[0]);
-    best[1] = wave_best<true>(best[1]);
     // the sum in a fixed order: the lane's strided partial sum, an xor butterfly in the wave (a + b = b + a: every lane
     // holds the same bits), the four waves in index order
 #pragma unroll
@@ -602,7 +647,7 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_kernel(const dou
     __shared__ double sh_sum[DIR_THREADS / 64];
     __shared__ int sh_bad[DIR_THREADS / 64];
     if ((t & 63) == 0) sh_sum[t >> 6] = sum, sh_bad[t >> 6] = bad;
-    block_best<2>(best, ext + b * 3, arg + b * 2, t);   // (its barrier covers sh_sum / sh_bad as well)
+    block_best<2, true>(best, ext + b * 3, arg + b * 2, t);   // (its barrier covers sh_sum / sh_bad as well)
     if (t == 0) {
         double total = sh_sum[0];
         int n_bad = sh_bad[0];
@@ -649,7 +694,7 @@ __device__ __forceinline__ void block_sum(double (&a)[NV], double* __restrict__ 
 }
 
 // The adjoint of elastic_directional_kernel, one workgroup per crystal, a lane per direction in strides of DIR_THREADS.
-// Nothing but the compliance is kept, so E(n) is made again per direction (the forward's expression: the same bits).
+// Nothing but the compliance is kept, so E(n) is made again per direction (by the forward's helpers: the same bits).
 // With e = (1,1,1,0,0,0):  H = sum_d ( -gE_d E_d^2 v_d v_d^T + gbeta_d v_d e^T ),  g_compliance = (H + H^T) / 2.
 // gE_d = the map's gradient plus the extremes' at the directions the forward recorded (a subgradient where values tie),
 // gbeta_d likewise.  A lane accumulates the 21 distinct entries of the symmetric part and the 6 of sum_d gbeta_d v_d.
@@ -666,13 +711,8 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_directional_bwd_kernel(
         if (t < 36) out[t] = 0.0;
         return;
     }
-    const double* s = compliance + b * 36;
     double S[6][6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = i; j < 6; ++j) S[i][j] = S[j][i] = 0.5 * (s[i * 6 + j] + s[j * 6 + i]);
-    }
+    load_sym6(compliance + b * 36, S);
     int at[4] = {-1, -1, -1, -1};            // E_min, E_max, beta_min, beta_max: where, and their upstream gradients
     double gx[4] = {0.0, 0.0, 0.0, 0.0};
     if (g_ext) {
@@ -684,17 +724,10 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_directional_bwd_kernel(
 #pragma unroll
     for (int q = 0; q < 27; ++q) acc[q] = 0.0;
     for (int d = t; d < n_dirs; d += DIR_THREADS) {
-        const double n1 = dirs[d * 3 + 0], n2 = dirs[d * 3 + 1], n3 = dirs[d * 3 + 2];
-        const double v[6] = {n1 * n1, n2 * n2, n3 * n3, n2 * n3, n1 * n3, n1 * n2};
-        double q = 0.0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double row = 0.0;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) row += S[i][j] * v[j];
-            q += v[i] * row;
-        }
-        const double E = 1.0 / q;
+        double v[6], Sv[6];
+        voigt_dyad(load_dir(dirs, d), v);
+        matvec6(S, v, Sv);
+        const double E = 1.0 / dot6(v, Sv);
         double gE = 0.0, gb = 0.0;
         if (g_young) gE = g_young[b * n_dirs + d];
         if (g_beta) gb = g_beta[b * n_dirs + d];
@@ -721,43 +754,9 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_directional_bwd_kernel(
     }
 }
 
-// jacobi_rotate with the rotation accumulated into the eigenvectors: the same arithmetic on the matrix (so the eigenvalues
-// are the forward's, bit for bit), then columns p and q of U turned by the same (sn, tau)
-__device__ __forceinline__ void jacobi_rotate_vec(double& app, double& aqq, double& apq, double& arp, double& arq, double& u0p,
-                                                  double& u0q, double& u1p, double& u1q, double& u2p, double& u2q) {
-    const double theta = (aqq - app) / (2.0 * apq);
-    double tn = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));   // (theta^2 = inf: 0)
-    tn = apq == 0.0 ? 0.0 : tn;
-    const double c = 1.0 / sqrt(tn * tn + 1.0), sn = tn * c, tau = sn / (1.0 + c);
-    const double h = tn * apq;
-    app -= h;
-    aqq += h;
-    apq = 0.0;
-    const double g = arp, f = arq;
-    arp = g - sn * (f + g * tau);
-    arq = f + sn * (g - f * tau);
-    const double g0 = u0p, f0 = u0q, g1 = u1p, f1 = u1q, g2 = u2p, f2 = u2q;
-    u0p = g0 - sn * (f0 + g0 * tau);
-    u0q = f0 + sn * (g0 - f0 * tau);
-    u1p = g1 - sn * (f1 + g1 * tau);
-    u1q = f1 + sn * (g1 - f1 * tau);
-    u2p = g2 - sn * (f2 + g2 * tau);
-    u2q = f2 + sn * (g2 - f2 * tau);
-}
-
-// one comparator of the sorting network: (value, eigenvector column) pairs exchanged by selects where lp > lq
-__device__ __forceinline__ void sort_pair(double& lp, double& lq, double& u0p, double& u0q, double& u1p, double& u1q,
-                                          double& u2p, double& u2q) {
-    const bool sw = lp > lq;
-    const double a = lp, b = lq, a0 = u0p, b0 = u0q, a1 = u1p, b1 = u1q, a2 = u2p, b2 = u2q;
-    lp = sw ? b : a, lq = sw ? a : b;
-    u0p = sw ? b0 : a0, u0q = sw ? a0 : b0;
-    u1p = sw ? b1 : a1, u1q = sw ? a1 : b1;
-    u2p = sw ? b2 : a2, u2q = sw ? a2 : b2;
-}
-
 // The adjoint of elastic_acoustic_kernel, one workgroup per crystal, a lane per direction in strides of DIR_THREADS.
-// Gamma and its Jacobi sweeps are run again with the eigenvectors u_k; with s = modulus_unit / rho, v_k = sqrt(lambda_k s):
+// Gamma and its Jacobi sweeps are run again (christoffel, sym3_eig) with the eigenvectors u_k; with s = modulus_unit / rho,
+// v_k = sqrt(lambda_k s):
 //   w_k = (g_vel_k + [slowest here] g_ext_0 + [fastest here] g_ext_1 - 3 g_ext_2 v_k^-4) s / (2 v_k),
 //   Gbar = sum_k w_k u_k u_k^T,   Hc[V[i][j]][V[k][l]] += Gbar_ik n_j n_l  (symmetric: 21 distinct entries per lane),
 //   g_voigt = (Hc + Hc^T) / 2 = Hc.
@@ -777,14 +776,8 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_bwd_kernel(
         if (t < 36) out[t] = 0.0;
         return;
     }
-    const double* cp = voigt + b * 36;
     double C[6][6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = i; j < 6; ++j) C[i][j] = C[j][i] = 0.5 * (cp[i * 6 + j] + cp[j * 6 + i]);
-    }
-    constexpr int V[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}};   // Cartesian pair -> Voigt index
+    load_sym6(voigt + b * 36, C);
     const double scale = modulus_unit / rho;
     int at_slow = -1, at_fast = -1;
     double gx_slow = 0.0, gx_fast = 0.0, gx_sum = 0.0;
@@ -798,34 +791,11 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_bwd_kernel(
     for (int q = 0; q < 21; ++q) acc[q] = 0.0;
     for (int d = t; d < n_dirs; d += DIR_THREADS) {
         const double n[3] = {dirs[d * 3 + 0], dirs[d * 3 + 1], dirs[d * 3 + 2]};
-        double G[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int k = i; k < 3; ++k) {
-                double g = 0.0;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-#pragma unroll
-                    for (int l = 0; l < 3; ++l) g += C[V[i][j]][V[k][l]] * (n[j] * n[l]);
-                }
-                G[i][k] = g;
-            }
-        }
-        double a00 = G[0][0], a11 = G[1][1], a22 = G[2][2], a01 = G[0][1], a02 = G[0][2], a12 = G[1][2];
-        double u00 = 1.0, u01 = 0.0, u02 = 0.0, u10 = 0.0, u11 = 1.0, u12 = 0.0, u20 = 0.0, u21 = 0.0, u22 = 1.0;
-#pragma unroll
-        for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-            jacobi_rotate_vec(a00, a11, a01, a02, a12, u00, u01, u10, u11, u20, u21);   // (p, q, r) = (0, 1, 2)
-            jacobi_rotate_vec(a00, a22, a02, a01, a12, u00, u02, u10, u12, u20, u22);   //             (0, 2, 1)
-            jacobi_rotate_vec(a11, a22, a12, a01, a02, u01, u02, u11, u12, u21, u22);   //             (1, 2, 0)
-        }
-        const bool ok = a00 > 0.0 && a11 > 0.0 && a22 > 0.0 && finite64(a00) && finite64(a11) && finite64(a22);
-        sort_pair(a00, a11, u00, u01, u10, u11, u20, u21);
-        sort_pair(a11, a22, u01, u02, u11, u12, u21, u22);
-        sort_pair(a00, a11, u00, u01, u10, u11, u20, u21);
-        const double lam[3] = {a00, a11, a22};
-        const double U[3][3] = {{u00, u01, u02}, {u10, u11, u12}, {u20, u21, u22}};   // column k = u_k
+        double G[3][3], lam[3], U[3][3];   // column k of U = u_k
+        christoffel(C, n, G);
+        sym3_eig<true>(G, lam, U);
+        const bool ok = stable3(lam);
+        sort3(lam, U);
         double w[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -854,7 +824,7 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_bwd_kernel(
                 for (int k = 0; k < 3; ++k) {
 #pragma unroll
                     for (int l = 0; l < 3; ++l) {
-                        if (V[i][j] <= V[k][l]) h[tri6(V[i][j], V[k][l])] += Gb[i][k] * (n[j] * n[l]);
+                        if (VOIGT_OF[i][j] <= VOIGT_OF[k][l]) h[tri6(VOIGT_OF[i][j], VOIGT_OF[k][l])] += Gb[i][k] * (n[j] * n[l]);
                     }
                 }
             }
@@ -874,29 +844,11 @@ __global__ void __launch_bounds__(DIR_THREADS) elastic_acoustic_bwd_kernel(
 // refinement of the grid's extremes (elastic_properties(refine=True)): the winners of the directional and the pair kernel
 // polished off the grid.  matten_amd/elastic.py:refine_extremes_host is the same iteration in numpy.
 // ---------------------------------------------------------------------------------------------------
-struct V3 {
-    double x, y, z;
-};
 __device__ __forceinline__ V3 cross3(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ double dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ V3 add3(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
 __device__ __forceinline__ V3 scale3(double c, V3 a) { return {c * a.x, c * a.y, c * a.z}; }
 
-__device__ __forceinline__ void matvec6(const double (&S)[6][6], const double (&x)[6], double (&y)[6]) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double row = 0.0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) row += S[i][j] * x[j];
-        y[i] = row;
-    }
-}
-__device__ __forceinline__ double dot6(const double (&a)[6], const double (&b)[6]) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) s += a[i] * b[i];
-    return s;
-}
 // A(a) x with the symmetric A(a) = [[2 a0, a5, a4], [a5, 2 a1, a3], [a4, a3, 2 a2]]: a . v(n) = n^T A(a) n / 2 and
 // a . w(n,m) = n^T A(a) m, so A(a) x is the derivative of either
 __device__ __forceinline__ V3 sym_apply(const double (&a)[6], V3 x) {
@@ -908,9 +860,8 @@ __device__ __forceinline__ V3 sym_apply(const double (&a)[6], V3 x) {
 // independent vectors
 __device__ __forceinline__ void refine_eval(int kind, const double (&S)[6][6], V3 n, V3 m, double& f, V3& dn, V3& dm) {
     if (kind == 1) {
-        const double w[6] = {2.0 * n.x * m.x, 2.0 * n.y * m.y, 2.0 * n.z * m.z, n.y * m.z + n.z * m.y, n.x * m.z + n.z * m.x,
-                             n.x * m.y + n.y * m.x};
-        double Sw[6];
+        double w[6], Sw[6];
+        voigt_pair(n, m, w);
         matvec6(S, w, Sw);
         f = 1.0 / dot6(w, Sw);
         const double c = -2.0 * f * f;
@@ -918,8 +869,8 @@ __device__ __forceinline__ void refine_eval(int kind, const double (&S)[6][6], V
         dm = scale3(c, sym_apply(Sw, n));
         return;
     }
-    const double v[6] = {n.x * n.x, n.y * n.y, n.z * n.z, n.y * n.z, n.x * n.z, n.x * n.y};
-    double Sv[6];
+    double v[6], Sv[6];
+    voigt_dyad(n, v);
     matvec6(S, v, Sv);
     const double q = dot6(v, Sv);
     if (kind == 0) {
@@ -928,8 +879,8 @@ __device__ __forceinline__ void refine_eval(int kind, const double (&S)[6][6], V
         dm = {0.0, 0.0, 0.0};
         return;
     }
-    const double vm[6] = {m.x * m.x, m.y * m.y, m.z * m.z, m.y * m.z, m.x * m.z, m.x * m.y};
-    double Svm[6];
+    double vm[6], Svm[6];
+    voigt_dyad(m, vm);
     matvec6(S, vm, Svm);
     const double p = dot6(Sv, vm);
     f = -p / q;
@@ -984,8 +935,8 @@ constexpr int REFINE_THREADS = 64;
 // One thread per (extreme q, crystal b), item = q n + b: a wave works on one kind of extreme (but for the one that holds a
 // boundary).  q = 0..3: E_min, E_max, beta_min, beta_max from the directional kernel's ext / arg; 4..7: G_min, G_max,
 // nu_min, nu_max from the pair kernel's.  The start pair is the winner's n with m = cos(chi_k) e1 + sin(chi_k) e2 in the
-// pair kernel's frame (k = 0 for E and beta).  E, G, nu: F(w) = +-f(R(w) n, R(w) m) is maximised by a damped Newton
-// iteration -- the analytic gradient at w = 0, the Hessian as the symmetric part of that gradient's central differences
+// pair kernel's frame (pair_frame, frame_dir; k = 0 for E and beta).  E, G, nu: F(w) = +-f(R(w) n, R(w) m) is maximised by a
+// damped Newton iteration -- the analytic gradient at w = 0, the Hessian as the symmetric part of that gradient's central differences
 // over rotations about the three axes, diagonalised by cyclic Jacobi, every eigenvalue clamped to the ascent side
 // (min(lambda, -1e-3 max|lambda|), so directions the function does not depend on -- m for E, chi for G at a cubic [100] --
 // and an isotropic tensor are harmless), the step capped at 0.3 rad, accepted only if the value strictly improves, else
@@ -1014,16 +965,14 @@ __global__ void __launch_bounds__(REFINE_THREADS) elastic_refine_kernel(
     int st = -1, it = 0;
     if (!(fl & 1) && at >= 0 && at < n_start) {   // (an index outside the tables is never followed)
         const int d = pairq ? at / n_ang : at, k = pairq ? at - d * n_ang : 0;
-        const V3 n0 = {dirs[d * 3 + 0], dirs[d * 3 + 1], dirs[d * 3 + 2]};
-        // the pair kernel's frame and its m, expression for expression
-        const double sg = n0.z >= 0.0 ? 1.0 : -1.0;
-        const double fa = -1.0 / (sg + n0.z), fb = n0.x * n0.y * fa;
-        const double e1[3] = {1.0 + sg * n0.x * n0.x * fa, sg * fb, -sg * n0.x};
-        const double e2[3] = {fb, sg + n0.y * n0.y * fa, -n0.y};
-        const double c = pairq ? cos_sin[2 * (int64_t)k] : 1.0, sn = pairq ? cos_sin[2 * (int64_t)k + 1] : 0.0;
-        const V3 m0 = {c * e1[0] + sn * e2[0], c * e1[1] + sn * e2[1], c * e1[2] + sn * e2[2]};
+        const V3 n0 = load_dir(dirs, d);
+        V3 e1, e2;
+        pair_frame(n0, e1, e2);
+        const V3 m0 = frame_dir(pairq ? cos_sin[2 * (int64_t)k] : 1.0, pairq ? cos_sin[2 * (int64_t)k + 1] : 0.0, e1, e2);
         const double sign = (q & 1) ? 1.0 : -1.0;
-
+        // load_sym6, written out: through the helper the compiler orders this kernel's arithmetic differently, and at one
+        // wave per SIMD that schedule took 0.15 ms where this one takes 0.11 (docs/LAB_NOTES.md).  The mean of two values
+        // does not depend on their order, so S holds the other kernels' bits either way.
         const double* s = compliance + b * 36;
         double S[6][6];
 #pragma unroll
@@ -1037,24 +986,15 @@ __global__ void __launch_bounds__(REFINE_THREADS) elastic_refine_kernel(
             val = grid;
             st = 2;
         } else if (q == 2 || q == 3) {
-            double r[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) r[i] = S[i][0] + S[i][1] + S[i][2];
-            double a00 = r[0], a11 = r[1], a22 = r[2], a01 = 0.5 * r[5], a02 = 0.5 * r[4], a12 = 0.5 * r[3];
-            double u00 = 1.0, u01 = 0.0, u02 = 0.0, u10 = 0.0, u11 = 1.0, u12 = 0.0, u20 = 0.0, u21 = 0.0, u22 = 1.0;
-#pragma unroll
-            for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-                jacobi_rotate_vec(a00, a11, a01, a02, a12, u00, u01, u10, u11, u20, u21);   // (p, q, r) = (0, 1, 2)
-                jacobi_rotate_vec(a00, a22, a02, a01, a12, u00, u02, u10, u12, u20, u22);   //             (0, 2, 1)
-                jacobi_rotate_vec(a11, a22, a12, a01, a02, u01, u02, u11, u12, u21, u22);   //             (1, 2, 0)
-            }
-            sort_pair(a00, a11, u00, u01, u10, u11, u20, u21);
-            sort_pair(a11, a22, u01, u02, u11, u12, u21, u22);
-            sort_pair(a00, a11, u00, u01, u10, u11, u20, u21);
+            double r[6], A[3][3], lam[3], U[3][3];
+            compress_rows(S, r);
+            A[0][0] = r[0], A[1][1] = r[1], A[2][2] = r[2], A[0][1] = 0.5 * r[5], A[0][2] = 0.5 * r[4], A[1][2] = 0.5 * r[3];
+            sym3_eig<true>(A, lam, U);
+            sort3(lam, U);
             const bool top = q == 3;
-            val = top ? a22 : a00;
-            nn = top ? V3{u02, u12, u22} : V3{u00, u10, u20};
-            mm = {u01, u11, u21};
+            val = top ? lam[2] : lam[0];
+            nn = top ? V3{U[0][2], U[1][2], U[2][2]} : V3{U[0][0], U[1][0], U[2][0]};
+            mm = {U[0][1], U[1][1], U[2][1]};
             st = 0;
         } else {
             const int kind = q < 2 ? 0 : (q < 6 ? 1 : 2);
@@ -1085,24 +1025,21 @@ __global__ void __launch_bounds__(REFINE_THREADS) elastic_refine_kernel(
                 const V3 d1 = refine_fd(kind, sign, S, nn, mm, {0.0, REFINE_FD_STEP, 0.0}, ah, bh, inv_2h);
                 const V3 d2 = refine_fd(kind, sign, S, nn, mm, {0.0, 0.0, REFINE_FD_STEP}, ah, bh, inv_2h);
                 // H_ij = (D_ij + D_ji) / 2, D_ij = d g_i / d w_j (column j = d_j)
-                double a00 = d0.x, a11 = d1.y, a22 = d2.z, a01 = 0.5 * (d1.x + d0.y), a02 = 0.5 * (d2.x + d0.z),
-                       a12 = 0.5 * (d2.y + d1.z);
-                double u00 = 1.0, u01 = 0.0, u02 = 0.0, u10 = 0.0, u11 = 1.0, u12 = 0.0, u20 = 0.0, u21 = 0.0, u22 = 1.0;
-#pragma unroll
-                for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-                    jacobi_rotate_vec(a00, a11, a01, a02, a12, u00, u01, u10, u11, u20, u21);
-                    jacobi_rotate_vec(a00, a22, a02, a01, a12, u00, u02, u10, u12, u20, u22);
-                    jacobi_rotate_vec(a11, a22, a12, a01, a02, u01, u02, u11, u12, u21, u22);
-                }
-                const double dl = REFINE_CLAMP * fmax(fabs(a00), fmax(fabs(a11), fabs(a22))) + 1e-300;
-                const double l0 = fmin(a00, -dl), l1 = fmin(a11, -dl), l2 = fmin(a22, -dl);
-                const double ug0 = u00 * g.x + u10 * g.y + u20 * g.z, ug1 = u01 * g.x + u11 * g.y + u21 * g.z,
-                             ug2 = u02 * g.x + u12 * g.y + u22 * g.z;
+                double A[3][3], lam[3], U[3][3];
+                A[0][0] = d0.x, A[1][1] = d1.y, A[2][2] = d2.z;
+                A[0][1] = 0.5 * (d1.x + d0.y), A[0][2] = 0.5 * (d2.x + d0.z), A[1][2] = 0.5 * (d2.y + d1.z);
+                sym3_eig<true>(A, lam, U);
+                const double dl = REFINE_CLAMP * fmax(fabs(lam[0]), fmax(fabs(lam[1]), fabs(lam[2]))) + 1e-300;
+                const double l0 = fmin(lam[0], -dl), l1 = fmin(lam[1], -dl), l2 = fmin(lam[2], -dl);
+                const double ug0 = U[0][0] * g.x + U[1][0] * g.y + U[2][0] * g.z,
+                             ug1 = U[0][1] * g.x + U[1][1] * g.y + U[2][1] * g.z,
+                             ug2 = U[0][2] * g.x + U[1][2] * g.y + U[2][2] * g.z;
                 double damp = 0.0;
                 bool moved = false;
                 for (int tries = 0; tries < REFINE_DAMP_TRIES; ++tries) {
                     const double c0 = -ug0 / (l0 - damp), c1 = -ug1 / (l1 - damp), c2 = -ug2 / (l2 - damp);
-                    V3 step = {u00 * c0 + u01 * c1 + u02 * c2, u10 * c0 + u11 * c1 + u12 * c2, u20 * c0 + u21 * c1 + u22 * c2};
+                    V3 step = {U[0][0] * c0 + U[0][1] * c1 + U[0][2] * c2, U[1][0] * c0 + U[1][1] * c1 + U[1][2] * c2,
+                               U[2][0] * c0 + U[2][1] * c1 + U[2][2] * c2};
                     const double len = sqrt(dot3(step, step));
                     step = len > REFINE_MAX_STEP ? scale3(REFINE_MAX_STEP / len, step) : step;
                     double ra, rb;
@@ -1183,11 +1120,18 @@ extern "C" int matten_elastic_props_bwd(const double* voigt, const double* compl
     return MATTEN_OK;
 }
 
+// the sizes of a direction-set entry: n crystals (n_max bounds the kernel's 32-bit item count), n_dirs directions of three
+// coordinates, n_angles angles per direction (1 where the entry has none), the pairs counted in 32 bits
+static bool dir_set_ok(int64_t n, int64_t n_max, int64_t n_dirs, int64_t n_angles) {
+    return n >= 0 && n <= n_max && n_dirs >= 1 && n_dirs <= 0x7fffffff / 3 && n_angles >= 0 && n_angles <= 0x7fffffff &&
+           n_dirs * n_angles <= 0x7fffffff;
+}
+
 extern "C" int matten_elastic_directional(const double* compliance, const int32_t* flags, const double* dirs, int64_t n,
                                           int64_t n_dirs, double* young, double* beta, double* ext, int32_t* arg,
                                           matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n < 0 || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || n > 0x7fffffff) return MATTEN_EINVAL;
+    if (!dir_set_ok(n, 0x7fffffff, n_dirs, 1)) return MATTEN_EINVAL;
     if (n == 0) return MATTEN_OK;
     if (!compliance || !flags || !dirs || !ext || !arg) return MATTEN_EINVAL;
     elastic_directional_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(compliance, flags, dirs, (int)n_dirs, young, beta, ext,
@@ -1200,9 +1144,7 @@ extern "C" int matten_elastic_pair(const double* compliance, const int32_t* flag
                                    int64_t n, int64_t n_dirs, int64_t n_angles, double* maps, double* ext, int32_t* arg,
                                    matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n < 0 || n > 0x7fffffff || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || n_angles < 1 || n_angles > 0x7fffffff ||
-        n_dirs * n_angles > 0x7fffffff)
-        return MATTEN_EINVAL;
+    if (!dir_set_ok(n, 0x7fffffff, n_dirs, n_angles) || n_angles < 1) return MATTEN_EINVAL;
     if (n == 0) return MATTEN_OK;
     if (!compliance || !flags || !dirs || !cos_sin || !ext || !arg) return MATTEN_EINVAL;
     elastic_pair_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(compliance, flags, dirs, (int)n_dirs, cos_sin, (int)n_angles,
@@ -1215,7 +1157,7 @@ extern "C" int matten_elastic_acoustic(const double* voigt, const int32_t* flags
                                        int64_t n, int64_t n_dirs, double modulus_unit, double* vel, double* ext, int32_t* arg,
                                        int32_t* n_unstable, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n < 0 || n > 0x7fffffff || n_dirs < 1 || n_dirs > 0x7fffffff / 3) return MATTEN_EINVAL;
+    if (!dir_set_ok(n, 0x7fffffff, n_dirs, 1)) return MATTEN_EINVAL;
     if (n == 0) return MATTEN_OK;
     if (!voigt || !flags || !density || !dirs || !ext || !arg || !n_unstable) return MATTEN_EINVAL;
     elastic_acoustic_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(voigt, flags, density, dirs, (int)n_dirs, modulus_unit, vel,
@@ -1228,7 +1170,7 @@ extern "C" int matten_elastic_directional_bwd(const double* compliance, const in
                                               int64_t n_dirs, const double* g_young, const double* g_beta, const double* g_ext,
                                               const int32_t* arg, double* g_compliance, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n < 0 || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || n > 0x7fffffff || (g_ext && !arg)) return MATTEN_EINVAL;
+    if (!dir_set_ok(n, 0x7fffffff, n_dirs, 1) || (g_ext && !arg)) return MATTEN_EINVAL;
     if (n == 0) return MATTEN_OK;
     if (!compliance || !flags || !dirs || !g_compliance) return MATTEN_EINVAL;
     elastic_directional_bwd_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(compliance, flags, dirs, (int)n_dirs, g_young, g_beta,
@@ -1241,7 +1183,7 @@ extern "C" int matten_elastic_acoustic_bwd(const double* voigt, const int32_t* f
                                            int64_t n, int64_t n_dirs, double modulus_unit, const double* g_vel,
                                            const double* g_ext, const int32_t* arg, double* g_voigt, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n < 0 || n > 0x7fffffff || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || (g_ext && !arg)) return MATTEN_EINVAL;
+    if (!dir_set_ok(n, 0x7fffffff, n_dirs, 1) || (g_ext && !arg)) return MATTEN_EINVAL;
     if (n == 0) return MATTEN_OK;
     if (!voigt || !flags || !density || !dirs || !g_voigt) return MATTEN_EINVAL;
     elastic_acoustic_bwd_kernel<<<(unsigned)n, DIR_THREADS, 0, stream>>>(voigt, flags, density, dirs, (int)n_dirs, modulus_unit,
@@ -1256,8 +1198,8 @@ extern "C" int matten_elastic_refine(const double* compliance, const int32_t* fl
                                      int64_t max_iter, double* value, double* vec_n, double* vec_m, int32_t* status,
                                      int32_t* iterations, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n < 0 || n > 0x7fffffff / 8 || n_dirs < 1 || n_dirs > 0x7fffffff / 3 || n_angles < 0 || n_angles > 0x7fffffff ||
-        n_dirs * n_angles > 0x7fffffff || !(tol > 0.0) || !(tol <= 1.7976931348623157e308) || max_iter < 0 || max_iter > 0x7fffffff)
+    if (!dir_set_ok(n, 0x7fffffff / 8, n_dirs, n_angles) || !(tol > 0.0) || !(tol <= 1.7976931348623157e308) || max_iter < 0 ||
+        max_iter > 0x7fffffff)
         return MATTEN_EINVAL;
     if (n == 0) return MATTEN_OK;
     if (!compliance || !flags || !dirs || !ext_dir || !arg_dir || !value || !vec_n || !vec_m || !status || !iterations)

@@ -843,6 +843,55 @@ def elastic_props(c, layout: int):
     return voigt, compliance, props, flags
 
 
+def _opt_grad(g, shape, name: str):
+    """an optional fp64 upstream gradient: None stays None (a null pointer for the kernel)"""
+    if g is None:
+        return None
+    g = _need(g, torch.float64, name)
+    if g.shape != shape:
+        raise ValueError(f"{name}: expected {tuple(shape)}, got {tuple(g.shape)}")
+    return g
+
+
+def _ext_grad(g_ext, arg, B: int, n_ext: int, n_arg: int):
+    """the extremes' optional upstream gradient g_ext [B,n_ext] and, with it, the forward's arg [B,n_arg] int32"""
+    g_ext = _opt_grad(g_ext, (B, n_ext), "g_ext")
+    if g_ext is None:
+        return None, None
+    if arg is None:
+        raise ValueError("arg: the extremes' gradient g_ext needs the direction indices the forward returned")
+    arg = _need(arg, torch.int32, "arg")
+    if arg.shape != (B, n_arg):
+        raise ValueError(f"arg: expected {(B, n_arg)}, got {tuple(arg.shape)}")
+    return g_ext, arg
+
+
+_ABSENT = object()
+
+
+def _dir_set_args(matrix, name: str, flags, dirs, density=_ABSENT, cos_sin=_ABSENT):
+    """the inputs the direction-set entries share, checked: ``matrix`` (``name`` = compliance or voigt) [B,6,6], flags [B],
+    dirs [D>=1,3] and, for the entries that take them, density [B] and cos_sin [M>=1,2] -> those tensors (an argument the
+    entry does not take stays as it is), B, D"""
+    matrix = _need(matrix, torch.float64, name)
+    flags = _need(flags, torch.int32, "flags")
+    if density is not _ABSENT:
+        density = _need(density, torch.float64, "density")
+    dirs = _need(dirs, torch.float64, "dirs")
+    if cos_sin is not _ABSENT:
+        cos_sin = _need(cos_sin, torch.float64, "cos_sin")
+    B = flags.shape[0]
+    if (matrix.shape != (B, 6, 6) or (density is not _ABSENT and density.shape != (B,)) or dirs.dim() != 2
+            or dirs.shape[1] != 3 or dirs.shape[0] < 1
+            or (cos_sin is not _ABSENT and (cos_sin.dim() != 2 or cos_sin.shape[1] != 2 or cos_sin.shape[0] < 1))):
+        took = [(f"{name} [B,6,6]", matrix), ("flags [B]", flags), ("density [B]", density), ("dirs [D>=1,3]", dirs),
+                ("cos_sin [M>=1,2]", cos_sin)]
+        took = [(what, t) for what, t in took if t is not _ABSENT]
+        raise ValueError("expected " + ", ".join(what for what, _ in took) + "; got "
+                         + ", ".join(str(tuple(t.shape)) for _, t in took))
+    return matrix, flags, dirs, density, cos_sin, B, dirs.shape[0]
+
+
 def elastic_props_bwd(voigt, compliance, props, flags, g_props, g_voigt, g_compliance, layout: int, dtype):
     """the adjoint of ``elastic_props``: its four outputs and the upstream gradients g_props [B,10], g_voigt [B,6,6] or
     None, g_compliance [B,6,6] or None (fp64; None = zero) -> the gradient of c, [B,81] (layout 0) or [B,36] (layout 1) in
@@ -857,16 +906,12 @@ def elastic_props_bwd(voigt, compliance, props, flags, g_props, g_voigt, g_compl
     props = _need(props, torch.float64, "props")
     flags = _need(flags, torch.int32, "flags")
     g_props = _need(g_props, torch.float64, "g_props")
-    g_voigt = None if g_voigt is None else _need(g_voigt, torch.float64, "g_voigt")
-    g_compliance = None if g_compliance is None else _need(g_compliance, torch.float64, "g_compliance")
     B = flags.shape[0]
-    if (voigt.shape != (B, 6, 6) or compliance.shape != (B, 6, 6) or props.shape != (B, 10) or g_props.shape != (B, 10)
-            or (g_voigt is not None and g_voigt.shape != (B, 6, 6))
-            or (g_compliance is not None and g_compliance.shape != (B, 6, 6))):
-        raise ValueError(f"expected voigt / compliance / g_voigt / g_compliance [B,6,6], props / g_props [B,10], flags [B]; got "
-                         f"{tuple(voigt.shape)}, {tuple(compliance.shape)}, {tuple(props.shape)}, {tuple(flags.shape)}, "
-                         f"{tuple(g_props.shape)}, {None if g_voigt is None else tuple(g_voigt.shape)}, "
-                         f"{None if g_compliance is None else tuple(g_compliance.shape)}")
+    if voigt.shape != (B, 6, 6) or compliance.shape != (B, 6, 6) or props.shape != (B, 10) or g_props.shape != (B, 10):
+        raise ValueError(f"expected voigt / compliance [B,6,6], props / g_props [B,10], flags [B]; got {tuple(voigt.shape)}, "
+                         f"{tuple(compliance.shape)}, {tuple(props.shape)}, {tuple(flags.shape)}, {tuple(g_props.shape)}")
+    g_voigt = _opt_grad(g_voigt, (B, 6, 6), "g_voigt")
+    g_compliance = _opt_grad(g_compliance, (B, 6, 6), "g_compliance")
     g_c = torch.empty(B, (81, 36)[layout], dtype=dtype, device=flags.device)
     _lib.check(lib.matten_elastic_props_bwd(_ptr(voigt), _ptr(compliance), _ptr(props), _ptr(flags), _ptr(g_props),
                                             _ptr(g_voigt), _ptr(g_compliance), int(dtype == torch.float64), layout, B,
@@ -878,14 +923,7 @@ def elastic_directional(compliance, flags, dirs, keep: bool = False):
     """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64 -> (young [B,D] or None, beta [B,D] or
     None, ext [B,4] = E_min, E_max, beta_min, beta_max, arg [B,4] int32) (matten_elastic_directional)"""
     lib = _lib.load()
-    compliance = _need(compliance, torch.float64, "compliance")
-    flags = _need(flags, torch.int32, "flags")
-    dirs = _need(dirs, torch.float64, "dirs")
-    B = flags.shape[0]
-    if compliance.shape != (B, 6, 6) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
-        raise ValueError(f"expected compliance [B,6,6], flags [B], dirs [D>=1,3]; got {tuple(compliance.shape)}, "
-                         f"{tuple(flags.shape)}, {tuple(dirs.shape)}")
-    D = dirs.shape[0]
+    compliance, flags, dirs, _, _, B, D = _dir_set_args(compliance, "compliance", flags, dirs)
     young = torch.empty(B, D, dtype=torch.float64, device=dirs.device) if keep else None
     beta = torch.empty(B, D, dtype=torch.float64, device=dirs.device) if keep else None
     ext = torch.empty(B, 4, dtype=torch.float64, device=dirs.device)
@@ -899,16 +937,8 @@ def elastic_pair(compliance, flags, dirs, cos_sin, keep: bool = False):
     """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64, cos_sin [M,2] fp64 -> (maps [B,D,4] or
     None, ext [B,4] = G_min, G_max, nu_min, nu_max, arg [B,4] int32 = flat pair indices d M + k) (matten_elastic_pair)"""
     lib = _lib.load()
-    compliance = _need(compliance, torch.float64, "compliance")
-    flags = _need(flags, torch.int32, "flags")
-    dirs = _need(dirs, torch.float64, "dirs")
-    cos_sin = _need(cos_sin, torch.float64, "cos_sin")
-    B = flags.shape[0]
-    if (compliance.shape != (B, 6, 6) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1 or cos_sin.dim() != 2
-            or cos_sin.shape[1] != 2 or cos_sin.shape[0] < 1):
-        raise ValueError(f"expected compliance [B,6,6], flags [B], dirs [D>=1,3], cos_sin [M>=1,2]; got "
-                         f"{tuple(compliance.shape)}, {tuple(flags.shape)}, {tuple(dirs.shape)}, {tuple(cos_sin.shape)}")
-    D, M = dirs.shape[0], cos_sin.shape[0]
+    compliance, flags, dirs, _, cos_sin, B, D = _dir_set_args(compliance, "compliance", flags, dirs, cos_sin=cos_sin)
+    M = cos_sin.shape[0]
     maps = torch.empty(B, D, 4, dtype=torch.float64, device=dirs.device) if keep else None
     ext = torch.empty(B, 4, dtype=torch.float64, device=dirs.device)
     arg = torch.empty(B, 4, dtype=torch.int32, device=dirs.device)
@@ -922,15 +952,7 @@ def elastic_acoustic(voigt, flags, density, dirs, modulus_unit: float = 1e9, kee
     per unit of voigt -> (vel [B,D,3] or None, ext [B,3] = v_slow_min, v_fast_max, sum of v^-3, arg [B,2] int32,
     n_unstable [B] int32) (matten_elastic_acoustic)"""
     lib = _lib.load()
-    voigt = _need(voigt, torch.float64, "voigt")
-    flags = _need(flags, torch.int32, "flags")
-    density = _need(density, torch.float64, "density")
-    dirs = _need(dirs, torch.float64, "dirs")
-    B = flags.shape[0]
-    if voigt.shape != (B, 6, 6) or density.shape != (B,) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
-        raise ValueError(f"expected voigt [B,6,6], flags [B], density [B], dirs [D>=1,3]; got {tuple(voigt.shape)}, "
-                         f"{tuple(flags.shape)}, {tuple(density.shape)}, {tuple(dirs.shape)}")
-    D = dirs.shape[0]
+    voigt, flags, dirs, density, _, B, D = _dir_set_args(voigt, "voigt", flags, dirs, density=density)
     vel = torch.empty(B, D, 3, dtype=torch.float64, device=dirs.device) if keep else None
     ext = torch.empty(B, 3, dtype=torch.float64, device=dirs.device)
     arg = torch.empty(B, 2, dtype=torch.int32, device=dirs.device)
@@ -948,17 +970,11 @@ def elastic_refine(compliance, flags, dirs, ext_dir, arg_dir, cos_sin=None, ext_
     [Q,B] int32), Q = 4 (E_min, E_max, beta_min, beta_max) or 8 (then G_min, G_max, nu_min, nu_max)
     (matten_elastic_refine)"""
     lib = _lib.load()
-    compliance = _need(compliance, torch.float64, "compliance")
-    flags = _need(flags, torch.int32, "flags")
-    dirs = _need(dirs, torch.float64, "dirs")
+    compliance, flags, dirs, _, _, B, D = _dir_set_args(compliance, "compliance", flags, dirs)
     ext_dir = _need(ext_dir, torch.float64, "ext_dir")
     arg_dir = _need(arg_dir, torch.int32, "arg_dir")
-    B = flags.shape[0]
-    if (compliance.shape != (B, 6, 6) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1 or ext_dir.shape != (B, 4)
-            or arg_dir.shape != (B, 4)):
-        raise ValueError(f"expected compliance [B,6,6], flags [B], dirs [D>=1,3], ext_dir / arg_dir [B,4]; got "
-                         f"{tuple(compliance.shape)}, {tuple(flags.shape)}, {tuple(dirs.shape)}, {tuple(ext_dir.shape)}, "
-                         f"{tuple(arg_dir.shape)}")
+    if ext_dir.shape != (B, 4) or arg_dir.shape != (B, 4):
+        raise ValueError(f"expected ext_dir / arg_dir [B,4]; got {tuple(ext_dir.shape)}, {tuple(arg_dir.shape)}")
     pair = (cos_sin is not None, ext_pair is not None, arg_pair is not None)
     if any(pair) != all(pair):
         raise ValueError("cos_sin, ext_pair and arg_pair go together: all three or none")
@@ -971,7 +987,7 @@ def elastic_refine(compliance, flags, dirs, ext_dir, arg_dir, cos_sin=None, ext_
             raise ValueError(f"expected cos_sin [M>=1,2], ext_pair / arg_pair [B,4]; got {tuple(cos_sin.shape)}, "
                              f"{tuple(ext_pair.shape)}, {tuple(arg_pair.shape)}")
         M = cos_sin.shape[0]
-    D, Q = dirs.shape[0], 8 if M else 4
+    Q = 8 if M else 4
     value = torch.empty(Q, B, dtype=torch.float64, device=dirs.device)
     vec_n = torch.empty(Q, B, 3, dtype=torch.float64, device=dirs.device)
     vec_m = torch.empty(Q, B, 3, dtype=torch.float64, device=dirs.device)
@@ -984,40 +1000,15 @@ def elastic_refine(compliance, flags, dirs, ext_dir, arg_dir, cos_sin=None, ext_
     return value, vec_n, vec_m, status, iterations
 
 
-def _opt_grad(g, shape, name: str):
-    """an optional fp64 upstream gradient: None stays None (a null pointer for the kernel)"""
-    if g is None:
-        return None
-    g = _need(g, torch.float64, name)
-    if g.shape != shape:
-        raise ValueError(f"{name}: expected {tuple(shape)}, got {tuple(g.shape)}")
-    return g
-
-
 def elastic_directional_bwd(compliance, flags, dirs, g_young=None, g_beta=None, g_ext=None, arg=None) -> torch.Tensor:
     """the adjoint of ``elastic_directional``: its inputs, the upstream gradients g_young / g_beta [B,D] and g_ext [B,4] (fp64;
     None = zero) and the forward's arg [B,4] int32 (needed with g_ext) -> the gradient of compliance [B,6,6]; rows with
     flag bit 0 are zero (matten_elastic_directional_bwd)"""
     lib = _lib.load()
-    compliance = _need(compliance, torch.float64, "compliance")
-    flags = _need(flags, torch.int32, "flags")
-    dirs = _need(dirs, torch.float64, "dirs")
-    B = flags.shape[0]
-    if compliance.shape != (B, 6, 6) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
-        raise ValueError(f"expected compliance [B,6,6], flags [B], dirs [D>=1,3]; got {tuple(compliance.shape)}, "
-                         f"{tuple(flags.shape)}, {tuple(dirs.shape)}")
-    D = dirs.shape[0]
+    compliance, flags, dirs, _, _, B, D = _dir_set_args(compliance, "compliance", flags, dirs)
     g_young = _opt_grad(g_young, (B, D), "g_young")
     g_beta = _opt_grad(g_beta, (B, D), "g_beta")
-    g_ext = _opt_grad(g_ext, (B, 4), "g_ext")
-    if g_ext is not None:
-        if arg is None:
-            raise ValueError("arg: the extremes' gradient g_ext needs the direction indices the forward returned")
-        arg = _need(arg, torch.int32, "arg")
-        if arg.shape != (B, 4):
-            raise ValueError(f"arg: expected {(B, 4)}, got {tuple(arg.shape)}")
-    else:
-        arg = None
+    g_ext, arg = _ext_grad(g_ext, arg, B, 4, 4)
     g_compliance = torch.empty(B, 6, 6, dtype=torch.float64, device=dirs.device)
     _lib.check(lib.matten_elastic_directional_bwd(_ptr(compliance), _ptr(flags), _ptr(dirs), B, D, _ptr(g_young), _ptr(g_beta),
                                                   _ptr(g_ext), _ptr(arg), _ptr(g_compliance), _stream()),
@@ -1031,25 +1022,9 @@ def elastic_acoustic_bwd(voigt, flags, density, dirs, modulus_unit: float = 1e9,
     voigt [B,6,6]; rows with flag bit 0 or a bad density are zero, unstable directions add nothing
     (matten_elastic_acoustic_bwd)"""
     lib = _lib.load()
-    voigt = _need(voigt, torch.float64, "voigt")
-    flags = _need(flags, torch.int32, "flags")
-    density = _need(density, torch.float64, "density")
-    dirs = _need(dirs, torch.float64, "dirs")
-    B = flags.shape[0]
-    if voigt.shape != (B, 6, 6) or density.shape != (B,) or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
-        raise ValueError(f"expected voigt [B,6,6], flags [B], density [B], dirs [D>=1,3]; got {tuple(voigt.shape)}, "
-                         f"{tuple(flags.shape)}, {tuple(density.shape)}, {tuple(dirs.shape)}")
-    D = dirs.shape[0]
+    voigt, flags, dirs, density, _, B, D = _dir_set_args(voigt, "voigt", flags, dirs, density=density)
     g_vel = _opt_grad(g_vel, (B, D, 3), "g_vel")
-    g_ext = _opt_grad(g_ext, (B, 3), "g_ext")
-    if g_ext is not None:
-        if arg is None:
-            raise ValueError("arg: the extremes' gradient g_ext needs the direction indices the forward returned")
-        arg = _need(arg, torch.int32, "arg")
-        if arg.shape != (B, 2):
-            raise ValueError(f"arg: expected {(B, 2)}, got {tuple(arg.shape)}")
-    else:
-        arg = None
+    g_ext, arg = _ext_grad(g_ext, arg, B, 3, 2)
     g_voigt = torch.empty(B, 6, 6, dtype=torch.float64, device=dirs.device)
     _lib.check(lib.matten_elastic_acoustic_bwd(_ptr(voigt), _ptr(flags), _ptr(density), _ptr(dirs), B, D, float(modulus_unit),
                                                _ptr(g_vel), _ptr(g_ext), _ptr(arg), _ptr(g_voigt), _stream()),

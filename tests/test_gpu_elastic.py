@@ -389,6 +389,39 @@ def test_duplicated_directions_resolve_to_the_lowest_index(fixture_set):
         assert (same[k] == 0).all(), k
 
 
+def _directional_of_identity(dirs):
+    """ops.elastic_directional(keep=True) of two unflagged crystals whose compliance is the 6x6 identity"""
+    from matten_amd import ops
+    S = torch.eye(6, dtype=torch.float64, device=DEV).repeat(2, 1, 1)
+    flags = torch.zeros(2, dtype=torch.int32, device=DEV)
+    return [t.cpu().numpy() for t in ops.elastic_directional(S, flags, torch.from_numpy(dirs).to(DEV), keep=True)]
+
+
+@pytest.mark.parametrize("D", [1, 65, 257])
+def test_directional_without_a_comparable_value_keeps_the_sentinel(D):
+    """An unflagged row of which no direction gives a comparable value (every direction NaN): the maps are NaN and the
+    extremes are what the reduction started from, +-inf with the index 0x7fffffff -- not the NaN / -1 that the pair and
+    the acoustic kernel write in this corner.  The expectation is read from the kernel's code (a NaN candidate fails
+    both comparisons of `better`, so no lane, wave or workgroup merge replaces the start value) and was confirmed on the
+    build before the reduction moved into block_best, which gives exactly these values: they are that build's output."""
+    young, beta, ext, arg = _directional_of_identity(np.full((D, 3), np.nan))
+    assert young.shape == beta.shape == (2, D) and np.isnan(young).all() and np.isnan(beta).all()
+    assert np.array_equal(ext, np.tile([np.inf, -np.inf, np.inf, -np.inf], (2, 1)))
+    assert arg.dtype == np.int32 and (arg == 2147483647).all()
+
+
+def test_directional_lone_comparable_value_in_the_second_wave():
+    """D = 65, every direction NaN but the last, (0, 0, 1): lane 0 of the second wave holds the only candidate, so all
+    four extremes reach the output through the cross-wave merge in LDS.  With S = 1: 1 / E = v . v = 1 and beta = the
+    first three entries of v summed = 1, exactly."""
+    dirs = np.full((65, 3), np.nan)
+    dirs[64] = (0.0, 0.0, 1.0)
+    young, beta, ext, arg = _directional_of_identity(dirs)
+    assert np.isnan(young[:, :64]).all() and np.isnan(beta[:, :64]).all()
+    assert (young[:, 64] == 1.0).all() and (beta[:, 64] == 1.0).all()
+    assert np.array_equal(ext, np.ones((2, 4))) and np.array_equal(arg, np.full((2, 4), 64))
+
+
 def test_from_irreps_matches_the_cartesian_route(fixture_set):
     """Both routes run the same 21-term fp32 dot product per entry (ops.dense_rows) with basis values that are the same
     fp64 numbers rounded to fp32: voigt_basis copies columns of the Cartesian basis.  The Voigt route keeps ONE of the
