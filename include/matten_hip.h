@@ -121,6 +121,23 @@ int matten_edge_geom(const float* pos, const int64_t* edge_index, const float* e
                      int64_t n_edges, int64_t n_nodes, int lmax, int n_basis, float r_start, float r_end,
                      float* geom_sorted, float* sh_sorted, int sh_stride, float* edge_vectors, float* edge_lengths,
                      float* edge_attrs, float* edge_embedding, matten_stream_t stream);
+/* Adjoint of matten_edge_geom w.r.t. positions and cells (the reference differentiates with_edge_vectors,
+ * nn/_nequip.py:214-268, and o3.SphericalHarmonics, nn/_nequip.py:167-174, by autograd).  Per sorted edge e, with
+ * n = v / max(r, 1e-12) from geom_sorted:
+ *   dn   = J(n)^T dy[e, 1:]          J: the polynomial derivative of the harmonics (column 0 contributes nothing)
+ *   dv_e = dlen[e] n + (dn - (n . dn) n) / max(r, 1e-12)                   (dv_e = 0 where r < 1e-12)
+ * then, in a fixed order and without atomics,
+ *   dpos[a]      = sum_{e in [rowptr[a], rowptr[a+1])} dv_e - sum_{t in [out_ptr[a], out_ptr[a+1])} dv_{out_perm[t]}
+ *   dcell[b,k,:] = sum over the crystal's sorted edges, ascending, of edge_cell_shift[perm[e], k] dv_e
+ * (out_ptr / out_perm: the source-keyed CSR of matten_tp_backward_lit).  A crystal's edges are the contiguous range
+ * rowptr[ptr[b]] .. rowptr[ptr[b+1]] (ptr [n_cells+1] int64: first atom of every crystal); with n_cells == 1 the range
+ * is every edge and ptr may be NULL.  dy [E, sh_stride] and dlen [E] are the sums over all conv layers; either may be
+ * NULL.  dcell may be NULL (then edge_cell_shift, perm, ptr are not read: open structures have no shift term).
+ * dv [E,4] is caller-owned scratch.  n_edges == 0 zeroes dpos [n_nodes,3] and dcell [n_cells,3,3].  Nothing synchronises. */
+int matten_edge_geom_bwd(const float* geom_sorted, const float* dy, int64_t sh_stride, const float* dlen, int lmax,
+                         int64_t n_edges, int64_t n_nodes, const int32_t* rowptr, const int32_t* out_ptr,
+                         const int32_t* out_perm, const int32_t* perm, const float* edge_cell_shift, int64_t n_cells,
+                         const int64_t* ptr, float* dv, float* dpos, float* dcell, matten_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Radial MLP: e3nn FullyConnectedNet([nb, h, h, W], act=silu) applied to the Bessel embedding
@@ -347,6 +364,17 @@ int matten_radial_mlp_bwd_deep(const float* geom_sorted, int64_t n_edges, int n_
                                int w_pad, int w_cols, const void* dw, int64_t dw_ld, int dw_is_bf16, float* h2_scratch,
                                float* part_small, float* part_w2, float scale0, float scale1, float scale2,
                                float* grad_small, float* grad_w2, matten_stream_t stream);
+/* Adjoint of the radial MLP w.r.t. its INPUT, the edge length (the reference differentiates soft_one_hot_linspace,
+ * nn/embedding.py:185-199, and FullyConnectedNet, nn/utils.py:246-251,260, by autograd).  One entry for every depth:
+ * w_mid [n_mid,32,32], n_mid = 0 .. 3 (NULL at 0); the packed layers as matten_radial_mlp_deep takes them; dw as above.
+ *   dlen[e] = sum_k dL/demb[e,k] b_k'(r_e),   b_k(r) = sqrt(2/c) sqrt(nb) sin((k+1) pi x / c) / x,  x = r - r_start,
+ *   c = r_end - r_start;  b_k' = 0 where b_k is (x <= 0 or x >= c)
+ * dL/demb comes from dw back through the last layer (the same dw W2p^T stage on the matrix cores as the weight
+ * adjoint), the silu layers (recomputed from r) and the first layer.  dlen [E] fp32, every element written. */
+int matten_radial_mlp_bwd_len(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                              const float* w0p, int nb_pad, const float* w_mid, int n_mid, const float* w2p, int hidden,
+                              int w_pad, int w_cols, const void* dw, int64_t dw_ld, int dw_is_bf16, float* dlen,
+                              matten_stream_t stream);
 /* the raw layers (w0 [nb,32], w1 [32,32], w2 [32,W]) -> packed operands w0p = scale0 w0 (rows padded to nb_pad),
  * w1p = scale1 w1, w2p = scale2 w2 (columns padded to w_pad), one launch; matten_radial_mlp_bwd multiplies its partial
  * sums by the same three factors, so they are gradients w.r.t. the RAW layers */
@@ -593,6 +621,20 @@ int matten_tp_backward_lit_wfree(const float* x, int64_t d_in, const uint16_t* h
  * coupling code (about half the registers, twice the resident waves). */
 /* lds_floats (2048 .. 15360): floats of LDS per workgroup for its [edge][path][column] weight tile; a block whose paths do not
  * fit takes them in rounds (plan.bw_wfree_lds_floats = what the widest block needs in one round, capped at 4096). */
+/* The third adjoint of the 'uvu' product (nn/utils.py:230-237,263, differentiated by autograd in the reference), w.r.t. the
+ * edge harmonics:
+ *   dy[e, l2^2 + j] = norm(dst_e) * sum_paths p sum_u w[e, w_off_p + u]
+ *                       * sum_{i,k} C^{l1 l2 l3}_{ijk} x[src_e, x_off + u*D1 + i] * g_agg[dst_e, out_off_p + u*D3 + k]
+ * with the same blocks / paths tables, the same scaled literals and the same max_l instantiations as
+ * matten_tp_backward_lit.  A launch row owns the whole edge (lanes = channels, max_mul = the widest block's channel count
+ * sizes them; wider blocks loop), one fixed-order cross-lane sum per edge, no atomics: bitwise reproducible.
+ * dy [E, sh_stride] fp32, every column of every row written (zeros from (max_l <= 2 ? 9 : 25) on, and in the columns of
+ * degrees no path reads); sh_stride >= that count.  w_edge fp32, or bf16 when edge_is_bf16. */
+int matten_tp_backward_sh(const float* x, int64_t d_in, const void* w_edge, int64_t w_ld, const int32_t* src_sorted,
+                          const int32_t* dst_sorted, const int32_t* blocks, int64_t n_blocks, int64_t max_mul,
+                          const int32_t* paths, int64_t n_paths, const float* g_agg, int64_t d_mid, float avg_num_neighbors,
+                          const float* num_neigh, int64_t n_edges, int edge_is_bf16, float* dy, int64_t sh_stride, int max_l,
+                          matten_stream_t stream);
 
 /* adjoint of matten_species_linear w.r.t. the packed weights (the adjoint w.r.t. x is matten_species_linear
  * itself with the transposed segment table and transposed packed weights):

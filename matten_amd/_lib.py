@@ -78,6 +78,11 @@ SIGNATURES = {
                                        P, c_int64, P, P, c_int64, c_int, c_int64, P, P, P, c_int, P]),
     "matten_tp_backward_lit_wfree": (c_int, [P, c_int64, P, P, P, P, c_int64, P, P, P, c_int64, c_int64, P, c_int64, P, c_int64, c_float,
                                              P, c_int64, P, P, c_int64, c_int, c_int64, P, P, P, c_int64, c_int, c_int, P]),
+    "matten_tp_backward_sh": (c_int, [P, c_int64, P, c_int64, P, P, P, c_int64, c_int64, P, c_int64, P, c_int64, c_float, P, c_int64,
+                                      c_int, P, c_int64, c_int, P]),
+    "matten_radial_mlp_bwd_len": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, P, c_int, c_int, c_int, P,
+                                          c_int64, c_int, P, P]),
+    "matten_edge_geom_bwd": (c_int, [P, P, c_int64, P, c_int, c_int64, c_int64, P, P, P, P, P, c_int64, P, P, P, P, P]),
     "matten_adam_step": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, c_float, P]),
     "matten_adam_ctl_workspace_bytes": (c_size_t, [c_int64]),
     "matten_adam_step_ctl": (c_int, [P, P, P, P, P, c_int64, P, P, P, P, c_size_t, c_float, c_float, c_float, c_float, c_float,

@@ -135,8 +135,50 @@ class RadialMLPFn(torch.autograd.Function):
     def backward(ctx, g):
         geom, w0p, w1p, w2p = ctx.saved_tensors
         mod = ctx.mod
-        grads = _radial_mlp_bwd(mod, geom, ctx.rbf, w0p, w1p, w2p, g.contiguous(), mod.pack_scales())
-        return (None, None, None, None, None) + grads
+        g = g.contiguous()
+        dgeom = None
+        if ctx.needs_input_grad[1]:
+            # geometry gradients: only the length column of geom_sorted feeds the MLP (matten_radial_mlp_bwd_len)
+            dgeom = torch.zeros_like(geom)
+            dgeom[:, 3] = ops.radial_mlp_bwd_len(geom, *ctx.rbf, w0p, w1p, w2p, mod.hs[-1], g)
+        if any(ctx.needs_input_grad[5:]):
+            grads = _radial_mlp_bwd(mod, geom, ctx.rbf, w0p, w1p, w2p, g, mod.pack_scales())
+        else:   # every layer frozen (saliency)
+            grads = (None,) * (len(ctx.needs_input_grad) - 5)
+        return (None, dgeom, None, None, None) + grads
+
+
+class EdgeGeomFn(torch.autograd.Function):
+    """(geom_sorted, sh_sorted) = matten_edge_geom(pos, cell) with its adjoint kernel (matten_edge_geom_bwd): gradients
+    for positions and cells.  ``graph`` = (edge_index, edge_cell_shift, batch, perm, rowptr, (out_ptr, out_perm), ptr);
+    the requested original-order tensors (edge_vectors, ...) land in ``extras`` and carry no gradient.  The backward
+    receives the sums over all conv layers of dL/dgeom (only its length column is ever non-zero) and dL/dsh.  Once
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, pos, cell, graph, lmax, rbf, wants, extras):
+        edge_index, shift, batch, perm, rowptr, out_csr, ptr = graph
+        out = ops.edge_geom(pos, edge_index, shift, cell, batch, perm, lmax, *rbf, **wants)
+        geom, sh = out.pop("geom_sorted"), out.pop("sh_sorted")
+        extras.update(out)
+        ctx.graph, ctx.lmax, ctx.n_nodes = (shift, perm, rowptr, out_csr, ptr), lmax, pos.shape[0]
+        ctx.cell_shape = None if cell is None else cell.shape
+        ctx.save_for_backward(geom)
+        ctx.set_materialize_grads(False)
+        return geom, sh
+
+    @staticmethod
+    def backward(ctx, dgeom, dsh):
+        (geom,) = ctx.saved_tensors
+        shift, perm, rowptr, out_csr, ptr = ctx.graph
+        want_cell = ctx.cell_shape is not None and ctx.needs_input_grad[1]
+        n_cells = ctx.cell_shape.numel() // 9 if want_cell else 0   # (ops.edge_geom reads the cells as [-1, 3, 3])
+        dlen = None if dgeom is None else dgeom[:, 3].contiguous()
+        dpos, dcell = ops.edge_geom_bwd(geom, None if dsh is None else dsh.contiguous(), dlen, ctx.lmax, ctx.n_nodes, rowptr,
+                                        out_csr, perm, shift if want_cell else None, n_cells, ptr)
+        if dcell is not None:
+            dcell = dcell.reshape(ctx.cell_shape)
+        return dpos, dcell, None, None, None, None, None
 
 
 # training forward: batches below this many nodes walk their CSR segments in pieces (see TensorProductScatterFn.forward)
@@ -144,18 +186,20 @@ TRAIN_HUB_SPLIT_MAX_ROWS = int(os.environ.get("MATTEN_HUB_SPLIT_MAX_ROWS_TRAIN",
 
 
 class TensorProductScatterFn(torch.autograd.Function):
-    """agg = sum_{edges -> n} uvu(x[src], Y, w) * norm   with w[E,W] in the reference column order."""
+    """agg = sum_{edges -> n} uvu(x[src], Y, w) * norm   with w[E,W] in the reference column order.  Y (``sh``, the batch's
+    harmonics) is an input: when it requires grad (geometry gradients) the backward returns dL/dY as well
+    (matten_tp_backward_sh); autograd adds the conv layers' contributions."""
 
     @staticmethod
-    def forward(ctx, x, w_edge, mod, data, avg, num_neigh):
+    def forward(ctx, x, w_edge, sh, mod, data, avg, num_neigh):
         from .data.irreps import DataKey
 
         dev = x.device
         p = mod.plan
         ctx.mod, ctx.avg, ctx.num_neigh = mod, avg, num_neigh
-        ctx.graph = (data[DataKey.AMD_SH], data[DataKey.AMD_SRC], data["_amd_dst_sorted"])
+        ctx.graph = (data[DataKey.AMD_SRC], data["_amd_dst_sorted"])
         ctx.out_csr = data.get("_amd_out_csr")
-        ctx.save_for_backward(x, w_edge)
+        ctx.save_for_backward(x, w_edge, sh)   # sh: the batch's harmonics, an input so that autograd sees the dependency
         # the forward walks a destination node's CSR segment serially: irregular batches (real crystals: 30 neighbours on
         # average, 80 in the one-atom cells) are cut into pieces of <= HUB_SPLIT_LEN edges and summed in order afterwards,
         # like the inference forward of small batches (nn/utils.py); the adjoint is per edge and does not care
@@ -169,17 +213,25 @@ class TensorProductScatterFn(torch.autograd.Function):
             if split is None or split[3] is not rowptr:
                 split = ops.csr_split(rowptr, data[DataKey.AMD_SRC].shape[0], nnu.HUB_SPLIT_LEN, num_neigh) + (rowptr,)
                 data[key] = split
-        agg = ops.tp_paths(x, w_edge, data[DataKey.AMD_SH], rowptr if split is None else split[0], data[DataKey.AMD_SRC],
+        agg = ops.tp_paths(x, w_edge, sh, rowptr if split is None else split[0], data[DataKey.AMD_SRC],
                            mod._tables.get("entries", dev), mod._tables.get("unit_start", dev), p.units_per_tile,
                            p.d_mid, avg, num_neigh if split is None else split[2])
         return agg if split is None else ops.segment_reduce(agg, split[1], mean=False)
 
     @staticmethod
     def backward(ctx, g):
-        x, w_edge = ctx.saved_tensors
+        x, w_edge, sh = ctx.saved_tensors
         mod, dev = ctx.mod, g.device
-        sh, src, dst = ctx.graph
+        src, dst = ctx.graph
         impl = os.environ.get("MATTEN_TP_BWD", "lit")   # "lit": literal-coefficient kernel; "table": the table-driven ones
+        dsh = None
+        if ctx.needs_input_grad[2]:   # geometry gradients: the third adjoint, on the tables of the literal kernel
+            if impl != "lit":
+                raise NotImplementedError("MATTEN_TP_BWD=table has no adjoint for the edge harmonics: geometry gradients "
+                                          "need MATTEN_TP_BWD=lit (the default)")
+            dsh = ops.tp_backward_sh(x, w_edge, src, dst, mod._tables.get("bw_blocks", dev), mod._tables.get("bw_paths", dev),
+                                     mod.plan.bw_max_mul, g.contiguous(), ctx.avg, ctx.num_neigh, max_l=mod.plan.bw_max_l,
+                                     sh_stride=sh.shape[1])
         if impl == "lit":
             # dx summed per source node in a fixed order (MATTEN_TP_BWD_DX=atomic: fp32 atomics, order not fixed)
             out_csr = ctx.out_csr if os.environ.get("MATTEN_TP_BWD_DX", "ordered") != "atomic" else None
@@ -188,13 +240,13 @@ class TensorProductScatterFn(torch.autograd.Function):
                                          ctx.num_neigh, out_csr=out_csr, max_l=mod.plan.bw_max_l,
                                          blocks_cover_input=int(mod.plan.bw_blocks[:, 1].dot(2 * mod.plan.bw_blocks[:, 2] + 1))
                                          == mod.plan.d_in)
-            return dx, dw, None, None, None, None
+            return dx, dw, dsh, None, None, None, None
         dx, dw = ops.tp_backward(x, w_edge, sh, src, dst, mod._tables.get("bw_col_meta", dev),
                                  mod._tables.get("bw_nnz_ijk", dev), mod._tables.get("bw_nnz_c", dev), g.contiguous(),
                                  ctx.avg, ctx.num_neigh,
                                  in_groups=None if os.environ.get("MATTEN_TP_BWD_GROUPED", "1") == "0" else
                                  (mod._tables.get("bw_in_ptr", dev), mod._tables.get("bw_in_cols", dev)))
-        return dx, dw, None, None, None, None
+        return dx, dw, None, None, None, None, None
 
 
 # training on the fused forward: the adjoint re-evaluates w inside its workgroups (0 = matten_radial_mlp writes it for one layer

@@ -1535,6 +1535,149 @@ extern "C" int matten_tp_backward_lit_wfree(const float* x, int64_t d_in, const 
     return MATTEN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// 'uvu' TP adjoint w.r.t. the edge harmonics (geometry gradients), the third adjoint beside dx and dw above:
+//     dY[e, l2^2 + j] = norm(dst_e) * sum_paths sum_u w[e, w_off + u] * s_j,   s_j = sum_ik C_ijk x_i G_k
+// (cg_gen.h CG<l1,l2,l3>::harmonic).  The sum runs over every channel of every input block and every path of ONE edge, so
+// a launch row owns the whole edge: `cu` lanes per edge (the widest block's channels rounded up to a power of two, at
+// most a wave), 64 / cu edges per wave; a lane takes the channels u = lane, lane + cu, ... of each block in turn and
+// keeps (LMAX+1)^2 accumulators across the walk.  One xor-butterfly over the edge's lanes follows (every lane ends with
+// the same bits: each step adds the same two numbers on both sides), then the row is stored whole, zeros behind
+// (LMAX+1)^2.  No atomics; the same tables as tp_backward_lit_kernel.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct ShArgs {
+    const float* x;
+    const void* w_edge;
+    const int32_t* src;
+    const int32_t* dst;
+    const float* g_agg;
+    const float* num_neigh;
+    float* dy;
+    int64_t E;
+    int d_in, w_ld, sh_stride, d_mid, edge_bf16;
+    float avg_nn;
+};
+
+template <int L1, int L2, int L3>
+__device__ __forceinline__ void sh_path(const int4 pth, float wv, int u, const float* __restrict__ x,
+                                        const float* __restrict__ grow, float* __restrict__ acc) {
+    constexpr int D2 = 2 * L2 + 1, D3 = 2 * L3 + 1;
+    float g[D3], s[D2];
+    const float* gp = grow + pth.z + u * D3;
+#pragma unroll
+    for (int k = 0; k < D3; ++k) g[k] = gp[k];
+#pragma unroll
+    for (int j = 0; j < D2; ++j) s[j] = 0.0f;
+    matten::CG<L1, L2, L3>::harmonic(x, g, s);
+#pragma unroll
+    for (int j = 0; j < D2; ++j) acc[L2 * L2 + j] = fmaf(wv, s[j], acc[L2 * L2 + j]);
+}
+
+#undef MATTEN_LIT_CASE
+#define MATTEN_LIT_CASE(L1, L2, L3) \
+    case (L1 * 25 + L2 * 5 + L3): sh_path<L1, L2, L3>(pth, wv, u, x, grow, acc); break;
+
+// the channels u = lu, lu + cu, ... of one input block for one edge, all of the block's paths
+template <int L1, int LMAX>
+__device__ __forceinline__ void sh_block(const ShArgs& a, const int4 blk, const int4* __restrict__ paths, int64_t e, int src,
+                                         const float* __restrict__ grow, int lu, int cu, float* __restrict__ acc) {
+    constexpr int D1 = 2 * L1 + 1;
+    const int p0 = blk.w & 0xffff, np = blk.w >> 16;
+    for (int u = lu; u < blk.y; u += cu) {
+        const float* xp = a.x + (int64_t)src * a.d_in + blk.x + u * D1;
+        float x[D1];
+#pragma unroll
+        for (int i = 0; i < D1; ++i) x[i] = xp[i];
+        for (int p = p0; p < p0 + np; ++p) {
+            const int4 pth = paths[p];
+            const float wv = matten_ld_edge(a.w_edge, e * a.w_ld + pth.y + u, a.edge_bf16);
+            if constexpr (LMAX <= 2) {
+                if constexpr (L1 == 0) { switch (pth.x) { MATTEN_LIT_LIST2_0 default: break; } }
+                if constexpr (L1 == 1) { switch (pth.x) { MATTEN_LIT_LIST2_1 default: break; } }
+                if constexpr (L1 == 2) { switch (pth.x) { MATTEN_LIT_LIST2_2 default: break; } }
+            } else {
+                if constexpr (L1 == 0) { switch (pth.x) { MATTEN_LIT_LIST_0 default: break; } }
+                if constexpr (L1 == 1) { switch (pth.x) { MATTEN_LIT_LIST_1 default: break; } }
+                if constexpr (L1 == 2) { switch (pth.x) { MATTEN_LIT_LIST_2 default: break; } }
+                if constexpr (L1 == 3) { switch (pth.x) { MATTEN_LIT_LIST_3 default: break; } }
+                if constexpr (L1 == 4) { switch (pth.x) { MATTEN_LIT_LIST_4 default: break; } }
+            }
+        }
+    }
+}
+
+template <int LMAX>
+__global__ __launch_bounds__(256) void tp_backward_sh_kernel(ShArgs a, const int4* __restrict__ blocks, int n_blocks,
+                                                             const int4* __restrict__ paths, int cu) {
+    constexpr int SH = (LMAX + 1) * (LMAX + 1);
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e_raw = idx / cu;
+    const int lu = (int)(idx - e_raw * cu);
+    // lanes behind the last edge stay for the butterfly (cu divides 64: an edge's lanes share a wave) and add zeros
+    const bool live = e_raw < a.E;
+    const int64_t e = live ? e_raw : a.E - 1;
+    const int src = a.src[e], dst = a.dst[e];
+    float acc[SH];
+#pragma unroll
+    for (int k = 0; k < SH; ++k) acc[k] = 0.0f;
+    if (live) {
+        const float* grow = a.g_agg + (int64_t)dst * a.d_mid;
+        for (int b = 0; b < n_blocks; ++b) {
+            const int4 blk = blocks[b];
+            switch (blk.z) {   // uniform over the launch
+                case 0: sh_block<0, LMAX>(a, blk, paths, e, src, grow, lu, cu, acc); break;
+                case 1: sh_block<1, LMAX>(a, blk, paths, e, src, grow, lu, cu, acc); break;
+                case 2: sh_block<2, LMAX>(a, blk, paths, e, src, grow, lu, cu, acc); break;
+                case 3: if constexpr (LMAX > 2) sh_block<3, LMAX>(a, blk, paths, e, src, grow, lu, cu, acc); break;
+                case 4: if constexpr (LMAX > 2) sh_block<4, LMAX>(a, blk, paths, e, src, grow, lu, cu, acc); break;
+                default: break;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        if (d < cu) {
+#pragma unroll
+            for (int k = 0; k < SH; ++k) acc[k] += __shfl_xor(acc[k], d, 64);
+        }
+    }
+    if (!live) return;
+    const float norm = 1.0f / sqrtf(a.avg_nn > 0.0f ? a.avg_nn : a.num_neigh[dst]);
+    float* row = a.dy + e * a.sh_stride;
+#pragma unroll
+    for (int k = 0; k < SH; ++k)
+        if (lu == (k & (cu - 1)) && k < a.sh_stride) row[k] = norm * acc[k];
+    for (int k = SH + lu; k < a.sh_stride; k += cu) row[k] = 0.0f;
+}
+#undef MATTEN_LIT_CASE
+}  // namespace
+
+extern "C" int matten_tp_backward_sh(const float* x, int64_t d_in, const void* w_edge, int64_t w_ld, const int32_t* src_sorted,
+                                     const int32_t* dst_sorted, const int32_t* blocks, int64_t n_blocks, int64_t max_mul,
+                                     const int32_t* paths, int64_t n_paths, const float* g_agg, int64_t d_mid,
+                                     float avg_num_neighbors, const float* num_neigh, int64_t n_edges, int edge_is_bf16,
+                                     float* dy, int64_t sh_stride, int max_l, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_edges < 0 || d_in <= 0 || n_blocks <= 0 || n_blocks > 65535 || n_paths <= 0 || d_mid <= 0 || max_mul <= 0 ||
+        w_ld <= 0 || max_l < 0 || max_l > 4 || sh_stride < (max_l <= 2 ? 9 : 25))
+        return MATTEN_EINVAL;
+    if (n_edges == 0) return MATTEN_OK;
+    if (!x || !w_edge || !src_sorted || !dst_sorted || !blocks || !paths || !g_agg || !dy) return MATTEN_EINVAL;
+    if (!(avg_num_neighbors > 0.0f) && !num_neigh) return MATTEN_EINVAL;
+    int cu = 1;   // lanes per edge
+    while (cu < max_mul && cu < 64) cu <<= 1;
+    const int64_t gx = matten_cdiv(n_edges * cu, 256);
+    if (gx >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
+    ShArgs a{x, w_edge, src_sorted, dst_sorted, g_agg, num_neigh, dy, n_edges, (int)d_in, (int)w_ld, (int)sh_stride, (int)d_mid,
+             edge_is_bf16, avg_num_neighbors};
+    if (max_l <= 2) tp_backward_sh_kernel<2><<<(unsigned)gx, 256, 0, stream>>>(a, (const int4*)blocks, (int)n_blocks, (const int4*)paths, cu);
+    else tp_backward_sh_kernel<4><<<(unsigned)gx, 256, 0, stream>>>(a, (const int4*)blocks, (int)n_blocks, (const int4*)paths, cu);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
 // ---- packed[s, j] = weight[gather[s, j]] * scale[j]  (and its adjoint through the inverse permutation) in one launch.
 // The species-indexed linears keep the reference's flat e3nn parameter; every step re-packs 14 of them and maps 14
 // gradients back: as torch index + multiply that was 56 tiny launches per optimisation step.

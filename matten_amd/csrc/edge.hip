@@ -126,7 +126,155 @@ __global__ void species_embed_kernel(const int64_t* __restrict__ Z, int64_t N, c
         for (int64_t c = threadIdx.x; c < S; c += blockDim.x) attrs[n * S + c] = (c == idx) ? 1.0f : 0.0f;
 }
 
+// ---- adjoint of edge_geom_kernel (geometry gradients) -----------------------------------------------------------------
+// per sorted edge: dv = dlen n + (dn - (n . dn) n) / max(r, 1e-12), dn = J(n)^T dY (sh.h real_sh_vjp); r < 1e-12: dv = 0
+template <int LMAX>
+__global__ __launch_bounds__(256) void edge_geom_bwd_edges_kernel(const float4* __restrict__ geom, const float* __restrict__ dy,
+                                                                  int sh_stride, const float* __restrict__ dlen, int64_t E,
+                                                                  float4* __restrict__ dv) {
+    constexpr int SH = (LMAX + 1) * (LMAX + 1);
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const float4 v = geom[e];
+    const float inv = 1.0f / fmaxf(v.w, 1e-12f);
+    const float nx = v.x * inv, ny = v.y * inv, nz = v.z * inv;
+    float ox = 0.0f, oy = 0.0f, oz = 0.0f;
+    if (dy && LMAX > 0) {
+        float d[SH];
+#pragma unroll
+        for (int k = 0; k < SH; ++k) d[k] = dy[e * sh_stride + k];
+        float gx, gy, gz;
+        matten::real_sh_vjp<LMAX>(nx, ny, nz, d, gx, gy, gz);
+        const float t = nx * gx + ny * gy + nz * gz;
+        ox = (gx - t * nx) * inv;
+        oy = (gy - t * ny) * inv;
+        oz = (gz - t * nz) * inv;
+    }
+    if (dlen) {
+        const float dl = dlen[e];
+        ox = fmaf(dl, nx, ox);
+        oy = fmaf(dl, ny, oy);
+        oz = fmaf(dl, nz, oz);
+    }
+    if (v.w < 1e-12f) ox = oy = oz = 0.0f;
+    dv[e] = make_float4(ox, oy, oz, 0.0f);
+}
+
+// dpos[a] = sum of dv over the edges arriving at a (its CSR segment, ascending) - sum over the edges leaving a (in the
+// order of out_perm): one thread per atom, no atomics
+__global__ void edge_geom_bwd_nodes_kernel(const float4* __restrict__ dv, const int32_t* __restrict__ rowptr,
+                                           const int32_t* __restrict__ out_ptr, const int32_t* __restrict__ out_perm,
+                                           int64_t N, int64_t E, float* __restrict__ dpos) {
+    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= N) return;
+    float px = 0.0f, py = 0.0f, pz = 0.0f, mx = 0.0f, my = 0.0f, mz = 0.0f;
+    const int e0 = max(rowptr[a], 0), e1 = (int)min((int64_t)rowptr[a + 1], E);
+    for (int e = e0; e < e1; ++e) {
+        const float4 d = dv[e];
+        px += d.x, py += d.y, pz += d.z;
+    }
+    const int t0 = max(out_ptr[a], 0), t1 = (int)min((int64_t)out_ptr[a + 1], E);
+    for (int t = t0; t < t1; ++t) {
+        int e = out_perm[t];
+        e = e < 0 ? 0 : (e >= E ? (int)E - 1 : e);
+        const float4 d = dv[e];
+        mx += d.x, my += d.y, mz += d.z;
+    }
+    dpos[3 * a + 0] = px - mx;
+    dpos[3 * a + 1] = py - my;
+    dpos[3 * a + 2] = pz - mz;
+}
+
+// dcell[b, k, :] = sum over the crystal's sorted edges of shift[perm[e], k] dv_e: a workgroup per crystal, thread t adds the
+// edges t, t + 256, ... in ascending order, then the threads' sums meet in a fixed tree
+__global__ __launch_bounds__(256) void edge_geom_bwd_cell_kernel(const float4* __restrict__ dv, const float* __restrict__ shift,
+                                                                 const int32_t* __restrict__ perm,
+                                                                 const int32_t* __restrict__ rowptr,
+                                                                 const int64_t* __restrict__ ptr, int64_t n_cells, int64_t N,
+                                                                 int64_t E, float* __restrict__ dcell) {
+    __shared__ float red[9][256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    int64_t e0 = 0, e1 = E;
+    if (n_cells > 1) {
+        int64_t n0 = ptr[b], n1 = ptr[b + 1];
+        n0 = n0 < 0 ? 0 : (n0 > N ? N : n0);
+        n1 = n1 < n0 ? n0 : (n1 > N ? N : n1);
+        e0 = rowptr[n0], e1 = rowptr[n1];
+        e0 = e0 < 0 ? 0 : (e0 > E ? E : e0);
+        e1 = e1 < e0 ? e0 : (e1 > E ? E : e1);
+    }
+    float acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = 0.0f;
+    for (int64_t e = e0 + t; e < e1; e += 256) {
+        int64_t o = perm ? (int64_t)perm[e] : e;
+        o = o < 0 ? 0 : (o >= E ? E - 1 : o);
+        const float4 d = dv[e];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float s = shift[3 * o + k];
+            acc[3 * k + 0] = fmaf(s, d.x, acc[3 * k + 0]);
+            acc[3 * k + 1] = fmaf(s, d.y, acc[3 * k + 1]);
+            acc[3 * k + 2] = fmaf(s, d.z, acc[3 * k + 2]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) red[i][t] = acc[i];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) red[i][t] += red[i][t + o];
+        }
+        __syncthreads();
+    }
+    if (t < 9) dcell[9 * (int64_t)b + t] = red[t][0];
+}
+
 }  // namespace
+
+extern "C" int matten_edge_geom_bwd(const float* geom_sorted, const float* dy, int64_t sh_stride, const float* dlen, int lmax,
+                                    int64_t n_edges, int64_t n_nodes, const int32_t* rowptr, const int32_t* out_ptr,
+                                    const int32_t* out_perm, const int32_t* perm, const float* edge_cell_shift,
+                                    int64_t n_cells, const int64_t* ptr, float* dv, float* dpos, float* dcell,
+                                    matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_edges < 0 || n_nodes < 0 || (n_edges > 0 && n_nodes == 0) || lmax < 0 || lmax > 4 || n_cells < 0 ||
+        n_edges >= ((int64_t)1 << 31) || (dy && sh_stride < (lmax + 1) * (lmax + 1)))
+        return MATTEN_EINVAL;
+    if (dcell && (n_cells < 1 || (n_cells > 1 && !ptr))) return MATTEN_EINVAL;
+    if (n_nodes > 0 && !dpos) return MATTEN_EINVAL;
+    if (n_edges == 0) {
+        if (n_nodes > 0 && hipMemsetAsync(dpos, 0, sizeof(float) * 3 * (size_t)n_nodes, stream) != hipSuccess) return MATTEN_ELAUNCH;
+        if (dcell && hipMemsetAsync(dcell, 0, sizeof(float) * 9 * (size_t)n_cells, stream) != hipSuccess) return MATTEN_ELAUNCH;
+        return MATTEN_OK;
+    }
+    if (!geom_sorted || !rowptr || !out_ptr || !out_perm || !dv || (dcell && !edge_cell_shift)) return MATTEN_EINVAL;
+    const int T = 256;
+    const unsigned grid = (unsigned)matten_cdiv(n_edges, T);
+#define LAUNCH(L)                                                                                                   \
+    edge_geom_bwd_edges_kernel<L><<<grid, T, 0, stream>>>((const float4*)geom_sorted, dy, (int)sh_stride, dlen, n_edges, \
+                                                          (float4*)dv)
+    switch (lmax) {
+        case 0: LAUNCH(0); break;
+        case 1: LAUNCH(1); break;
+        case 2: LAUNCH(2); break;
+        case 3: LAUNCH(3); break;
+        default: LAUNCH(4); break;
+    }
+#undef LAUNCH
+    MATTEN_LAUNCH_CHECK();
+    edge_geom_bwd_nodes_kernel<<<(unsigned)matten_cdiv(n_nodes, T), T, 0, stream>>>((const float4*)dv, rowptr, out_ptr, out_perm,
+                                                                                   n_nodes, n_edges, dpos);
+    MATTEN_LAUNCH_CHECK();
+    if (dcell) {
+        if (n_cells >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
+        edge_geom_bwd_cell_kernel<<<(unsigned)n_cells, T, 0, stream>>>((const float4*)dv, edge_cell_shift, perm, rowptr, ptr,
+                                                                       n_cells, n_nodes, n_edges, dcell);
+        MATTEN_LAUNCH_CHECK();
+    }
+    return MATTEN_OK;
+}
 
 extern "C" int matten_species_embed(const int64_t* atomic_numbers, int64_t n_nodes, const int64_t* z_to_index,
                                     int64_t min_z, int64_t max_z, int64_t n_species, const float* weight,

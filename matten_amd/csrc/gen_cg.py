@@ -11,6 +11,9 @@ Two algebraically equal schedules are costed per triple and the cheaper one is e
     pair form :  p = xw[i]*y[j] once per distinct (i,j);   acc[k] += c * p
     M    form :  M[i][k] = sum_j c*y[j];                    acc[k] += xw[i] * M[i][k]
 
+Every triple also carries the two adjoints of the contraction: `adjoint` (w.r.t. the node features: training) and
+`harmonic` (w.r.t. the edge harmonics: geometry gradients), as the same kind of unrolled literal code.
+
 Run:  python gen_cg.py > cg_gen.h      (deterministic; tests/test_host.py checks the committed file)
 """
 import math
@@ -83,6 +86,23 @@ def emit_triple(l1, l2, l3, out):
         out.append(f"        {{ const float p = y[{j}] * g[{k}];")
         for i, c in terms:
             out.append(f"          t[{i}] = fmaf({lit(c)}, p, t[{i}]);")
+        out.append("        }")
+    out.append("    }")
+    # adjoint w.r.t. the second operand (geometry gradients): s[j] += sum_ik C_ijk x[i] g[k].  With it
+    #   d/dy[j] = w s[j]   for out[k] = w sum_ij C_ijk x[i] y[j]
+    out.append("    static __device__ __forceinline__ void harmonic(const float* __restrict__ x, "
+               "const float* __restrict__ g, float* __restrict__ s) {")
+    ik = sorted({(i, k) for i, _, k, _ in nz})
+    for (i, k) in ik:
+        terms = [(j, c) for (ii, j, kk, c) in nz if ii == i and kk == k]
+        if len(terms) == 1 and abs(abs(terms[0][1]) - 1.0) < 1e-12:
+            j, c = terms[0]
+            sign = "" if c > 0 else "-"
+            out.append(f"        s[{j}] = fmaf({sign}x[{i}], g[{k}], s[{j}]);")
+            continue
+        out.append(f"        {{ const float p = x[{i}] * g[{k}];")
+        for j, c in terms:
+            out.append(f"          s[{j}] = fmaf({lit(c)}, p, s[{j}]);")
         out.append("        }")
     out.append("    }")
     out.append("};")

@@ -159,12 +159,30 @@ __device__ __forceinline__ void store_small(float* out, const f32x4 (&g_w0)[2], 
     }
 }
 
+// d/dr of matten::bessel_basis (sh.h): b_k = A sin(a x) / x, a = (k+1) pi / c  ->  b_k' = A a^2 (t cos t - sin t) / t^2, t = a x
+// (below t = 0.5 the difference cancels: its series -t/3 + t^3/30 - t^5/840 + t^7/45360, next term < 5e-10); 0 where b_k is
+__device__ __forceinline__ float bessel_basis_dr(float len, int k, int n_basis, float r_start, float r_end) {
+    const float xr = len - r_start;
+    const float c = r_end - r_start;
+    const bool in = (xr / c < 1.0f) && (0.0f < xr);
+    const float a = (float)(k + 1) * 3.14159265358979323846f / c;
+    const float t = (float)(k + 1) * 3.14159265358979323846f * xr / c;
+    const float t2 = t * t;
+    const float f = t < 0.5f ? t * (-1.0f / 3.0f + t2 * (1.0f / 30.0f + t2 * (-1.0f / 840.0f + t2 * (1.0f / 45360.0f))))
+                             : (t * cosf(t) - sinf(t)) / t2;
+    return in ? sqrtf(2.0f / c) * sqrtf((float)n_basis) * a * a * f : 0.0f;
+}
+
 // part_small[wave slice][nb_pad*32 (dW0p) + N_MID*32*32 (dWm_p)]
-template <int KS0, bool BF16, int N_MID>
+// LEN: the adjoint w.r.t. the MLP's INPUT instead of its weights (matten_radial_mlp_bwd_len): the same recomputation, the
+// same dw W2p^T stage and chain down to dz_0; then dL/demb = W0p dz_0 (one more matrix step, the D registers as the B
+// operand again) and dlen[e] = sum_k dL/demb[k] b_k'(r_e).  No weight gradients, no h2 scratch, no partial sums.
+template <int KS0, bool BF16, int N_MID, bool LEN = false>
 __global__ __launch_bounds__(BW_WAVES * 64) void radial_mlp_bwd_edges(
     const float4* __restrict__ geom, int64_t E, int n_basis, float r_start, float r_end, const float* __restrict__ w0p,
     const float* __restrict__ w_mid, const float* __restrict__ w2p, int w_pad, int w_cols, const void* __restrict__ dw,
-    int64_t dw_ld, float* __restrict__ h2_out, float* __restrict__ part_small, int tiles_per_wave, float s0, float s1) {
+    int64_t dw_ld, float* __restrict__ h2_out, float* __restrict__ part_small, int tiles_per_wave, float s0, float s1,
+    float* __restrict__ dlen = nullptr) {
     __shared__ float lds[BW_WAVES][(3 * HID + 16) * TS];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -193,6 +211,11 @@ __global__ __launch_bounds__(BW_WAVES * 64) void radial_mlp_bwd_edges(
             a1t[m][0][kk] = w1p[c * HID + k];                    // adjoint:  A[m = in c][K = out k]
             a1t[m][1][kk] = w1p[(16 + c) * HID + k];
         }
+    }
+    float a0t[LEN ? 8 : 1];   // LEN: A[m = basis c][K = hidden pi(kk, g)] of dL/demb = W0p dz_0
+    if constexpr (LEN) {
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) a0t[kk] = c < 4 * KS0 ? w0p[c * HID + 16 * (kk >> 2) + 4 * g + (kk & 3)] : 0.0f;
     }
     // dWm_p[m-tile over in][n-tile over out] per middle layer, dW0p[n-tile over hidden] (rows = basis index)
     f32x4 g_w1[nm1(N_MID)][2][2], g_w0[2];
@@ -241,7 +264,7 @@ __global__ __launch_bounds__(BW_WAVES * 64) void radial_mlp_bwd_edges(
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) h2[t][r] = silu(z[N_MID][t][r]);
-        if (e_ok) {   // h2[e, 16 t + 4 g + r]: four consecutive floats per tile
+        if (!LEN && e_ok) {   // h2[e, 16 t + 4 g + r]: four consecutive floats per tile
             *reinterpret_cast<f32x4*>(h2_out + e * HID + 4 * g) = h2[0];
             *reinterpret_cast<f32x4*>(h2_out + e * HID + 16 + 4 * g) = h2[1];
         }
@@ -277,10 +300,28 @@ __global__ __launch_bounds__(BW_WAVES * 64) void radial_mlp_bwd_edges(
                 }
             }
         }
+        if constexpr (LEN) {
+            // ---- dL/demb[k = 4 g + r][edge c], then this lane's four basis functions; the four lane groups add up ----
+            f32x4 de = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk)
+                de = __builtin_amdgcn_mfma_f32_16x16x4f32(a0t[kk], dz[0][kk >> 2][kk & 3], de, 0, 0, 0);
+            float dl = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * g + r;
+                if (k < n_basis) dl = fmaf(de[r], bessel_basis_dr(len, k, n_basis, r_start, r_end), dl);
+            }
+            dl += __shfl_xor(dl, 16, 64);
+            dl += __shfl_xor(dl, 32, 64);
+            if (g == 0 && e_ok) dlen[e] = dl;
+            continue;
+        }
         // ---- the small weight gradients: contraction over the tile's 16 edges, operands through LDS ----
         small_grads_tile<KS0, N_MID>(t_h1, t_dz2, t_dz1, t_b, h, dz, bes, g, c, g_w1, g_w0);
         __builtin_amdgcn_wave_barrier();
     }
+    if constexpr (LEN) return;
     const int nb_pad = 4 * KS0;
     store_small<KS0, N_MID>(part_small + slice * (int64_t)(nb_pad * HID + N_MID * HID * HID), g_w0, g_w1, g, c, s0, s1);
 }
@@ -694,6 +735,45 @@ extern "C" int matten_radial_mlp_bwd_deep(const float* geom_sorted, int64_t n_ed
     return radial_mlp_bwd_launch(geom_sorted, n_edges, n_basis, r_start, r_end, w0p, nb_pad, w_mid, n_mid, w2p, hidden,
                                  w_pad, w_cols, dw, dw_ld, dw_is_bf16, h2_scratch, part_small, part_w2, scale0, scale1,
                                  scale2, grad_small, grad_w2, stream_);
+}
+
+// adjoint w.r.t. the edge length: radial_mlp_bwd_edges in its LEN form, every depth through one entry
+extern "C" int matten_radial_mlp_bwd_len(const float* geom_sorted, int64_t n_edges, int n_basis, float r_start, float r_end,
+                                         const float* w0p, int nb_pad, const float* w_mid, int n_mid, const float* w2p,
+                                         int hidden, int w_pad, int w_cols, const void* dw, int64_t dw_ld, int dw_is_bf16,
+                                         float* dlen, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_edges < 0 || hidden != HID || (w_pad & 15) || w_pad <= 0 || w_cols <= 0 || w_cols > w_pad || (nb_pad & 3) ||
+        nb_pad < n_basis || nb_pad <= 0 || nb_pad > 16 || dw_ld < w_pad || (dw_ld & 3) || n_mid < 0 ||
+        n_mid > MATTEN_RADIAL_MAX_MID)
+        return MATTEN_EINVAL;
+    if (n_edges == 0) return MATTEN_OK;
+    if (!geom_sorted || !w0p || (n_mid > 0 && !w_mid) || !w2p || !dw || !dlen) return MATTEN_EINVAL;
+    const unsigned grid1 = (unsigned)(matten_radial_mlp_bwd_small_slices(n_edges) / BW_WAVES);
+#define LAUNCH(K, B, NM)                                                                                                  \
+    radial_mlp_bwd_edges<K, B, NM, true><<<grid1, BW_WAVES * 64, 0, stream>>>(                                            \
+        (const float4*)geom_sorted, n_edges, n_basis, r_start, r_end, w0p, w_mid, w2p, w_pad, w_cols, dw, dw_ld, nullptr, \
+        nullptr, bw_tiles(n_edges), 1.0f, 1.0f, dlen)
+#define LAUNCH_NM(K, B)                   \
+    switch (n_mid) {                      \
+        case 0: LAUNCH(K, B, 0); break;   \
+        case 1: LAUNCH(K, B, 1); break;   \
+        case 2: LAUNCH(K, B, 2); break;   \
+        default: LAUNCH(K, B, 3); break;  \
+    }
+#define LAUNCH_K(B)                       \
+    switch (nb_pad >> 2) {                \
+        case 1: LAUNCH_NM(1, B); break;   \
+        case 2: LAUNCH_NM(2, B); break;   \
+        case 3: LAUNCH_NM(3, B); break;   \
+        default: LAUNCH_NM(4, B); break;  \
+    }
+    if (dw_is_bf16) { LAUNCH_K(true) } else { LAUNCH_K(false) }
+#undef LAUNCH_K
+#undef LAUNCH_NM
+#undef LAUNCH
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
 }
 
 // (w0 [nb,32], w1 [N_MID,32,32], w2 [32,W] raw parameters) -> the packed operands of matten_radial_mlp / _bwd in ONE

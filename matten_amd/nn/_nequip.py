@@ -13,6 +13,7 @@ from typing import Union
 
 import torch
 
+from .. import autograd as _ag
 from .. import ops
 from ..data.irreps import DataKey, ModuleIrreps
 from ..o3 import Irreps
@@ -44,6 +45,12 @@ def ensure_edge_geometry(data: DataKey.Type, lmax: int = None, want_vectors=Fals
         or (want_attrs and DataKey.EDGE_ATTRS not in data)
         or (want_embedding and DataKey.EDGE_EMBEDDING not in data)
     )
+    pos, cell = data[DataKey.POSITIONS], data.get(DataKey.CELL)
+    # geometry gradients: positions or cells require grad, so the per-edge tensors must come out of EdgeGeomFn (a batch
+    # whose cached tensors carry no graph is evaluated again)
+    grad = _ag.needs_grad(pos, cell)
+    if grad and have and not data[DataKey.AMD_GEOM].requires_grad:
+        have = False
     if have and not missing:
         return data
     ensure_graph(data)
@@ -54,12 +61,22 @@ def ensure_edge_geometry(data: DataKey.Type, lmax: int = None, want_vectors=Fals
     if DataKey.AMD_RBF in data:
         nb, r0, r1 = data[DataKey.AMD_RBF].tolist()
         nb = int(nb)
-    out = ops.edge_geom(
-        data[DataKey.POSITIONS], data[DataKey.EDGE_INDEX], data.get(DataKey.EDGE_CELL_SHIFT),
-        data.get(DataKey.CELL), data.get(DataKey.BATCH), data[DataKey.AMD_PERM], lmax, nb, r0, r1,
-        want_vectors=want_vectors, want_lengths=want_lengths, want_attrs=want_attrs,
-        want_embedding=want_embedding and nb > 0,
-    )
+    wants = dict(want_vectors=want_vectors, want_lengths=want_lengths, want_attrs=want_attrs,
+                 want_embedding=want_embedding and nb > 0)
+    if grad:
+        _training_edge_tensors(data)   # the source-keyed CSR: the order in which the adjoint sums per atom
+        ptr = None
+        if cell is not None and cell.numel() > 9:   # the crystals' first atoms (their edges are contiguous once sorted)
+            n_cells = cell.numel() // 9
+            ptr = torch.searchsorted(data[DataKey.BATCH].contiguous(),
+                                     torch.arange(n_cells + 1, dtype=torch.long, device=pos.device))
+        graph = (data[DataKey.EDGE_INDEX], data.get(DataKey.EDGE_CELL_SHIFT), data.get(DataKey.BATCH), data[DataKey.AMD_PERM],
+                 data[DataKey.AMD_ROWPTR], data["_amd_out_csr"], ptr)
+        out = {}
+        out["geom_sorted"], out["sh_sorted"] = _ag.EdgeGeomFn.apply(pos, cell, graph, lmax, (nb, r0, r1), wants, out)
+    else:
+        out = ops.edge_geom(pos, data[DataKey.EDGE_INDEX], data.get(DataKey.EDGE_CELL_SHIFT), cell, data.get(DataKey.BATCH),
+                            data[DataKey.AMD_PERM], lmax, nb, r0, r1, **wants)
     data[DataKey.AMD_GEOM], data[DataKey.AMD_SH] = out["geom_sorted"], out["sh_sorted"]
     for key, name in ((DataKey.EDGE_VECTORS, "edge_vectors"), (DataKey.EDGE_LENGTH, "edge_lengths"),
                       (DataKey.EDGE_ATTRS, "edge_attrs"), (DataKey.EDGE_EMBEDDING, "edge_embedding")):
@@ -73,6 +90,12 @@ def ensure_training_edge_tensors(data: DataKey.Type) -> DataKey.Type:
     destination-sorted order."""
     if "_amd_dst_sorted" not in data:
         ensure_edge_geometry(data)
+    return _training_edge_tensors(data)
+
+
+def _training_edge_tensors(data: DataKey.Type) -> DataKey.Type:
+    """ensure_training_edge_tensors on a batch whose destination-sorted CSR exists (ensure_graph)"""
+    if "_amd_dst_sorted" not in data:
         perm = data[DataKey.AMD_PERM].long()
         data["_amd_dst_sorted"] = data[DataKey.EDGE_INDEX][1][perm].to(torch.int32).contiguous()
         # the sorted edges grouped by SOURCE node (stable): the order in which dL/dx is summed per node -- the CSR builder

@@ -31,6 +31,12 @@ DEAD_PATH_ELIMINATION = _os.environ.get("MATTEN_DEAD_PATH_ELIMINATION", "1") != 
 AGG_KM_MIN_ROWS = int(_os.environ.get("MATTEN_AGG_KM_MIN_ROWS", "8192"))   # nodes per batch from which lin2 streams component-major rows
 
 
+def _geometry(data) -> tuple:
+    """the batch's per-edge geometry tensors: they require grad when positions or cells do (autograd.EdgeGeomFn), and the
+    layer then takes its differentiable route like it does for a parameter"""
+    return data.get(DataKey.AMD_GEOM), data.get(DataKey.AMD_SH)
+
+
 class PointConv(ModuleIrreps, torch.nn.Module):
     def __init__(
         self,
@@ -183,7 +189,8 @@ class PointConv(ModuleIrreps, torch.nn.Module):
     def forward(self, data: DataKey.Type) -> DataKey.Type:
         if self._view is not None and DEAD_PATH_ELIMINATION:
             # the consumer (model_factory.eliminate_dead_outputs paired it with this layer) takes the kept irreps only
-            data = self._view_forward(data, _ag.needs_grad_lazy(lambda: (data[DataKey.NODE_FEATURES], *_ag.params_of(self))))
+            data = self._view_forward(data, _ag.needs_grad_lazy(lambda: (data[DataKey.NODE_FEATURES], *_geometry(data),
+                                                                         *_ag.params_of(self))))
             data[KEPT_ONLY] = True
             return data
         data.pop(KEPT_ONLY, None)   # (a re-used batch dict may carry the marker of an earlier forward)
@@ -203,7 +210,8 @@ class PointConv(ModuleIrreps, torch.nn.Module):
         # and tables into LDS, species lookup -- is ~35 us of latency per launch that only a long stream pays back:
         # n100, 473 rows: 1.25 vs 1.08 ms per forward; 64 000 rows: -3 %)
         if (self.agg_plan is not None and x1.shape[0] >= AGG_KM_MIN_ROWS
-                and not _ag.needs_grad_lazy(lambda: (x1, self_connection, self.lin2.weight, *_ag.params_of(self.tp.weight_nn)))):
+                and not _ag.needs_grad_lazy(lambda: (x1, self_connection, self.lin2.weight, *_geometry(data),
+                                                     *_ag.params_of(self.tp.weight_nn)))):
             ap, t, dev = self.agg_plan, self._agg_tables, x1.device
             agg = self.tp(x1, data, self.avg_num_neighbors, out_layout=(t.get("entries", dev), ap.ld))
             gate = self.__dict__.get("_gate_fuse")   # set per call by PointConvWithActivation: (cmeta, act_cst, d_act, bn)
@@ -297,7 +305,7 @@ class PointConvWithActivation(ModuleIrreps, torch.nn.Module):
     def forward(self, data: DataKey.Type) -> DataKey.Type:
         x = data[DataKey.NODE_FEATURES]
         fuse = None
-        if not _ag.needs_grad_lazy(lambda: (x, *_ag.params_of(self.conv), *_ag.params_of(self.norm))) \
+        if not _ag.needs_grad_lazy(lambda: (x, *_geometry(data), *_ag.params_of(self.conv), *_ag.params_of(self.norm))) \
                 and x.shape[0] >= AGG_KM_MIN_ROWS:
             fuse = self._gate_fuse_args(x.device)
         self.conv.__dict__["_gate_fuse"] = fuse

@@ -360,7 +360,10 @@ class UVUTensorProduct(torch.nn.Module):
         dev = node_feats.device
         avg = avg_num_neighbors if avg_num_neighbors is not None else 0.0
         num_neigh = None if avg_num_neighbors is not None else data[DataKey.NUM_NEIGH]
-        if _ag.needs_grad_lazy(lambda: (node_feats, *_ag.params_of(self.weight_nn))):
+        # geometry gradients (positions / cells require grad: _nequip.ensure_edge_geometry went through EdgeGeomFn) take the
+        # training path too, with every parameter frozen and the model in eval() as well
+        geom_grad = _ag.needs_grad(data[DataKey.AMD_GEOM], data[DataKey.AMD_SH])
+        if geom_grad or _ag.needs_grad_lazy(lambda: (node_feats, *_ag.params_of(self.weight_nn))):
             # training path: radial weights materialised in the reference layout by the MLP kernel, the tensor
             # product + neighbour sum and both adjoints are HIP kernels too
             from ._nequip import ensure_training_edge_tensors
@@ -368,7 +371,14 @@ class UVUTensorProduct(torch.nn.Module):
             ensure_training_edge_tensors(data)
             mode = os.environ.get("MATTEN_TRAIN_TP", "auto")
             n_edges = data[DataKey.AMD_SRC].shape[0]
-            if mode == "auto":
+            if geom_grad:
+                # the w-free adjoint of the fused route does not provide dL/dY: materialised w, whatever MATTEN_TRAIN_TP says
+                # (and the module's automatic choice is not fixed by such a batch)
+                if os.environ.get("MATTEN_TP_BWD", "lit") != "lit":
+                    raise NotImplementedError("MATTEN_TP_BWD=table has no adjoint for the edge harmonics: geometry "
+                                              "gradients need MATTEN_TP_BWD=lit (the default)")
+                mode = "paths"
+            elif mode == "auto":
                 # decided ONCE per module, by the first training batch it sees: the two routes round differently (fused: split-fp16
                 # matrix products for w, fp32-class; paths: fp32 MFMA), and batches around the threshold must not flip a run
                 # between them from step to step (INTEGRATION.md "Training numerics")
@@ -381,7 +391,7 @@ class UVUTensorProduct(torch.nn.Module):
                 # between the passes; small batches keep the path kernels (fewer launches: 10 % faster at batch 32)
                 return _ag.FusedTensorProductFn.apply(node_feats, self, data, avg, num_neigh, *self.weight_nn.weights())
             w_edge = self.weight_nn.forward_train(data[DataKey.AMD_GEOM], int(nb), r0, r1)
-            return _ag.TensorProductScatterFn.apply(node_feats, w_edge, self, data, avg, num_neigh)
+            return _ag.TensorProductScatterFn.apply(node_feats, w_edge, data[DataKey.AMD_SH], self, data, avg, num_neigh)
         if self.impl == "fused":
             h2p, w2p = self.weight_nn.hidden(data[DataKey.AMD_GEOM], int(nb), r0, r1, data)
             rowptr = data[DataKey.AMD_ROWPTR]

@@ -1137,6 +1137,79 @@ def tp_backward_lit(x, w_edge, sh_sorted, src_sorted, dst_sorted, blocks, paths,
     return dx, dw
 
 
+def tp_backward_sh(x, w_edge, src_sorted, dst_sorted, blocks, paths, max_mul: int, g_agg, avg_num_neighbors: float,
+                   num_neigh=None, max_l: int = 4, sh_stride: int = SH_STRIDE) -> torch.Tensor:
+    """the adjoint of the 'uvu' product w.r.t. the edge harmonics (include/matten_hip.h matten_tp_backward_sh; the tables
+    of tp_backward_lit, max_mul = plan.bw_max_mul) -> dY [E, sh_stride] fp32, every column written"""
+    lib = _lib.load()
+    x = _need(x, torch.float32, "x")
+    g_agg = _need(g_agg, torch.float32, "grad agg")
+    w_edge = _edge_dtype(w_edge, "w_edge")
+    E = w_edge.shape[0]
+    dy = torch.empty(E, sh_stride, dtype=torch.float32, device=x.device)
+    if num_neigh is not None:
+        num_neigh = _need(num_neigh, torch.float32, "num_neigh")
+    with _timed(f"tp_backward_sh/d_mid={g_agg.shape[1]}/d_in={x.shape[1]}"):
+        rc = lib.matten_tp_backward_sh(_ptr(x), x.shape[1], _ptr(w_edge), w_edge.shape[1], _ptr(src_sorted), _ptr(dst_sorted),
+                                       _ptr(blocks), blocks.shape[0], int(max_mul), _ptr(paths), paths.shape[0], _ptr(g_agg),
+                                       g_agg.shape[1], float(avg_num_neighbors or 0.0), _ptr(num_neigh), E,
+                                       int(w_edge.dtype == torch.bfloat16), _ptr(dy), sh_stride, int(max_l), _stream())
+    _lib.check(rc, "matten_tp_backward_sh")
+    return dy
+
+
+def radial_mlp_bwd_len(geom_sorted, n_basis: int, r_start: float, r_end: float, w0p, w_mid, w2p, w_cols: int,
+                       dw) -> torch.Tensor:
+    """the adjoint of the radial MLP w.r.t. the edge length (matten_radial_mlp_bwd_len) -> dlen [E] fp32.
+    w_mid: the packed middle layers, [n_mid, 32, 32] or one [32, 32] layer (any depth through the one entry)"""
+    lib = _lib.load()
+    geom_sorted = _need(geom_sorted, torch.float32, "geom_sorted")
+    w0p, w2p = _need(w0p, torch.float32, "w0p"), _need(w2p, torch.float32, "w2p")
+    w_mid, n_mid = _mid(w_mid.unsqueeze(0) if w_mid is not None and w_mid.dim() == 2 else w_mid, "w_mid")
+    if dw.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("dw must be fp32 or bf16")
+    dw = _need(dw, dw.dtype, "dw")
+    E = geom_sorted.shape[0]
+    nb_pad, hidden = w0p.shape
+    dlen = torch.empty(E, dtype=torch.float32, device=geom_sorted.device)
+    with _timed(f"radial_mlp_bwd_len/w_pad={w2p.shape[1]}"):
+        rc = lib.matten_radial_mlp_bwd_len(_ptr(geom_sorted), E, n_basis, r_start, r_end, _ptr(w0p), nb_pad,
+                                           _ptr(w_mid) if n_mid else None, n_mid, _ptr(w2p), hidden, w2p.shape[1], int(w_cols),
+                                           _ptr(dw), dw.shape[1], int(dw.dtype == torch.bfloat16), _ptr(dlen), _stream())
+    _lib.check(rc, "matten_radial_mlp_bwd_len")
+    return dlen
+
+
+def edge_geom_bwd(geom_sorted, dy, dlen, lmax: int, n_nodes: int, rowptr, out_csr, perm=None, edge_cell_shift=None,
+                  n_cells: int = 0, ptr=None):
+    """the adjoint of edge_geom (matten_edge_geom_bwd) -> (dpos [N,3], dcell [n_cells,3,3] or None).
+    dy [E, stride] / dlen [E]: dL/d(harmonics) and dL/d(length) summed over the conv layers, either may be None;
+    out_csr = (out_ptr, out_perm) as tp_backward_lit takes it; n_cells > 0 with edge_cell_shift asks for dcell
+    (ptr [n_cells+1] int64, the crystals' first atoms, when n_cells > 1)"""
+    lib = _lib.load()
+    geom_sorted = _need(geom_sorted, torch.float32, "geom_sorted")
+    E, dev = geom_sorted.shape[0], geom_sorted.device
+    dy = None if dy is None else _need(dy, torch.float32, "dy")
+    dlen = None if dlen is None else _need(dlen, torch.float32, "dlen")
+    rowptr = _need(rowptr, torch.int32, "rowptr")
+    out_ptr, out_perm = (_need(t, torch.int32, n) for t, n in zip(out_csr, ("out_ptr", "out_perm")))
+    dcell = None
+    if n_cells > 0 and edge_cell_shift is not None:
+        edge_cell_shift = _need(edge_cell_shift, torch.float32, "edge_cell_shift")
+        perm = None if perm is None else _need(perm, torch.int32, "perm")
+        if n_cells > 1:
+            ptr = _need(ptr, torch.int64, "ptr")
+        dcell = torch.empty(n_cells, 3, 3, dtype=torch.float32, device=dev)
+    dv = torch.empty(E, 4, dtype=torch.float32, device=dev)
+    dpos = torch.empty(n_nodes, 3, dtype=torch.float32, device=dev)
+    with _timed("edge_geom_bwd"):
+        rc = lib.matten_edge_geom_bwd(_ptr(geom_sorted), _ptr(dy), dy.shape[1] if dy is not None else 0, _ptr(dlen), int(lmax), E,
+                                      n_nodes, _ptr(rowptr), _ptr(out_ptr), _ptr(out_perm), _ptr(perm), _ptr(edge_cell_shift),
+                                      n_cells if dcell is not None else 0, _ptr(ptr), _ptr(dv), _ptr(dpos), _ptr(dcell), _stream())
+    _lib.check(rc, "matten_edge_geom_bwd")
+    return dpos, dcell
+
+
 def species_linear_wgrad(x, dy, species_order, n_species: int, seg_tables, w_stride: int) -> torch.Tensor:
     lib = _lib.load()
     x = _need(x, torch.float32, "x")
