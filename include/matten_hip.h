@@ -916,6 +916,36 @@ int matten_batch_gather_padded(const int64_t* streams, int64_t n_streams, const 
                                int64_t n_nodes, int64_t n_edges, int64_t v_crystals, int64_t v_nodes, int64_t v_edges,
                                int64_t* n_valid, matten_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Loss over the selected atoms of a per-atom prediction (reference model/model.py:340-345: preds[atom_selector], then
+ * the task's mean loss and mean-absolute-error metric, model/task.py:238-248).  Boolean indexing has a data-dependent
+ * output shape (a host read per step, not capturable); here the selector is one int32 word per row, any nonzero value
+ * = selected, and pred / target share the shape [n_rows, d] (fp32, contiguous; rows without a target hold anything).
+ *   kind 0: squared error, kind 1: absolute error.
+ *   sum   (fp64, device)  the per-element loss summed over the selected rows
+ *   count (int64, device) the number of selected rows
+ *   loss  (fp32, device)  sum / (count * d), rounded once; count == 0 gives 0 (a definition: the reference's mean over
+ *                         nothing is NaN; a real batch has a selected atom, an all-padding row set stays finite)
+ * Differences and squares are formed in fp64; the reduction runs in a fixed order (lane, wave butterfly, workgroup
+ * through LDS, per-workgroup partials in index order): no floating-point atomics, two calls give the same bits.  A row
+ * with selector 0 never enters the arithmetic (NaN / Inf there changes no output bit); a NaN in a selected row reaches
+ * loss.  At most two launches (one up to matten_selected_loss_tile_elems() elements), no host read, no allocation.
+ *   workspace: matten_selected_loss_workspace_bytes(n_rows, d) bytes, 8-byte aligned (0 bytes: may be NULL).
+ * matten_selected_loss_bwd: grad_pred[i, c] = g * dl(pred - target) / (count * d) on selected rows (dl = 2x, or sign(x)
+ * with sign(0) = 0), formed in fp64 and rounded once, and +0.0 on every other row; count == 0 writes zeros.  g (fp32)
+ * and count (the forward's word) are read from device memory.  One elementwise launch.
+ * MATTEN_EINVAL: n_rows < 0, d < 1, n_rows * d >= 2^31, kind outside {0, 1}, a NULL or misaligned pointer;
+ * MATTEN_ENOMEM: a workspace smaller than the query.  Both before any launch.  n_rows == 0 writes (0, 0, 0).
+ * ------------------------------------------------------------------------------------------ */
+int matten_selected_loss_tile_elems(void);   /* elements (n_rows * d) one workgroup takes per round */
+int matten_selected_loss_max_blocks(void);   /* workgroups of the forward at most; more elements are strided over */
+size_t matten_selected_loss_workspace_bytes(int64_t n_rows, int64_t d);
+int matten_selected_loss(const float* pred, const float* target, const int32_t* selector, int64_t n_rows, int64_t d,
+                         int kind, double* sum, int64_t* count, float* loss, void* workspace, size_t workspace_bytes,
+                         matten_stream_t stream);
+int matten_selected_loss_bwd(const float* pred, const float* target, const int32_t* selector, int64_t n_rows, int64_t d,
+                             int kind, const float* g, const int64_t* count, float* grad_pred, matten_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,11 @@ SIGNATURES = {
     "matten_batch_gather_max_streams": (c_int, []),
     "matten_batch_gather": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P]),
     "matten_batch_gather_padded": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, P, P]),
+    "matten_selected_loss_tile_elems": (c_int, []),
+    "matten_selected_loss_max_blocks": (c_int, []),
+    "matten_selected_loss_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "matten_selected_loss": (c_int, [P, P, P, c_int64, c_int64, c_int, P, P, P, P, c_size_t, P]),
+    "matten_selected_loss_bwd": (c_int, [P, P, P, c_int64, c_int64, c_int, P, P, P, P]),
 }
 
 _lib = None

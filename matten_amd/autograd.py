@@ -553,6 +553,26 @@ class DenseRowsFn(torch.autograd.Function):
         return ops.dense_rows(g.contiguous(), qt), None, None
 
 
+class SelectedLossFn(torch.autograd.Function):
+    """(loss, count, sum) = matten_selected_loss(pred, target, selector, kind): the mean loss over the rows whose int32
+    selector word is nonzero, with its adjoint kernel (matten_selected_loss_bwd).  Only ``pred`` receives a gradient;
+    ``count`` (int64) and ``sum`` (fp64) carry none.  Nothing is read back: the upstream gradient and the count reach the
+    adjoint as device words, so forward and backward capture into a hipGraph."""
+
+    @staticmethod
+    def forward(ctx, pred, target, selector, kind):
+        loss, total, count = ops.selected_loss(pred, target, selector, kind)
+        ctx.kind = kind
+        ctx.save_for_backward(pred, target, selector, count)
+        ctx.mark_non_differentiable(count, total)
+        return loss, count, total
+
+    @staticmethod
+    def backward(ctx, g, _g_count, _g_sum):
+        pred, target, selector, count = ctx.saved_tensors
+        return ops.selected_loss_bwd(pred, target, selector, ctx.kind, g.contiguous(), count), None, None, None
+
+
 def needs_grad(*tensors: Optional[torch.Tensor]) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 

@@ -19,9 +19,12 @@ ATOMIC_NUMBER = {sym: z for z, sym in enumerate(_SYMBOLS, start=1)}
 
 
 def structures_from_json(path: str, target_columns=("elastic_tensor_full",),
-                         honor_lattice_pbc: bool = False) -> List[Dict[str, np.ndarray]]:
+                         honor_lattice_pbc: bool = False, bool_columns=()) -> List[Dict[str, np.ndarray]]:
     """-> one dict per row, in row order: lattice [3,3], cart_coords [n,3], atomic_numbers [n] (+ the target columns
     that are present).  These dicts are what ``matten_amd.predict.predict`` accepts in place of pymatgen structures.
+
+    ``bool_columns``: columns of true / false flags (the per-atom ``atom_selector`` of the reference's
+    datasets/si_nmr_data.json), read as ``bool`` arrays; a value that is not a flag is a ``ValueError`` naming the row.
 
     A ``Molecule`` record has no lattice: its dict has none either and carries ``pbc = (False, False, False)``.  A
     ``Structure`` record is fully periodic, as in the reference (``from_pymatgen`` ignores ``lattice.pbc``), unless
@@ -48,5 +51,11 @@ def structures_from_json(path: str, target_columns=("elastic_tensor_full",),
         for col in target_columns:
             if col in table:
                 item[col] = np.asarray(table[col][r], dtype=np.float64)
+        for col in bool_columns:
+            if col in table:
+                flags = np.asarray(table[col][r])
+                if flags.dtype != np.bool_ and not (flags.dtype.kind in "iu" and np.isin(flags, (0, 1)).all()):
+                    raise ValueError(f"row {r}: column '{col}' holds values that are not true / false flags")
+                item[col] = flags.astype(np.bool_).reshape(-1)
         out.append(item)
     return out

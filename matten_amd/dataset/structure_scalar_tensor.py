@@ -5,9 +5,15 @@ dataset/structure_scalar_tensor.py:368-666), reduced to what feeds the message-p
 neighbour list of ``matten_amd.data.graph`` -> collated batch dicts whose target is the irreps vector of the tensor
 (``CartesianTensor.from_cartesian``, reference :262-267).  pymatgen / pandas / PyG / Lightning are not needed.
 
+Per-atom targets (scripts/train_atomic_tensor.py, configs/atomic_tensor.yaml of the reference): ``atom_selector`` names a
+column of per-atom flags and the target column holds one tensor per flagged atom.  ``atom_target_layout`` picks how the
+labels are stored: "compact" is the reference's ([M, d] targets + a ``bool`` selector, consumed by ``preds[selector]``),
+"dense" keeps one target row per atom (zeros where unselected) + an ``int32`` selector, which the device store, the
+padded batches and the selected-loss kernels take as ordinary per-node keys.  The selector's dtype picks the route.
+
 Not carried over (outside the path; ``NotImplementedError`` when asked for): featurizers (``global_featurizer``,
 ``atom_featurizer``), scalar targets, on-disk caching (``reuse``); target normalisation is available through
-``normalize_tensor_target`` + ``matten_amd.data.transform``.
+``normalize_tensor_target`` + ``matten_amd.data.transform`` (crystal targets only).
 """
 import os
 from typing import Any, Dict, Iterator, List, Optional
@@ -106,12 +112,25 @@ class TensorDataModule:
         device=None,
         pbc=None,
         device_resident: bool = False,
+        atom_selector: Optional[str] = None,
+        atom_target_layout: Optional[str] = None,
         **unsupported,
     ):
         bad = {k: v for k, v in unsupported.items() if v not in (None, False, [], {})
-               and k in ("global_featurizer", "atom_featurizer", "scalar_target_names", "tensor_target_weight", "atom_selector")}
+               and k in ("global_featurizer", "atom_featurizer", "scalar_target_names", "tensor_target_weight")}
         if bad:
             raise NotImplementedError(f"TensorDataModule options outside the accelerated path: {sorted(bad)}")
+        # per-atom targets: "compact" = the reference's layout, "dense" = one row per atom + an int32 selector
+        self.atom_selector = atom_selector or None
+        if atom_target_layout is None:
+            atom_target_layout = "dense" if device_resident else "compact"
+        if atom_target_layout not in ("compact", "dense"):
+            raise ValueError(f'atom_target_layout = {atom_target_layout!r}: "compact" or "dense"')
+        if self.atom_selector is not None and device_resident and atom_target_layout == "compact":
+            raise ValueError('atom_target_layout="compact" with device_resident=True: the compact target holds M <= N rows '
+                             'per crystal and a bool selector, and the device store gathers per-atom, per-edge and '
+                             'per-crystal keys of 4- or 8-byte elements only; use "dense" (the default there)')
+        self.atom_target_layout = atom_target_layout
         if normalize_tensor_target:
             raise NotImplementedError("normalize_tensor_target: standardise with matten_amd.data.transform.TensorTargetTransform")
         self.files = {"train": trainset_filename, "val": valset_filename, "test": testset_filename}
@@ -138,12 +157,15 @@ class TensorDataModule:
 
     def _load(self, filename: str) -> List[Dict[str, torch.Tensor]]:
         path = filename if os.path.isabs(filename) else os.path.join(self.root, filename)
-        rows = structures_from_json(path, target_columns=(self.tensor_target_name,))
+        bool_columns = (self.atom_selector,) if self.atom_selector is not None else ()
+        rows = structures_from_json(path, target_columns=(self.tensor_target_name,), bool_columns=bool_columns)
         converter = CartesianTensorWrapper(self.tensor_target_formula)
         graphs = []
-        for r in rows:
+        for i, r in enumerate(rows):
             y = {}
-            if self.tensor_target_name in r:
+            if self.atom_selector is not None:
+                y = self._atom_targets(r, i, filename, converter)
+            elif self.tensor_target_name in r:
                 t = torch.as_tensor(r[self.tensor_target_name], dtype=torch.float64) * self.tensor_target_scale
                 if self.tensor_target_format == "irreps":   # reference dataset/structure_scalar_tensor.py:262-267
                     t = converter.from_cartesian(t)
@@ -151,6 +173,33 @@ class TensorDataModule:
             pbc = self.pbc if self.pbc is not None else r.get("pbc", "lattice" in r)
             graphs.append(crystal_graph(r["cart_coords"], r.get("lattice"), r["atomic_numbers"], self.r_cut, y=y, pbc=pbc))
         return graphs
+
+    def _atom_targets(self, r, i: int, filename: str, converter) -> Dict[str, torch.Tensor]:
+        """the labels of one crystal with per-atom targets (reference dataset/structure_scalar_tensor.py:256-312): the
+        tensors of the flagged atoms, scaled and converted like a crystal's, and the selector.  The tensors are taken as
+        they are -- NMR shielding tensors are not symmetric; ``from_cartesian`` projects them, like the reference."""
+        n = int(r["atomic_numbers"].shape[0])
+        where = f"row {i} of {filename}"
+        if self.atom_selector not in r or self.tensor_target_name not in r:
+            raise ValueError(f"{where}: per-atom targets need the columns '{self.atom_selector}' and "
+                             f"'{self.tensor_target_name}'")
+        sel = torch.as_tensor(r[self.atom_selector])
+        if sel.shape[0] != n:
+            raise ValueError(f"{where}: '{self.atom_selector}' holds {sel.shape[0]} flags, the structure has {n} atoms")
+        t = torch.as_tensor(r[self.tensor_target_name], dtype=torch.float64)
+        m = int(sel.sum())
+        if t.dim() < 1 or t.shape[0] != m or (m and t.numel() == 0):
+            raise ValueError(f"{where}: '{self.tensor_target_name}' holds {t.shape[0] if t.dim() else 0} tensors, "
+                             f"'{self.atom_selector}' flags {m} atoms")
+        t = t * self.tensor_target_scale
+        if self.tensor_target_format == "irreps":
+            t = converter.from_cartesian(t)
+        t = t.to(torch.float32)
+        if self.atom_target_layout == "compact":
+            return {self.tensor_target_name: t, "atom_selector": sel}
+        dense = torch.zeros((n,) + tuple(t.shape[1:]), dtype=torch.float32)
+        dense[sel] = t
+        return {self.tensor_target_name: dense, "atom_selector": sel.to(torch.int32)}
 
     def setup(self, stage: Optional[str] = None):
         cache: Dict[str, List] = {}

@@ -107,6 +107,37 @@ def padded_mean_loss(fn: Callable, key: str = None) -> Callable:
     return loss
 
 
+def selected_mean_loss(kind="mse", key: str = None, selector_key: str = "atom_selector") -> Callable:
+    """The mean loss over the atoms that carry a target, for per-atom models on the dense label layout
+    (``TensorDataModule(atom_selector=..., atom_target_layout="dense")``): the per-atom counterpart of ``padded_mean_loss``.
+
+    `kind`: "mse" or "mae"; `key` picks the prediction out of the model's dict.  The returned
+    ``loss(preds, target, batch)`` reads the int32 selector from ``batch[selector_key]`` -- inside a captured step that is
+    the captured buffer, which every replay refreshes -- and runs ``autograd.SelectedLossFn``: one kernel forward, one
+    backward, nothing read back.  The rows a padded batch appends are unselected by construction (their selector words
+    are zero), so it needs no ``_amd_n_valid`` and serves plain and padded batches alike."""
+    from .autograd import SelectedLossFn
+    from .ops import LOSS_KINDS
+
+    if kind not in LOSS_KINDS or isinstance(kind, bool):
+        raise ValueError(f"kind = {kind!r}: 'mse' or 'mae'")
+    code = LOSS_KINDS[kind]
+
+    def loss(preds, target, batch):
+        if selector_key not in batch:
+            raise ValueError(f"selected_mean_loss needs batch['{selector_key}'] (the dense per-atom label layout)")
+        selector = batch[selector_key]
+        if selector.dtype == torch.bool or selector.is_floating_point():
+            raise TypeError(f"batch['{selector_key}'] is {selector.dtype}: the dense route takes an integer selector (a bool "
+                            f"selector belongs to the compact layout and preds[selector])")
+        if selector.dtype != torch.int32:
+            selector = selector.to(torch.int32)
+        return SelectedLossFn.apply(preds[key] if key is not None else preds, target, selector, code)[0]
+
+    loss.wants_batch = True
+    return loss
+
+
 def _train_step(model, optimizer, loss_fn: Callable, batch, target, task_name: str):
     """one optimisation step as it is captured, and as it runs eagerly: forward, loss, backward, optimiser"""
     preds, _ = model(dict(batch), task_name=task_name)

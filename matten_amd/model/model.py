@@ -50,6 +50,15 @@ class TimeMeter:
         return delta, now - self.t0
 
 
+_SELECTED_LOSS_KINDS = {torch.nn.MSELoss: 0, torch.nn.L1Loss: 1}   # matten_selected_loss's `kind`
+
+
+def _is_dense_selector(selector) -> bool:
+    """the selector's dtype picks the route: ``bool`` is the reference's compact layout (``preds[selector]``), an integer
+    dtype the dense one (one target row per atom)"""
+    return isinstance(selector, Tensor) and selector.dtype != torch.bool and not selector.is_floating_point()
+
+
 def _batchnorms(model):
     from ..nn.utils import _IrrepBatchNorm
 
@@ -138,6 +147,34 @@ class BaseModel(_Base):
             total_loss = total_loss + task.loss_weight * loss
         return individual_losses, total_loss
 
+    def compute_selected_loss(self, preds: Dict[str, Tensor], labels: Dict[str, Tensor], weight: Tensor = None):
+        """``compute_loss`` over the atoms an integer ``labels["atom_selector"]`` flags (the dense per-atom layout): the
+        task's loss class picks the kernel's kind and the mean runs over the selected rows on the device
+        (autograd.SelectedLossFn), where the reference indexes ``preds[selector]`` first (model/model.py:340-345)."""
+        from ..autograd import SelectedLossFn
+
+        if weight is not None:
+            raise NotImplementedError("target_weight with dense per-atom labels (an integer atom_selector) is not supported")
+        selector = labels["atom_selector"]
+        if selector.dtype != torch.int32:
+            selector = selector.to(torch.int32)
+        individual_losses, total_loss = {}, 0.0
+        for task_name, task in self.tasks.items():
+            fn = self.loss_fns[task_name]
+            kind = _SELECTED_LOSS_KINDS.get(type(fn))
+            if kind is None or getattr(fn, "reduction", "mean") != "mean":
+                raise NotImplementedError(f"dense per-atom labels: the selected-loss kernel computes the mean of MSELoss or "
+                                          f"L1Loss, task '{task_name}' uses {fn!r}")
+            p = task.transform_pred_loss(preds[task_name])
+            l = task.transform_target_loss(labels[task_name])
+            if l.shape[0] != p.shape[0]:
+                raise ValueError(f"dense per-atom labels: '{task_name}' holds {l.shape[0]} target rows for {p.shape[0]} "
+                                 f"predicted atoms (one row per atom, zeros where the selector is 0)")
+            loss = SelectedLossFn.apply(p, l, selector, kind)[0]
+            individual_losses[task_name] = loss
+            total_loss = total_loss + task.loss_weight * loss
+        return individual_losses, total_loss
+
     # ---- reference model/model.py:282-312 ----
     def training_step(self, batch, batch_idx):
         loss, preds, labels = self.shared_step(batch, "train")
@@ -173,11 +210,15 @@ class BaseModel(_Base):
         batch_size = batch.num_graphs if hasattr(batch, "num_graphs") else int(batch["ptr"].shape[0]) - 1
         graphs, labels = self.preprocess_batch(batch)
         preds = self.decode(graphs)
-        if "atom_selector" in labels:
-            selector = labels["atom_selector"]
-            preds = {k: v[selector] for k, v in preds.items()}
         target_weight = graphs.get("target_weight", None)
-        individual_loss, total_loss = self.compute_loss(preds, labels, weight=target_weight)
+        if _is_dense_selector(labels.get("atom_selector")):
+            # dense per-atom labels (one target row per atom, integer selector): no indexing, no host read
+            individual_loss, total_loss = self.compute_selected_loss(preds, labels, weight=target_weight)
+        else:
+            if "atom_selector" in labels:
+                selector = labels["atom_selector"]
+                preds = {k: v[selector] for k, v in preds.items()}
+            individual_loss, total_loss = self.compute_loss(preds, labels, weight=target_weight)
         self.log_dict({f"{mode}/loss/{name}": loss for name, loss in individual_loss.items()},
                       on_step=False, on_epoch=True, prog_bar=False, batch_size=batch_size)
         self.log(f"{mode}/total_loss", total_loss, on_step=False, on_epoch=True, prog_bar=True, batch_size=batch_size)
@@ -185,6 +226,16 @@ class BaseModel(_Base):
 
     # ---- reference model/model.py:374-445 ----
     def update_metrics(self, preds: Dict, labels: Dict, mode: str):
+        selector = labels.get("atom_selector")
+        if _is_dense_selector(selector):   # dense per-atom labels: the metric masks on the device
+            for task_name, metric in self.metrics["metric_" + mode].items():
+                task = self.tasks[task_name]
+                if task.task_type == TaskType.CLASSIFICATION:
+                    raise NotImplementedError("dense per-atom labels serve regression tasks")
+                p = task.transform_pred_metric(preds[task_name])
+                l = task.transform_target_metric(labels[task_name])
+                metric(p.detach(), l.detach(), selector=selector)
+            return
         for task_name, metric in self.metrics["metric_" + mode].items():
             task = self.tasks[task_name]
             p = task.transform_pred_metric(preds[task_name])

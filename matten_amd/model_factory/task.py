@@ -28,7 +28,19 @@ class MeanAbsoluteError(torch.nn.Module):
         self.register_buffer("sum_abs", torch.zeros((), dtype=torch.float64), persistent=False)
         self.register_buffer("count", torch.zeros((), dtype=torch.float64), persistent=False)
 
-    def forward(self, preds: Tensor, target: Tensor) -> None:
+    def forward(self, preds: Tensor, target: Tensor, selector: Tensor = None) -> None:
+        if selector is not None:
+            # dense per-atom labels: |pred - target| over the rows an int32 selector flags (matten_selected_loss, kind 1).
+            # Its fp64 sum and its row count are added on the device: nothing is read back.
+            from .. import ops
+
+            if selector.dtype != torch.int32:
+                selector = selector.to(torch.int32)
+            _, total, rows = ops.selected_loss(preds, target, selector, 1)
+            per_row = preds.numel() // max(preds.shape[0], 1)
+            self.sum_abs += total.to(self.sum_abs.device)
+            self.count += (rows * per_row).to(self.count)
+            return
         self.sum_abs += (preds.double() - target.double()).abs().sum().to(self.sum_abs.device)
         self.count += preds.numel()
 
@@ -45,9 +57,12 @@ class MeanAbsoluteError(torch.nn.Module):
 class MetricCollection(torch.nn.ModuleDict):
     """{metric class name: metric}; called with (preds, target) it updates every member (torchmetrics.MetricCollection)"""
 
-    def forward(self, preds: Tensor, target: Tensor) -> None:
+    def forward(self, preds: Tensor, target: Tensor, selector: Tensor = None) -> None:
         for m in self.values():
-            m(preds, target)
+            if selector is None:
+                m(preds, target)
+            else:
+                m(preds, target, selector=selector)
 
     def compute(self) -> Dict[str, Tensor]:
         return {k: m.compute() for k, m in self.items()}

@@ -1410,6 +1410,55 @@ def segment_reduce_bwd(dy, ptr, n_rows: int, mean: bool) -> torch.Tensor:
     return dx
 
 
+LOSS_KINDS = {"mse": 0, "l2": 0, "squared": 0, 0: 0, "mae": 1, "l1": 1, "absolute": 1, 1: 1}
+
+
+def _selected_args(pred, target, selector, kind):
+    if kind not in LOSS_KINDS or isinstance(kind, bool):
+        raise ValueError(f"kind = {kind!r}: 0 / 'mse' (squared error) or 1 / 'mae' (absolute error)")
+    pred = _need(pred, torch.float32, "pred")
+    target = _need(target, torch.float32, "target")
+    selector = _need(selector, torch.int32, "selector")
+    if pred.dim() < 1 or selector.dim() != 1 or selector.shape[0] != pred.shape[0]:
+        raise ValueError(f"selector {tuple(selector.shape)} does not hold one word per row of pred {tuple(pred.shape)}")
+    if target.shape[0] != pred.shape[0] or target.numel() != pred.numel():
+        raise ValueError(f"target {tuple(target.shape)} and pred {tuple(pred.shape)} differ: the dense per-atom layout keeps "
+                         f"one target row per atom (zeros where the selector is 0)")
+    n_rows = pred.shape[0]
+    d = pred.numel() // n_rows if n_rows else max(1, int(np.prod(pred.shape[1:])))
+    return pred, target, selector, n_rows, d, LOSS_KINDS[kind]
+
+
+def selected_loss(pred, target, selector, kind=0):
+    """mean of the per-element loss over the rows with selector != 0 (include/matten_hip.h: matten_selected_loss) ->
+    (loss fp32 [], sum fp64 [], count int64 []), all on the device; trailing dimensions of pred / target are flattened"""
+    lib = _lib.load()
+    pred, target, selector, n_rows, d, kind = _selected_args(pred, target, selector, kind)
+    dev = pred.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    total = torch.empty((), dtype=torch.float64, device=dev)
+    count = torch.empty((), dtype=torch.int64, device=dev)
+    nbytes = int(lib.matten_selected_loss_workspace_bytes(n_rows, d))
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev) if nbytes else None
+    _lib.check(lib.matten_selected_loss(_ptr(pred), _ptr(target), _ptr(selector), n_rows, d, kind, _ptr(total), _ptr(count),
+                                        _ptr(loss), _ptr(ws), nbytes, _stream()), "matten_selected_loss")
+    return loss, total, count
+
+
+def selected_loss_bwd(pred, target, selector, kind, g, count) -> torch.Tensor:
+    """the adjoint of selected_loss with respect to pred; g (fp32 []) and count (int64 [], the forward's) stay on the device"""
+    lib = _lib.load()
+    pred, target, selector, n_rows, d, kind = _selected_args(pred, target, selector, kind)
+    g = _need(g, torch.float32, "g")
+    count = _need(count, torch.int64, "count")
+    if g.numel() != 1 or count.numel() != 1:
+        raise ValueError("g and count are one word each")
+    grad = torch.empty_like(pred)
+    _lib.check(lib.matten_selected_loss_bwd(_ptr(pred), _ptr(target), _ptr(selector), n_rows, d, kind, _ptr(g), _ptr(count),
+                                            _ptr(grad), _stream()), "matten_selected_loss_bwd")
+    return grad
+
+
 def graph_prep(pos64, cell64, ptr, r_cut: float):
     """per-crystal prologue of the device graph builder (include/matten_hip.h matten_graph_prep)
     -> (frac [N,3] f64, bound [B,3] f64, batch [N] i64, pos [N,3] f32, cell [3B,3] f32)"""
