@@ -532,6 +532,41 @@ int matten_elastic_refine(const double* compliance, const int32_t* flags, const 
                           int64_t n, int64_t n_dirs, int64_t n_angles, double tol, int64_t max_iter, double* value,
                           double* vec_n, double* vec_m, int32_t* status, int32_t* iterations, matten_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Derived quantities of per-atom rank-2 tensors (predict.py:117-148: the reference hands back one 3x3 array per atom;
+ * NMR users read the isotropic value, span and skew or the Haeberlen anisotropy and asymmetry off it, with the
+ * principal axes).  fp64 arithmetic, one atom per thread, values in the units of the input.
+ * matten_rank2_props:
+ *   t [n,9] (= [n,3,3] row-major), fp32 (is_fp64 = 0) or fp64 (1).  The input is symmetrised first, A = (T + T^T)/2
+ *   (shielding tensors are not symmetric); the isotropic part t = tr(A)/3 comes off before the cyclic Jacobi in
+ *   registers (csrc/sym3.h) and is added back to the values: the axes and the scalars below are those of the deviator,
+ *   resolved to eps span / gap however large the isotropic part is.  Eigenvalues ascending.
+ *   vals [n,3] = l1 <= l2 <= l3; axes [n,9] = the orthonormal U row-major, eigenvectors in its columns in the same order
+ *   (the sign of a column is unspecified but deterministic); axes may be NULL (= not written);
+ *   props [n,5] = iso = (l1 + l2 + l3)/3, span = l3 - l1, skew = 3 (l2 - iso)/span (of the tensor as given: for a
+ *   shielding tensor the Herzfeld-Berger kappa is its negative), zeta = l_z - iso (Haeberlen reduced anisotropy: z the
+ *   principal value furthest from iso, l3 when skew <= 0 -- ties included -- else l1; y = 2, x the other extreme),
+ *   eta = (l_y - l_x)/zeta in [0, 1];
+ *   flags [n] int32: bit 0 = one of the nine inputs is not finite, every output of the row is NaN; bit 1 = span == 0
+ *   exactly (a multiple of the identity): skew = eta = 0 by definition.
+ * matten_rank2_props_bwd: the adjoint, from what the forward wrote (vals, axes, props, flags; the input is not kept and
+ *   Jacobi is not run again).  g_vals [n,3], g_props [n,5] (fp64): the upstream gradients, each may be NULL (= zero).  With
+ *   w = g_vals + sum_q g_props[q] dq/dl, d iso = (1,1,1)/3, d span = (-1,0,1), d skew = ((skew-1), 2, (-skew-1))/span,
+ *   d zeta = e_z - (1,1,1)/3, d eta = (e_y - e_x)/zeta - (eta/zeta) d zeta:  g_t [n,9] = U diag(w) U^T in fp32
+ *   (is_fp64 = 0) or fp64 (1), every element written, symmetric (it passes through the symmetrisation's transpose).  A row
+ *   with flag bit 0 gets zeros whatever arrives (NaN included: selects, not products); a row with bit 1 ignores the
+ *   upstream gradients of skew and eta.  The principal axes carry no gradient.  Exactly degenerate eigenvalues: the
+ *   per-value gradients take the basis Jacobi left (finite; basis-dependent, as for matten_elastic_acoustic_bwd);
+ *   symmetric functions (iso) do not depend on it.
+ * Both: no atomics, no cross-lane traffic, nothing read back: bitwise reproducible, each row independent of the others,
+ * capturable.  n = 0 is a no-op.  MATTEN_EINVAL: n < 0, is_fp64 outside {0, 1}, a NULL required pointer with n > 0.
+ * ------------------------------------------------------------------------------------------ */
+int matten_rank2_props(const void* t, int is_fp64, int64_t n, double* vals, double* axes, double* props, int32_t* flags,
+                       matten_stream_t stream);
+int matten_rank2_props_bwd(const double* vals, const double* axes, const double* props, const int32_t* flags,
+                           const double* g_vals, const double* g_props, int is_fp64, int64_t n, void* g_t,
+                           matten_stream_t stream);
+
 
 /* ==========================================================================================
  * Adjoint (backward) operators for the training step (reference: autograd through

@@ -132,6 +132,8 @@ SIGNATURES = {
     "matten_elastic_acoustic_bwd": (c_int, [P, P, P, P, c_int64, c_int64, ctypes.c_double, P, P, P, P, P]),
     "matten_elastic_refine": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, ctypes.c_double, c_int64, P, P, P, P, P,
                                       P]),
+    "matten_rank2_props": (c_int, [P, c_int, c_int64, P, P, P, P, P]),
+    "matten_rank2_props_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int64, P, P]),
     "matten_batch_gather_lds_rows": (c_int, []),
     "matten_batch_gather_max_streams": (c_int, []),
     "matten_batch_gather": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P]),

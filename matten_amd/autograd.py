@@ -538,6 +538,26 @@ class ElasticAcousticFn(torch.autograd.Function):
                 None, None)
 
 
+class Rank2PropsFn(torch.autograd.Function):
+    """(vals, axes, props, flags) = matten_rank2_props(t) with its adjoint kernel (matten_rank2_props_bwd): the backward
+    works from the four outputs alone, so the input is not kept and Jacobi is not run again.  An output that nothing
+    downstream used reaches the kernel as a null pointer; ``axes`` and ``flags`` carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, t):
+        vals, axes, props, flags = ops.rank2_props(t)
+        ctx.dtype = t.dtype
+        ctx.save_for_backward(vals, axes, props, flags)
+        ctx.mark_non_differentiable(axes, flags)
+        ctx.set_materialize_grads(False)
+        return vals, axes, props, flags
+
+    @staticmethod
+    def backward(ctx, g_vals, _g_axes, g_props, _g_flags):
+        vals, axes, props, flags = ctx.saved_tensors
+        return ops.rank2_props_bwd(vals, axes, props, flags, g_vals, g_props, ctx.dtype)
+
+
 class DenseRowsFn(torch.autograd.Function):
     """out = x @ q (matten_dense_rows) for a constant q [n_in, n_out]; the adjoint is the same kernel with q^T, which the
     caller keeps next to q (``qt`` [n_out, n_in])."""

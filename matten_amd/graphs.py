@@ -138,6 +138,40 @@ def selected_mean_loss(kind="mse", key: str = None, selector_key: str = "atom_se
     return loss
 
 
+def rank2_selected_loss(names=("iso",), kind: str = "mse", key: str = None, selector_key: str = "atom_selector",
+                        formula: str = "ij=ji", weights=None) -> Callable:
+    """The loss on derived scalars of per-atom tensors (``rank2.Rank2Loss``: isotropic value, span, skew, zeta, eta) over
+    the atoms that carry a target, on the dense label layout: the counterpart of ``selected_mean_loss`` for fine-tuning a
+    per-atom tensor model on, say, isotropic shieldings.
+
+    The returned ``loss(preds, target, batch)`` takes the model's irreps rows [N,6] (``preds[key]``) through
+    ``rank2.rank2_invariants_from_irreps`` and ``Rank2Loss``.  ``target`` is a dict name -> [N] / [N,1], or a tensor [N,k]
+    (or [N] for one name) whose columns follow `names` -- an ordinary per-node key of the batch, which the device store
+    gathers and pads like any other.  The selector comes from ``batch[selector_key]``; padding rows are unselected.
+    Nothing is read back: ``GraphedTrainStep`` and ``BucketedTrainStep`` take it as it is."""
+    from .rank2 import Rank2Loss, rank2_basis, rank2_invariants_from_irreps
+
+    rank2_basis(formula)      # (a formula that is not a symmetric rank 2 fails here, not in the first step)
+    loss_mod = Rank2Loss(names, weights, kind)
+    names = loss_mod.names
+
+    def loss(preds, target, batch):
+        if selector_key not in batch:
+            raise ValueError(f"rank2_selected_loss needs batch['{selector_key}'] (the dense per-atom label layout)")
+        x = preds[key] if key is not None else preds
+        if not isinstance(target, dict):
+            if target.dim() == 1:
+                target = target.unsqueeze(1)
+            if target.dim() != 2 or target.shape[1] != len(names):
+                raise ValueError(f"target: expected a dict or [N,{len(names)}] with one column for each of {names}, got "
+                                 f"{tuple(target.shape)}")
+            target = {n: target[:, q] for q, n in enumerate(names)}
+        return loss_mod(rank2_invariants_from_irreps(x, formula), target, batch[selector_key])
+
+    loss.wants_batch = True
+    return loss
+
+
 def _train_step(model, optimizer, loss_fn: Callable, batch, target, task_name: str):
     """one optimisation step as it is captured, and as it runs eagerly: forward, loss, backward, optimiser"""
     preds, _ = model(dict(batch), task_name=task_name)

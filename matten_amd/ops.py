@@ -919,6 +919,48 @@ def elastic_props_bwd(voigt, compliance, props, flags, g_props, g_voigt, g_compl
     return g_c
 
 
+def rank2_props(t, want_axes: bool = True):
+    """t [N,9] (= [N,3,3] row-major), fp32 or fp64 -> (vals [N,3], axes [N,3,3] or None, props [N,5], flags [N] int32),
+    all fp64 (include/matten_hip.h: matten_rank2_props)"""
+    lib = _lib.load()
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.float64):
+        raise TypeError("t: expected an fp32 or fp64 tensor")
+    t = _need(t, t.dtype, "t")
+    if t.dim() != 2 or t.shape[1] != 9:
+        raise ValueError(f"t: expected [N,9], got {tuple(t.shape)}")
+    N = t.shape[0]
+    vals = torch.empty(N, 3, dtype=torch.float64, device=t.device)
+    axes = torch.empty(N, 3, 3, dtype=torch.float64, device=t.device) if want_axes else None
+    props = torch.empty(N, 5, dtype=torch.float64, device=t.device)
+    flags = torch.empty(N, dtype=torch.int32, device=t.device)
+    _lib.check(lib.matten_rank2_props(_ptr(t), int(t.dtype == torch.float64), N, _ptr(vals), _ptr(axes), _ptr(props),
+                                      _ptr(flags), _stream()), "matten_rank2_props")
+    return vals, axes, props, flags
+
+
+def rank2_props_bwd(vals, axes, props, flags, g_vals, g_props, dtype):
+    """the adjoint of ``rank2_props``: its four outputs and the upstream gradients g_vals [N,3] or None, g_props [N,5] or
+    None (fp64; None = zero) -> the gradient of t, [N,9] in ``dtype`` (fp32 or fp64); rows with flag bit 0 are zero
+    (matten_rank2_props_bwd)"""
+    lib = _lib.load()
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError("dtype: expected fp32 or fp64")
+    vals = _need(vals, torch.float64, "vals")
+    axes = _need(axes, torch.float64, "axes")
+    props = _need(props, torch.float64, "props")
+    flags = _need(flags, torch.int32, "flags")
+    N = flags.shape[0]
+    if vals.shape != (N, 3) or axes.shape != (N, 3, 3) or props.shape != (N, 5):
+        raise ValueError(f"expected vals [N,3], axes [N,3,3], props [N,5], flags [N]; got {tuple(vals.shape)}, "
+                         f"{tuple(axes.shape)}, {tuple(props.shape)}, {tuple(flags.shape)}")
+    g_vals = _opt_grad(g_vals, (N, 3), "g_vals")
+    g_props = _opt_grad(g_props, (N, 5), "g_props")
+    g_t = torch.empty(N, 9, dtype=dtype, device=flags.device)
+    _lib.check(lib.matten_rank2_props_bwd(_ptr(vals), _ptr(axes), _ptr(props), _ptr(flags), _ptr(g_vals), _ptr(g_props),
+                                          int(dtype == torch.float64), N, _ptr(g_t), _stream()), "matten_rank2_props_bwd")
+    return g_t
+
+
 def elastic_directional(compliance, flags, dirs, keep: bool = False):
     """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64 -> (young [B,D] or None, beta [B,D] or
     None, ext [B,4] = E_min, E_max, beta_min, beta_max, arg [B,4] int32) (matten_elastic_directional)"""

@@ -471,9 +471,10 @@ def evaluate(model, graphs: List, batch_size: int = 200,
 
 
 def evaluate_atomic(model, graphs: List, batch_size: int = 200, tensor_target_name: str = "nmr_tensor",
-                    tensor_target_formula: str = "ij=ji", r_cut: float = None) -> List[torch.Tensor]:
+                    tensor_target_formula: str = "ij=ji", r_cut: float = None, sink: list = None) -> List[torch.Tensor]:
     """Per-atom tensors of all atoms of all structures, in input order, as ONE flat list -- what the reference's
-    ``evaluate`` produces for an ``AtomicTensorModel`` (predict.py:117-148: ``predictions.extend(p)``)."""
+    ``evaluate`` produces for an ``AtomicTensorModel`` (predict.py:117-148: ``predictions.extend(p)``).
+    ``sink`` (a list): receives each forward's device tensor [n, 3, ...] for a consumer that works on the device."""
     converter = _converter(tensor_target_formula)
     device = model.device
     outs = []
@@ -487,6 +488,8 @@ def evaluate_atomic(model, graphs: List, batch_size: int = 200, tensor_target_na
             if p.dim() == 2:
                 p = converter.to_cartesian(p)
             outs.append(p)
+            if sink is not None:
+                sink.append(p)
     return list(torch.cat(outs, dim=0).cpu())
 
 
@@ -607,6 +610,7 @@ def predict(
     refine: bool = False,
     refine_tol: float = 1e-9,
     refine_max_iter: int = 32,
+    shielding: bool = False,
 ):
     """See the module docstring.  ``model`` / ``config`` let a caller reuse an already loaded model.
     ``properties=True`` (elasticity tensors only: ``ValueError`` with ``is_atomic_tensor``) returns ``(tensors, props)``:
@@ -621,7 +625,12 @@ def predict(
     ``batch_size`` (reference predict.py:155) is the memory knob it is there: consecutive batches are merged into one forward
     only while the merged batch stays within ``node_budget`` atoms (default MATTEN_PREDICT_NODE_BUDGET = 65536, ~2 GB) and
     only when batch_size is at least the reference's default of 200; ``node_budget=0`` never merges.  A merged forward
-    that runs out of device memory is retried unmerged."""
+    that runs out of device memory is retried unmerged.
+    ``shielding=True`` (per-atom tensors only: needs ``is_atomic_tensor`` and a symmetric rank-2 target formula, ``ValueError``
+    before any forward otherwise) returns ``(tensors, props)``: the usual flat list and a ``rank2.Rank2Properties`` over all
+    atoms in the order of that list (principal values and axes, isotropic value, span, skew, Haeberlen anisotropy and
+    asymmetry), computed from the forwards' device buffers, with ``ptr`` [S+1]: the atoms of structure s are rows
+    ptr[s]:ptr[s+1]."""
     from .log import set_logger
 
     set_logger(logger_level)  # reference predict.py:194
@@ -636,6 +645,15 @@ def predict(
                 raise ValueError(f"{name} belongs to the derived properties: pass properties=True")
         if refine:
             raise ValueError("refine belongs to the derived properties: pass properties=True")
+    if shielding:
+        from .rank2 import rank2_basis
+
+        if not is_atomic_tensor:
+            raise ValueError("shielding=True derives the shielding parameters of per-atom rank-2 tensors: pass "
+                             "is_atomic_tensor=True")
+        if config is None:
+            config = get_pretrained_config(model_identifier)
+        rank2_basis(config["data"]["tensor_target_formula"])      # (ValueError unless a symmetric rank 2)
     single = not isinstance(structure, (list, tuple))
     structures = [structure] if single else list(structure)
     if properties:
@@ -666,9 +684,16 @@ def predict(
         graphs, failed = build_graphs(structures, r_cut=r_cut, on_gpu=True, pbc=pbc)
         if failed:
             raise RuntimeError(f"Cannot build the graph of structures {failed}.")
+        sink = [] if shielding else None
         preds = evaluate_atomic(model, graphs, batch_size=batch_size,
                                 tensor_target_name=config["data"]["tensor_target_name"],
-                                tensor_target_formula=config["data"]["tensor_target_formula"], r_cut=r_cut)
+                                tensor_target_formula=config["data"]["tensor_target_formula"], r_cut=r_cut, sink=sink)
+        if shielding:      # (from the forwards' device buffers; the list above is their host copy)
+            from .rank2 import rank2_properties
+
+            counts = [int(g["pos"].shape[0]) if isinstance(g, dict) else len(g[0]) for g in graphs]
+            ptr = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int64, device=sink[0].device)
+            return [t.numpy() for t in preds], rank2_properties(torch.cat(sink, dim=0), ptr=ptr)
         return [t.numpy() for t in preds]
     # fast path: the structures are packed into flat arrays slab by slab (PREDICT_SLAB structures each); while the
     # device runs the forwards of slab k the host packs slab k + 1 (a 1000-structure slab packs in 2-3 ms, its forwards
