@@ -2,7 +2,7 @@
 torch.autograd bindings of the HIP operators for the training step.
 
 The reference trains by autograd through e3nn's einsums and torch_scatter (model/model.py:276-372).  Here
-each operator's adjoint is a hand-written kernel (matten_amd/csrc/backward.hip); autograd only chains them
+each operator's adjoint is a hand-written kernel (matten_amd/csrc/tp_backward.hip, backward.hip); autograd only chains them
 and carries the cheap differentiable re-packings of the parameters (index + scale).  The radial MLP runs forward
 (matten_radial_mlp) and backward (matten_radial_mlp_bwd) on this library's own fp32-MFMA kernels; no library GEMM is
 left on the step (the 16-wide species embedding is an index lookup).

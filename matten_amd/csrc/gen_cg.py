@@ -303,6 +303,12 @@ def main():
     out.append("template <int L1, int G> struct Group;")
     out.append("#define MATTEN_FOR_EACH_GROUP(X) " + " ".join(
         f"X({l1}, {gi})" for l1, ranges in GROUPS.items() for gi in range(len(ranges))))
+    # the coupling triples X(L1, L2, L3): all of them, per input degree, and per input degree with every degree <= 2
+    lists = [("", lambda t: True)]
+    lists += [(f"_L1_{n}", lambda t, n=n: t[0] == n) for n in range(LMAX + 1)]
+    lists += [(f"_LE2_L1_{n}", lambda t, n=n: t[0] == n and max(t) <= 2) for n in range(3)]
+    for name, keep in lists:
+        out.append(f"#define MATTEN_FOR_EACH_TRIPLE{name}(X) " + " ".join(f"X({a}, {b}, {c})" for a, b, c in filter(keep, triples())))
     out.append("")
     for l1, groups in GROUPS.items():
         for gi, combos in enumerate(groups):

@@ -126,21 +126,7 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void tp_path_kernel(Args a, c
     for (int off = 32; off > 0; off >>= 1) maxdeg = max(maxdeg, __shfl_xor(maxdeg, off));
 
     switch (pe.triple) {
-        MATTEN_CASE(0, 0, 0) MATTEN_CASE(0, 1, 1) MATTEN_CASE(0, 2, 2) MATTEN_CASE(0, 3, 3) MATTEN_CASE(0, 4, 4)
-        MATTEN_CASE(1, 0, 1) MATTEN_CASE(1, 1, 0) MATTEN_CASE(1, 1, 1) MATTEN_CASE(1, 1, 2) MATTEN_CASE(1, 2, 1)
-        MATTEN_CASE(1, 2, 2) MATTEN_CASE(1, 2, 3) MATTEN_CASE(1, 3, 2) MATTEN_CASE(1, 3, 3) MATTEN_CASE(1, 3, 4)
-        MATTEN_CASE(1, 4, 3) MATTEN_CASE(1, 4, 4)
-        MATTEN_CASE(2, 0, 2) MATTEN_CASE(2, 1, 1) MATTEN_CASE(2, 1, 2) MATTEN_CASE(2, 1, 3) MATTEN_CASE(2, 2, 0)
-        MATTEN_CASE(2, 2, 1) MATTEN_CASE(2, 2, 2) MATTEN_CASE(2, 2, 3) MATTEN_CASE(2, 2, 4) MATTEN_CASE(2, 3, 1)
-        MATTEN_CASE(2, 3, 2) MATTEN_CASE(2, 3, 3) MATTEN_CASE(2, 3, 4) MATTEN_CASE(2, 4, 2) MATTEN_CASE(2, 4, 3)
-        MATTEN_CASE(2, 4, 4)
-        MATTEN_CASE(3, 0, 3) MATTEN_CASE(3, 1, 2) MATTEN_CASE(3, 1, 3) MATTEN_CASE(3, 1, 4) MATTEN_CASE(3, 2, 1)
-        MATTEN_CASE(3, 2, 2) MATTEN_CASE(3, 2, 3) MATTEN_CASE(3, 2, 4) MATTEN_CASE(3, 3, 0) MATTEN_CASE(3, 3, 1)
-        MATTEN_CASE(3, 3, 2) MATTEN_CASE(3, 3, 3) MATTEN_CASE(3, 3, 4) MATTEN_CASE(3, 4, 1) MATTEN_CASE(3, 4, 2)
-        MATTEN_CASE(3, 4, 3) MATTEN_CASE(3, 4, 4)
-        MATTEN_CASE(4, 0, 4) MATTEN_CASE(4, 1, 3) MATTEN_CASE(4, 1, 4) MATTEN_CASE(4, 2, 2) MATTEN_CASE(4, 2, 3)
-        MATTEN_CASE(4, 2, 4) MATTEN_CASE(4, 3, 1) MATTEN_CASE(4, 3, 2) MATTEN_CASE(4, 3, 3) MATTEN_CASE(4, 3, 4)
-        MATTEN_CASE(4, 4, 0) MATTEN_CASE(4, 4, 1) MATTEN_CASE(4, 4, 2) MATTEN_CASE(4, 4, 3) MATTEN_CASE(4, 4, 4)
+        MATTEN_FOR_EACH_TRIPLE(MATTEN_CASE)
         default: break;
     }
 }

@@ -1157,25 +1157,20 @@ def tp_backward_lit(x, w_edge, sh_sorted, src_sorted, dst_sorted, blocks, paths,
     dw = torch.empty(E, dw_ld, dtype=dw_dtype, device=x.device)
     if num_neigh is not None:
         num_neigh = _need(num_neigh, torch.float32, "num_neigh")
-    if wfree is not None:
-        with _timed(f"tp_backward/d_mid={g_agg.shape[1]}/d_in={d_in}"):
-            rc = lib.matten_tp_backward_lit_wfree(_ptr(x), d_in, _ptr(h2s), _ptr(frag), _ptr(w_inv), _ptr(sh_sorted),
-                                                  sh_sorted.shape[1], _ptr(src_sorted), _ptr(dst_sorted), _ptr(blocks),
-                                                  blocks.shape[0], int(sum_lanes), _ptr(paths), paths.shape[0], _ptr(g_agg),
-                                                  g_agg.shape[1], float(avg_num_neighbors or 0.0), _ptr(num_neigh), E, _ptr(dx),
-                                                  _ptr(dw), dw_ld, int(dw_dtype == torch.bfloat16), N, _ptr(out_ptr),
-                                                  _ptr(out_perm), _ptr(dx_edges), int(lds_floats), int(max_l), int(max_mul),
-                                                  _stream())
-        _lib.check(rc, "matten_tp_backward_lit_wfree")
-        return dx, dw
+    # the run of arguments the two entries share, from sh_sorted to dx_edges
+    shared = (_ptr(sh_sorted), sh_sorted.shape[1], _ptr(src_sorted), _ptr(dst_sorted), _ptr(blocks), blocks.shape[0],
+              int(sum_lanes), _ptr(paths), paths.shape[0], _ptr(g_agg), g_agg.shape[1], float(avg_num_neighbors or 0.0),
+              _ptr(num_neigh), E, _ptr(dx), _ptr(dw), dw_ld, int(dw_dtype == torch.bfloat16), N, _ptr(out_ptr), _ptr(out_perm),
+              _ptr(dx_edges))
     with _timed(f"tp_backward/d_mid={g_agg.shape[1]}/d_in={d_in}"):
-        rc = lib.matten_tp_backward_lit(_ptr(x), d_in, _ptr(w_edge), w_edge.shape[1], _ptr(sh_sorted), sh_sorted.shape[1],
-                                        _ptr(src_sorted), _ptr(dst_sorted), _ptr(blocks), blocks.shape[0], int(sum_lanes),
-                                        _ptr(paths), paths.shape[0], _ptr(g_agg), g_agg.shape[1],
-                                        float(avg_num_neighbors or 0.0), _ptr(num_neigh), E, _ptr(dx), _ptr(dw),
-                                        dw.shape[1], int(w_edge.dtype == torch.bfloat16), N, _ptr(out_ptr), _ptr(out_perm),
-                                        _ptr(dx_edges), int(max_l), _stream())
-    _lib.check(rc, "matten_tp_backward_lit")
+        if wfree is not None:
+            entry = "matten_tp_backward_lit_wfree"
+            rc = lib.matten_tp_backward_lit_wfree(_ptr(x), d_in, _ptr(h2s), _ptr(frag), _ptr(w_inv), *shared, int(lds_floats),
+                                                  int(max_l), int(max_mul), _stream())
+        else:
+            entry = "matten_tp_backward_lit"
+            rc = lib.matten_tp_backward_lit(_ptr(x), d_in, _ptr(w_edge), dw_ld, *shared, int(max_l), _stream())
+    _lib.check(rc, entry)
     return dx, dw
 
 

@@ -1,5 +1,5 @@
 """
-The tensor-product adjoint (csrc/backward.hip) at the operator level, per edge and per path, against a plain fp64 reference.
+The tensor-product adjoint (csrc/tp_backward.hip) at the operator level, per edge and per path, against a plain fp64 reference.
 
     agg[n] = norm(n) * sum_{e: dst(e) = n} uvu(x[src(e)], Y[e], w[e]),   norm(n) = 1/sqrt(avg) or 1/sqrt(num_neigh[n])
 
@@ -391,3 +391,84 @@ def test_adjoint_identity_and_forward(case):
         # bf16 dw: every value rounded to 8 bits, i.e. by at most 2^-9 of itself
         tol_w = tol + (BF16_REL * wdw_terms.abs().sum().item() if c.bf16 else 0.0)
         assert abs(wdw - ga) <= tol_w, f"{c.name} {route}: <dw, w> = {wdw:.9e} vs <g, agg> = {ga:.9e} (allowed {tol_w:.3e})"
+
+
+def test_entry_points_refuse_bad_arguments_before_any_launch():
+    """The argument contract of matten_tp_backward_lit, _lit_wfree (one launcher body behind both) and _sh, called through the
+    C ABI on the `uncovered` plan with E = 4, N = 3 and every buffer valid: each bad argument alone gives MATTEN_EINVAL with
+    dx / dw / dy untouched; an empty batch zeroes dx in the ordered mode (out_ptr marks it) and touches nothing otherwise."""
+    from matten_amd import _lib, ops, plan as mplan
+    from matten_amd.nn._tables import DeviceTables
+
+    lib = _lib.load()
+    irreps_in, lmax, target = IRREPS["uncovered"]
+    p = mplan.plan_uvu(irreps_in, _sh_irreps(lmax), target)
+    t = DeviceTables(bw_blocks=p.bw_blocks, bw_paths=p.bw_paths, bw_w_entries=p.bw_w_entries)
+    blocks, paths = t.get("bw_blocks", DEV), t.get("bw_paths", DEV)
+    E, N, W = 4, 3, p.weight_numel
+    ld = (W + 16) // 16 * 16
+    gen = torch.Generator().manual_seed(7)
+    rnd = lambda *shape: torch.randn(*shape, generator=gen).to(DEV)
+    x, g, w, Y = rnd(N, p.d_in), rnd(N, p.d_mid), rnd(E, ld), rnd(E, SH_STRIDE)
+    src = torch.tensor([0, 1, 1, 2], dtype=torch.int32, device=DEV)
+    dst = torch.tensor([0, 0, 1, 2], dtype=torch.int32, device=DEV)
+    out_ptr = torch.tensor([0, 1, 3, 4], dtype=torch.int32, device=DEV)
+    out_perm = torch.arange(E, dtype=torch.int32, device=DEV)
+    num_neigh = torch.tensor([2.0, 1.0, 1.0], device=DEV)
+    h2s = ops.split_hidden(rnd(E, 32))
+    W2p = torch.zeros(32, ld)
+    W2p[:, :W] = torch.randn(32, W, generator=gen)
+    frag, w_inv = ops.split_a_tiles_dev(W2p.to(DEV), t.get("bw_w_entries", DEV), p.bw_a_tiles)
+    SENTINEL = 7.0
+    dx, dx_edges = torch.empty(N, p.d_in, device=DEV), torch.zeros(E, p.d_in, device=DEV)   # (zeros: the 4e block has no path)
+    dw, dy = torch.empty(E, ld, device=DEV), torch.empty(E, SH_STRIDE, device=DEV)
+    outs = (dx, dw, dy)
+    ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
+
+    shared = dict(sh=Y, sh_stride=SH_STRIDE, src=src, dst=dst, blocks=blocks, n_blocks=blocks.shape[0], sum_lanes=p.bw_sum_lanes,
+                  paths=paths, n_paths=paths.shape[0], g_agg=g, d_mid=p.d_mid, avg=AVG, num_neigh=num_neigh, n_edges=E, dx=dx,
+                  dw=dw, dw_ld=ld, bf16=0, n_nodes=N, out_ptr=out_ptr, out_perm=out_perm, dx_edges=dx_edges)
+    base = {
+        "lit": dict(x=x, d_in=p.d_in, w_edge=w, w_ld=ld, **shared, max_l=p.bw_max_l),
+        "wfree": dict(x=x, d_in=p.d_in, h2s=h2s, frag=frag, w_inv=w_inv, **shared, lds_floats=p.bw_wfree_lds_floats,
+                      max_l=p.bw_max_l, max_mul=p.bw_max_mul),
+        "sh": dict(x=x, d_in=p.d_in, w_edge=w, w_ld=ld, src=src, dst=dst, blocks=blocks, n_blocks=blocks.shape[0],
+                   max_mul=p.bw_max_mul, paths=paths, n_paths=paths.shape[0], g_agg=g, d_mid=p.d_mid, avg=AVG,
+                   num_neigh=num_neigh, n_edges=E, bf16=0, dy=dy, sh_stride=SH_STRIDE, max_l=p.bw_max_l),
+    }
+    entry = {"lit": lib.matten_tp_backward_lit, "wfree": lib.matten_tp_backward_lit_wfree, "sh": lib.matten_tp_backward_sh}
+
+    def call(kind, **change):
+        """-> the entry's return code with `change` applied to the valid arguments; the outputs start as the sentinel"""
+        for o in outs:
+            o.fill_(SENTINEL)
+        args = dict(base[kind], **change)
+        rc = entry[kind](*(ptr(v) for v in args.values()), ops._stream())
+        torch.cuda.synchronize()
+        return rc
+
+    def untouched():
+        return all(bool((o == SENTINEL).all()) for o in outs)
+
+    n_blocks = blocks.shape[0]
+    both = [dict(n_blocks=0), dict(n_paths=0), dict(d_mid=0), dict(dw_ld=0), dict(sum_lanes=0), dict(out_ptr=None),
+            dict(avg=0.0, num_neigh=None)]
+    bad = {
+        "lit": both + [dict(w_ld=0), dict(sum_lanes=4096 * n_blocks + 1), dict(w_edge=None)],
+        "wfree": both + [dict(sum_lanes=256 * n_blocks + 1), dict(lds_floats=2047), dict(lds_floats=15 * 1024 + 1),
+                         dict(max_mul=0), dict(max_mul=257), dict(h2s=None), dict(frag=None), dict(w_inv=None)],
+        "sh": [dict(sh_stride=8, max_l=2), dict(sh_stride=24, max_l=3), dict(max_l=5), dict(max_mul=0)],
+    }
+    for kind, changes in bad.items():
+        for change in changes:
+            assert call(kind, **change) == -1, (kind, change)          # MATTEN_EINVAL
+            assert untouched(), (kind, change)
+    for kind in ("lit", "wfree"):
+        assert call(kind, n_edges=0) == 0, kind                        # ordered mode: nobody else initialises dx
+        assert bool((dx == 0).all()) and bool((dw == SENTINEL).all()), kind
+        assert call(kind, n_edges=0, out_ptr=None, out_perm=None, dx_edges=None) == 0, kind
+        assert untouched(), kind
+    # the valid arguments themselves are accepted, so each refusal above is the changed argument's
+    for kind, out in (("lit", dx), ("wfree", dx), ("sh", dy)):
+        assert call(kind) == 0, kind
+        assert not bool((out == SENTINEL).any()), kind

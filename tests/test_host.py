@@ -755,6 +755,24 @@ def test_alternative_coupling_groups_are_taken_only_by_blocks_they_cover():
     listed = re.search(r"#define MATTEN_FOR_EACH_GROUP\(X\) (.*)", header).group(1)
     want = " ".join(f"X({l1}, {gi})" for l1, g in mplan.TP_GROUPS.items() for gi in range(len(g)))
     assert listed.strip() == want, "cg_gen.h is stale: python matten_amd/csrc/gen_cg.py > matten_amd/csrc/cg_gen.h"
+    # the coupling-triple lists the kernels switch over (tp_path.hip, tp_backward.hip): gen_cg.triples(), filtered
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_cg", os.path.join(ROOT, "matten_amd", "csrc", "gen_cg.py"))
+    gen_cg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen_cg)
+
+    def triples_of(name):
+        body = re.search(rf"#define MATTEN_FOR_EACH_TRIPLE{name}\(X\) (.*)", header).group(1)
+        return [tuple(int(v) for v in t) for t in re.findall(r"X\((\d), (\d), (\d)\)", body)]
+
+    every = list(gen_cg.triples())
+    assert triples_of("") == every and len(every) == 65
+    per_l1 = [triples_of(f"_L1_{n}") for n in range(5)]
+    assert per_l1 == [[t for t in every if t[0] == n] for n in range(5)]
+    assert tuple(len(l) for l in per_l1) == (5, 12, 16, 17, 15)
+    le2 = [triples_of(f"_LE2_L1_{n}") for n in range(3)]
+    assert le2 == [[t for t in every if t[0] == n and max(t) <= 2] for n in range(3)]
+    assert tuple(len(l) for l in le2) == (3, 6, 6)
 
 
 def test_inline_asm_mfma_objects_keep_their_hazard_distance(tmp_path):

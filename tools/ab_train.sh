@@ -1,10 +1,10 @@
 #!/bin/bash
 # A/B over compile flags of ONE source file on the batch-2048 training step (tools/train_b2048.py): step time and the HIP-event
-# times of the tensor-product kernels.   FLAGSETS="|-DX=1" SRC=backward REPS=2 bash tools/ab_train.sh
+# times of the tensor-product kernels.   FLAGSETS="|-DX=1" SRC=tp_backward REPS=2 bash tools/ab_train.sh
 cd "$GRAFT_REPO_ROOT/matten_amd/csrc" || exit 1
 make -j8 > /dev/null 2>&1
 source ../../tools/_restore.sh
-SRC=${SRC:-backward}
+SRC=${SRC:-tp_backward}
 IFS='|' read -ra SETS <<< "${FLAGSETS:-|}"
 i=0
 for fl in "${SETS[@]}"; do
