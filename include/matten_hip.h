@@ -981,6 +981,31 @@ int matten_selected_loss(const float* pred, const float* target, const int32_t* 
 int matten_selected_loss_bwd(const float* pred, const float* target, const int32_t* selector, int64_t n_rows, int64_t d,
                              int kind, const float* g, const int64_t* count, float* grad_pred, matten_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Loss and metric sums over the VALID rows of a padded crystal batch: the crystal-level twin of matten_selected_loss.
+ * The real rows of pred / target ([n_rows, d], fp32, contiguous) are [0, *n_valid); n_valid is a device word (the B word
+ * of a padded batch's `_amd_n_valid`, which the gather kernel writes and every replay of a captured step refreshes) and
+ * is clamped to [0, n_rows].  One pass produces what a step's loss and its mean-absolute-error metric need:
+ *   sums  (fp64 [2], device) sums[0] = sum (p - t)^2, sums[1] = sum |p - t| over the valid rows and their d columns
+ *   count (int64, device)    the number of valid rows = clamp(*n_valid, 0, n_rows)
+ *   loss  (fp32, device)     sums[kind] / (count * d), rounded once; count == 0 gives 0
+ * Arithmetic, element order and reduction are matten_selected_loss's (the same kernels, another row predicate): with
+ * selector[row] = (row < *n_valid) that entry gives the same bits for sums[kind], count and loss.  A row at or beyond
+ * *n_valid is loaded but never enters the arithmetic (a select: NaN / Inf there changes no output bit).  At most two
+ * launches, no floating-point atomics, no host read, no allocation.
+ *   workspace: matten_valid_loss_workspace_bytes(n_rows, d) bytes, 8-byte aligned (0 bytes: may be NULL).
+ * matten_valid_loss_bwd: grad_pred[i, c] = g * dl(pred - target) / (count * d) on valid rows (dl = 2x, or sign(x) with
+ * sign(0) = 0), formed in fp64 and rounded once, and +0.0 on every other row; count == 0 writes zeros.  g (fp32) and
+ * count (the forward's word) are read from device memory.  One elementwise launch.
+ * MATTEN_EINVAL / MATTEN_ENOMEM: as matten_selected_loss, and a NULL or misaligned n_valid.  n_rows == 0 writes zeros.
+ * ------------------------------------------------------------------------------------------ */
+size_t matten_valid_loss_workspace_bytes(int64_t n_rows, int64_t d);
+int matten_valid_loss(const float* pred, const float* target, const int64_t* n_valid, int64_t n_rows, int64_t d,
+                      int kind, double* sums, int64_t* count, float* loss, void* workspace, size_t workspace_bytes,
+                      matten_stream_t stream);
+int matten_valid_loss_bwd(const float* pred, const float* target, const int64_t* n_valid, int64_t n_rows, int64_t d,
+                          int kind, const float* g, const int64_t* count, float* grad_pred, matten_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

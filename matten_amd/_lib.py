@@ -143,6 +143,9 @@ SIGNATURES = {
     "matten_selected_loss_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "matten_selected_loss": (c_int, [P, P, P, c_int64, c_int64, c_int, P, P, P, P, c_size_t, P]),
     "matten_selected_loss_bwd": (c_int, [P, P, P, c_int64, c_int64, c_int, P, P, P, P]),
+    "matten_valid_loss_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "matten_valid_loss": (c_int, [P, P, P, c_int64, c_int64, c_int, P, P, P, P, c_size_t, P]),
+    "matten_valid_loss_bwd": (c_int, [P, P, P, c_int64, c_int64, c_int, P, P, P, P]),
 }
 
 _lib = None

@@ -593,6 +593,27 @@ class SelectedLossFn(torch.autograd.Function):
         return ops.selected_loss_bwd(pred, target, selector, ctx.kind, g.contiguous(), count), None, None, None
 
 
+class ValidLossFn(torch.autograd.Function):
+    """(loss, sums, count) = matten_valid_loss(pred, target, n_valid, kind): the mean loss over the rows [0, *n_valid) of a
+    padded crystal batch, with its adjoint kernel (matten_valid_loss_bwd).  ``n_valid`` is the device word
+    ``batch["_amd_n_valid"][2:3]``.  Only ``pred`` receives a gradient; ``sums`` (fp64 [2]: squared, absolute -- what the
+    mean-absolute-error metric adds) and ``count`` (int64) carry none.  Nothing is read back, so forward and backward
+    capture into a hipGraph and a replay follows the refreshed word."""
+
+    @staticmethod
+    def forward(ctx, pred, target, n_valid, kind):
+        loss, sums, count = ops.valid_loss(pred, target, n_valid, kind)
+        ctx.kind = kind
+        ctx.save_for_backward(pred, target, n_valid, count)
+        ctx.mark_non_differentiable(sums, count)
+        return loss, sums, count
+
+    @staticmethod
+    def backward(ctx, g, _g_sums, _g_count):
+        pred, target, n_valid, count = ctx.saved_tensors
+        return ops.valid_loss_bwd(pred, target, n_valid, ctx.kind, g.contiguous(), count), None, None, None
+
+
 def needs_grad(*tensors: Optional[torch.Tensor]) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 

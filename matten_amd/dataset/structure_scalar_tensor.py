@@ -11,6 +11,11 @@ labels are stored: "compact" is the reference's ([M, d] targets + a ``bool`` sel
 "dense" keeps one target row per atom (zeros where unselected) + an ``int32`` selector, which the device store, the
 padded batches and the selected-loss kernels take as ordinary per-node keys.  The selector's dtype picks the route.
 
+Padding: ``device_resident=True`` with ``loader_kwargs["pad"] = (node_quantum, edge_quantum)`` pads every TRAINING batch to a
+few bucket shapes; ``pad_eval=True`` pads the validation and test batches the same way (unshuffled as ever), so that
+``matten_amd.model.trainer.Trainer(graphed=True)`` replays captured steps in all three loops.  A model that sees padded
+batches must keep the padding crystals out of loss and metric: ``BaseModel.loss_over_valid_rows``.
+
 Not carried over (outside the path; ``NotImplementedError`` when asked for): featurizers (``global_featurizer``,
 ``atom_featurizer``), scalar targets, on-disk caching (``reuse``); target normalisation is available through
 ``normalize_tensor_target`` + ``matten_amd.data.transform`` (crystal targets only).
@@ -114,6 +119,7 @@ class TensorDataModule:
         device_resident: bool = False,
         atom_selector: Optional[str] = None,
         atom_target_layout: Optional[str] = None,
+        pad_eval: bool = False,
         **unsupported,
     ):
         bad = {k: v for k, v in unsupported.items() if v not in (None, False, [], {})
@@ -148,6 +154,15 @@ class TensorDataModule:
         if self.loader_kwargs.get("pad") is not None and not self.device_resident:
             raise ValueError("loader_kwargs['pad'] pads batches in the device loader's gather: it needs device_resident=True "
                              "(the host loader does not pad)")
+        # pad_eval: the validation and test loaders pad like the training loader (a few bucket shapes: their steps replay
+        # captured graphs, Trainer(graphed=True)); the model then needs loss_over_valid_rows, which that Trainer sets
+        self.pad_eval = bool(pad_eval)
+        if self.pad_eval:
+            missing = [what for what, ok in (("device_resident=True", self.device_resident),
+                                             ("loader_kwargs['pad']", self.loader_kwargs.get("pad") is not None)) if not ok]
+            if missing:
+                raise ValueError(f"pad_eval=True pads the validation and test batches in the device loader's gather: it needs "
+                                 f"{' and '.join(missing)}")
         self._data: Dict[str, List[Dict[str, torch.Tensor]]] = {}
         self._stores: Dict[str, Any] = {}
 
@@ -226,10 +241,12 @@ class TensorDataModule:
         return _Loader(self._data["train"], device=self.device, **self.loader_kwargs)
 
     def _eval_kwargs(self) -> Dict[str, Any]:
-        """validation and test batches are never padded (`pad` serves the captured training step)"""
+        """validation and test batches are unshuffled, and unpadded (`pad` serves the captured training step) unless
+        ``pad_eval`` keeps `pad`, `pad_species` and `pad_length` for them"""
         kw = dict(self.loader_kwargs, shuffle=False)
-        for k in ("pad", "pad_species", "pad_length"):
-            kw.pop(k, None)
+        if not self.pad_eval:
+            for k in ("pad", "pad_species", "pad_length"):
+                kw.pop(k, None)
         return kw
 
     def val_dataloader(self):

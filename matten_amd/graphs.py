@@ -24,7 +24,7 @@ from typing import Callable, Dict
 
 import torch
 
-from .nn._tables import bump_weights_epoch
+from .nn._tables import bump_weights_epoch, record_derived, refresh_derived
 
 
 # rocPRIM's radix sort switches algorithm above 2^20 keys and that path does not survive a capture on this ROCm (memory
@@ -102,6 +102,32 @@ def padded_mean_loss(fn: Callable, key: str = None) -> Callable:
         keep = (torch.arange(rows, device=per.device) < n_real).view((rows,) + (1,) * (per.dim() - 1))
         kept = torch.where(keep, per, torch.zeros((), dtype=per.dtype, device=per.device))
         return kept.sum() / (n_real * (per.numel() // max(rows, 1))).to(per.dtype)
+
+    loss.wants_batch = True
+    return loss
+
+
+def valid_mean_loss(kind="mse", key: str = None) -> Callable:
+    """The mean loss over the REAL crystals of a padded batch in one kernel: the counterpart of ``padded_mean_loss`` for
+    squared and absolute error.
+
+    `kind`: "mse" or "mae"; `key` picks the prediction out of the model's dict.  The returned
+    ``loss(preds, target, batch)`` hands the crystal-count word ``batch["_amd_n_valid"][2:3]`` -- inside a captured step a
+    view of the captured buffer, which every replay refreshes -- to ``autograd.ValidLossFn``: one kernel forward (two
+    launches above one tile of elements), one backward, fp64 sums in a fixed order, nothing read back.  A padding row
+    never enters the arithmetic, NaN included, and gets a +0.0 gradient."""
+    from .autograd import ValidLossFn
+    from .ops import LOSS_KINDS
+
+    if kind not in LOSS_KINDS or isinstance(kind, bool):
+        raise ValueError(f"kind = {kind!r}: 'mse' or 'mae'")
+    code = LOSS_KINDS[kind]
+
+    def loss(preds, target, batch):
+        if "_amd_n_valid" not in batch:
+            raise ValueError("valid_mean_loss needs a padded batch (DeviceGraphStore.batch(pad_to=...) or "
+                             "_DeviceLoader(pad=...)): this batch has no '_amd_n_valid'")
+        return ValidLossFn.apply(preds[key] if key is not None else preds, target, batch["_amd_n_valid"][2:3], code)[0]
 
     loss.wants_batch = True
     return loss
@@ -187,16 +213,32 @@ class GraphedTrainStep:
                  warmup: int = 3, task_name: str = "elastic_tensor_full"):
         _check_capturable(batch)
         self.model, self.optimizer, self.loss_fn, self.task_name = model, optimizer, loss_fn, task_name
-        dev = target.device
         self._static = {k: v.clone() if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
         self._target = target.clone()
+        self._capture(target.device, warmup)
+
+    def _model_state(self) -> dict:
+        """the model tensors the step mutates (snapshotted before the warm-up steps, restored in place after them)"""
+        return self.model.state_dict()
+
+    def _extra_state(self) -> list:
+        """tensors the step mutates beyond model.state_dict() and the optimiser state (snapshotted and restored with them)"""
+        return []
+
+    def _capture(self, dev, warmup: int) -> None:
+        """warm up `self._eager_step` on a side stream, put back in place what the warm-up steps changed, and capture one
+        more call of it; its return value becomes ``self._loss``"""
+        model, optimizer = self.model, self.optimizer
         embeds = [m for m in model.modules() if hasattr(m, "check_species")]
         self._embeds = embeds
+        opt_state = optimizer.state if optimizer is not None else {}
         # the warm-up steps below are real optimiser steps: snapshot what they mutate
         with torch.no_grad():
-            snap_model = {k: v.detach().clone() for k, v in model.state_dict().items()}
+            snap_model = {k: v.detach().clone() for k, v in self._model_state().items()}
             snap_opt = {p: {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in st.items()}
-                        for p, st in optimizer.state.items()}
+                        for p, st in opt_state.items()}
+            extra = self._extra_state()
+            snap_extra = [v.detach().clone() for v in extra]
         # warm-up on a side stream (allocator pools, lazily built tables), with the range checks on
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -205,9 +247,11 @@ class GraphedTrainStep:
                 self._eager_step()
             # restore in place: the capture below must see the tensors the warm-up allocated (optimiser moments, step)
             with torch.no_grad():
-                for k, v in model.state_dict().items():
+                for k, v in self._model_state().items():
                     v.copy_(snap_model[k])
-                for p, st in optimizer.state.items():
+                for v, old in zip(extra, snap_extra):
+                    v.copy_(old)
+                for p, st in opt_state.items():
                     old = snap_opt.get(p)
                     for k, v in st.items():
                         if isinstance(v, torch.Tensor):
@@ -224,7 +268,8 @@ class GraphedTrainStep:
             m.check_species = False   # validated above; a host sync cannot be captured
         try:
             self.graph = torch.cuda.CUDAGraph()
-            self.optimizer.zero_grad(set_to_none=True)
+            if optimizer is not None:
+                optimizer.zero_grad(set_to_none=True)
             with torch.cuda.graph(self.graph):
                 self._loss = self._eager_step()
         finally:
@@ -290,6 +335,151 @@ class BucketedTrainStep:
         else:
             self.replays += 1
         return graphed.step(batch, target, validate=validate)
+
+
+MODEL_STEP_MODES = {"train": "training_step", "val": "validation_step", "test": "test_step"}
+
+
+def _model_step(model, mode: str, optimizer, batch, batch_idx: int = 0):
+    """the model's OWN step as it is captured, and as it runs eagerly: ``training_step`` (loss, logging, metric update),
+    backward and the optimiser for "train"; ``validation_step`` / ``test_step`` without gradients for "val" / "test"""
+    fn = getattr(model, MODEL_STEP_MODES[mode])
+    if mode != "train":
+        with torch.no_grad():
+            return fn(batch, batch_idx)["loss"]
+    loss = fn(batch, batch_idx)["loss"]
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    optimizer.step()
+    return loss
+
+
+def _check_model_step(model, mode: str, optimizer) -> None:
+    if mode not in MODEL_STEP_MODES:
+        raise ValueError(f"mode = {mode!r}: one of {sorted(MODEL_STEP_MODES)}")
+    if (mode == "train") != (optimizer is not None):
+        raise ValueError('mode "train" takes the optimizer its steps drive; "val" and "test" take none')
+    if not hasattr(model, MODEL_STEP_MODES[mode]):
+        raise TypeError(f"{type(model).__name__} has no {MODEL_STEP_MODES[mode]}: a model step captures the training shell "
+                        f"of matten_amd.model.model.BaseModel")
+    if bool(model.training) != (mode == "train"):
+        raise ValueError(f'a "{mode}" step runs the model in {"training" if mode == "train" else "eval"} mode: call '
+                         f'model.{"train" if mode == "train" else "eval"}() first (a captured step keeps the mode it saw)')
+
+
+class GraphedModelStep(GraphedTrainStep):
+    """``GraphedTrainStep`` around the model's own step in place of ``model(batch)`` plus a loss function: mode "train"
+    captures ``model.training_step(batch, i)["loss"]``, ``zero_grad``, ``backward`` and ``optimizer.step()``; "val" and
+    "test" capture ``model.validation_step`` / ``model.test_step`` under ``no_grad``.  The labels travel inside the batch.
+
+    Two things such a step does beyond a forward and a loss are kept right across warm-up, capture and replay:
+
+    * the metric accumulators (``model.metrics``: non-persistent buffers, so not in ``state_dict``) are snapshotted and put
+      back in place with the parameters -- the warm-up steps leave no trace in the epoch's metric, and the replayed
+      in-place adds land in the buffers ``compute()`` and ``reset()`` use;
+    * ``model.log`` runs at capture time only.  The step keeps what it logged (``{mode}/total_loss``, ``{mode}/loss/<task>``:
+      tensors of ITS graph) and re-installs it in ``model.logged`` after each replay: pointer swaps, no host read.
+
+    A "val" / "test" step reads the weight-derived packs (packed radial layers, folded BatchNorm) that its warm-up left in
+    the caches of ``nn._tables``; it records which, pins them (they refresh in place from then on) and re-derives the stale
+    ones before each replay, so a replay follows the weights of the moment like an eager eval forward."""
+
+    def __init__(self, model, mode: str, optimizer, batch: Dict[str, torch.Tensor], warmup: int = 3, batch_idx: int = 0):
+        _check_model_step(model, mode, optimizer)
+        _check_capturable(batch)
+        self.model, self.mode, self.optimizer, self.batch_idx = model, mode, optimizer, int(batch_idx)
+        self._static = {k: v.clone() if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
+        dev = self._static["pos"].device
+        outer = getattr(model, "logged", None)
+        keep = isinstance(outer, dict)
+        if keep:
+            model.logged = {}   # what warm-up and capture log stays with this step
+        try:
+            self._capture(dev, warmup)
+        finally:
+            self._logged = {}
+            if keep:
+                self._logged, model.logged = model.logged, outer
+            if mode == "train":
+                bump_weights_epoch()   # (a pack derived during the capture has not been computed yet)
+
+    def _model_state(self) -> dict:
+        # an eval-mode step under no_grad writes no parameter and no running statistic; putting them "back" would move
+        # their version counters, and the capture would re-derive every pack inside the graph instead of reading it
+        return self.model.state_dict() if self.mode == "train" else {}
+
+    def _extra_state(self) -> list:
+        metrics = getattr(self.model, "metrics", None)
+        return list(metrics.buffers()) if isinstance(metrics, torch.nn.Module) else []
+
+    def _eager_step(self):
+        if self.mode != "train" and torch.cuda.is_current_stream_capturing():
+            with record_derived() as self._derived:   # (all fresh after the warm-up: the capture reads them where they are)
+                return _model_step(self.model, self.mode, self.optimizer, self._static, self.batch_idx)
+        return _model_step(self.model, self.mode, self.optimizer, self._static, self.batch_idx)
+
+    def step(self, batch: Dict[str, torch.Tensor], validate: bool = False) -> torch.Tensor:
+        """copy the batch into the captured buffers (same tensors, shapes and dtypes) and replay; returns the captured loss
+        tensor and points ``model.logged`` at this graph's logged tensors.  `validate`: GraphedTrainStep.step's."""
+        _check_model_step(self.model, self.mode, self.optimizer)
+        _copy_batch(self._static, batch, "step")
+        if self.optimizer is not None and hasattr(self.optimizer, "sync_hyperparameters"):
+            self.optimizer.sync_hyperparameters()   # a scheduler's new learning rate reaches the device before the replay
+        if self.mode != "train":
+            refresh_derived(self._derived)   # the packs the graph reads, re-derived in place where the weights have moved
+        self.graph.replay()
+        if self.mode == "train":
+            bump_weights_epoch()   # the replayed optimiser step (and BatchNorm's running statistics) moved no _version counter
+        if isinstance(getattr(self.model, "logged", None), dict):
+            self.model.logged.update(self._logged)
+        if validate:
+            _raise_for_flags(self._embeds, self._static)
+        return self._loss
+
+
+class BucketedModelStep:
+    """``BucketedTrainStep`` for the model's own step (``GraphedModelStep``): one captured step per bucket
+    (N_b, E_b, B_b) of the padded device loader, eager ``training_step`` / ``validation_step`` / ``test_step`` beyond
+    `max_graphs` distinct buckets, and the same ``captures`` / ``replays`` / ``eager_steps`` counters.  A batch without
+    ``_amd_n_valid`` (an unpadded loader) is accepted: every shape is then its own bucket.
+
+    What ``matten_amd.model.trainer.Trainer(graphed=True)`` drives, one per mode; a Lightning user calls ``step`` from a
+    manual-optimisation ``training_step``."""
+
+    def __init__(self, model, mode: str, optimizer=None, max_graphs: int = 8, warmup: int = 2):
+        if mode not in MODEL_STEP_MODES:
+            raise ValueError(f"mode = {mode!r}: one of {sorted(MODEL_STEP_MODES)}")
+        if (mode == "train") != (optimizer is not None):
+            raise ValueError('mode "train" takes the optimizer its steps drive; "val" and "test" take none')
+        self.model, self.mode, self.optimizer = model, mode, optimizer
+        self.max_graphs, self.warmup = int(max_graphs), int(warmup)
+        self.graphs: Dict[tuple, GraphedModelStep] = {}
+        self.captures = self.replays = self.eager_steps = 0
+
+    bucket = staticmethod(BucketedTrainStep.bucket)
+
+    @property
+    def counts(self) -> Dict[str, int]:
+        return {"captures": self.captures, "replays": self.replays, "eager_steps": self.eager_steps}
+
+    def step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0, validate: bool = False) -> torch.Tensor:
+        """one step of the mode on `batch`; returns the loss tensor (a captured step's is overwritten by its next replay)"""
+        key = self.bucket(batch)
+        graphed = self.graphs.get(key)
+        if graphed is None and len(self.graphs) >= self.max_graphs:
+            self.eager_steps += 1
+            _check_model_step(self.model, self.mode, self.optimizer)
+            if self.optimizer is not None and hasattr(self.optimizer, "sync_hyperparameters"):
+                self.optimizer.sync_hyperparameters()   # (as before a replay)
+            return _model_step(self.model, self.mode, self.optimizer, batch, batch_idx)
+        if graphed is None:
+            # (the warm-up steps are undone, metric accumulators included: the replay below is this batch's one step)
+            graphed = self.graphs[key] = GraphedModelStep(self.model, self.mode, self.optimizer, batch, warmup=self.warmup,
+                                                          batch_idx=batch_idx)
+            self.captures += 1
+        else:
+            self.replays += 1
+        return graphed.step(batch, validate=validate)
 
 
 class GraphedForward:

@@ -98,6 +98,9 @@ def unfreeze_batchnorm(model):
 
 class BaseModel(_Base):
     monitor_key = "val/score"
+    # True: on a batch that carries `_amd_n_valid` (a padded batch of the device loader) loss and metric run over the real
+    # crystals only (compute_valid_loss).  Off by default; Trainer(graphed=True) switches it on for the run.
+    loss_over_valid_rows = False
 
     # ---- what a subclass's __init__ calls once backbone and tasks exist (reference model/model.py:66-99) ----
     def _init_training_shell(self, hparams: Dict[str, Any]) -> None:
@@ -175,6 +178,35 @@ class BaseModel(_Base):
             total_loss = total_loss + task.loss_weight * loss
         return individual_losses, total_loss
 
+    def compute_valid_loss(self, preds: Dict[str, Tensor], labels: Dict[str, Tensor], n_valid: Tensor, weight: Tensor = None):
+        """``compute_loss`` over the real crystals of a padded batch: the rows [0, *n_valid), `n_valid` being the crystal
+        word of ``batch["_amd_n_valid"]`` on the device (autograd.ValidLossFn; the twin of ``compute_selected_loss``).  The
+        padding crystals' targets are zero and their predictions are not: the model's plain mean would average them in.
+        Returns a third value beside the two of ``compute_loss``: per task, the tensors the kernel saw and its (sums,
+        count), which ``update_metrics`` reuses where the metric transforms hand it the same tensors."""
+        from ..autograd import ValidLossFn
+
+        if weight is not None:
+            raise NotImplementedError("target_weight with loss_over_valid_rows (the valid-rows loss of a padded batch) is "
+                                      "not supported")
+        individual_losses, total_loss, seen = {}, 0.0, {}
+        for task_name, task in self.tasks.items():
+            fn = self.loss_fns[task_name]
+            kind = _SELECTED_LOSS_KINDS.get(type(fn))
+            if task.task_type == TaskType.CLASSIFICATION or kind is None or getattr(fn, "reduction", "mean") != "mean":
+                raise NotImplementedError(f"loss_over_valid_rows: the valid-loss kernel computes the mean of MSELoss or "
+                                          f"L1Loss of a regression task, task '{task_name}' uses {fn!r}")
+            p = task.transform_pred_loss(preds[task_name])
+            l = task.transform_target_loss(labels[task_name])
+            if l.shape[0] != p.shape[0]:
+                raise ValueError(f"loss_over_valid_rows: '{task_name}' holds {l.shape[0]} target rows for {p.shape[0]} "
+                                 f"predicted crystals (a padded batch keeps one row per crystal, padding included)")
+            loss, sums, count = ValidLossFn.apply(p, l, n_valid, kind)
+            seen[task_name] = (p, l, sums, count)
+            individual_losses[task_name] = loss
+            total_loss = total_loss + task.loss_weight * loss
+        return individual_losses, total_loss, seen
+
     # ---- reference model/model.py:282-312 ----
     def training_step(self, batch, batch_idx):
         loss, preds, labels = self.shared_step(batch, "train")
@@ -214,6 +246,11 @@ class BaseModel(_Base):
         if _is_dense_selector(labels.get("atom_selector")):
             # dense per-atom labels (one target row per atom, integer selector): no indexing, no host read
             individual_loss, total_loss = self.compute_selected_loss(preds, labels, weight=target_weight)
+        elif self.loss_over_valid_rows and "_amd_n_valid" in graphs and "atom_selector" not in labels:
+            # a padded crystal batch: loss (and, through the labels, the metric) over the real crystals only
+            n_valid = graphs["_amd_n_valid"][2:3]
+            individual_loss, total_loss, seen = self.compute_valid_loss(preds, labels, n_valid, weight=target_weight)
+            labels = dict(labels, _amd_n_valid=n_valid, _amd_valid_sums=seen)
         else:
             if "atom_selector" in labels:
                 selector = labels["atom_selector"]
@@ -235,6 +272,21 @@ class BaseModel(_Base):
                 p = task.transform_pred_metric(preds[task_name])
                 l = task.transform_target_metric(labels[task_name])
                 metric(p.detach(), l.detach(), selector=selector)
+            return
+        n_valid = labels.get("_amd_n_valid")
+        if n_valid is not None:   # a padded crystal batch under loss_over_valid_rows: the metric skips the padding rows
+            seen = labels.get("_amd_valid_sums", {})
+            for task_name, metric in self.metrics["metric_" + mode].items():
+                task = self.tasks[task_name]
+                if task.task_type == TaskType.CLASSIFICATION:
+                    raise NotImplementedError("loss_over_valid_rows serves regression tasks")
+                p = task.transform_pred_metric(preds[task_name])
+                l = task.transform_target_metric(labels[task_name])
+                p_loss, l_loss, sums, count = seen.get(task_name, (None,) * 4)
+                if p is p_loss and l is l_loss:   # identity transforms (no normaliser): the loss's kernel call serves both
+                    metric(p.detach(), l.detach(), n_valid=n_valid, valid_sums=(sums, count))
+                else:
+                    metric(p.detach(), l.detach(), n_valid=n_valid)
             return
         for task_name, metric in self.metrics["metric_" + mode].items():
             task = self.tasks[task_name]

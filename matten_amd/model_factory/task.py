@@ -28,7 +28,24 @@ class MeanAbsoluteError(torch.nn.Module):
         self.register_buffer("sum_abs", torch.zeros((), dtype=torch.float64), persistent=False)
         self.register_buffer("count", torch.zeros((), dtype=torch.float64), persistent=False)
 
-    def forward(self, preds: Tensor, target: Tensor, selector: Tensor = None) -> None:
+    def forward(self, preds: Tensor, target: Tensor, selector: Tensor = None, n_valid: Tensor = None,
+                valid_sums=None) -> None:
+        if n_valid is not None:
+            # a padded crystal batch: |pred - target| over the rows [0, *n_valid) (matten_valid_loss; n_valid is the device
+            # word batch["_amd_n_valid"][2:3]).  `valid_sums` = the (sums, count) of a call the loss already made on these
+            # very tensors.  The fp64 sum and the row count are added on the device: nothing is read back.
+            if selector is not None:
+                raise ValueError("MeanAbsoluteError: selector and n_valid are two routes, pass one")
+            if valid_sums is None:
+                from .. import ops
+
+                _, sums, rows = ops.valid_loss(preds, target, n_valid, 1)
+            else:
+                sums, rows = valid_sums
+            per_row = preds.numel() // max(preds.shape[0], 1)
+            self.sum_abs += sums[1].to(self.sum_abs.device)
+            self.count += (rows * per_row).to(self.count)
+            return
         if selector is not None:
             # dense per-atom labels: |pred - target| over the rows an int32 selector flags (matten_selected_loss, kind 1).
             # Its fp64 sum and its row count are added on the device: nothing is read back.
@@ -57,9 +74,12 @@ class MeanAbsoluteError(torch.nn.Module):
 class MetricCollection(torch.nn.ModuleDict):
     """{metric class name: metric}; called with (preds, target) it updates every member (torchmetrics.MetricCollection)"""
 
-    def forward(self, preds: Tensor, target: Tensor, selector: Tensor = None) -> None:
+    def forward(self, preds: Tensor, target: Tensor, selector: Tensor = None, n_valid: Tensor = None,
+                valid_sums=None) -> None:
         for m in self.values():
-            if selector is None:
+            if n_valid is not None:
+                m(preds, target, n_valid=n_valid, valid_sums=valid_sums)
+            elif selector is None:
                 m(preds, target)
             else:
                 m(preds, target, selector=selector)

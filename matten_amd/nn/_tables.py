@@ -1,4 +1,5 @@
 """Device-resident copies of immutable plan tables, and version-tracked derived weights."""
+import contextlib
 from typing import Callable, Dict, Tuple
 
 import numpy as np
@@ -37,6 +38,50 @@ def weights_epoch() -> int:
     return _WEIGHTS_EPOCH[0]
 
 
+# A captured eval-mode step (graphs.GraphedModelStep, "val" / "test") reads the caches below as they are at capture time:
+# the graph holds the ADDRESSES of their tensors, and the weights move between its replays.  ``record_derived`` collects,
+# in order of use, every (cache, arguments) pair asked for inside its block and pins those caches: a pinned cache
+# refreshes IN PLACE, so the addresses stay good, and ``refresh_derived`` re-asks the recorded pairs (eagerly, before a
+# replay), which recomputes exactly the stale ones.  Nothing changes for a cache that was never recorded.
+_RECORDER = [None]
+
+
+@contextlib.contextmanager
+def record_derived():
+    outer, mine = _RECORDER[0], []
+    _RECORDER[0] = mine
+    try:
+        yield mine
+    finally:
+        _RECORDER[0] = outer
+
+
+def refresh_derived(recorded) -> None:
+    for cache, args in recorded:
+        cache.get(*args)
+
+
+def _record(cache, args) -> None:
+    rec = _RECORDER[0]
+    cache._pinned = True
+    if not any(c is cache and len(a) == len(args) and all(x is y for x, y in zip(a, args)) for c, a in rec):
+        rec.append((cache, args))
+
+
+def _refresh_in_place(old, new):
+    """copy `new` into the tensors of `old` (same nesting, shapes, dtypes and devices) and return `old`"""
+    if isinstance(old, torch.Tensor) and isinstance(new, torch.Tensor):
+        if old.device != new.device:
+            return new      # the model moved: steps captured on the old device are not its steps any more
+        if old.shape == new.shape and old.dtype == new.dtype and old.device == new.device:
+            return old.copy_(new)
+    elif isinstance(old, (tuple, list)) and type(old) is type(new) and len(old) == len(new):
+        return type(old)(_refresh_in_place(o, n) for o, n in zip(old, new))
+    elif not isinstance(new, torch.Tensor) and old == new:
+        return old
+    raise RuntimeError("a weight-derived pack that a captured step reads changed its layout; capture the step again")
+
+
 class DerivedWeight:
     """Caches f(*params) until any parameter changes (optimizer step, load_state_dict, .to(), or a raw in-place write
     announced through ``bump_weights_epoch``)."""
@@ -45,12 +90,16 @@ class DerivedWeight:
         self._fn = fn
         self._key = None
         self._val = None
+        self._pinned = False
 
     def get(self, *params: torch.Tensor):
+        if _RECORDER[0] is not None:
+            _record(self, params)
         key = (_WEIGHTS_EPOCH[0],) + tuple((p.data_ptr(), p._version, p.device, p.dtype) for p in params)
         if key != self._key:
             with torch.no_grad():
-                self._val = self._fn(*params)
+                val = self._fn(*params)
+                self._val = _refresh_in_place(self._val, val) if self._pinned and self._val is not None else val
             self._key = key
         return self._val
 
@@ -75,6 +124,8 @@ class WeightSlice:
         return w.index_select(self._dim, self._idx.get("idx", w.device))
 
     def get(self, w: torch.Tensor) -> torch.Tensor:
+        if _RECORDER[0] is not None:
+            _record(self, (w,))
         key = (_WEIGHTS_EPOCH[0], w.data_ptr(), w._version, w.device, w.dtype)
         if key != self._key:
             with torch.no_grad():

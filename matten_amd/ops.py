@@ -1496,6 +1496,87 @@ def selected_loss_bwd(pred, target, selector, kind, g, count) -> torch.Tensor:
     return grad
 
 
+def _valid_args(pred, target, n_valid, kind):
+    if kind not in LOSS_KINDS or isinstance(kind, bool):
+        raise ValueError(f"kind = {kind!r}: 0 / 'mse' (squared error) or 1 / 'mae' (absolute error)")
+    pred = _need(pred, torch.float32, "pred")
+    target = _need(target, torch.float32, "target")
+    n_valid = _need(n_valid, torch.int64, "n_valid")
+    if pred.dim() < 1 or n_valid.numel() != 1:
+        raise ValueError(f"n_valid {tuple(n_valid.shape)} is not one int64 word (batch['_amd_n_valid'][2:3]) or pred "
+                         f"{tuple(pred.shape)} has no rows")
+    if target.shape[0] != pred.shape[0] or target.numel() != pred.numel():
+        raise ValueError(f"target {tuple(target.shape)} and pred {tuple(pred.shape)} differ: a padded batch keeps one "
+                         f"target row per crystal, padding crystals included")
+    n_rows = pred.shape[0]
+    d = pred.numel() // n_rows if n_rows else max(1, int(np.prod(pred.shape[1:])))
+    return pred, target, n_valid, n_rows, d, LOSS_KINDS[kind]
+
+
+def valid_loss(pred, target, n_valid, kind=0):
+    """mean of the per-element loss over the rows [0, *n_valid) of a padded crystal batch, and the sums its metric keeps
+    (include/matten_hip.h: matten_valid_loss) -> (loss fp32 [], sums fp64 [2] = (squared, absolute), count int64 []), all
+    on the device; n_valid is a device word (``batch["_amd_n_valid"][2:3]``), clamped to [0, n_rows]"""
+    lib = _lib.load()
+    pred, target, n_valid, n_rows, d, kind = _valid_args(pred, target, n_valid, kind)
+    dev = pred.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    count = torch.empty((), dtype=torch.int64, device=dev)
+    nbytes = int(lib.matten_valid_loss_workspace_bytes(n_rows, d))
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev) if nbytes else None
+    _lib.check(lib.matten_valid_loss(_ptr(pred), _ptr(target), _ptr(n_valid), n_rows, d, kind, _ptr(sums), _ptr(count),
+                                     _ptr(loss), _ptr(ws), nbytes, _stream()), "matten_valid_loss")
+    return loss, sums, count
+
+
+def valid_loss_bwd(pred, target, n_valid, kind, g, count) -> torch.Tensor:
+    """the adjoint of valid_loss with respect to pred; g (fp32 []) and count (int64 [], the forward's) stay on the device"""
+    lib = _lib.load()
+    pred, target, n_valid, n_rows, d, kind = _valid_args(pred, target, n_valid, kind)
+    g = _need(g, torch.float32, "g")
+    count = _need(count, torch.int64, "count")
+    if g.numel() != 1 or count.numel() != 1:
+        raise ValueError("g and count are one word each")
+    grad = torch.empty_like(pred)
+    _lib.check(lib.matten_valid_loss_bwd(_ptr(pred), _ptr(target), _ptr(n_valid), n_rows, d, kind, _ptr(g), _ptr(count),
+                                         _ptr(grad), _stream()), "matten_valid_loss_bwd")
+    return grad
+
+
+def valid_loss_host(pred, target, n_valid: int, kind=0):
+    """numpy fp64 restatement of valid_loss (what the tests hold the kernel to): pred / target array-likes [n_rows, ...],
+    n_valid an integer -> (loss np.float32, sums np.float64 [2], count int).  Rows at or beyond n_valid are sliced away,
+    whatever they hold."""
+    if kind not in LOSS_KINDS or isinstance(kind, bool):
+        raise ValueError(f"kind = {kind!r}: 0 / 'mse' (squared error) or 1 / 'mae' (absolute error)")
+    p = np.asarray(pred, dtype=np.float64)
+    t = np.asarray(target, dtype=np.float64)
+    n_rows = p.shape[0]
+    count = min(max(int(n_valid), 0), n_rows)
+    x = p[:count] - t[:count]
+    d = max(1, int(np.prod(p.shape[1:])))
+    sums = np.array([np.sum(x * x), np.sum(np.abs(x))], dtype=np.float64)
+    loss = np.float32(sums[LOSS_KINDS[kind]] / (count * d)) if count > 0 else np.float32(0.0)
+    return loss, sums, count
+
+
+def valid_loss_bwd_host(pred, target, n_valid: int, kind=0, g: float = 1.0):
+    """numpy restatement of valid_loss_bwd: g * dl / (count * d) in fp64 on the valid rows, rounded once to fp32; +0.0 on
+    every other row"""
+    p = np.asarray(pred, dtype=np.float64)
+    t = np.asarray(target, dtype=np.float64)
+    n_rows = p.shape[0]
+    count = min(max(int(n_valid), 0), n_rows)
+    grad = np.zeros(p.shape, dtype=np.float32)
+    if count > 0:
+        x = p[:count] - t[:count]
+        d = max(1, int(np.prod(p.shape[1:])))
+        dl = 2.0 * x if LOSS_KINDS[kind] == 0 else np.sign(x)
+        grad[:count] = (float(np.float32(g)) * dl / (float(count) * float(d))).astype(np.float32)
+    return grad
+
+
 def graph_prep(pos64, cell64, ptr, r_cut: float):
     """per-crystal prologue of the device graph builder (include/matten_hip.h matten_graph_prep)
     -> (frac [N,3] f64, bound [B,3] f64, batch [N] i64, pos [N,3] f32, cell [3B,3] f32)"""
