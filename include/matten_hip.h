@@ -533,6 +533,43 @@ int matten_elastic_refine(const double* compliance, const int32_t* flags, const 
                           double* vec_n, double* vec_m, int32_t* status, int32_t* iterations, matten_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Kelvin moduli and mechanical stability (csrc/kelvin.hip, csrc/sym6.h): the eigen-decomposition of the 6x6 Mandel matrix
+ * C^ = D C D, D = diag(1,1,1,sqrt2,sqrt2,sqrt2), of the symmetrised Voigt matrix C_IJ that matten_elastic_props writes
+ * (pymatgen order xx, yy, zz, yz, xz, xy, no factors).  The Mandel map preserves the Frobenius norm of the rank-4 tensor,
+ * so the eigenvalues of C^ are the six Kelvin moduli (eigen-stiffnesses; 3K once and 2G five times for an isotropic solid)
+ * and its eigenvectors the eigenstrains.  fp64, one crystal per thread, cyclic Jacobi in registers, values in the units of
+ * the input.
+ * matten_elastic_kelvin: replaces diagonalising each ElasticTensor(t) the reference hands back (predict.py:217-218) on the
+ *   host, one crystal at a time.
+ *   voigt [n,36], flags [n] as matten_elastic_props wrote them (the mean of the two triangles is used) ->
+ *   moduli [n,6] ascending; vectors [n,36] = the orthonormal U row-major, eigenvectors of C^ in its columns in the same
+ *   order (the sign of a column is unspecified but deterministic), may be NULL; dilatation [n,6] = (tr eps_k)^2 / 3 in
+ *   [0,1] (1: a purely volumetric mode, 0: an isochoric one; tr eps_k = U_0k + U_1k + U_2k), may be NULL.  The moduli are
+ *   the same bits whichever of the two are asked for.  A row with flag bit 0, or with an entry of C^ that is not finite,
+ *   is NaN in every output.
+ * matten_elastic_kelvin_bwd: replaces autograd through a host eigvalsh per crystal.  The adjoint of the moduli from the
+ *   forward's vectors (Jacobi is not run again): g_C^ = U diag(g_moduli) U^T, g_voigt [n,36] = D g_C^ D, every element
+ *   written, symmetric.  A row with flag bit 0, or whose vectors are not finite, gets exact zeros whatever arrives
+ *   (selects, not products).  Vectors and dilatation carry no gradient.  Exactly degenerate moduli: per-modulus gradients
+ *   take the basis Jacobi left; a spectral function's gradient (sum_k h(l_k)) does not depend on it.
+ * matten_elastic_kelvin_clamp: replaces the host loop eigh -> clip -> rebuild per crystal.  The tensor nearest to C in the
+ *   Frobenius norm of the rank-4 tensor among those whose Kelvin moduli are all >= floor:
+ *   out [n,36] = D^-1 U diag(max(l_k, floor)) U^T D^-1 from (moduli, vectors) as the forward wrote them, summed in the
+ *   fixed order k = 0..5.  A row whose moduli are all >= floor is its 36 entries of `voigt` copied bit for bit (a select):
+ *   `voigt` must be the symmetrised matrix matten_elastic_props wrote, or such a row comes back as unsymmetric as it came;
+ *   a row with a NaN modulus is NaN.
+ * All three: no atomics, no cross-lane traffic, nothing read back: bitwise reproducible, each row independent of the others,
+ * capturable.  n = 0 is a no-op.  MATTEN_EINVAL: n < 0 or above 2^31 - 1 workgroups, a NULL required pointer with n > 0,
+ * floor negative or not finite.
+ * ------------------------------------------------------------------------------------------ */
+int matten_elastic_kelvin(const double* voigt, const int32_t* flags, int64_t n, double* moduli, double* vectors,
+                          double* dilatation, matten_stream_t stream);
+int matten_elastic_kelvin_bwd(const double* vectors, const int32_t* flags, const double* g_moduli, int64_t n,
+                              double* g_voigt, matten_stream_t stream);
+int matten_elastic_kelvin_clamp(const double* voigt, const double* moduli, const double* vectors, double floor, int64_t n,
+                                double* out, matten_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Derived quantities of per-atom rank-2 tensors (predict.py:117-148: the reference hands back one 3x3 array per atom;
  * NMR users read the isotropic value, span and skew or the Haeberlen anisotropy and asymmetry off it, with the
  * principal axes).  fp64 arithmetic, one atom per thread, values in the units of the input.

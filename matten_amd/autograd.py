@@ -538,6 +538,30 @@ class ElasticAcousticFn(torch.autograd.Function):
                 None, None)
 
 
+class ElasticKelvinFn(torch.autograd.Function):
+    """(moduli, vectors, dilatation) = matten_elastic_kelvin(voigt, flags) with its adjoint kernel
+    (matten_elastic_kelvin_bwd): the backward works from the forward's vectors alone, so the input is not kept and Jacobi
+    is not run again.  Only the moduli are differentiated, and only ``voigt`` receives a gradient; ``vectors`` and
+    ``dilatation`` carry none.  ``want_dilatation=False`` (a loss that reads the moduli alone) hands the kernel a null pointer
+    for the dilatation, which then comes back as None; the vectors are always written, the adjoint needs them.  When nothing
+    downstream used the moduli no kernel runs and no zero tensor is made."""
+
+    @staticmethod
+    def forward(ctx, voigt, flags, want_dilatation=True):
+        moduli, vectors, dilatation = ops.elastic_kelvin(voigt, flags, want_dilatation=bool(want_dilatation))
+        ctx.save_for_backward(vectors, flags)
+        ctx.mark_non_differentiable(*(t for t in (vectors, dilatation) if t is not None))
+        ctx.set_materialize_grads(False)
+        return moduli, vectors, dilatation
+
+    @staticmethod
+    def backward(ctx, g_moduli, _g_vectors, _g_dilatation):
+        if g_moduli is None:
+            return None, None, None
+        vectors, flags = ctx.saved_tensors
+        return ops.elastic_kelvin_bwd(vectors, flags, g_moduli.contiguous()), None, None
+
+
 class Rank2PropsFn(torch.autograd.Function):
     """(vals, axes, props, flags) = matten_rank2_props(t) with its adjoint kernel (matten_rank2_props_bwd): the backward
     works from the four outputs alone, so the input is not kept and Jacobi is not run again.  An output that nothing

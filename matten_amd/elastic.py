@@ -27,6 +27,13 @@ temperature (K) alone are SI: ``density`` is kg/m^3, ``number_density`` atoms/m^
 over rotations of the pair (n, m) from each grid winner, the compressibility by a 3x3 eigen-decomposition);
 ``refine_extremes_host`` states the algorithm in numpy.  ``elastic_moduli*`` do not take it: the refined extremes carry no
 gradient.
+
+``kelvin=True`` adds the Kelvin (eigen-stiffness) decomposition, the eigen-decomposition of the 6x6 Mandel matrix
+(``matten_elastic_kelvin``, csrc/kelvin.hip): the six Kelvin moduli, their eigenstrains (``eigenstrains``) and dilatations, a
+signed stability margin and a condition number -- how far an unstable prediction is from stable, and in which mode.
+``nearest_stable`` repairs a tensor (``matten_elastic_kelvin_clamp``), ``StabilityPenalty`` trains against instability on the
+moduli that ``elastic_moduli*`` attach to the graph (``matten_elastic_kelvin_bwd``); ``kelvin_host`` / ``kelvin_bwd_host`` /
+``nearest_stable_host`` restate them in numpy.  Conventions: INTEGRATION.md, "Kelvin moduli and mechanical stability".
 """
 import numpy as np
 import torch
@@ -65,6 +72,8 @@ class ElasticProperties:
     (with ``angles``) ``shear_min`` / ``shear_max`` / ``poisson_min`` / ``poisson_max``: ``X_refined`` [B], the extreme off the
     grid, ``X_refined_n`` [B,3] and (pair quantities) ``X_refined_m`` [B,3] where it is taken, ``X_refined_status`` [B] int32
     (0 converged, 1 iteration cap, 2 not refined, -1 singular row) and ``X_refined_iterations`` [B] int32.
+    With ``kelvin`` also ``kelvin_moduli`` [B,6] (ascending), ``kelvin_vectors`` [B,6,6] (columns), ``kelvin_dilatation``
+    [B,6], ``stability_margin`` [B] and ``kelvin_condition`` [B] (NaN where the margin is <= 0).
     An unbatched input ([3,3,3,3] or [6,6]) gives the same without the leading dimension."""
 
     def __init__(self, **fields):
@@ -499,6 +508,175 @@ def _upload(rows):
     return rows.contiguous()
 
 
+# ---------------------------------------------------------------------------------------------------
+# Kelvin (eigen-stiffness) decomposition (``kelvin=True``; matten_elastic_kelvin, csrc/kelvin.hip)
+# ---------------------------------------------------------------------------------------------------
+KELVIN_NAMES = ("kelvin_moduli", "kelvin_vectors", "kelvin_dilatation", "stability_margin", "kelvin_condition")
+# the Mandel factors d_I d_J of C^ = D C D, D = diag(1,1,1,sqrt2,sqrt2,sqrt2): 1, sqrt2 and exactly 2 (not sqrt2 * sqrt2),
+# as in the kernel
+_MANDEL_D = np.array([1.0, 1.0, 1.0, np.sqrt(2.0), np.sqrt(2.0), np.sqrt(2.0)])
+MANDEL_WEIGHT = np.where(np.arange(6)[:, None] < 3, np.where(np.arange(6)[None, :] < 3, 1.0, np.sqrt(2.0)),
+                         np.where(np.arange(6)[None, :] < 3, np.sqrt(2.0), 2.0))
+MANDEL_UNWEIGHT = np.where(MANDEL_WEIGHT == 1.0, 1.0, np.where(MANDEL_WEIGHT == 2.0, 0.5, 0.70710678118654757))
+# Voigt index of a Cartesian pair: C_ijkl = C_IJ with I = _VOIGT_OF[i, j], J = _VOIGT_OF[k, l]
+_VOIGT_OF = np.array([[0, 5, 4], [5, 1, 3], [4, 3, 2]])
+
+
+def _check_kelvin(kelvin):
+    if not isinstance(kelvin, (bool, np.bool_)):
+        raise ValueError(f"kelvin: expected True or False, got {kelvin!r}")
+
+
+def _check_number(value, name: str, lowest=None) -> float:
+    """a finite real number, python or numpy (not a bool, not a string), at least `lowest` -> float; else ValueError: the
+    one check of ``floor``, ``margin`` and ``weight``"""
+    if (isinstance(value, (bool, np.bool_)) or not isinstance(value, (float, int, np.floating, np.integer))
+            or not np.isfinite(value) or (lowest is not None and value < lowest)):
+        raise ValueError(f"{name}: expected a finite number{'' if lowest is None else f' >= {lowest:g}'}, got {value!r}")
+    return float(value)
+
+
+def _check_floor(floor, name: str = "floor") -> float:
+    return _check_number(floor, name, 0.0)
+
+
+def _host_voigt(voigt):
+    """-> ([B,6,6] fp64 numpy, unbatched?)"""
+    if isinstance(voigt, torch.Tensor):
+        voigt = voigt.detach().cpu().numpy()
+    C = np.asarray(voigt, dtype=np.float64)
+    if C.shape[-2:] != (6, 6) or C.ndim not in (2, 3):
+        raise ValueError(f"voigt: expected [B,6,6] or [6,6], got {C.shape}")
+    return C.reshape(-1, 6, 6), C.ndim == 2
+
+
+def _host_flags(flags, C):
+    """the rows the kernel writes as NaN: flag bit 0 (``flags`` None: none set), or a non-finite entry of C^"""
+    with np.errstate(all="ignore"):
+        Ch = MANDEL_WEIGHT * (0.5 * (C + C.transpose(0, 2, 1)))
+    bad = ~np.isfinite(Ch).all(axis=(1, 2))
+    if flags is not None:
+        flags = np.asarray(flags.detach().cpu().numpy() if isinstance(flags, torch.Tensor) else flags).reshape(-1)
+        if flags.shape[0] != C.shape[0]:
+            raise ValueError(f"flags: expected {C.shape[0]} word(s), got {flags.shape[0]}")
+        bad = bad | ((flags & FLAG_SINGULAR) != 0)
+    return Ch, bad
+
+
+def kelvin_host(voigt, flags=None) -> dict:
+    """The Kelvin decomposition in numpy fp64 (``numpy.linalg.eigh``), what the tests hold ``matten_elastic_kelvin`` to.
+    ``voigt`` [B,6,6] or [6,6]: the symmetrised Voigt matrix C_IJ (pymatgen order, no factors; the mean of the two
+    triangles is used), ``flags`` [B] as ``matten_elastic_props`` sets them, or None.  With C^ = D C D,
+    D = diag(1,1,1,sqrt2,sqrt2,sqrt2) -> dict of ``kelvin_moduli`` [B,6] (eigenvalues of C^, ascending), ``kelvin_vectors``
+    [B,6,6] (orthonormal eigenvectors in the columns), ``kelvin_dilatation`` [B,6] = (tr eps_k)^2 / 3, ``stability_margin``
+    [B] = the smallest modulus, ``kelvin_condition`` [B] = largest / smallest (NaN where the smallest is <= 0), and
+    ``mandel`` [B,6,6] = C^.  A row with flag bit 0 or a non-finite entry is NaN."""
+    C, single = _host_voigt(voigt)
+    Ch, bad = _host_flags(flags, C)
+    lam, U = np.linalg.eigh(np.where(bad[:, None, None], np.eye(6), Ch))
+    tr = (U[:, 0, :] + U[:, 1, :]) + U[:, 2, :]
+    with np.errstate(all="ignore"):
+        cond = np.where(lam[:, 0] > 0.0, lam[:, 5] / np.where(lam[:, 0] > 0.0, lam[:, 0], 1.0), np.nan)
+    nan = np.nan
+    out = dict(kelvin_moduli=np.where(bad[:, None], nan, lam), kelvin_vectors=np.where(bad[:, None, None], nan, U),
+               kelvin_dilatation=np.where(bad[:, None], nan, tr * tr / 3.0), stability_margin=np.where(bad, nan, lam[:, 0]),
+               kelvin_condition=np.where(bad, nan, cond), mandel=np.where(bad[:, None, None], nan, Ch))
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
+def kelvin_bwd_host(voigt, g_moduli, flags=None, vectors=None) -> np.ndarray:
+    """The adjoint of the Kelvin moduli in numpy fp64: ``g_moduli`` [B,6] -> g_voigt [B,6,6] = D (U diag(g_moduli) U^T) D,
+    symmetric, with U of ``kelvin_host(voigt)`` or, when given, ``vectors`` [B,6,6] (the kernel's: at degenerate moduli a
+    per-modulus gradient depends on the basis).  Rows with flag bit 0, a non-finite entry or non-finite vectors are zero."""
+    C, single = _host_voigt(voigt)
+    _, bad = _host_flags(flags, C)
+    if vectors is None:
+        U = kelvin_host(C, flags)["kelvin_vectors"]
+    else:
+        U = _host_voigt(vectors)[0]
+    bad = bad | ~np.isfinite(U).all(axis=(1, 2))
+    U = np.where(bad[:, None, None], 0.0, U)
+    g = np.asarray(g_moduli.detach().cpu().numpy() if isinstance(g_moduli, torch.Tensor) else g_moduli, dtype=np.float64)
+    g = np.where(bad[:, None], 0.0, g.reshape(-1, 6))
+    out = MANDEL_WEIGHT * np.einsum("bik,bk,bjk->bij", U, g, U)
+    out = np.where(bad[:, None, None], 0.0, 0.5 * (out + out.transpose(0, 2, 1)))
+    return out[0] if single else out
+
+
+def voigt_to_cartesian(voigt):
+    """[...,6,6] -> [...,3,3,3,3], C_ijkl = C_IJ (a torch tensor or a numpy array; a gather, no arithmetic)"""
+    if isinstance(voigt, torch.Tensor):
+        idx = torch.as_tensor(_VOIGT_OF, device=voigt.device)
+        return voigt[..., idx[:, :, None, None], idx[None, None, :, :]]
+    return np.asarray(voigt)[..., _VOIGT_OF[:, :, None, None], _VOIGT_OF[None, None, :, :]]
+
+
+def nearest_stable_host(voigt, floor: float = 0.0, flags=None):
+    """``nearest_stable`` in numpy fp64 for Voigt matrices [B,6,6] or [6,6]: C+ = D^-1 U diag(max(l_k, floor)) U^T D^-1
+    with (l, U) of ``kelvin_host`` -> (voigt [B,6,6], cartesian [B,3,3,3,3], changed [B] bool).  A row whose moduli are
+    all >= floor is returned as it came; a NaN row stays NaN."""
+    floor = _check_floor(floor)
+    C, single = _host_voigt(voigt)
+    h = kelvin_host(C, flags)
+    lam, U = h["kelvin_moduli"], h["kelvin_vectors"]
+    with np.errstate(invalid="ignore"):
+        changed = (lam < floor).any(axis=1)
+        keep = (lam >= floor).all(axis=1)
+        w = np.where(lam < floor, floor, lam)
+    rebuilt = MANDEL_UNWEIGHT * np.einsum("bik,bk,bjk->bij", U, w, U)
+    rebuilt = 0.5 * (rebuilt + rebuilt.transpose(0, 2, 1))
+    out = np.where(keep[:, None, None], C, rebuilt)
+    cart = voigt_to_cartesian(out)
+    return (out[0], cart[0], changed[0]) if single else (out, cart, changed)
+
+
+def _kelvin_fields(moduli, vectors, dilatation) -> dict:
+    """the outputs of the Kelvin kernel under their field names, with the margin and the condition number (torch
+    expressions on the moduli)"""
+    lo, hi = moduli[:, 0], moduli[:, 5]
+    stable = lo.detach() > 0.0
+    cond = torch.where(stable, hi.detach() / torch.where(stable, lo.detach(), torch.ones_like(lo)),
+                       torch.full((), float("nan"), dtype=moduli.dtype, device=moduli.device))
+    return dict(kelvin_moduli=moduli, kelvin_vectors=vectors, kelvin_dilatation=dilatation, stability_margin=lo,
+                kelvin_condition=cond)
+
+
+def eigenstrains(props):
+    """The eigenstrains of the Kelvin modes as symmetric 3 x 3 tensors: ``props`` an ``ElasticProperties`` made with
+    ``kelvin=True`` (or its ``kelvin_vectors``, [B,6,6] or [6,6], torch or numpy) -> [B,6,3,3] (or [6,3,3]), mode k at index
+    k.  The Mandel shear components are divided by sqrt2, so every tensor has unit Frobenius norm.  No gradient."""
+    U = getattr(props, "kelvin_vectors", props)
+    if U is None or isinstance(U, ElasticProperties):
+        raise ValueError("props: no kelvin_vectors; pass kelvin=True to elastic_properties / elastic_moduli / predict")
+    if isinstance(U, torch.Tensor):
+        U = U.detach()
+        comp = (U * torch.as_tensor(1.0 / _MANDEL_D, dtype=U.dtype, device=U.device)[:, None]).transpose(-1, -2)   # [..., k, I]
+        idx = torch.as_tensor(_VOIGT_OF, device=U.device)
+        return comp[..., idx]
+    U = np.asarray(U, dtype=np.float64)
+    if U.shape[-2:] != (6, 6):
+        raise ValueError(f"kelvin_vectors: expected [B,6,6] or [6,6], got {U.shape}")
+    return np.swapaxes(U / _MANDEL_D[:, None], -1, -2)[..., _VOIGT_OF]
+
+
+def nearest_stable(tensors, floor: float = 0.0):
+    """The tensor nearest to each input, in the Frobenius norm of the rank-4 tensor, among those whose Kelvin moduli are all
+    >= ``floor`` (finite, >= 0: else ValueError): C^+ = U diag(max(l_k, floor)) U^T on the Mandel matrix
+    (``matten_elastic_kelvin_clamp``).  ``tensors`` as for ``elastic_properties`` -> (voigt [B,6,6], cartesian
+    [B,3,3,3,3], changed [B] bool) on the device, fp64; an unbatched input gives an unbatched result.  A row with
+    ``changed`` False is the symmetrised input, bit for bit; a row ``elastic_properties`` answers with NaN (flag bit 0)
+    stays NaN and unchanged.  ``floor=0`` leaves a semi-definite tensor (flag bit 1 may stay set); a small positive floor
+    gives a positive definite one.  No gradient."""
+    floor = _check_floor(floor)
+    rows, layout, single, _ = _as_rows(tensors)
+    voigt, _, _, flags = ops.elastic_props(_upload(rows), layout)
+    moduli, vectors, _ = ops.elastic_kelvin(voigt, flags, want_dilatation=False)
+    out = ops.elastic_kelvin_clamp(voigt, moduli, vectors, floor)
+    changed = (moduli < floor).any(dim=1)
+    cart = voigt_to_cartesian(out)
+    return (out[0], cart[0], changed[0]) if single else (out, cart, changed)
+
+
 def _directional_fields(young, beta, ext, arg, dirs) -> dict:
     """the outputs of the directional kernel under their field names"""
     return dict(young=young, compressibility=beta,
@@ -521,9 +699,10 @@ def _acoustic_fields(vel, ext, arg, n_unstable, n_dirs: int, number_density) -> 
 
 def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, failed=None, angles=None, density=None,
                number_density=None, modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
-               refine_max_iter: int = 32) -> ElasticProperties:
+               refine_max_iter: int = 32, kelvin: bool = False) -> ElasticProperties:
     """rows on the device -> ElasticProperties; ``dirs``: unit vectors out of ``check_directions`` (host) or None;
-    ``density`` / ``number_density``: out of ``_check_per_row`` or None; ``refine*``: checked by ``_check_refine``"""
+    ``density`` / ``number_density``: out of ``_check_per_row`` or None; ``refine*``: checked by ``_check_refine``;
+    ``kelvin``: checked by ``_check_kelvin``"""
     voigt, compliance, props, flags = ops.elastic_props(rows, layout)
     if failed is not None and failed.any():
         flags |= torch.as_tensor(failed.astype(np.int32) * FLAG_FAILED_STRUCTURE, device=flags.device)
@@ -561,6 +740,8 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
         rho = torch.as_tensor(density, dtype=torch.float64).to(rows.device)
         fields.update(_acoustic_fields(*ops.elastic_acoustic(voigt, flags, rho, dirs, modulus_unit, keep=keep_directional),
                                        dirs.shape[0], number_density))
+    if kelvin:      # (after the failed-structure bit went into the flags: the kernel reads bit 0 only)
+        fields.update(_kelvin_fields(*ops.elastic_kelvin(voigt, flags)))
     if single:
         fields = {k: (v if v is None or k in ("directions", "angles") else v[0]) for k, v in fields.items()}
     return ElasticProperties(**fields)
@@ -568,7 +749,7 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
 
 def elastic_properties(tensors, directions=None, keep_directional: bool = False, angles=None, density=None,
                        number_density=None, modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
-                       refine_max_iter: int = 32) -> ElasticProperties:
+                       refine_max_iter: int = 32, kelvin: bool = False) -> ElasticProperties:
     """``tensors``: a torch tensor or numpy array [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], fp32 or fp64, on the device or
     on the host (copied once), or a list of such tensors as ``predict`` returns (stacked; a ``None`` entry becomes a NaN
     row with flag bit 2).  ``directions``: an int D (``fibonacci_hemisphere(D)``) or an array [D,3] (validated and
@@ -588,7 +769,12 @@ def elastic_properties(tensors, directions=None, keep_directional: bool = False,
     the grid fields, which stay as they are.  ``refine_tol`` is the relative gradient residual at which the iteration stops,
     ``refine_max_iter`` its cap.  The refined extreme is the stationary point of the basin the grid winner lies in: on a
     coarse grid that need not be the global extreme.  The sign of n and of m is unspecified (all four functions are even).
+    ``kelvin=True`` adds the Kelvin decomposition (``matten_elastic_kelvin``; INTEGRATION.md, "Kelvin moduli and mechanical
+    stability"): ``kelvin_moduli`` [B,6] ascending, ``kelvin_vectors`` [B,6,6] (columns), ``kelvin_dilatation`` [B,6],
+    ``stability_margin`` [B] (the smallest modulus, signed) and ``kelvin_condition`` [B] (NaN where the margin is <= 0);
+    ``eigenstrains(props)`` gives the 3 x 3 eigenstrains.  Every other field and flag bit is the same with and without it.
     The results stay on the device."""
+    _check_kelvin(kelvin)
     _check_extras(directions, angles, density, number_density)
     _check_refine(refine, directions, refine_tol, refine_max_iter)
     dirs = None if directions is None else check_directions(directions)      # (before anything is uploaded)
@@ -598,7 +784,7 @@ def elastic_properties(tensors, directions=None, keep_directional: bool = False,
     if number_density is not None:
         number_density = _check_per_row("number_density", number_density, rows.shape[0], single)
     return _from_rows(_upload(rows), layout, dirs, keep_directional, single, failed, angles, density, number_density,
-                      modulus_unit, refine, refine_tol, refine_max_iter)
+                      modulus_unit, refine, refine_tol, refine_max_iter, kelvin)
 
 
 _VOIGT_Q = {}
@@ -607,11 +793,12 @@ _VOIGT_Q = {}
 def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = False,
                                    formula: str = "ijkl=jikl=klij", angles=None, density=None, number_density=None,
                                    modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
-                                   refine_max_iter: int = 32) -> ElasticProperties:
+                                   refine_max_iter: int = 32, kelvin: bool = False) -> ElasticProperties:
     """The same from the model's irreps rows ``x`` [B,21] (fp32, on the device): one ``dense_rows`` with ``voigt_basis``
     gives the Voigt matrices [B,36] directly -- no [B,81] Cartesian intermediate."""
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
         raise ValueError("x: expected a tensor [B,21] or [21]")
+    _check_kelvin(kelvin)
     _check_extras(directions, angles, density, number_density)
     _check_refine(refine, directions, refine_tol, refine_max_iter)
     dirs = None if directions is None else check_directions(directions)
@@ -631,16 +818,16 @@ def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = 
         _VOIGT_Q[key] = torch.tensor(V, dtype=torch.float32, device=x.device)
     rows = ops.dense_rows(x.to(torch.float32), _VOIGT_Q[key])
     return _from_rows(rows, 1, dirs, keep_directional, single, None, angles, density, number_density, modulus_unit, refine,
-                      refine_tol, refine_max_iter)
+                      refine_tol, refine_max_iter, kelvin)
 
 
 # ---------------------------------------------------------------------------------------------------
 # differentiable: training on moduli
 # ---------------------------------------------------------------------------------------------------
 def _moduli_fields(rows, layout, single, dirs=None, keep_directional=False, density=None, number_density=None,
-                   modulus_unit: float = 1e9) -> ElasticProperties:
+                   modulus_unit: float = 1e9, kelvin: bool = False, kelvin_dilatation: bool = True) -> ElasticProperties:
     """``_from_rows`` attached to the autograd graph (no pair quantities): the same kernels, so the same bits"""
-    from .autograd import ElasticAcousticFn, ElasticDirectionalFn, ElasticPropsFn
+    from .autograd import ElasticAcousticFn, ElasticDirectionalFn, ElasticKelvinFn, ElasticPropsFn
 
     voigt, compliance, props, flags = ElasticPropsFn.apply(rows, layout)
     fields = {"voigt": voigt, "compliance": compliance}
@@ -656,6 +843,8 @@ def _moduli_fields(rows, layout, single, dirs=None, keep_directional=False, dens
         rho = torch.as_tensor(density, dtype=torch.float64).to(rows.device)
         fields.update(_acoustic_fields(*ElasticAcousticFn.apply(voigt, flags, rho, dirs, float(modulus_unit),
                                                                 bool(keep_directional)), dirs.shape[0], number_density))
+    if kelvin:
+        fields.update(_kelvin_fields(*ElasticKelvinFn.apply(voigt, flags, bool(kelvin_dilatation))))
     if single:
         fields = {k: (v if v is None or k == "directions" else v[0]) for k, v in fields.items()}
     return ElasticProperties(**fields)
@@ -677,7 +866,8 @@ def _check_moduli_extras(directions, angles, density, number_density, B: int, si
 
 
 def elastic_moduli(tensors, directions=None, keep_directional: bool = False, density=None, number_density=None,
-                   modulus_unit: float = 1e9, angles=None) -> ElasticProperties:
+                   modulus_unit: float = 1e9, angles=None, kelvin: bool = False,
+                   kelvin_dilatation: bool = True) -> ElasticProperties:
     """The differentiable ``elastic_properties``: ``tensors`` is a device tensor [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6],
     fp32 or fp64; ``voigt``, ``compliance`` and the ten scalars of ``PROP_NAMES`` come back attached to its autograd graph
     (``flags``, ``is_stable``, ``is_singular`` as in ``elastic_properties``).  A row with flag bit 0 is NaN and sends a zero
@@ -687,7 +877,12 @@ def elastic_moduli(tensors, directions=None, keep_directional: bool = False, den
     ``v_fast_max``, ``sum_inv_v3``, ``v_mean``, ``debye_temperature`` and, when kept, the maps ``young`` / ``compressibility``
     / ``velocities`` are attached too (``DIRECTIONAL_NAMES``); an extreme's gradient is that of the direction where it was
     found, an acoustically unstable direction contributes nothing.  The directions and densities receive no gradient.
-    ``angles`` is refused: the pair quantities carry no gradient."""
+    ``angles`` is refused: the pair quantities carry no gradient.  ``kelvin=True`` adds the Kelvin fields of
+    ``elastic_properties``: ``kelvin_moduli`` and ``stability_margin`` are attached to the graph
+    (``matten_elastic_kelvin_bwd``; what ``StabilityPenalty`` trains on), the vectors, the dilatation and
+    ``kelvin_condition`` carry no gradient.  ``kelvin_dilatation=False`` leaves the dilatation out (the field is None, the
+    kernel gets a null pointer for it): for a loss that reads the moduli alone, as ``graphs.stability_penalized`` does."""
+    _check_kelvin(kelvin)
     if not isinstance(tensors, torch.Tensor):
         raise ValueError("tensors: elastic_moduli differentiates device tensors only; for arrays, lists and host tensors "
                          "use elastic_properties (no gradient)")
@@ -706,19 +901,21 @@ def elastic_moduli(tensors, directions=None, keep_directional: bool = False, den
         raise ValueError("tensors: elastic_moduli differentiates device tensors only; a host tensor goes through "
                          "elastic_properties (no gradient)")
     return _moduli_fields(tensors.reshape(-1, width), layout, single, dirs, keep_directional, density, number_density,
-                          modulus_unit)
+                          modulus_unit, kelvin, kelvin_dilatation)
 
 
 _VOIGT_QT = {}
 
 
 def elastic_moduli_from_irreps(x, formula: str = "ijkl=jikl=klij", directions=None, keep_directional: bool = False,
-                               density=None, number_density=None, modulus_unit: float = 1e9, angles=None) -> ElasticProperties:
+                               density=None, number_density=None, modulus_unit: float = 1e9, angles=None,
+                               kelvin: bool = False, kelvin_dilatation: bool = True) -> ElasticProperties:
     """The differentiable ``elastic_properties_from_irreps``: ``x`` [B,21] (or [21]) fp32 on the device, usually the model's
     output with its ``grad_fn``.  The forward is the same ``dense_rows`` with ``voigt_basis``; its adjoint is ``dense_rows``
-    with the transposed basis [36,21].  The directional arguments are those of ``elastic_moduli``."""
+    with the transposed basis [36,21].  The directional arguments and ``kelvin`` are those of ``elastic_moduli``."""
     from .autograd import DenseRowsFn
 
+    _check_kelvin(kelvin)
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
         raise ValueError("x: expected a tensor [B,21] or [21]")
     V = voigt_basis(formula)
@@ -736,7 +933,8 @@ def elastic_moduli_from_irreps(x, formula: str = "ijkl=jikl=klij", directions=No
     if key not in _VOIGT_QT:
         _VOIGT_QT[key] = _VOIGT_Q[key].t().contiguous()
     rows = DenseRowsFn.apply(x.reshape(-1, x.shape[-1]), _VOIGT_Q[key], _VOIGT_QT[key])
-    return _moduli_fields(rows, 1, single, dirs, keep_directional, density, number_density, modulus_unit)
+    return _moduli_fields(rows, 1, single, dirs, keep_directional, density, number_density, modulus_unit, kelvin,
+                          kelvin_dilatation)
 
 
 class ModuliLoss(torch.nn.Module):
@@ -799,3 +997,37 @@ class ModuliLoss(torch.nn.Module):
             total = term if total is None else total + term
             count = use.sum() if count is None else count + use.sum()
         return total / count.clamp(min=1).to(total.dtype)
+
+
+class StabilityPenalty(torch.nn.Module):
+    """Penalty on mechanically unstable predictions: ``forward(props, n_valid=None)`` with ``props`` an ``ElasticProperties``
+    made with ``kelvin=True`` (of ``elastic_moduli`` or ``elastic_moduli_from_irreps`` to train on it) returns the mean over
+    the crystals and their six Kelvin modes of h(margin - l_k), h(x) = max(x, 0) for ``kind="hinge"`` and max(x, 0)^2 for
+    ``"squared"``: zero exactly where every modulus is at least ``margin`` (units of the tensor).  A spectral function, so
+    its gradient U diag(-h') U^T does not depend on the basis Jacobi left at degenerate moduli.  A row with flag bit 0 (or
+    NaN moduli) is replaced with ``torch.where``, never multiplied away: it adds nothing to the value and gets a zero
+    gradient.  ``n_valid``: the device word of a padded batch (``batch["_amd_n_valid"][2:3]``, int64 [1]); the mean then runs
+    over the first ``n_valid`` crystals only, in the valid-loss kernel (``autograd.ValidLossFn`` against zeros, fp32 result),
+    with no host read, so it captures; without it the mean is a torch expression in fp64."""
+
+    def __init__(self, margin: float = 0.0, kind: str = "squared"):
+        super().__init__()
+        margin = _check_number(margin, "margin")
+        if kind not in ("hinge", "squared"):
+            raise ValueError(f"kind: expected 'hinge' or 'squared', got {kind!r}")
+        self.margin, self.kind = margin, kind
+
+    def forward(self, props: ElasticProperties, n_valid=None) -> torch.Tensor:
+        lam = getattr(props, "kelvin_moduli", None)
+        if lam is None:
+            raise ValueError("props: no kelvin_moduli; pass kelvin=True to elastic_moduli / elastic_moduli_from_irreps")
+        lam = lam.reshape(-1, 6)
+        bad = ((props.flags.reshape(-1) & FLAG_SINGULAR) != 0)[:, None] | ~torch.isfinite(lam.detach())
+        short = torch.relu(torch.where(bad, torch.zeros((), dtype=lam.dtype, device=lam.device), self.margin - lam))
+        if n_valid is None:
+            return (short if self.kind == "hinge" else short * short).mean()
+        from .autograd import ValidLossFn
+
+        short = short.to(torch.float32)
+        return ValidLossFn.apply(short, torch.zeros_like(short), n_valid,
+                                 ops.LOSS_KINDS["mae" if self.kind == "hinge" else "mse"])[0]

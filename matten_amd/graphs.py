@@ -198,6 +198,43 @@ def rank2_selected_loss(names=("iso",), kind: str = "mse", key: str = None, sele
     return loss
 
 
+def stability_penalized(base_loss: Callable, weight: float, margin: float = 0.0, kind: str = "squared", key: str = None,
+                        formula: str = "ijkl=jikl=klij", inverse: Callable = None) -> Callable:
+    """``base_loss`` plus ``weight`` times the stability penalty of the predicted elasticity tensors
+    (``elastic.StabilityPenalty(margin, kind)`` on their Kelvin moduli): fine-tuning towards mechanically stable
+    predictions.
+
+    ``base_loss`` is any loss the training steps take (``loss(preds, target)``, or ``loss(preds, target, batch)`` when it
+    ``wants_batch``: ``valid_mean_loss("mse", key)``, say); `key` picks the irreps rows [B,21] out of the model's dict for
+    the penalty.  ``inverse`` maps standardised predictions back to physical units before the penalty (a task normaliser's
+    ``inverse``; default: the identity) -- a margin is in the units of the tensor, and definiteness is not preserved by a
+    shift.  The returned ``loss(preds, target, batch)`` takes the rows through ``elastic.elastic_moduli_from_irreps(...,
+    kelvin=True)``; on a padded batch the penalty is the mean over the real crystals (``batch["_amd_n_valid"][2:3]``, a
+    device word), else over all rows.  Nothing is read back: ``GraphedTrainStep`` and ``BucketedTrainStep`` take it as it
+    is."""
+    from .elastic import StabilityPenalty, _check_floor, elastic_moduli_from_irreps, voigt_basis
+
+    if not callable(base_loss):
+        raise ValueError("base_loss: expected a callable loss")
+    weight = _check_floor(weight, "weight")      # (the same check as floor and margin: numpy scalars are numbers too)
+    if inverse is not None and not callable(inverse):
+        raise ValueError("inverse: expected a callable (a task normaliser's inverse) or None")
+    voigt_basis(formula)      # (a formula that is not a rank 4 fails here, not in the first step)
+    penalty = StabilityPenalty(margin, kind)
+
+    def loss(preds, target, batch):
+        base = _apply_loss(base_loss, preds, target, batch)
+        x = preds[key] if key is not None else preds
+        if inverse is not None:
+            x = inverse(x)
+        props = elastic_moduli_from_irreps(x, formula, kelvin=True, kelvin_dilatation=False)      # (the moduli alone)
+        n_valid = batch["_amd_n_valid"][2:3] if batch is not None and "_amd_n_valid" in batch else None
+        return base + weight * penalty(props, n_valid).to(base.dtype)
+
+    loss.wants_batch = True
+    return loss
+
+
 def _train_step(model, optimizer, loss_fn: Callable, batch, target, task_name: str):
     """one optimisation step as it is captured, and as it runs eagerly: forward, loss, backward, optimiser"""
     preds, _ = model(dict(batch), task_name=task_name)

@@ -961,6 +961,67 @@ def rank2_props_bwd(vals, axes, props, flags, g_vals, g_props, dtype):
     return g_t
 
 
+def _kelvin_rows(voigt, flags):
+    voigt = _need(voigt, torch.float64, "voigt")
+    flags = _need(flags, torch.int32, "flags")
+    B = flags.shape[0] if flags.dim() == 1 else -1
+    if voigt.shape != (B, 6, 6):
+        raise ValueError(f"expected voigt [B,6,6], flags [B]; got {tuple(voigt.shape)}, {tuple(flags.shape)}")
+    return voigt, flags, B
+
+
+def elastic_kelvin(voigt, flags, want_vectors: bool = True, want_dilatation: bool = True):
+    """voigt [B,6,6] fp64 and flags [B] int32 as ``elastic_props`` returns them -> (moduli [B,6] ascending, vectors [B,6,6]
+    or None, dilatation [B,6] or None), fp64: the Kelvin moduli of the Mandel matrix, their eigenvectors (columns) and
+    (tr eps_k)^2 / 3; a row with flag bit 0 or a non-finite entry is NaN (include/matten_hip.h: matten_elastic_kelvin)"""
+    lib = _lib.load()
+    voigt, flags, B = _kelvin_rows(voigt, flags)
+    moduli = torch.empty(B, 6, dtype=torch.float64, device=voigt.device)
+    vectors = torch.empty(B, 6, 6, dtype=torch.float64, device=voigt.device) if want_vectors else None
+    dilatation = torch.empty(B, 6, dtype=torch.float64, device=voigt.device) if want_dilatation else None
+    _lib.check(lib.matten_elastic_kelvin(_ptr(voigt), _ptr(flags), B, _ptr(moduli), _ptr(vectors), _ptr(dilatation),
+                                         _stream()), "matten_elastic_kelvin")
+    return moduli, vectors, dilatation
+
+
+def elastic_kelvin_bwd(vectors, flags, g_moduli) -> torch.Tensor:
+    """the adjoint of ``elastic_kelvin``'s moduli: the forward's vectors [B,6,6], flags [B] and the upstream gradient
+    g_moduli [B,6] (fp64) -> g_voigt [B,6,6] fp64, symmetric; rows with flag bit 0 or non-finite vectors are zero
+    (matten_elastic_kelvin_bwd)"""
+    lib = _lib.load()
+    vectors, flags, B = _kelvin_rows(vectors, flags)
+    g_moduli = _need(g_moduli, torch.float64, "g_moduli")
+    if g_moduli.shape != (B, 6):
+        raise ValueError(f"g_moduli: expected {(B, 6)}, got {tuple(g_moduli.shape)}")
+    g_voigt = torch.empty(B, 6, 6, dtype=torch.float64, device=vectors.device)
+    _lib.check(lib.matten_elastic_kelvin_bwd(_ptr(vectors), _ptr(flags), _ptr(g_moduli), B, _ptr(g_voigt), _stream()),
+               "matten_elastic_kelvin_bwd")
+    return g_voigt
+
+
+def elastic_kelvin_clamp(voigt, moduli, vectors, floor: float = 0.0) -> torch.Tensor:
+    """voigt [B,6,6] and the moduli [B,6] and vectors [B,6,6] ``elastic_kelvin`` gave for it (fp64), floor >= 0 ->
+    [B,6,6] fp64: the Voigt matrix of the nearest tensor whose Kelvin moduli are all >= floor; rows that already are come
+    back as they went in, bit for bit (matten_elastic_kelvin_clamp).  ``voigt`` must be the SYMMETRISED matrix, as
+    ``elastic_props`` returns it: a kept row is a copy of its 36 entries, so an unsymmetric row would come back unsymmetric
+    beside rebuilt rows that are symmetric."""
+    lib = _lib.load()
+    floor = float(floor)
+    if not (np.isfinite(floor) and floor >= 0.0):
+        raise ValueError(f"floor: expected a finite number >= 0, got {floor!r}")
+    voigt = _need(voigt, torch.float64, "voigt")
+    moduli = _need(moduli, torch.float64, "moduli")
+    vectors = _need(vectors, torch.float64, "vectors")
+    B = moduli.shape[0]
+    if voigt.shape != (B, 6, 6) or moduli.shape != (B, 6) or vectors.shape != (B, 6, 6):
+        raise ValueError(f"expected voigt / vectors [B,6,6], moduli [B,6]; got {tuple(voigt.shape)}, {tuple(vectors.shape)}, "
+                         f"{tuple(moduli.shape)}")
+    out = torch.empty(B, 6, 6, dtype=torch.float64, device=voigt.device)
+    _lib.check(lib.matten_elastic_kelvin_clamp(_ptr(voigt), _ptr(moduli), _ptr(vectors), floor, B, _ptr(out), _stream()),
+               "matten_elastic_kelvin_clamp")
+    return out
+
+
 def elastic_directional(compliance, flags, dirs, keep: bool = False):
     """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64 -> (young [B,D] or None, beta [B,D] or
     None, ext [B,4] = E_min, E_max, beta_min, beta_max, arg [B,4] int32) (matten_elastic_directional)"""

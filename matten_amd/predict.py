@@ -571,7 +571,7 @@ def _structure_densities(structures) -> np.ndarray:
 
 
 def _properties_of_slabs(device_rows, n, failed, directions, single, angles=None, density=None, number_density=None,
-                         modulus_unit=1e9, refine=False, refine_tol=1e-9, refine_max_iter=32):
+                         modulus_unit=1e9, refine=False, refine_tol=1e-9, refine_max_iter=32, kelvin=False):
     """ElasticProperties of all n input structures from the slabs' device tensors: they never come back from the host.
     Structures without a prediction (``failed``) keep NaN rows and get flag bit 2."""
     from .elastic import _from_rows
@@ -586,7 +586,7 @@ def _properties_of_slabs(device_rows, n, failed, directions, single, angles=None
     mask = np.zeros(n, dtype=bool)
     mask[list(failed)] = True
     return _from_rows(rows, 0, directions, False, single, mask, angles, density, number_density, modulus_unit, refine,
-                      refine_tol, refine_max_iter)
+                      refine_tol, refine_max_iter, kelvin)
 
 
 def predict(
@@ -610,6 +610,7 @@ def predict(
     refine: bool = False,
     refine_tol: float = 1e-9,
     refine_max_iter: int = 32,
+    kelvin: bool = False,
     shielding: bool = False,
 ):
     """See the module docstring.  ``model`` / ``config`` let a caller reuse an already loaded model.
@@ -622,6 +623,8 @@ def predict(
     those of ``elastic.elastic_properties`` (shear modulus and Poisson's ratio over direction pairs, sound velocities, Debye
     temperature); they need ``properties=True`` and are checked before any forward runs.  So are ``refine``, ``refine_tol``
     and ``refine_max_iter``: the directional extremes polished off the grid (the ``*_refined*`` fields; needs ``directions``).
+    ``kelvin=True`` (needs ``properties=True``) adds the Kelvin decomposition of ``elastic.elastic_properties(kelvin=True)``:
+    ``kelvin_moduli``, ``kelvin_vectors``, ``kelvin_dilatation``, ``stability_margin``, ``kelvin_condition``.
     ``batch_size`` (reference predict.py:155) is the memory knob it is there: consecutive batches are merged into one forward
     only while the merged batch stays within ``node_budget`` atoms (default MATTEN_PREDICT_NODE_BUDGET = 65536, ~2 GB) and
     only when batch_size is at least the reference's default of 200; ``node_budget=0`` never merges.  A merged forward
@@ -645,6 +648,8 @@ def predict(
                 raise ValueError(f"{name} belongs to the derived properties: pass properties=True")
         if refine:
             raise ValueError("refine belongs to the derived properties: pass properties=True")
+        if kelvin:
+            raise ValueError("kelvin belongs to the derived properties: pass properties=True")
     if shielding:
         from .rank2 import rank2_basis
 
@@ -657,8 +662,9 @@ def predict(
     single = not isinstance(structure, (list, tuple))
     structures = [structure] if single else list(structure)
     if properties:
-        from .elastic import _check_extras, _check_per_row, _check_refine
+        from .elastic import _check_extras, _check_kelvin, _check_per_row, _check_refine
 
+        _check_kelvin(kelvin)
         _check_extras(directions, angles, density, number_density)
         _check_refine(refine, directions, refine_tol, refine_max_iter)
         if isinstance(density, str):
@@ -713,7 +719,7 @@ def predict(
         raise RuntimeError("Cannot successfully convert any structures.")
     if properties:
         props = _properties_of_slabs(device_rows, len(structures), failed, directions, single, angles, density,
-                                     number_density, modulus_unit, refine, refine_tol, refine_max_iter)
+                                     number_density, modulus_unit, refine, refine_tol, refine_max_iter, kelvin)
     if is_elasticity_tensor:
         try:
             from pymatgen.analysis.elasticity import ElasticTensor
