@@ -225,11 +225,15 @@ int matten_agg_linear_gate_sets(void);
  *                         fp32: fp32-class rounding at 1/5 of the fp32 MFMA time) into a wave-private LDS tile, consumed in place by the
  *                         literal-coefficient CG contraction + CSR neighbour sum
  *   w2p[32, w_pad]: last layer weights pre-scaled (1/sqrt(32) * normalize2mom(silu)), columns in the
- *                   fused [entry][u][coupling] order of group_entries, w_pad >= w_cols + 16
+ *                   fused [entry][u][coupling] order of group_entries, w_pad >= w_cols + 16, the columns from w_cols on ZERO
+ *                   (whole tiles are read from any entry on; the stage rows of an empty segment are read from the last four)
  *   group_entries[n_entries, 32] int32 {l1*8+g, x_off, mul, log2(lanes per node), coupling mask, w_base, first A tile,
  *                   A tiles, t_off[12], out_off[12]}: one entry per (input irrep block chunk, l2 group g); couplings in the
  *                   order of cg_gen.h Group<l1,g>, weight columns [u][c] (absent couplings: zero columns), mul * couplings
- *                   <= matten_tp_max_cols*(); out_off[c] = first float of channel 0 in the output row, t_off[c] = 0
+ *                   <= matten_tp_max_cols*(); word 0 + 256: a merged entry (two two-channel blocks, its second record
+ *                   follows); word 0 + 512: weight columns coupling-major, column mul * c + u, for an entry with mul == lanes
+ *                   per node == 16 or 8 and l1 < matten_tp_wreg(): shared and paired workgroups pass its weights from the
+ *                   matrix phase to the contraction in registers instead of through the LDS tile; out_off[c] = first float of channel 0 in the output row, t_off[c] = 0
  *                   (the reference's mul_ir row) or the floats between two components (component-major row)
  *   unit_map[units_per_tile]: wave index inside a node tile -> flags | entry << 8 | node group (of 64 >> cu_log2 nodes);
  *                   flags: bit 24 = the unit's workgroup (four consecutive units) shares an LDS stage: same node
@@ -274,6 +278,7 @@ int matten_tp_fused(const float* x, int64_t d_in, const uint16_t* h2s, const flo
                     const float* num_neigh, const uint16_t* a_split, const float* a_scale_inv,
                     float* agg /*[N,d_mid]*/, matten_stream_t stream);
 
+int matten_tp_wreg(void);       /* 0: no entry may carry the coupling-major flag (built with -DTPF_WREG=0); else 1 + the largest l1 that may */
 int matten_tp_max_cols(void);   /* weight columns (mul * couplings) a group entry of matten_tp_fused may have */
 int matten_tp_max_cols_l0(void);   /* the same for entries of scalar (l1 = 0) input blocks */
 int matten_tp_max_cols_l1(void);   /* ... and of vector (l1 = 1) input blocks */

@@ -48,6 +48,7 @@ SIGNATURES = {
     "matten_agg_linear_gate_sets": (c_int, []),
     "matten_radial_hidden": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, P, P, P]),
     "matten_radial_hidden_deep": (c_int, [P, c_int64, c_int, c_float, c_float, P, c_int, P, c_int, c_int, P, P, P]),
+    "matten_tp_wreg": (c_int, []),
     "matten_tp_max_cols": (c_int, []),
     "matten_tp_max_cols_l0": (c_int, []),
     "matten_tp_max_cols_l1": (c_int, []),

@@ -28,6 +28,8 @@
 //               LDS tile with one 16-byte store.
 //   VALU phase  each lane reads its NC weights of its node's edge from LDS and contracts them with
 //               x[src] and Y(e) through the literal-coefficient CG code (cg_gen.h).
+//   (Entries flagged KIND_WREG in shared / paired workgroups skip the LDS tile: edges as M, coupling-major weight columns as N,
+//    and the D fragment is the consumer lane's w[coupling][slot] in registers -- tp_walk.h, TPF_WREG.)
 // Matrix-core and vector work of different waves overlap on the SIMD; HBM traffic per edge drops from
 // ~7.7 KB (write + read of w) to ~0.3 KB (h2 + harmonics + indices).
 //
@@ -47,6 +49,8 @@ using namespace matten_walk;
 // first block's channels and use this record's offsets, lanes u = 2, 3 the second block's and use the record that follows
 // it in the entry array (its own coupling mask there too; the first half's own mask travels in that record's w_base word).
 constexpr int KIND_MERGED = 256;   // == plan.TP_KIND_MERGED
+constexpr int KIND_WREG = 512;     // == plan.TP_KIND_WREG: the entry's weight columns are coupling-major (column mul * c + u, mul == lanes
+                                   // per node): shared and paired workgroups hand its weights over in registers (tp_walk.h, WR)
 struct StoreAgg {
     template <class G>
     __device__ __forceinline__ void store(const Args& a, const GroupEntry& ge, const float* __restrict__ acc,
@@ -105,6 +109,10 @@ __device__ __forceinline__ void run_group(const Args& a, const GroupEntry& ge, f
     const int u = lane & (cu - 1);
     const int g = lane >> 4, c = lane & 15;      // MFMA role
     const int xcol = ge.x_off + u * G::D1;
+    // the lane's weight of coupling cc: column u * NC + cc, or cu * cc + u of a coupling-major entry (KIND_WREG)
+    // (only the kinds that can carry the flag pay for the two values: the heavy kinds' frames are the kernel's deepest)
+    const bool cmajor = WregOk<L1, GI, 3>::value && (ge.kind & KIND_WREG) != 0;   // wave-uniform
+    const int wcol0 = cmajor ? u : u * NC, wstep = cmajor ? cu : 1;
     // A operand (the entry's weight columns, <= 64 by construction of the plan) stays in registers for the
     // whole CSR walk: av[mt][kk] = W2p[pi(kk,g)][w_base + 16*mt + c]
     // MTMAX: the plan caps an entry at the largest power-of-two channel count whose [u][c] block fits 64 columns
@@ -206,13 +214,13 @@ __device__ __forceinline__ void run_group(const Args& a, const GroupEntry& ge, f
                 src_nn = a.src_sorted[min(beg + s + 2, e_last)];
             }
             if (s < deg) {
-                const float* wp = tile + ((j << ch_log2) + so) * stride + u * NC;
+                const float* wp = tile + ((j << ch_log2) + so) * stride + wcol0;
                 const float* yp = tile + ((j << ch_log2) + so) * stride + ycol + G::Y0;
                 float y[G::NY], w[NC];
 #pragma unroll
                 for (int jj = 0; jj < G::NY; ++jj) y[jj] = yp[jj];
 #pragma unroll
-                for (int cc = 0; cc < NC; ++cc) w[cc] = wp[cc];
+                for (int cc = 0; cc < NC; ++cc) w[cc] = wp[cc * wstep];
                 G::apply(mask, x, y, w, acc);
             }
         }
@@ -222,13 +230,33 @@ __device__ __forceinline__ void run_group(const Args& a, const GroupEntry& ge, f
 }
 
 #define MATTEN_RGS_ARGS a, ge, tile, stage, (um >> 8) & 0xffff, tile_id, r, reps, lane, StoreAgg{}
-#define MATTEN_RGS(L1, GI, TT, TD, P) \
+#define MATTEN_RGS_WR(L1, GI, TT, TD, P, WR) \
     do { \
         using HM = HotMask<L1, GI>; \
-        if (HM::M0 && ge.mask == HM::M0) run_group_shared<L1, GI, TT, TD, P, HM::M0>(MATTEN_RGS_ARGS); \
-        else if (HM::M1 && ge.mask == HM::M1) run_group_shared<L1, GI, TT, TD, P, HM::M1>(MATTEN_RGS_ARGS); \
-        else run_group_shared<L1, GI, TT, TD, P, 0u>(MATTEN_RGS_ARGS); \
+        if (HM::M0 && ge.mask == HM::M0) run_group_shared<L1, GI, TT, TD, P, HM::M0, WR>(MATTEN_RGS_ARGS); \
+        else if (HM::M1 && ge.mask == HM::M1) run_group_shared<L1, GI, TT, TD, P, HM::M1, WR>(MATTEN_RGS_ARGS); \
+        else run_group_shared<L1, GI, TT, TD, P, 0u, WR>(MATTEN_RGS_ARGS); \
     } while (0)
+// coupling-major entries (KIND_WREG) of a one-tile chunk take the register hand-over of their lanes-per-node class
+template <int L1, int GI, int TT, int TD, bool P>
+__device__ __forceinline__ void run_group_shared_any(const Args& a, const GroupEntry& ge, float* __restrict__ tile,
+                                                     float* __restrict__ stage, int um, int tile_id, int r, int reps, int lane) {
+    if constexpr (TT == 1 && WregOk<L1, GI, 4>::value) {
+        if ((ge.kind & KIND_WREG) && ge.cu_log2 == 4) {
+            MATTEN_RGS_WR(L1, GI, TT, TD, P, 4);
+            return;
+        }
+    }
+    if constexpr (TT == 1 && WregOk<L1, GI, 3>::value) {
+        if ((ge.kind & KIND_WREG) && ge.cu_log2 == 3) {
+            MATTEN_RGS_WR(L1, GI, TT, TD, P, 3);
+            return;
+        }
+    }
+    if (ge.kind & KIND_WREG) return;   // (unreachable with a plan for this library: ops.tp_fused checks matten_tp_wreg)
+    MATTEN_RGS_WR(L1, GI, TT, TD, P, 0);
+}
+#define MATTEN_RGS(L1, GI, TT, TD, P) run_group_shared_any<L1, GI, TT, TD, P>(a, ge, tile, stage, um, tile_id, r, reps, lane)
 #if defined(MATTEN_LAB) && defined(TPF_ONLY_VARIANT)
 // tools/isa_mix.py: ONE (kind, walk variant, coupling mask) per object, so that every loop of the disassembly has a name.
 //   TPF_ONLY_VARIANT 0 = paired workgroup, 1 = two MFMA tiles per chunk (32 nodes per wave), 2 = two rows in flight, 3 = plain
@@ -236,7 +264,11 @@ __device__ __forceinline__ void run_group(const Args& a, const GroupEntry& ge, f
 #ifndef TPF_ONLY_MASK
 #define TPF_ONLY_MASK 0
 #endif
-#define MATTEN_RGS_ONLY(L1, GI, TT, TD, P) run_group_shared<L1, GI, TT, TD, P, (unsigned)(TPF_ONLY_MASK)>(MATTEN_RGS_ARGS)
+//   TPF_ONLY_WR      0 = weights through the wave's LDS tile, 3 / 4 = register hand-over at 8 / 16 lanes per node (variants 0, 2, 3)
+#ifndef TPF_ONLY_WR
+#define TPF_ONLY_WR 0
+#endif
+#define MATTEN_RGS_ONLY(L1, GI, TT, TD, P) run_group_shared<L1, GI, TT, TD, P, (unsigned)(TPF_ONLY_MASK), (TT == 1 ? TPF_ONLY_WR : 0)>(MATTEN_RGS_ARGS)
 #define MATTEN_GROUP_CASE_SHARED(L1, GI) \
     case (L1 * matten::GROUP_KIND_STRIDE + GI): \
         if (TPF_ONLY_VARIANT == 0) MATTEN_RGS_ONLY(L1, GI, 1, (TPF_CHUNK_DEEP && L1 == 0 ? 2 : 0), true); \
@@ -311,7 +343,7 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64, TPF_MIN_BLOCKS) void tp_fused
             else run_loader_only(a, ge, stage, tile_id, r, reps, lane);
             return;
         }
-        switch (ge.kind & (KIND_MERGED - 1)) {
+        switch (ge.kind & (KIND_MERGED - 1)) {   // (the flag bits are not part of the kind)
             TPF_FOR_EACH_GROUP(MATTEN_GROUP_CASE_SHARED)
             default: break;
         }
@@ -683,6 +715,7 @@ extern "C" int matten_tp_fused(const float* x, int64_t d_in, const uint16_t* h2s
     return MATTEN_OK;
 }
 
+extern "C" int matten_tp_wreg(void) { return TPF_WREG ? TPF_WREG_MAX_L1 + 1 : 0; }   // 0, or 1 + the largest l1 compiled for it
 extern "C" int matten_tp_max_cols(void) { return TPF_MAX_COLS; }
 extern "C" int matten_tp_max_cols_l0(void) { return TPF_MAX_COLS_L0; }
 extern "C" int matten_tp_max_cols_l1(void) { return TPF_MAX_COLS_L1; }

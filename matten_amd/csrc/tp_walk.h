@@ -125,6 +125,30 @@ __device__ __forceinline__ void split_f16(float v, _Float16& hi, _Float16& lo) {
 #define TPF_EXACT_Y0 0
 #endif
 
+// REGISTER HAND-OVER of the radial weights (template parameter WR of run_group_shared; plan.TP_KIND_WREG).  The LDS path
+// below computes w = h2 . W2p with the weights as the A (M) and the chunk's 16 edge rows as the B (N) operand: lane
+// (g = lane >> 4, c = lane & 15) holds D[column 4g + i][edge c], stores it to the wave's tile, waits, and every edge step
+// reads its NC weights back.  Both fragments of v_mfma_f32_16x16x32_f16 share one lane / k layout, so exchanging the
+// builtin's first two arguments gives D[edge row 4g + i][column c] from the same registers.  With 16 lanes per node (4 nodes
+// per wave, 4 slots per chunk, chunk row = 4 j + slot) the consumer lane is (node slot j = g, channel u = c): if tile cc of
+// the entry is coupling cc and column u is channel u (coupling-major columns: the plan's part), D[i] of tile cc IS
+// w[cc] of slot i for this lane.  With 8 lanes per node (8 nodes, 2 slots, row = 2 j + slot) the consumer lane (j, u) is
+// lane (g = j >> 1, c = 8 (j & 1) + u) and needs D[2 (c >> 3) + slot]; a tile holds [coupling a x 8 | coupling b x 8], so
+// the lower half row holds a and the upper b: one rotate by 8 inside the 16-lane row (DPP row_ror:8, written to one half of
+// the row only) hands each half the other's coupling.  No LDS write of w, no wait on it, no read back; the same three
+// products summed over the same k as the LDS path.  -DTPF_WREG=0: the LDS path only (plans need MATTEN_TP_WREG=0 then).
+#ifndef TPF_WREG
+#define TPF_WREG 1
+#endif
+#ifndef TPF_WREG_ALO_LDS_MT
+#define TPF_WREG_ALO_LDS_MT 5   // register hand-over entries of this many tiles or more (the 16-lane scalar kind: five) keep the lo halves of
+#endif                          // their A fragments in the wave's LDS tile, idle in this variant, and read them at the top of every chunk
+                                // (address known, nothing waits on the read): with them and w[5][4] in registers the kind spilled three
+                                // fragments, reloaded from scratch in front of the chunk's matrix instructions
+#ifndef TPF_WREG_MAX_L1
+#define TPF_WREG_MAX_L1 1   // == plan.TP_WREG_MAX_L1: the variant is compiled for the scalar and vector input blocks only (the heavier
+#endif                      // kinds reach 8 or 16 lanes per node in no shipped model; each further kind costs compile time and code size)
+
 #ifndef TPF_REP_PREFETCH
 #define TPF_REP_PREFETCH 1   // persistent units: the next node group's loads go out in front of this group's agg stores
 #endif
@@ -237,6 +261,15 @@ constexpr int STAGE_TMAX = 2;               // MFMA tiles (16 edge rows each) pe
 constexpr int STAGE_FLOATS = 16 * STAGE_TMAX * STAGE_ROW;
 constexpr int STAGE_TOTAL_FLOATS = 2 * STAGE_FLOATS;
 
+// What the stage loaders fetch for the rows of an EMPTY segment (their loads are unconditional): the last four floats of the first
+// row of w2p, zero padding by contract (w_pad >= w_cols + 16, zero from w_cols on: matten_hip.h) -- hidden features and harmonics
+// of such a row are then 0 and so are its weights.  (Until round 7 this was the START of w2p: weights, whose low halves read as
+// fp16 are inf or NaN one time in 32; the pair pass of the vector input blocks contracts a slot past the end with x = 0, and
+// 0 x NaN left NaN in the rows of nodes nothing arrives at.)
+__device__ __forceinline__ const char* stage_safe_row(const Args& a) {
+    return reinterpret_cast<const char*>(a.w2p + ((max(a.w_pad, 4) - 4) & ~3));
+}
+
 // w tile rows [edge][col]: D fragments of MTC column tiles, hi.hi + 2^-11 (lo.hi + hi.lo), 16-byte LDS stores
 template <int MTC>
 __device__ __forceinline__ void mfma_tiles(const f16x8* __restrict__ ah, const f16x8* __restrict__ al, f16x8 bh, f16x8 bl,
@@ -275,7 +308,7 @@ struct StageLoader {
         base = piece < 8 ? reinterpret_cast<const char*>(a.h2s) + piece * 16
                          : reinterpret_cast<const char*>(a.sh) + (piece - 8) * 16;
         row_bytes = piece < 8 ? (int64_t)(2 * HID * sizeof(_Float16)) : (int64_t)a.sh_stride * 4;
-        safe = reinterpret_cast<const char*>(a.w2p);
+        safe = stage_safe_row(a);
         st_w = stage + (threadIdx.x >> 4) * STAGE_ROW + piece * 4;
 #pragma unroll
         for (int t = 0; t < TT; ++t) {
@@ -335,7 +368,7 @@ struct PairLoader {
         base = piece < 8 ? reinterpret_cast<const char*>(a.h2s) + piece * 16
                          : reinterpret_cast<const char*>(a.sh) + (piece - 8) * 16;
         row_bytes = piece < 8 ? (int64_t)(2 * HID * sizeof(_Float16)) : (int64_t)a.sh_stride * 4;
-        safe = reinterpret_cast<const char*>(a.w2p);
+        safe = stage_safe_row(a);
         const int n = (int)(threadIdx.x >> 4);
         st_w = stage + n * STAGE_ROW + piece * 4;
         const int jn = (n >> ch_log2) & (npw - 1);
@@ -405,6 +438,24 @@ __device__ __forceinline__ void run_loader_only(const Args& a, const GroupEntry&
 }
 
 // the kinds with registers to spare for a second neighbour row in flight (two-slot chunks: 8 lanes per node)
+// compile-time edge slots of the register hand-over (a slot selects REGISTERS there); the LDS path keeps run-time slots
+template <int SO> using Slot = std::integral_constant<int, SO>;
+__device__ __forceinline__ int slot_next(int so) { return so + 1; }
+template <int SO> __device__ __forceinline__ Slot<SO + 1> slot_next(Slot<SO>) { return {}; }
+template <int I, int N, int STEP, class F>
+__device__ __forceinline__ void for_slots(F&& f) {
+    if constexpr (I < N) {
+        f(Slot<I>{});
+        for_slots<I + STEP, N, STEP>(f);
+    }
+}
+// lanes-per-node classes (log2) of the register hand-over a kind can have: the plan's cap on channels per entry decides
+template <int L1, int GI, int WR>
+struct WregOk {
+    static constexpr bool value = TPF_WREG && L1 <= TPF_WREG_MAX_L1 && (WR == 3 || WR == 4) &&
+                                  cap_channels(L1, matten::Group<L1, GI>::NC) >= (1 << WR);
+};
+
 template <int L1, int GI>
 struct TwoDeepOk { static constexpr bool value = L1 == 0 || (L1 == 1 && (GI == 0 || TPF_PAIR_SUM)); };
 
@@ -422,11 +473,14 @@ struct TwoDeepOk { static constexpr bool value = L1 == 0 || (L1 == 1 && (GI == 0
 // than a gather's latency under load, and the wave waited on every step (phase trace, round 5: 2100-3200 cycles of contraction
 // per four-slot chunk for 150-190 instructions).  The two row buffers swap roles by a two-fold unrolled chunk loop, not by moves:
 // a move out of a register with a load in flight would wait for it.
-template <int L1, int GI, int TT, int TWO_DEEP, bool PAIRED, unsigned CMASK, class Epilogue>
+// WR != 0: the register hand-over (see TPF_WREG above) for entries at 1 << WR = 16 or 8 lanes per node whose columns are
+// coupling-major; the wave's LDS tile is not touched
+template <int L1, int GI, int TT, int TWO_DEEP, bool PAIRED, unsigned CMASK, int WR, class Epilogue>
 __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry& ge, float* __restrict__ tile,
                                                  float* __restrict__ stage, int entry, int tile_id, int r0, int reps, int lane,
                                                  const Epilogue& epi) {
     static_assert(!PAIRED || TT == 1, "paired workgroups stage 2 x 16 rows");
+    static_assert(WR == 0 || (TT == 1 && (WR == 3 || WR == 4)), "register hand-over: one MFMA tile per chunk, 8 or 16 lanes per node");
 #if TPF_TRACING
     const unsigned tr_in_hi = tpf_stamp_hi();
     const unsigned tr_in = tpf_stamp();     // (covers every node group of a persistent unit)
@@ -439,17 +493,19 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
     constexpr int NC = G::NC;
 
     const unsigned mask = ge.mask;
-    const int cu_log2 = ge.cu_log2;              // >= 1 here: at most 32 nodes per wave
+    const int cu_log2 = WR ? WR : ge.cu_log2;    // >= 1 here: at most 32 nodes per wave
     const int cu = 1 << cu_log2;
     const int npw = 64 >> cu_log2;
     const int ch_log2 = npw >= 16 ? 0 : 4 - (6 - cu_log2);
     const int CH = 1 << ch_log2;
     // the weight block holds the columns of ALL couplings of the group, [u][c] (absent ones: zero columns)
     const int ncols = ge.mul * NC;
+    constexpr int WCH = WR == 4 ? 4 : WR == 3 ? 2 : 1;            // register hand-over: slots per chunk ...
+    constexpr int MTW = WR == 4 ? NC : WR == 3 ? (NC + 1) / 2 : 0;   // ... and tiles (mul == lanes per node), at compile time
 #if defined(MATTEN_LAB) && defined(TPF_ONLY_MT)
     const int MT = TPF_ONLY_MT;   // tools/isa_mix.py: the tile count of the one entry kind in the object, at compile time
 #else
-    const int MT = (ncols + 15) >> 4;
+    const int MT = WR ? MTW : (ncols + 15) >> 4;
 #endif
 
     const int j = lane >> cu_log2;
@@ -458,7 +514,11 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
     const int xcol = ge.x_off + u * G::D1;
     constexpr int CAPC = cap_channels(L1, NC);
     constexpr int MTMAX = (CAPC * NC + 15) / 16;
+    static_assert(MTW <= MTMAX, "a register hand-over entry is no wider than the plan's cap");
     const int stride = MT * 16 + 4;              // floats per edge row of the wave's weight tile
+    float wr[WR ? NC * WCH : 1];                 // register hand-over: w[coupling][slot] of this lane's node for the chunk
+    constexpr bool ALO_LDS = WR != 0 && MTW >= TPF_WREG_ALO_LDS_MT;   // lo fragments parked in the wave's tile: MTW x 64 lanes x 16 B
+    f16x8* const alo_lds = reinterpret_cast<f16x8*>(tile) + lane;     // (the tile holds 16 rows of 16 MTW + 36 floats)
     f16x8 ah[MTMAX], al[MTMAX];
     float a_scale_inv;
     if (a.a_split) {
@@ -503,6 +563,10 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
         }
     }
 
+    if constexpr (ALO_LDS) {
+#pragma unroll
+        for (int mt = 0; mt < MTW; ++mt) alo_lds[mt * 64] = al[mt];   // (read back by this lane only: LDS is in order per wave)
+    }
     // Per node group: (i) start_group -- everything of the group's prologue that is a LOAD (segment bounds, the first chunk's
     // stage rows, the first neighbour rows) -- and (ii) the walk + the agg stores.  A persistent unit runs (i) of group
     // rep + 1 BEFORE the stores of group rep: vector-memory operations retire in order, so loads issued behind ~100 stores
@@ -597,7 +661,45 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
                 const f16x8 bh = *reinterpret_cast<const f16x8*>(sb + (16 * t + c) * STAGE_ROW + g * 4);
                 const f16x8 bl = *reinterpret_cast<const f16x8*>(sb + (16 * t + c) * STAGE_ROW + 16 + g * 4);
                 if constexpr (TPF_LAB_NO_MFMA) {
-                    if ((float)bh[0] == 12345.f) tile[c] = (float)bl[0];
+                    if constexpr (WR) {
+#pragma unroll
+                        for (int k = 0; k < NC * WCH; ++k) wr[k] = (float)bh[0] + (float)bl[0];
+                    } else if ((float)bh[0] == 12345.f) tile[c] = (float)bl[0];
+                    continue;
+                }
+                if constexpr (WR) {
+                    // edges are M, weight columns N: this lane's D[i] = (edge row 4 g + i, column c) of each tile
+                    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+                    f32x4 dx[MTW], dh[MTW];
+#pragma unroll
+                    for (int mt = 0; mt < MTW; ++mt) {
+                        const f16x8 alo = ALO_LDS ? alo_lds[mt * 64] : al[mt];
+                        dx[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, alo, zero, 0, 0, 0);
+                        dh[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh, ah[mt], zero, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int mt = 0; mt < MTW; ++mt) dx[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl, ah[mt], dx[mt], 0, 0, 0);
+#pragma unroll
+                    for (int mt = 0; mt < MTW; ++mt) {
+                        const f32x4 d = dh[mt] + SPLIT_LO_INV * dx[mt];
+                        if constexpr (WR == 4) {   // tile mt = coupling mt, rows 4 g + i = the four slots of node slot j = g
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) wr[mt * WCH + i] = d[i];
+                        } else {
+                            // tile mt = [coupling 2 mt x 8 channels | coupling 2 mt + 1 x 8 channels]; this lane's slots are rows
+                            // 2 (c >> 3) + {0, 1}.  Lanes c < 8 keep d[0], d[1] for coupling 2 mt, lanes c >= 8 take d[2], d[3]
+                            // of lane c - 8 (row_ror:8 written to banks 2, 3); the other way round for coupling 2 mt + 1
+                            constexpr int ROR8 = 0x128;
+#pragma unroll
+                            for (int so = 0; so < 2; ++so) {
+                                wr[2 * mt * WCH + so] = __int_as_float(__builtin_amdgcn_update_dpp(
+                                    __float_as_int(d[so]), __float_as_int(d[2 + so]), ROR8, 0xf, 0xc, false));
+                                if (2 * mt + 1 < NC)
+                                    wr[(2 * mt + 1) * WCH + so] = __int_as_float(__builtin_amdgcn_update_dpp(
+                                        __float_as_int(d[2 + so]), __float_as_int(d[so]), ROR8, 0xf, 0x3, false));
+                            }
+                        }
+                    }
                     continue;
                 }
                 float* trow = tile + (16 * t + c) * stride + 4 * g;
@@ -611,17 +713,28 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
                 else mfma_tiles<MTMAX>(ah, al, bh, bl, trow);
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the weight tile is written
-        __builtin_amdgcn_wave_barrier();
+        if constexpr (WR == 0) {
+            __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the weight tile is written
+            __builtin_amdgcn_wave_barrier();
+        }
         __builtin_amdgcn_s_setprio(0);
 #if TPF_TRACING
-        const unsigned tr_b = tpf_stamp();
+        unsigned tr_b;
+        if constexpr (WR) tr_b = tpf_stamp_after(wr);   // (once the weights exist: nothing else waits for the matrix phase)
+        else tr_b = tpf_stamp();
 #endif
-        auto contract = [&](int so, const float* __restrict__ x) {
+        auto contract = [&](auto so_c, const float* __restrict__ x) {
+            const int so = so_c;
             const float* wp = tile + ((j << ch_log2) + so) * stride + u * NC;
             const float* yp = sb + ((j << ch_log2) + so) * STAGE_ROW + 32 + G::Y0;
             float y[G::NY], w[NC];
-            if constexpr (TPF_W_FIRST) {
+            if constexpr (WR) {
+#pragma unroll
+                for (int cc = 0; cc < NC; ++cc) w[cc] = wr[cc * WCH + decltype(so_c)::value];
+                // (the slots are unrolled here: without a fence the harmonics of every slot of the chunk are requested up front,
+                //  4 x 25 registers of the scalar kind -- spills)
+                asm volatile("" ::: "memory");
+            } else if constexpr (TPF_W_FIRST) {
                 // the weights are requested BEFORE the harmonics: whole quads over [Y0, Y0 + NY) leave up to four dead registers,
                 // and weights requested afterwards land IN them -- a write-after-read on a load in flight, i.e. a second LDS
                 // round trip per edge step (seen in the ISA of the l1 = 0 kind, docs/LAB_NOTES.md round 5)
@@ -656,7 +769,7 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
 #pragma unroll
                 for (int jj = 0; jj < G::NY; ++jj) y[jj] = yq[G::Y0 - Q0 + jj];
             }
-            if constexpr (!TPF_W_FIRST) {
+            if constexpr (!WR && !TPF_W_FIRST) {
 #pragma unroll
                 for (int cc = 0; cc < NC; ++cc) w[cc] = wp[cc];
             }
@@ -668,10 +781,14 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
             // are added before they meet the coupling coefficients, -22 / -25 % vector instructions per pair).  The harmonics
             // and weights of both slots are read unconditionally (every slot of a chunk has a staged row: past a segment's
             // end its last edge again); a slot past the end contracts x = 0 -- an exact + 0 to every accumulator.
-            auto fetch = [&](int so, float (&y)[G::NY], float (&w)[NC]) {
+            auto fetch = [&](auto so_c, float (&y)[G::NY], float (&w)[NC]) {
+                const int so = so_c;
                 const float* wp = tile + ((j << ch_log2) + so) * stride + u * NC;
                 const float* yp = sb + ((j << ch_log2) + so) * STAGE_ROW + 32 + G::Y0;
-                if constexpr (TPF_W_FIRST2) {   // weights before harmonics: see `contract` below
+                if constexpr (WR) {
+#pragma unroll
+                    for (int cc = 0; cc < NC; ++cc) w[cc] = wr[cc * WCH + decltype(so_c)::value];
+                } else if constexpr (TPF_W_FIRST2) {   // weights before harmonics: see `contract` below
 #pragma unroll
                     for (int cc = 0; cc < NC; ++cc) w[cc] = wp[cc];
                     asm volatile("" ::: "memory");
@@ -686,16 +803,17 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
                 }
 #pragma unroll
                 for (int jj = 0; jj < G::NY; ++jj) y[jj] = yq[G::Y0 - Q0 + jj];
-                if constexpr (!TPF_W_FIRST2) {
+                if constexpr (!WR && !TPF_W_FIRST2) {
 #pragma unroll
                     for (int cc = 0; cc < NC; ++cc) w[cc] = wp[cc];
                 }
             };
-            for (int so = 0; so < CH; so += 2) {
+            auto pair_pass = [&](auto so_c) {
+                const int so = so_c;
                 const int s = s0 + so;
                 float ya[G::NY], wa[NC], yb[G::NY], wb[NC], xa[G::D1], xc[G::D1];
-                fetch(so, ya, wa);
-                fetch(so + 1, yb, wb);
+                fetch(so_c, ya, wa);
+                fetch(slot_next(so_c), yb, wb);
 #pragma unroll
                 for (int i = 0; i < G::D1; ++i) xa[i] = s < deg ? xn[i] : 0.0f, xc[i] = s + 1 < deg ? xb[i] : 0.0f;
                 {
@@ -711,7 +829,9 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
                     src_b = a.src_sorted[min(beg + s + 5, e_last)];
                 }
                 G::apply2(CMASK ? CMASK : mask, xa, ya, wa, xc, yb, wb, acc);
-            }
+            };
+            if constexpr (WR) for_slots<0, WCH, 2>(pair_pass);
+            else for (int so = 0; so < CH; so += 2) pair_pass(so);
         } else if constexpr (chunk_deep) {
             // rows of the NEXT chunk (their indices arrived a chunk ago), then the indices of the chunk after it
 #pragma unroll
@@ -721,28 +841,54 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
             }
 #pragma unroll
             for (int i = 0; i < XQ; ++i) sq[i] = a.src_sorted[min(beg + s0 + 2 * CH + i, e_last)];
+            if constexpr (WR) {
+                for_slots<0, WCH, 1>([&](auto so_c) {
+                    if (s0 + so_c < deg) contract(so_c, xcur + so_c);
+                });
+            } else {
 #pragma unroll
-            for (int so = 0; so < XQ; ++so) {
-                if (so < CH && s0 + so < deg) contract(so, xcur + so);
+                for (int so = 0; so < XQ; ++so) {
+                    if (so < CH && s0 + so < deg) contract(so, xcur + so);
+                }
             }
         } else if (two_deep) {
-            for (int so = 0; so < CH; so += 2) {   // CH is 2, 4 or 8 here: slot pairs, one row buffer per parity
+            auto pair_steps = [&](auto so_c) {   // CH is 2, 4 or 8 here: slot pairs, one row buffer per parity
+                const int so = so_c;
                 const int s = s0 + so;
-                if (s < deg) contract(so, xn);
+                if (s < deg) contract(so_c, xn);
                 {
                     const float* xp = a.x + (int64_t)TPF_SRC(src_nn) * a.d_in + xcol;
 #pragma unroll
                     for (int i = 0; i < G::D1; ++i) xn[i] = TPF_XLD(xp, i, src_nn);
                     src_nn = a.src_sorted[min(beg + s + 4, e_last)];
                 }
-                if (s + 1 < deg) contract(so + 1, xb);
+                if (s + 1 < deg) contract(slot_next(so_c), xb);
                 {
                     const float* xp = a.x + (int64_t)TPF_SRC(src_b) * a.d_in + xcol;
 #pragma unroll
                     for (int i = 0; i < G::D1; ++i) xb[i] = TPF_XLD(xp, i, src_b);
                     src_b = a.src_sorted[min(beg + s + 5, e_last)];
                 }
-            }
+            };
+            if constexpr (WR) for_slots<0, WCH, 2>(pair_steps);
+            else for (int so = 0; so < CH; so += 2) pair_steps(so);
+        } else if constexpr (WR != 0) {
+            bool go = true;   // (wave-uniform: the LDS path's `break`)
+            for_slots<0, WCH, 1>([&](auto so_c) {
+                const int s = s0 + so_c;
+                go = go && s < maxdeg;
+                if (!go) return;
+                float x[G::D1];
+#pragma unroll
+                for (int i = 0; i < G::D1; ++i) x[i] = xn[i];
+                {
+                    const float* xp = a.x + (int64_t)TPF_SRC(src_nn) * a.d_in + xcol;
+#pragma unroll
+                    for (int i = 0; i < G::D1; ++i) xn[i] = TPF_XLD(xp, i, src_nn);
+                    src_nn = a.src_sorted[min(beg + s + 2, e_last)];
+                }
+                if (s < deg) contract(so_c, x);
+            });
         } else {
             for (int so = 0; so < CH; ++so) {
                 const int s = s0 + so;

@@ -638,6 +638,10 @@ def tp_fused(x, h2p, w2p, sh_sorted, rowptr, src_sorted, entries, unit_map, unit
     if (lib.matten_tp_max_cols() != TP_MAX_COLS or lib.matten_tp_max_cols_l0() != TP_MAX_COLS_L0
             or lib.matten_tp_max_cols_l1() != TP_MAX_COLS_L1):
         raise _lib.MattenHipError("plan.TP_MAX_COLS does not match the library's entry width (-DTPF_MAX_COLS)")
+    from .plan import TP_WREG_MAX_L1, tp_wreg
+    if tp_wreg() and lib.matten_tp_wreg() != TP_WREG_MAX_L1 + 1:
+        raise _lib.MattenHipError("plans mark coupling-major entries (plan.TP_KIND_WREG) that this library was not built for "
+                                  "(-DTPF_WREG=0 / -DTPF_WREG_MAX_L1): set MATTEN_TP_WREG=0")
     global _GROUPS_CHECKED
     from .plan import tp_groups_hash
     if not _GROUPS_CHECKED and lib.matten_tp_groups_hash() != tp_groups_hash():

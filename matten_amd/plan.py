@@ -119,6 +119,19 @@ LIGHT_LMAX = 1   # scalar and vector input blocks: every chunk of a block cut at
 # and offsets and, in its w_base word, the first half's own mask.  MATTEN_TP_MERGE=0 keeps one entry per block.
 TP_KIND_MERGED = 256
 TP_MERGE = os.environ.get("MATTEN_TP_MERGE", "1") != "0"
+# matten_tp_fused: an entry of a scalar or vector input block whose channels fill its lanes (mul == lanes per node, 16 or 8)
+# carries TP_KIND_WREG and has its weight columns COUPLING-MAJOR -- 16 channels per coupling, or two couplings x 8 channels
+# per 16-column tile -- instead of [u][c].  With the edge rows as the M and the weight columns as the N operand of the
+# matrix instruction, the D fragment of a tile is then what the consumer lane (node slot, channel) contracts: the radial
+# weights pass from the matrix phase to the contraction in registers, not through LDS (tp_walk.h, WR).  The tile count
+# does not grow: 16 * NC or 8 * NC columns either way.  MATTEN_TP_WREG=0 (read when a plan is built) keeps [u][c].
+TP_KIND_WREG = 512
+TP_WREG_MAX_L1 = 1      # == TPF_WREG_MAX_L1 of the library: the kinds the register hand-over is compiled for
+TP_WREG_DEFAULT = "1"
+
+
+def tp_wreg() -> bool:
+    return os.environ.get("MATTEN_TP_WREG", TP_WREG_DEFAULT) != "0"
 
 FUSED_UNIT_SHARED = 1 << 24       # the unit's workgroup stages hidden features / harmonics once for its four waves
 FUSED_UNIT_LOADER_ONLY = 1 << 25  # padding unit of a shared workgroup: feeds the stage, contracts nothing
@@ -164,7 +177,7 @@ def fused_workgroups(group_entries, order: Optional[str] = None):
         classes.setdefault(int(ent[e][3]), []).append(e)
     for cu_log2, members in classes.items():
         npw = max(1, 64 >> cu_log2)
-        run = sorted(members, key=lambda e: int(ent[e][0]) & (TP_KIND_MERGED - 1))
+        run = sorted(members, key=lambda e: int(ent[e][0]) & (TP_KIND_MERGED - 1))   # (flag bits are not part of the kind)
         if order != "node" or cu_log2 < 1:
             out.append((cu_log2, run, "plain"))
         elif npw <= 16 and os.environ.get("MATTEN_FUSED_PAIRED", "1") != "0":
@@ -469,6 +482,8 @@ def plan_uvu(irreps_in1, irreps_sh, irreps_target) -> UVUPlan:
         lds_need = max(lds_need, 16 * n_tiles16 * (16 * (-(-(mul_c * len(live)) // 16)) + 32 + 4))
         n_mt = -(-(mul_c * len(live)) // 16)  # 16-column MFMA tiles of the entry's weight block
         merged = len(halves) == 2
+        # register hand-over of the weights (TP_KIND_WREG): full entries of the light kinds at 16 or 8 lanes per node
+        wreg = (tp_wreg() and not merged and l1 <= TP_WREG_MAX_L1 and cu_log2 in (3, 4) and mul_c == (1 << cu_log2))
         rows = []
         for h, (mul_h, present) in enumerate(halves):
             row = [-1, 0, mul_h, cu_log2, 0, 0, 0, 0] + [0] * 24
@@ -481,17 +496,19 @@ def plan_uvu(irreps_in1, irreps_sh, irreps_target) -> UVUPlan:
             row[4] = mask
             rows.append(row)
         head = rows[0]
-        head[0] = l1 * TP_KIND_STRIDE + gi + (TP_KIND_MERGED if merged else 0)
+        head[0] = l1 * TP_KIND_STRIDE + gi + (TP_KIND_MERGED if merged else 0) + (TP_KIND_WREG if wreg else 0)
         head[1], head[2], head[5], head[6], head[7] = x_off + u0 * d1_, mul_c, len(fused_cols), fused_a_tiles, n_mt
         if merged:
             rows[1][5] = head[4]                 # the first half's own mask travels in the continuation record
             head[4] |= rows[1][4]                # the walk contracts the union (absent couplings: zero weight columns)
         fused_a_tiles += n_mt
-        # fused weight layout of this entry: [u][live c] -> column of the reference's weight row (-1: absent in this half)
+        # fused weight layout of this entry: [u][live c] -> column of the reference's weight row (-1: absent in this half);
+        # TP_KIND_WREG: [live c][u] (mul_c * c + u: whole tiles at 16 channels, two couplings per tile at 8)
         for (mul_h, present) in halves:
-            for uu in range(mul_h):
-                for key in live:
-                    fused_cols.append(present[key].w_off + u0 + uu if key in present else -1)
+            order = ([(uu, key) for key in live for uu in range(mul_h)] if wreg else
+                     [(uu, key) for uu in range(mul_h) for key in live])
+            for uu, key in order:
+                fused_cols.append(present[key].w_off + u0 + uu if key in present else -1)
         for r_, (mul_h, present) in zip(rows, halves):
             gentries.append(r_)
             gentry_paths.append({c: paths.index(present[key]) for c, key in enumerate(combos) if key in present})

@@ -262,7 +262,9 @@ def main():
             npw = 64 // cu
             ch = 1 if npw >= 16 else 16 // npw
             chunks = reps * -(-DEG // ch)
-            key = (l1, gi, var, cmask, int(r[7]))
+            # register hand-over of the weights (plan.TP_KIND_WREG): log2 of the lanes per node, 0 = through the LDS tile
+            wr = int(r[3]) if int(r[0]) & mplan.TP_KIND_WREG and var != 1 else 0
+            key = (l1, gi, var, cmask, int(r[7]), wr)
             rec = rows.setdefault(key, {"cu": cu, "ch": ch, "layers": Counter(), "masks": set(), "mul": int(r[2]), "merged": bool(int(r[0]) & 256),
                                         "hot": hot, "n_mt": int(r[7])})
             rec["layers"][lname] += chunks
@@ -274,10 +276,10 @@ def main():
              "-DMATTEN_LAB"]
 
     def build(key):
-        l1, gi, var, cmask, n_mt = key
-        obj = os.path.join(work, f"tpf_{l1}_{gi}_{var}_{cmask:x}_{n_mt}.o")
+        l1, gi, var, cmask, n_mt, wr = key
+        obj = os.path.join(work, f"tpf_{l1}_{gi}_{var}_{cmask:x}_{n_mt}_{wr}.o")
         subprocess.run(["hipcc"] + flags + [f"-DTPF_ONLY_L1={l1}", f"-DTPF_ONLY_GI={gi}", f"-DTPF_ONLY_VARIANT={var}", f"-DTPF_ONLY_MASK={cmask}",
-                                             f"-DTPF_ONLY_MT={n_mt}", "-c", os.path.join(CSRC, "tp_fused.hip"), "-o", obj], check=True, capture_output=True)
+                                             f"-DTPF_ONLY_MT={n_mt}", f"-DTPF_ONLY_WR={wr}", "-c", os.path.join(CSRC, "tp_fused.hip"), "-o", obj], check=True, capture_output=True)
         text = device_disassembly(obj)
         if keep:
             open(obj[:-2] + ".s", "w").write(text)
@@ -298,9 +300,9 @@ def main():
     print(hdr)
     agg = {ln: Counter() for ln, _ in LAYERS}
     for key, rec in rows.items():
-        l1, gi, var, cmask, n_mt = key
+        l1, gi, var, cmask, n_mt, wr = key
         ch = rec["ch"]
-        trips = ch // 2 if var == 2 else ch
+        trips = 1 if wr else ch // 2 if var == 2 else ch   # (the register hand-over unrolls a chunk's slots: they select registers)
         mix, n_body, inner, grp, unit = chunk_loop_mix(listings[key], trips)
         combos = G[l1][gi]
         masks = sorted(rec["masks"])
