@@ -575,6 +575,53 @@ int matten_elastic_kelvin_clamp(const double* voigt, const double* moduli, const
                                 double* out, matten_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Polycrystal bounds and the self-consistent estimate (csrc/polycrystal.hip): the bulk and shear modulus of an untextured
+ * aggregate of equiaxed grains, beyond Voigt, Reuss and Hill -- the Hashin-Shtrikman (HS) bounds and the self-consistent
+ * (SC; Kroener, Hershey, Willis) estimate, for any crystal symmetry.  Replaces a host loop over the ElasticTensor(t) objects
+ * the reference hands back (predict.py:217-218).  Mandel form as above; u = (1,1,1,0,0,0)/sqrt3, J = u u^T, K_d = 1 - J,
+ * iso(K,G) = 3K J + 2G K_d; c_J(T) = u^T T u, c_K(T) = (tr T - c_J(T)) / 5.  With the isotropic comparison medium (K0,G0),
+ * Hill's polarisation tensor of a sphere in it, P = J / (3K0 + 4G0) + K_d 3 (K0 + 2G0) / (5 G0 (3K0 + 4G0)),
+ * R = C^ - iso(K0,G0) and A = (1 + P R)^-1:
+ *     F_K(C^; K0,G0) = c_J(C^ A) / 3 c_J(A)        F_G(C^; K0,G0) = c_K(C^ A) / 2 c_K(A)
+ * (C0 -> 0: Reuss, C0 -> infinity: Voigt).  fp64, one crystal per thread, values in the units of the input.
+ * matten_elastic_polycrystal:
+ *   voigt [n,36], flags [n] as matten_elastic_props wrote them; moduli [n,6] (l_k, ascending), vectors [n,36] as
+ *   matten_elastic_kelvin wrote them for that voigt (Jacobi does not run a second time; F is evaluated from the
+ *   decomposition, no matrix is inverted).  out [n,6] = k_hs_lower, g_hs_lower, k_sc, g_sc, k_hs_upper, g_hs_upper;
+ *   media [n,8] = the (K0, G0) of k_hs_lower, g_hs_lower, k_hs_upper, g_hs_upper, may be NULL (out is the same bits);
+ *   status [n,2] int32 = status, iterations.
+ *   SC: the fixed point (K,G) = F(C^; K,G) by plain iteration from the Voigt pair, until |dK| + |dG| <= sc_tol (K + G) or
+ *   sc_max_iter applications of F; iterations counts the applications.
+ *   HS: F is a lower bound on both moduli for every medium with C^ - iso(K0,G0) positive semi-definite, an upper bound
+ *   for every medium with iso(K0,G0) - C^ so, and monotone in the medium, so the best media lie on the frontier of the
+ *   feasible set, with w_k = (U_k . u)^2:
+ *     lower: G0 in (0, l_min/2],        3K0 - 2G0 =  1 / sum_k w_k / (l_k - 2G0)
+ *     upper: G0 in [l_max/2, infinity), 3K0 - 2G0 = -1 / sum_k w_k / (2G0 - l_k)
+ *   Each of the four bounds is a one-dimensional search: a grid of hs_grid points (lower: G0 = (l_min/2)(1 - 1e-12) i/M,
+ *   i = 1..M; upper: G0 = (l_max/2)(1 + 1e-12) 4^(i/(M-1)), i = 0..M-1), 60 golden-section steps in the bracket of the grid
+ *   winner's two neighbours, the best point visited.  Every point visited is feasible: the result is a valid bound
+ *   whatever the search does, the search decides only how tight it is.  The frontiers stop at l_min/2 and l_max/2 on
+ *   purpose: beyond them feasible media exist only where the softest (stiffest) Kelvin mode carries dilatation.
+ *   Row states: flag bit 0 or a decomposition that is not finite: every output NaN, status -1; flag bit 1 or l_min not > 0:
+ *   every output NaN, status 2 (neither is defined); SC stopped at sc_max_iter: the last iterate, status 1; else status 0.
+ * matten_elastic_polycrystal_bwd: replaces autograd through a host fixed-point loop.  The adjoint of (k_sc, g_sc) by the
+ *   implicit-function theorem: g_C^ = (dF/dC^)^T l with (1 - dF/dx)^T l = g_sc [n,2], a 2x2 solve; dF/dC^ and dF/dx are
+ *   analytic, from one Cholesky inverse of the positive definite C^ + P^-1 - iso(K,G) at the fixed point.  voigt, flags as
+ *   the forward got them, out and status as it wrote them; g_voigt [n,36] = D g_C^ D, every element written, symmetric.
+ *   A row with status -1 or 2 (or flag bit 0, or a value that is not finite) gets exact zeros by a select; a status-1 row
+ *   is differentiated as if its last iterate were the fixed point.  The HS bounds carry no gradient: their medium sits
+ *   on a constraint that moves with C^.
+ * Both: no atomics, no cross-lane traffic, nothing read back: bitwise reproducible, each row independent of the others,
+ * capturable.  n = 0 is a no-op.  MATTEN_EINVAL: n < 0 or above 2^31 - 1 workgroups, a NULL required pointer with n > 0,
+ * hs_grid < 2, sc_tol not positive and finite, sc_max_iter < 1.
+ * ------------------------------------------------------------------------------------------ */
+int matten_elastic_polycrystal(const double* voigt, const int32_t* flags, const double* moduli, const double* vectors,
+                               int64_t n, int hs_grid, double sc_tol, int sc_max_iter, double* out, double* media,
+                               int32_t* status, matten_stream_t stream);
+int matten_elastic_polycrystal_bwd(const double* voigt, const int32_t* flags, const double* out, const int32_t* status,
+                                   const double* g_sc, int64_t n, double* g_voigt, matten_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Derived quantities of per-atom rank-2 tensors (predict.py:117-148: the reference hands back one 3x3 array per atom;
  * NMR users read the isotropic value, span and skew or the Haeberlen anisotropy and asymmetry off it, with the
  * principal axes).  fp64 arithmetic, one atom per thread, values in the units of the input.

@@ -136,6 +136,8 @@ SIGNATURES = {
     "matten_elastic_kelvin": (c_int, [P, P, c_int64, P, P, P, P]),
     "matten_elastic_kelvin_bwd": (c_int, [P, P, P, c_int64, P, P]),
     "matten_elastic_kelvin_clamp": (c_int, [P, P, P, ctypes.c_double, c_int64, P, P]),
+    "matten_elastic_polycrystal": (c_int, [P, P, P, P, c_int64, c_int, ctypes.c_double, c_int, P, P, P, P]),
+    "matten_elastic_polycrystal_bwd": (c_int, [P, P, P, P, P, c_int64, P, P]),
     "matten_rank2_props": (c_int, [P, c_int, c_int64, P, P, P, P, P]),
     "matten_rank2_props_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int64, P, P]),
     "matten_batch_gather_lds_rows": (c_int, []),

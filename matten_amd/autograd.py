@@ -562,6 +562,30 @@ class ElasticKelvinFn(torch.autograd.Function):
         return ops.elastic_kelvin_bwd(vectors, flags, g_moduli.contiguous()), None, None
 
 
+class ElasticPolycrystalFn(torch.autograd.Function):
+    """(out, media, status) = matten_elastic_polycrystal(voigt, flags, moduli, vectors) with its adjoint kernel
+    (matten_elastic_polycrystal_bwd).  Of ``out`` only the self-consistent pair (columns 2 and 3) is differentiated -- the
+    Hashin-Shtrikman columns carry no gradient, whatever arrives for them is dropped -- and only ``voigt`` receives one:
+    ``moduli`` and ``vectors`` are the decomposition of that same ``voigt``, the adjoint is the total derivative with respect
+    to it.  When nothing downstream used ``out`` no kernel runs."""
+
+    @staticmethod
+    def forward(ctx, voigt, flags, moduli, vectors, hs_grid, sc_tol, sc_max_iter):
+        out, media, status = ops.elastic_polycrystal(voigt, flags, moduli, vectors, hs_grid, sc_tol, sc_max_iter)
+        ctx.save_for_backward(voigt, flags, out, status)
+        ctx.mark_non_differentiable(media, status)
+        ctx.set_materialize_grads(False)
+        return out, media, status
+
+    @staticmethod
+    def backward(ctx, g_out, _g_media, _g_status):
+        if g_out is None:
+            return None, None, None, None, None, None, None
+        voigt, flags, out, status = ctx.saved_tensors
+        return (ops.elastic_polycrystal_bwd(voigt, flags, out, status, g_out[:, 2:4].contiguous()), None, None, None, None,
+                None, None)
+
+
 class Rank2PropsFn(torch.autograd.Function):
     """(vals, axes, props, flags) = matten_rank2_props(t) with its adjoint kernel (matten_rank2_props_bwd): the backward
     works from the four outputs alone, so the input is not kept and Jacobi is not run again.  An output that nothing

@@ -34,6 +34,13 @@ signed stability margin and a condition number -- how far an unstable prediction
 ``nearest_stable`` repairs a tensor (``matten_elastic_kelvin_clamp``), ``StabilityPenalty`` trains against instability on the
 moduli that ``elastic_moduli*`` attach to the graph (``matten_elastic_kelvin_bwd``); ``kelvin_host`` / ``kelvin_bwd_host`` /
 ``nearest_stable_host`` restate them in numpy.  Conventions: INTEGRATION.md, "Kelvin moduli and mechanical stability".
+
+``polycrystal=True`` adds the polycrystal moduli beyond Voigt, Reuss and Hill (``matten_elastic_polycrystal``,
+csrc/polycrystal.hip): the Hashin-Shtrikman bounds and the self-consistent estimate of the bulk and shear modulus, for any
+crystal symmetry, from the Kelvin decomposition.  ``elastic_moduli*`` attach ``k_sc`` / ``g_sc`` / ``y_sc`` / ``poisson_sc`` to the
+graph (``matten_elastic_polycrystal_bwd``) and ``ModuliLoss`` takes those names: training on measured polycrystal moduli.  The
+bounds carry no gradient.  ``polycrystal_host`` / ``polycrystal_bwd_host`` state the algorithm in numpy.  Conventions:
+INTEGRATION.md, "Polycrystal bounds and the self-consistent estimate".
 """
 import numpy as np
 import torch
@@ -74,6 +81,10 @@ class ElasticProperties:
     (0 converged, 1 iteration cap, 2 not refined, -1 singular row) and ``X_refined_iterations`` [B] int32.
     With ``kelvin`` also ``kelvin_moduli`` [B,6] (ascending), ``kelvin_vectors`` [B,6,6] (columns), ``kelvin_dilatation``
     [B,6], ``stability_margin`` [B] and ``kelvin_condition`` [B] (NaN where the margin is <= 0).
+    With ``polycrystal`` also ``k_hs_lower`` / ``g_hs_lower`` / ``k_hs_upper`` / ``g_hs_upper`` [B] (Hashin-Shtrikman bounds),
+    ``hs_media`` [B,4,2] (their comparison media (K0, G0), in that order), ``k_sc`` / ``g_sc`` / ``y_sc`` / ``poisson_sc`` [B] (the
+    self-consistent estimate), ``sc_status`` [B] int32 (0 converged, 1 iteration cap, 2 not positive definite, -1 singular
+    row) and ``sc_iterations`` [B] int32.
     An unbatched input ([3,3,3,3] or [6,6]) gives the same without the leading dimension."""
 
     def __init__(self, **fields):
@@ -677,6 +688,263 @@ def nearest_stable(tensors, floor: float = 0.0):
     return (out[0], cart[0], changed[0]) if single else (out, cart, changed)
 
 
+# ---------------------------------------------------------------------------------------------------
+# polycrystal moduli: Hashin-Shtrikman bounds and the self-consistent estimate (``polycrystal=True``;
+# matten_elastic_polycrystal, csrc/polycrystal.hip)
+# ---------------------------------------------------------------------------------------------------
+# the [B] quantities that ``elastic_moduli(polycrystal=True)`` attaches to the graph and ``ModuliLoss`` accepts, with the
+# argument that produces each
+POLYCRYSTAL_NAMES = {"k_sc": "polycrystal", "g_sc": "polycrystal", "y_sc": "polycrystal", "poisson_sc": "polycrystal"}
+POLYCRYSTAL_FIELDS = ("k_hs_lower", "g_hs_lower", "k_hs_upper", "g_hs_upper", "k_sc", "g_sc", "y_sc", "poisson_sc",
+                      "sc_status", "sc_iterations", "hs_media")
+SC_CONVERGED, SC_ITERATION_CAP, SC_NOT_POSITIVE_DEFINITE, SC_SINGULAR = 0, 1, 2, -1
+# constants of the search, the same in the kernel: the relative distance the frontier grids keep from lambda_min / 2 and
+# lambda_max / 2, the factor the upper grid spans, the golden-section steps after the grid and the golden ratio's inverse
+HS_EDGE = 1e-12
+HS_UPPER_SPAN = 4.0
+HS_GOLDEN_STEPS = 60
+HS_GOLDEN = 0.6180339887498949
+_U6 = np.array([1.0, 1.0, 1.0, 0.0, 0.0, 0.0]) / np.sqrt(3.0)
+_J6 = np.outer(_U6, _U6)
+_K6 = np.eye(6) - _J6
+
+
+def _check_polycrystal(polycrystal, hs_grid=64, sc_tol=1e-12, sc_max_iter=200):
+    """the arguments of the polycrystal moduli (ValueError before anything else happens)"""
+    if not isinstance(polycrystal, (bool, np.bool_)):
+        raise ValueError(f"polycrystal: expected True or False, got {polycrystal!r}")
+    if not polycrystal:
+        return
+    if isinstance(hs_grid, (bool, np.bool_)) or not isinstance(hs_grid, (int, np.integer)) or not 2 <= hs_grid <= 0x7fffffff:
+        raise ValueError(f"hs_grid: expected an int >= 2, got {hs_grid!r}")
+    if (isinstance(sc_tol, (bool, np.bool_)) or not isinstance(sc_tol, (float, int, np.floating, np.integer))
+            or not np.isfinite(sc_tol) or not sc_tol > 0.0):
+        raise ValueError(f"sc_tol: expected a finite positive number, got {sc_tol!r}")
+    if (isinstance(sc_max_iter, (bool, np.bool_)) or not isinstance(sc_max_iter, (int, np.integer))
+            or not 1 <= sc_max_iter <= 0x7fffffff):
+        raise ValueError(f"sc_max_iter: expected an int >= 1, got {sc_max_iter!r}")
+
+
+def iso_mandel(K, G):
+    """iso(K, G) = 3K J + 2G K_d as Mandel matrices [...,6,6]"""
+    K, G = np.asarray(K, dtype=np.float64), np.asarray(G, dtype=np.float64)
+    return 3.0 * K[..., None, None] * _J6 + 2.0 * G[..., None, None] * _K6
+
+
+def polarisation_mandel(K0, G0):
+    """Hill's polarisation tensor of a sphere in the isotropic medium (K0, G0), as Mandel matrices [...,6,6]"""
+    K0, G0 = np.asarray(K0, dtype=np.float64), np.asarray(G0, dtype=np.float64)
+    pj = 1.0 / (3.0 * K0 + 4.0 * G0)
+    pk = 3.0 * (K0 + 2.0 * G0) / (5.0 * G0 * (3.0 * K0 + 4.0 * G0))
+    return pj[..., None, None] * _J6 + pk[..., None, None] * _K6
+
+
+def _c_jk(T):
+    """the isotropic projections (c_J, c_K) of Mandel matrices [...,6,6]: the orientation average is c_J J + c_K K_d"""
+    cj = np.einsum("i,...ij,j->...", _U6, T, _U6)
+    return cj, (np.trace(T, axis1=-2, axis2=-1) - cj) / 5.0
+
+
+def polycrystal_F(mandel, K0, G0):
+    """F(C^; K0, G0) -> (F_K, F_G) as documented, by the definition: R = C^ - iso(K0, G0), A = (1 + P R)^-1,
+    F_K = c_J(C^ A) / 3 c_J(A), F_G = c_K(C^ A) / 2 c_K(A).  ``mandel`` [...,6,6], K0 / G0 [...] (broadcast)."""
+    Ch = np.asarray(mandel, dtype=np.float64)
+    K0, G0 = np.broadcast_arrays(np.asarray(K0, dtype=np.float64), np.asarray(G0, dtype=np.float64))
+    A = np.linalg.inv(np.eye(6) + polarisation_mandel(K0, G0) @ (Ch - iso_mandel(K0, G0)))
+    aj, ak = _c_jk(A)
+    cj, ck = _c_jk(Ch @ A)
+    return cj / (3.0 * aj), ck / (2.0 * ak)
+
+
+def _hs_frontier_k0(lam, w, G0, upper: bool):
+    """K0 of the frontier medium at G0: the largest (lower frontier) or smallest (upper) K0 with C^ - iso(K0, G0) still
+    positive (negative) semi-definite; lam [B,6] ascending, w [B,6] = (U_k . u)^2, G0 [B]"""
+    if upper:
+        return (2.0 * G0 - 1.0 / (w / (2.0 * G0[:, None] - lam)).sum(axis=1)) / 3.0
+    return (2.0 * G0 + 1.0 / (w / (lam - 2.0 * G0[:, None])).sum(axis=1)) / 3.0
+
+
+def _hs_grid_g0(lam, i, M: int, upper: bool):
+    """the grid point i of the frontier (lower: i = 1..M, i = 0 is G0 = 0 and never evaluated; upper: i = 0..M-1)"""
+    if upper:
+        return (0.5 * lam[:, 5] * (1.0 + HS_EDGE)) * np.exp2(np.log2(HS_UPPER_SPAN) * i / (M - 1))
+    return (0.5 * lam[:, 0] * (1.0 - HS_EDGE)) * (i / M)
+
+
+def _hs_search(Ch, lam, w, M: int, upper: bool):
+    """the two searches along one frontier, for all rows at once -> (value [B,2], medium [B,2,2]): index 0 the bound on
+    K, 1 the bound on G; medium[:, q] = (K0, G0) where it was found.  The grid, then ``HS_GOLDEN_STEPS`` golden-section
+    steps in the bracket of the grid winner's two neighbours; the best point visited is kept (strictly better only: the
+    first wins a tie, a NaN never wins)."""
+    B = lam.shape[0]
+    sign = -1.0 if upper else 1.0
+
+    def evaluate(G0):
+        K0 = _hs_frontier_k0(lam, w, G0, upper)
+        FK, FG = polycrystal_F(Ch, K0, G0)
+        return K0, (FK, FG)
+
+    first, last = (0, M - 1) if upper else (1, M)
+    best = np.full((B, 2), -np.inf)          # of sign * F
+    medium = np.full((B, 2, 2), np.nan)
+    winner = np.full((B, 2), first, dtype=np.int64)
+
+    def keep(q, f, K0, G0):
+        take = sign * f > best[:, q]
+        best[:, q] = np.where(take, sign * f, best[:, q])
+        medium[:, q, 0] = np.where(take, K0, medium[:, q, 0])
+        medium[:, q, 1] = np.where(take, G0, medium[:, q, 1])
+        return take
+
+    for i in range(first, last + 1):
+        G0 = _hs_grid_g0(lam, np.full(B, float(i)), M, upper)
+        K0, F = evaluate(G0)
+        for q in (0, 1):
+            winner[:, q] = np.where(keep(q, F[q], K0, G0), i, winner[:, q])
+    for q in (0, 1):
+        a = _hs_grid_g0(lam, np.maximum(winner[:, q] - 1, 0).astype(np.float64), M, upper)
+        b = _hs_grid_g0(lam, np.minimum(winner[:, q] + 1, last).astype(np.float64), M, upper)
+        x1, x2 = b - HS_GOLDEN * (b - a), a + HS_GOLDEN * (b - a)
+        K1, F1 = evaluate(x1)
+        K2, F2 = evaluate(x2)
+        f1, f2 = sign * F1[q], sign * F2[q]
+        keep(q, F1[q], K1, x1)
+        keep(q, F2[q], K2, x2)
+        for _ in range(HS_GOLDEN_STEPS):
+            left = f1 > f2                       # the maximum is in [a, x2]
+            b = np.where(left, x2, b)
+            a = np.where(left, a, x1)
+            xn = np.where(left, b - HS_GOLDEN * (b - a), a + HS_GOLDEN * (b - a))
+            Kn, Fn = evaluate(xn)
+            fn = sign * Fn[q]
+            keep(q, Fn[q], Kn, xn)
+            x1, x2, f1, f2 = (np.where(left, xn, x2), np.where(left, x1, xn), np.where(left, fn, f2),
+                              np.where(left, f1, fn))
+    return sign * best, medium
+
+
+def _polycrystal_rows(voigt, flags):
+    """-> (C^ [B,6,6] with bad rows replaced by the identity, lam [B,6], w [B,6], singular [B], not_pd [B], unbatched?)"""
+    C, single = _host_voigt(voigt)
+    Ch, singular = _host_flags(flags, C)
+    not_pd = np.zeros(C.shape[0], dtype=bool)
+    if flags is not None:
+        f = np.asarray(flags.detach().cpu().numpy() if isinstance(flags, torch.Tensor) else flags).reshape(-1)
+        not_pd = (f & FLAG_NOT_POSITIVE_DEFINITE) != 0
+    Ch = np.where(singular[:, None, None], np.eye(6), Ch)
+    lam, U = np.linalg.eigh(Ch)
+    not_pd = (not_pd | ~(lam[:, 0] > 0.0)) & ~singular
+    Ch = np.where(not_pd[:, None, None], np.eye(6), Ch)
+    lam, U = np.where(not_pd[:, None], 1.0, lam), np.where(not_pd[:, None, None], np.eye(6), U)
+    w = ((U[:, 0, :] + U[:, 1, :]) + U[:, 2, :]) ** 2 / 3.0
+    return Ch, lam, w, singular, not_pd, single
+
+
+def _sc_iterate(Ch, lam, w, sc_tol: float, sc_max_iter: int):
+    """the fixed point (K, G) = F(C^; K, G) from the Voigt pair, all rows at once -> (K [B], G [B], status [B],
+    iterations [B])"""
+    B = lam.shape[0]
+    wl = (w * lam).sum(axis=1)
+    K, G = wl / 3.0, (lam.sum(axis=1) - wl) / 10.0
+    active = np.ones(B, dtype=bool)
+    status = np.full(B, SC_ITERATION_CAP, dtype=np.int32)
+    iterations = np.zeros(B, dtype=np.int32)
+    for _ in range(int(sc_max_iter)):
+        Kn, Gn = polycrystal_F(Ch, K, G)
+        iterations[active] += 1
+        done = active & (np.abs(Kn - K) + np.abs(Gn - G) <= sc_tol * (Kn + Gn))
+        K, G = np.where(active, Kn, K), np.where(active, Gn, G)
+        status[done] = SC_CONVERGED
+        active = active & ~done
+        if not active.any():
+            break
+    return K, G, status, iterations
+
+
+def polycrystal_host(voigt, hs_grid: int = 64, sc_tol: float = 1e-12, sc_max_iter: int = 200, flags=None) -> dict:
+    """The polycrystal moduli in numpy fp64 -- the documented algorithm ("Polycrystal bounds and the
+    self-consistent estimate"), what the tests hold ``matten_elastic_polycrystal`` to.  ``voigt`` [B,6,6] or [6,6]: the Voigt
+    matrix C_IJ (the mean of its two triangles is used), ``flags`` [B] as ``matten_elastic_props`` sets them, or None.
+    F is evaluated by its definition (``polycrystal_F``: one 6x6 inverse per point); the frontiers come from
+    ``numpy.linalg.eigh`` of the Mandel matrix.  -> dict of ``k_hs_lower``, ``g_hs_lower``, ``k_sc``, ``g_sc``, ``k_hs_upper``,
+    ``g_hs_upper``, ``y_sc`` = 9KG / (3K + G), ``poisson_sc`` = (3K - 2G) / (6K + 2G) [B], ``sc_status`` [B] int32 (0 converged,
+    1 iteration cap: the last iterate, 2 not positive definite: NaN, -1 flag bit 0 or a non-finite entry: NaN),
+    ``sc_iterations`` [B] int32 and ``hs_media`` [B,4,2]: the comparison medium (K0, G0) of ``k_hs_lower``, ``g_hs_lower``,
+    ``k_hs_upper``, ``g_hs_upper``.  A row counts as not positive definite with flag bit 1 or a smallest Kelvin modulus
+    that is not > 0."""
+    _check_polycrystal(True, hs_grid, sc_tol, sc_max_iter)
+    Ch, lam, w, singular, not_pd, single = _polycrystal_rows(voigt, flags)
+    bad = singular | not_pd
+    with np.errstate(all="ignore"):
+        K, G, status, iterations = _sc_iterate(Ch, lam, w, float(sc_tol), int(sc_max_iter))
+        lower, media_lo = _hs_search(Ch, lam, w, int(hs_grid), False)
+        upper, media_up = _hs_search(Ch, lam, w, int(hs_grid), True)
+        nan = np.nan
+        K, G = np.where(bad, nan, K), np.where(bad, nan, G)
+        out = dict(k_hs_lower=np.where(bad, nan, lower[:, 0]), g_hs_lower=np.where(bad, nan, lower[:, 1]), k_sc=K, g_sc=G,
+                   k_hs_upper=np.where(bad, nan, upper[:, 0]), g_hs_upper=np.where(bad, nan, upper[:, 1]),
+                   y_sc=9.0 * K * G / (3.0 * K + G), poisson_sc=(3.0 * K - 2.0 * G) / (6.0 * K + 2.0 * G),
+                   sc_status=np.where(singular, SC_SINGULAR, np.where(not_pd, SC_NOT_POSITIVE_DEFINITE, status)).astype(np.int32),
+                   sc_iterations=np.where(bad, 0, iterations).astype(np.int32),
+                   hs_media=np.where(bad[:, None, None], nan, np.concatenate([media_lo, media_up], axis=1)))
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
+def polycrystal_bwd_host(voigt, g_sc, flags=None, sc=None, sc_tol: float = 1e-12, sc_max_iter: int = 200) -> np.ndarray:
+    """The adjoint of the self-consistent pair in numpy fp64: ``g_sc`` [B,2] (the upstream gradients of k_sc and g_sc) ->
+    g_voigt [B,6,6], symmetric.  ``sc``: (k_sc [B], g_sc [B], sc_status [B]) as a forward returned them (None: those of
+    ``polycrystal_host``).  With x = (K, G) the fixed point of F and M = (C^ + C*)^-1, C* = 4G J + b K_d,
+    b = G (9K + 8G) / 3 (K + 2G), v = M u, m_J = u . v, m_K = (tr M - m_J) / 5:
+    dF_K/dC^ = v v^T / 3 m_J^2, dF_G/dC^ = (M^2 - v v^T) / 10 m_K^2; dF/dx is analytic as well (through C*: dM =
+    -M dC* M); (1 - dF/dx)^T l = g is a 2x2 solve, g_C^ = l_K dF_K/dC^ + l_G dF_G/dC^ and g_voigt = D g_C^ D.  Rows with
+    status -1 or 2 are zero."""
+    C, single = _host_voigt(voigt)
+    Ch, _ = _host_flags(flags, C)
+    g = np.asarray(g_sc.detach().cpu().numpy() if isinstance(g_sc, torch.Tensor) else g_sc, dtype=np.float64).reshape(-1, 2)
+    if sc is None:
+        rows = _polycrystal_rows(C, flags)
+        K, G, status, _ = _sc_iterate(rows[0], rows[1], rows[2], float(sc_tol), int(sc_max_iter))
+        status = np.where(rows[3], SC_SINGULAR, np.where(rows[4], SC_NOT_POSITIVE_DEFINITE, status))
+    else:
+        K, G, status = (np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t).reshape(-1) for t in sc)
+    status = np.asarray(status)
+    bad = ((status != SC_CONVERGED) & (status != SC_ITERATION_CAP)) | ~np.isfinite(K) | ~np.isfinite(G)
+    K, G = np.where(bad, 1.0, K).astype(np.float64), np.where(bad, 1.0, G).astype(np.float64)
+    Ch = np.where(bad[:, None, None], np.eye(6), Ch)
+    a = 4.0 * G
+    b = G * (9.0 * K + 8.0 * G) / (3.0 * (K + 2.0 * G))
+    M = np.linalg.inv(Ch + a[:, None, None] * _J6 + b[:, None, None] * _K6)
+    v = M @ _U6
+    mj = v @ _U6
+    q = (v * v).sum(axis=1)
+    t2 = (M * M).sum(axis=(1, 2))
+    mk = (np.trace(M, axis1=1, axis2=2) - mj) / 5.0
+    fk_b = (q - mj * mj) / (3.0 * mj * mj)
+    fg_a = (q - mj * mj) / (10.0 * mk * mk)
+    fg_b = (t2 - 2.0 * q + mj * mj) / (10.0 * mk * mk) - 0.5
+    den = 3.0 * (K + 2.0 * G) ** 2
+    b_k, b_g = 10.0 * G * G / den, (9.0 * K * K + 16.0 * K * G + 16.0 * G * G) / den
+    j11, j12, j21, j22 = fk_b * b_k, fk_b * b_g, fg_b * b_k, 4.0 * fg_a + fg_b * b_g
+    det = (1.0 - j11) * (1.0 - j22) - j12 * j21
+    lk = (g[:, 0] * (1.0 - j22) + j21 * g[:, 1]) / det
+    lg = ((1.0 - j11) * g[:, 1] + j12 * g[:, 0]) / det
+    vv = v[:, :, None] * v[:, None, :]
+    gc = (lk / (3.0 * mj * mj))[:, None, None] * vv + (lg / (10.0 * mk * mk))[:, None, None] * (M @ M - vv)
+    out = MANDEL_WEIGHT * (0.5 * (gc + gc.transpose(0, 2, 1)))
+    out = np.where(bad[:, None, None], 0.0, out)
+    return out[0] if single else out
+
+
+def _polycrystal_fields(out, media, status) -> dict:
+    """the outputs of the polycrystal kernel under their field names, with Young's modulus and Poisson's ratio of the
+    self-consistent pair (torch expressions on it); the Hashin-Shtrikman fields carry no gradient"""
+    hs = out.detach()
+    K, G = out[:, 2], out[:, 3]
+    return dict(k_hs_lower=hs[:, 0], g_hs_lower=hs[:, 1], k_hs_upper=hs[:, 4], g_hs_upper=hs[:, 5], k_sc=K, g_sc=G,
+                y_sc=9.0 * K * G / (3.0 * K + G), poisson_sc=(3.0 * K - 2.0 * G) / (6.0 * K + 2.0 * G),
+                sc_status=status[:, 0], sc_iterations=status[:, 1], hs_media=media.reshape(-1, 4, 2))
+
+
 def _directional_fields(young, beta, ext, arg, dirs) -> dict:
     """the outputs of the directional kernel under their field names"""
     return dict(young=young, compressibility=beta,
@@ -699,10 +967,11 @@ def _acoustic_fields(vel, ext, arg, n_unstable, n_dirs: int, number_density) -> 
 
 def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, failed=None, angles=None, density=None,
                number_density=None, modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
-               refine_max_iter: int = 32, kelvin: bool = False) -> ElasticProperties:
+               refine_max_iter: int = 32, kelvin: bool = False, polycrystal: bool = False, hs_grid: int = 64,
+               sc_tol: float = 1e-12, sc_max_iter: int = 200) -> ElasticProperties:
     """rows on the device -> ElasticProperties; ``dirs``: unit vectors out of ``check_directions`` (host) or None;
     ``density`` / ``number_density``: out of ``_check_per_row`` or None; ``refine*``: checked by ``_check_refine``;
-    ``kelvin``: checked by ``_check_kelvin``"""
+    ``kelvin``: checked by ``_check_kelvin``; ``polycrystal``, ``hs_grid``, ``sc_*``: checked by ``_check_polycrystal``"""
     voigt, compliance, props, flags = ops.elastic_props(rows, layout)
     if failed is not None and failed.any():
         flags |= torch.as_tensor(failed.astype(np.int32) * FLAG_FAILED_STRUCTURE, device=flags.device)
@@ -741,7 +1010,12 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
         fields.update(_acoustic_fields(*ops.elastic_acoustic(voigt, flags, rho, dirs, modulus_unit, keep=keep_directional),
                                        dirs.shape[0], number_density))
     if kelvin:      # (after the failed-structure bit went into the flags: the kernel reads bit 0 only)
-        fields.update(_kelvin_fields(*ops.elastic_kelvin(voigt, flags)))
+        moduli, vectors, dilatation = ops.elastic_kelvin(voigt, flags)
+        fields.update(_kelvin_fields(moduli, vectors, dilatation))
+    if polycrystal:      # (works from the Kelvin decomposition, whose fields appear only with ``kelvin``)
+        if not kelvin:
+            moduli, vectors, _ = ops.elastic_kelvin(voigt, flags, want_dilatation=False)
+        fields.update(_polycrystal_fields(*ops.elastic_polycrystal(voigt, flags, moduli, vectors, hs_grid, sc_tol, sc_max_iter)))
     if single:
         fields = {k: (v if v is None or k in ("directions", "angles") else v[0]) for k, v in fields.items()}
     return ElasticProperties(**fields)
@@ -749,7 +1023,8 @@ def _from_rows(rows, layout, dirs=None, keep_directional=False, single=False, fa
 
 def elastic_properties(tensors, directions=None, keep_directional: bool = False, angles=None, density=None,
                        number_density=None, modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
-                       refine_max_iter: int = 32, kelvin: bool = False) -> ElasticProperties:
+                       refine_max_iter: int = 32, kelvin: bool = False, polycrystal: bool = False, hs_grid: int = 64,
+                       sc_tol: float = 1e-12, sc_max_iter: int = 200) -> ElasticProperties:
     """``tensors``: a torch tensor or numpy array [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6], fp32 or fp64, on the device or
     on the host (copied once), or a list of such tensors as ``predict`` returns (stacked; a ``None`` entry becomes a NaN
     row with flag bit 2).  ``directions``: an int D (``fibonacci_hemisphere(D)``) or an array [D,3] (validated and
@@ -773,8 +1048,18 @@ def elastic_properties(tensors, directions=None, keep_directional: bool = False,
     stability"): ``kelvin_moduli`` [B,6] ascending, ``kelvin_vectors`` [B,6,6] (columns), ``kelvin_dilatation`` [B,6],
     ``stability_margin`` [B] (the smallest modulus, signed) and ``kelvin_condition`` [B] (NaN where the margin is <= 0);
     ``eigenstrains(props)`` gives the 3 x 3 eigenstrains.  Every other field and flag bit is the same with and without it.
+    ``polycrystal=True`` adds the polycrystal moduli beyond Voigt, Reuss and Hill (``matten_elastic_polycrystal``;
+    INTEGRATION.md, "Polycrystal bounds and the self-consistent estimate"): the Hashin-Shtrikman bounds ``k_hs_lower`` /
+    ``g_hs_lower`` / ``k_hs_upper`` / ``g_hs_upper`` [B] with their comparison media ``hs_media`` [B,4,2] (K0, G0 in that order
+    of bounds), the self-consistent estimate ``k_sc`` / ``g_sc`` with ``y_sc`` = 9KG / (3K + G) and ``poisson_sc`` =
+    (3K - 2G) / (6K + 2G), ``sc_status`` [B] int32 (0 converged, 1 iteration cap: the last iterate, 2 not positive
+    definite: NaN, -1 singular row: NaN) and ``sc_iterations`` [B] int32.  ``hs_grid`` (>= 2) is the number of grid points
+    per frontier before the golden-section polish -- every point visited is a feasible medium, so the bounds are valid
+    whatever the search does, it decides only how tight they are --, ``sc_tol`` the relative change at which the fixed-point
+    iteration stops, ``sc_max_iter`` its cap.  The Kelvin kernel runs for it; its fields appear only with ``kelvin=True``.
     The results stay on the device."""
     _check_kelvin(kelvin)
+    _check_polycrystal(polycrystal, hs_grid, sc_tol, sc_max_iter)
     _check_extras(directions, angles, density, number_density)
     _check_refine(refine, directions, refine_tol, refine_max_iter)
     dirs = None if directions is None else check_directions(directions)      # (before anything is uploaded)
@@ -784,7 +1069,7 @@ def elastic_properties(tensors, directions=None, keep_directional: bool = False,
     if number_density is not None:
         number_density = _check_per_row("number_density", number_density, rows.shape[0], single)
     return _from_rows(_upload(rows), layout, dirs, keep_directional, single, failed, angles, density, number_density,
-                      modulus_unit, refine, refine_tol, refine_max_iter, kelvin)
+                      modulus_unit, refine, refine_tol, refine_max_iter, kelvin, polycrystal, hs_grid, sc_tol, sc_max_iter)
 
 
 _VOIGT_Q = {}
@@ -793,12 +1078,14 @@ _VOIGT_Q = {}
 def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = False,
                                    formula: str = "ijkl=jikl=klij", angles=None, density=None, number_density=None,
                                    modulus_unit: float = 1e9, refine: bool = False, refine_tol: float = 1e-9,
-                                   refine_max_iter: int = 32, kelvin: bool = False) -> ElasticProperties:
+                                   refine_max_iter: int = 32, kelvin: bool = False, polycrystal: bool = False,
+                                   hs_grid: int = 64, sc_tol: float = 1e-12, sc_max_iter: int = 200) -> ElasticProperties:
     """The same from the model's irreps rows ``x`` [B,21] (fp32, on the device): one ``dense_rows`` with ``voigt_basis``
     gives the Voigt matrices [B,36] directly -- no [B,81] Cartesian intermediate."""
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
         raise ValueError("x: expected a tensor [B,21] or [21]")
     _check_kelvin(kelvin)
+    _check_polycrystal(polycrystal, hs_grid, sc_tol, sc_max_iter)
     _check_extras(directions, angles, density, number_density)
     _check_refine(refine, directions, refine_tol, refine_max_iter)
     dirs = None if directions is None else check_directions(directions)
@@ -818,16 +1105,17 @@ def elastic_properties_from_irreps(x, directions=None, keep_directional: bool = 
         _VOIGT_Q[key] = torch.tensor(V, dtype=torch.float32, device=x.device)
     rows = ops.dense_rows(x.to(torch.float32), _VOIGT_Q[key])
     return _from_rows(rows, 1, dirs, keep_directional, single, None, angles, density, number_density, modulus_unit, refine,
-                      refine_tol, refine_max_iter, kelvin)
+                      refine_tol, refine_max_iter, kelvin, polycrystal, hs_grid, sc_tol, sc_max_iter)
 
 
 # ---------------------------------------------------------------------------------------------------
 # differentiable: training on moduli
 # ---------------------------------------------------------------------------------------------------
 def _moduli_fields(rows, layout, single, dirs=None, keep_directional=False, density=None, number_density=None,
-                   modulus_unit: float = 1e9, kelvin: bool = False, kelvin_dilatation: bool = True) -> ElasticProperties:
+                   modulus_unit: float = 1e9, kelvin: bool = False, kelvin_dilatation: bool = True, polycrystal: bool = False,
+                   hs_grid: int = 64, sc_tol: float = 1e-12, sc_max_iter: int = 200) -> ElasticProperties:
     """``_from_rows`` attached to the autograd graph (no pair quantities): the same kernels, so the same bits"""
-    from .autograd import ElasticAcousticFn, ElasticDirectionalFn, ElasticKelvinFn, ElasticPropsFn
+    from .autograd import ElasticAcousticFn, ElasticDirectionalFn, ElasticKelvinFn, ElasticPolycrystalFn, ElasticPropsFn
 
     voigt, compliance, props, flags = ElasticPropsFn.apply(rows, layout)
     fields = {"voigt": voigt, "compliance": compliance}
@@ -844,7 +1132,15 @@ def _moduli_fields(rows, layout, single, dirs=None, keep_directional=False, dens
         fields.update(_acoustic_fields(*ElasticAcousticFn.apply(voigt, flags, rho, dirs, float(modulus_unit),
                                                                 bool(keep_directional)), dirs.shape[0], number_density))
     if kelvin:
-        fields.update(_kelvin_fields(*ElasticKelvinFn.apply(voigt, flags, bool(kelvin_dilatation))))
+        moduli, vectors, dilatation = ElasticKelvinFn.apply(voigt, flags, bool(kelvin_dilatation))
+        fields.update(_kelvin_fields(moduli, vectors, dilatation))
+    if polycrystal:      # (the gradient goes to voigt directly: the decomposition enters detached)
+        if kelvin:
+            moduli = moduli.detach()
+        else:
+            moduli, vectors, _ = ops.elastic_kelvin(voigt.detach(), flags, want_dilatation=False)
+        fields.update(_polycrystal_fields(*ElasticPolycrystalFn.apply(voigt, flags, moduli, vectors, int(hs_grid),
+                                                                      float(sc_tol), int(sc_max_iter))))
     if single:
         fields = {k: (v if v is None or k == "directions" else v[0]) for k, v in fields.items()}
     return ElasticProperties(**fields)
@@ -867,7 +1163,8 @@ def _check_moduli_extras(directions, angles, density, number_density, B: int, si
 
 def elastic_moduli(tensors, directions=None, keep_directional: bool = False, density=None, number_density=None,
                    modulus_unit: float = 1e9, angles=None, kelvin: bool = False,
-                   kelvin_dilatation: bool = True) -> ElasticProperties:
+                   kelvin_dilatation: bool = True, polycrystal: bool = False, hs_grid: int = 64, sc_tol: float = 1e-12,
+                   sc_max_iter: int = 200) -> ElasticProperties:
     """The differentiable ``elastic_properties``: ``tensors`` is a device tensor [B,3,3,3,3], [B,6,6], [3,3,3,3] or [6,6],
     fp32 or fp64; ``voigt``, ``compliance`` and the ten scalars of ``PROP_NAMES`` come back attached to its autograd graph
     (``flags``, ``is_stable``, ``is_singular`` as in ``elastic_properties``).  A row with flag bit 0 is NaN and sends a zero
@@ -881,8 +1178,14 @@ def elastic_moduli(tensors, directions=None, keep_directional: bool = False, den
     ``elastic_properties``: ``kelvin_moduli`` and ``stability_margin`` are attached to the graph
     (``matten_elastic_kelvin_bwd``; what ``StabilityPenalty`` trains on), the vectors, the dilatation and
     ``kelvin_condition`` carry no gradient.  ``kelvin_dilatation=False`` leaves the dilatation out (the field is None, the
-    kernel gets a null pointer for it): for a loss that reads the moduli alone, as ``graphs.stability_penalized`` does."""
+    kernel gets a null pointer for it): for a loss that reads the moduli alone, as ``graphs.stability_penalized`` does.
+    ``polycrystal=True`` (with ``hs_grid``, ``sc_tol``, ``sc_max_iter``) adds the polycrystal fields of ``elastic_properties``:
+    ``k_sc``, ``g_sc``, ``y_sc`` and ``poisson_sc`` are attached to the graph (``matten_elastic_polycrystal_bwd``, the
+    implicit-function theorem at the fixed point; ``POLYCRYSTAL_NAMES``, what ``ModuliLoss`` accepts); the Hashin-Shtrikman
+    bounds and their media are detached -- the optimal medium sits on a constraint that moves with the tensor, as the
+    refined extremes do.  A row with ``sc_status`` -1 or 2 is NaN and sends a zero gradient back."""
     _check_kelvin(kelvin)
+    _check_polycrystal(polycrystal, hs_grid, sc_tol, sc_max_iter)
     if not isinstance(tensors, torch.Tensor):
         raise ValueError("tensors: elastic_moduli differentiates device tensors only; for arrays, lists and host tensors "
                          "use elastic_properties (no gradient)")
@@ -901,7 +1204,7 @@ def elastic_moduli(tensors, directions=None, keep_directional: bool = False, den
         raise ValueError("tensors: elastic_moduli differentiates device tensors only; a host tensor goes through "
                          "elastic_properties (no gradient)")
     return _moduli_fields(tensors.reshape(-1, width), layout, single, dirs, keep_directional, density, number_density,
-                          modulus_unit, kelvin, kelvin_dilatation)
+                          modulus_unit, kelvin, kelvin_dilatation, polycrystal, hs_grid, sc_tol, sc_max_iter)
 
 
 _VOIGT_QT = {}
@@ -909,13 +1212,16 @@ _VOIGT_QT = {}
 
 def elastic_moduli_from_irreps(x, formula: str = "ijkl=jikl=klij", directions=None, keep_directional: bool = False,
                                density=None, number_density=None, modulus_unit: float = 1e9, angles=None,
-                               kelvin: bool = False, kelvin_dilatation: bool = True) -> ElasticProperties:
+                               kelvin: bool = False, kelvin_dilatation: bool = True, polycrystal: bool = False,
+                               hs_grid: int = 64, sc_tol: float = 1e-12, sc_max_iter: int = 200) -> ElasticProperties:
     """The differentiable ``elastic_properties_from_irreps``: ``x`` [B,21] (or [21]) fp32 on the device, usually the model's
     output with its ``grad_fn``.  The forward is the same ``dense_rows`` with ``voigt_basis``; its adjoint is ``dense_rows``
-    with the transposed basis [36,21].  The directional arguments and ``kelvin`` are those of ``elastic_moduli``."""
+    with the transposed basis [36,21].  The directional arguments, ``kelvin`` and ``polycrystal`` are those of
+    ``elastic_moduli``."""
     from .autograd import DenseRowsFn
 
     _check_kelvin(kelvin)
+    _check_polycrystal(polycrystal, hs_grid, sc_tol, sc_max_iter)
     if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2):
         raise ValueError("x: expected a tensor [B,21] or [21]")
     V = voigt_basis(formula)
@@ -934,7 +1240,7 @@ def elastic_moduli_from_irreps(x, formula: str = "ijkl=jikl=klij", directions=No
         _VOIGT_QT[key] = _VOIGT_Q[key].t().contiguous()
     rows = DenseRowsFn.apply(x.reshape(-1, x.shape[-1]), _VOIGT_Q[key], _VOIGT_QT[key])
     return _moduli_fields(rows, 1, single, dirs, keep_directional, density, number_density, modulus_unit, kelvin,
-                          kelvin_dilatation)
+                          kelvin_dilatation, polycrystal, hs_grid, sc_tol, sc_max_iter)
 
 
 class ModuliLoss(torch.nn.Module):
@@ -943,7 +1249,9 @@ class ModuliLoss(torch.nn.Module):
     square (``"mse"``), weighted per name, over the entries whose row has flag bit 0 clear and whose target is finite.
     ``names`` come from ``PROP_NAMES`` and ``DIRECTIONAL_NAMES`` (directional extremes, sound velocities, the Debye
     temperature: ``props`` must have been made with the directional arguments); an entry of the latter whose value is not
-    finite (a row with acoustically unstable directions, say) is excluded as well.
+    finite (a row with acoustically unstable directions, say) is excluded as well.  So are the names of
+    ``POLYCRYSTAL_NAMES`` (the self-consistent ``k_sc``, ``g_sc``, ``y_sc``, ``poisson_sc``: ``props`` must have been made with
+    ``polycrystal=True``; a row that is not positive definite has none and is excluded).
     Excluded entries are replaced with ``torch.where``, never multiplied away, so their NaN reaches neither the value nor
     the gradient; a batch without a single entry gives a zero that is still attached to the graph."""
 
@@ -952,9 +1260,9 @@ class ModuliLoss(torch.nn.Module):
         names = (names,) if isinstance(names, str) else tuple(names)
         if not names:
             raise ValueError("names: at least one property is needed")
-        unknown = [n for n in names if n not in PROP_NAMES and n not in DIRECTIONAL_NAMES]
+        unknown = [n for n in names if n not in PROP_NAMES and n not in DIRECTIONAL_NAMES and n not in POLYCRYSTAL_NAMES]
         if unknown:
-            raise ValueError(f"names: {unknown} not in {PROP_NAMES + tuple(DIRECTIONAL_NAMES)}")
+            raise ValueError(f"names: {unknown} not in {PROP_NAMES + tuple(DIRECTIONAL_NAMES) + tuple(POLYCRYSTAL_NAMES)}")
         if len(set(names)) != len(names):
             raise ValueError(f"names: repeated entry in {names}")
         if kind not in ("l1", "mse"):
@@ -983,13 +1291,14 @@ class ModuliLoss(torch.nn.Module):
         for name in self.names:
             value = getattr(props, name, None)
             if value is None:
-                raise ValueError(f"props: no {name!r}; pass {DIRECTIONAL_NAMES[name]} to elastic_moduli / "
-                                 f"elastic_moduli_from_irreps")
+                needs = f"{POLYCRYSTAL_NAMES[name]}=True" if name in POLYCRYSTAL_NAMES else DIRECTIONAL_NAMES[name]
+                raise ValueError(f"props: no {name!r}; pass {needs} to elastic_moduli / elastic_moduli_from_irreps")
             target = torch.as_tensor(targets[name], dtype=value.dtype, device=value.device)
             if target.shape != value.shape:
                 raise ValueError(f"targets[{name!r}]: expected shape {tuple(value.shape)}, got {tuple(target.shape)}")
             use = row_ok & torch.isfinite(target)
-            if name in DIRECTIONAL_NAMES:      # e.g. a row with acoustically unstable directions, a bad density
+            # (e.g. a row with acoustically unstable directions, a bad density, a row that is not positive definite)
+            if name in DIRECTIONAL_NAMES or name in POLYCRYSTAL_NAMES:
                 use = use & torch.isfinite(value.detach())
             zero = torch.zeros_like(value)
             diff = torch.where(use, value, zero) - torch.where(use, target, zero)

@@ -1026,6 +1026,52 @@ def elastic_kelvin_clamp(voigt, moduli, vectors, floor: float = 0.0) -> torch.Te
     return out
 
 
+def elastic_polycrystal(voigt, flags, moduli, vectors, hs_grid: int = 64, sc_tol: float = 1e-12, sc_max_iter: int = 200,
+                        want_media: bool = True):
+    """voigt [B,6,6] fp64 and flags [B] int32 as ``elastic_props`` returns them, moduli [B,6] and vectors [B,6,6] as
+    ``elastic_kelvin`` returns them for it -> (out [B,6] = k_hs_lower, g_hs_lower, k_sc, g_sc, k_hs_upper, g_hs_upper,
+    media [B,8] or None = the (K0, G0) of the four bounds, status [B,2] int32 = status, iterations): the Hashin-Shtrikman
+    bounds and the self-consistent estimate (include/matten_hip.h: matten_elastic_polycrystal)"""
+    lib = _lib.load()
+    hs_grid, sc_tol, sc_max_iter = int(hs_grid), float(sc_tol), int(sc_max_iter)
+    if not 2 <= hs_grid <= 0x7fffffff:
+        raise ValueError(f"hs_grid: expected an int >= 2, got {hs_grid!r}")
+    if not (np.isfinite(sc_tol) and sc_tol > 0.0):
+        raise ValueError(f"sc_tol: expected a finite positive number, got {sc_tol!r}")
+    if not 1 <= sc_max_iter <= 0x7fffffff:
+        raise ValueError(f"sc_max_iter: expected an int >= 1, got {sc_max_iter!r}")
+    voigt, flags, B = _kelvin_rows(voigt, flags)
+    moduli = _need(moduli, torch.float64, "moduli")
+    vectors = _need(vectors, torch.float64, "vectors")
+    if moduli.shape != (B, 6) or vectors.shape != (B, 6, 6):
+        raise ValueError(f"expected moduli [B,6], vectors [B,6,6]; got {tuple(moduli.shape)}, {tuple(vectors.shape)}")
+    out = torch.empty(B, 6, dtype=torch.float64, device=voigt.device)
+    media = torch.empty(B, 8, dtype=torch.float64, device=voigt.device) if want_media else None
+    status = torch.empty(B, 2, dtype=torch.int32, device=voigt.device)
+    _lib.check(lib.matten_elastic_polycrystal(_ptr(voigt), _ptr(flags), _ptr(moduli), _ptr(vectors), B, hs_grid, sc_tol,
+                                              sc_max_iter, _ptr(out), _ptr(media), _ptr(status), _stream()),
+               "matten_elastic_polycrystal")
+    return out, media, status
+
+
+def elastic_polycrystal_bwd(voigt, flags, out, status, g_sc) -> torch.Tensor:
+    """the adjoint of ``elastic_polycrystal``'s self-consistent pair: voigt [B,6,6], flags [B] as the forward got them, out
+    [B,6] and status [B,2] as it wrote them, the upstream gradient g_sc [B,2] of (k_sc, g_sc) (fp64) -> g_voigt [B,6,6]
+    fp64, symmetric; rows with status -1 or 2 are zero (matten_elastic_polycrystal_bwd)"""
+    lib = _lib.load()
+    voigt, flags, B = _kelvin_rows(voigt, flags)
+    out = _need(out, torch.float64, "out")
+    status = _need(status, torch.int32, "status")
+    g_sc = _need(g_sc, torch.float64, "g_sc")
+    if out.shape != (B, 6) or status.shape != (B, 2) or g_sc.shape != (B, 2):
+        raise ValueError(f"expected out [B,6], status [B,2], g_sc [B,2]; got {tuple(out.shape)}, {tuple(status.shape)}, "
+                         f"{tuple(g_sc.shape)}")
+    g_voigt = torch.empty(B, 6, 6, dtype=torch.float64, device=voigt.device)
+    _lib.check(lib.matten_elastic_polycrystal_bwd(_ptr(voigt), _ptr(flags), _ptr(out), _ptr(status), _ptr(g_sc), B,
+                                                  _ptr(g_voigt), _stream()), "matten_elastic_polycrystal_bwd")
+    return g_voigt
+
+
 def elastic_directional(compliance, flags, dirs, keep: bool = False):
     """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64 -> (young [B,D] or None, beta [B,D] or
     None, ext [B,4] = E_min, E_max, beta_min, beta_max, arg [B,4] int32) (matten_elastic_directional)"""

@@ -571,7 +571,8 @@ def _structure_densities(structures) -> np.ndarray:
 
 
 def _properties_of_slabs(device_rows, n, failed, directions, single, angles=None, density=None, number_density=None,
-                         modulus_unit=1e9, refine=False, refine_tol=1e-9, refine_max_iter=32, kelvin=False):
+                         modulus_unit=1e9, refine=False, refine_tol=1e-9, refine_max_iter=32, kelvin=False,
+                         polycrystal=False, hs_grid=64, sc_tol=1e-12, sc_max_iter=200):
     """ElasticProperties of all n input structures from the slabs' device tensors: they never come back from the host.
     Structures without a prediction (``failed``) keep NaN rows and get flag bit 2."""
     from .elastic import _from_rows
@@ -586,7 +587,7 @@ def _properties_of_slabs(device_rows, n, failed, directions, single, angles=None
     mask = np.zeros(n, dtype=bool)
     mask[list(failed)] = True
     return _from_rows(rows, 0, directions, False, single, mask, angles, density, number_density, modulus_unit, refine,
-                      refine_tol, refine_max_iter, kelvin)
+                      refine_tol, refine_max_iter, kelvin, polycrystal, hs_grid, sc_tol, sc_max_iter)
 
 
 def predict(
@@ -611,6 +612,10 @@ def predict(
     refine_tol: float = 1e-9,
     refine_max_iter: int = 32,
     kelvin: bool = False,
+    polycrystal: bool = False,
+    hs_grid: int = 64,
+    sc_tol: float = 1e-12,
+    sc_max_iter: int = 200,
     shielding: bool = False,
 ):
     """See the module docstring.  ``model`` / ``config`` let a caller reuse an already loaded model.
@@ -625,6 +630,10 @@ def predict(
     and ``refine_max_iter``: the directional extremes polished off the grid (the ``*_refined*`` fields; needs ``directions``).
     ``kelvin=True`` (needs ``properties=True``) adds the Kelvin decomposition of ``elastic.elastic_properties(kelvin=True)``:
     ``kelvin_moduli``, ``kelvin_vectors``, ``kelvin_dilatation``, ``stability_margin``, ``kelvin_condition``.
+    ``polycrystal=True`` (needs ``properties=True``; with ``hs_grid``, ``sc_tol``, ``sc_max_iter``) adds the polycrystal moduli of
+    ``elastic.elastic_properties(polycrystal=True)``: the Hashin-Shtrikman bounds ``k_hs_lower`` / ``g_hs_lower`` / ``k_hs_upper``
+    / ``g_hs_upper`` with ``hs_media``, the self-consistent ``k_sc`` / ``g_sc`` / ``y_sc`` / ``poisson_sc``, ``sc_status`` and
+    ``sc_iterations``.
     ``batch_size`` (reference predict.py:155) is the memory knob it is there: consecutive batches are merged into one forward
     only while the merged batch stays within ``node_budget`` atoms (default MATTEN_PREDICT_NODE_BUDGET = 65536, ~2 GB) and
     only when batch_size is at least the reference's default of 200; ``node_budget=0`` never merges.  A merged forward
@@ -650,6 +659,8 @@ def predict(
             raise ValueError("refine belongs to the derived properties: pass properties=True")
         if kelvin:
             raise ValueError("kelvin belongs to the derived properties: pass properties=True")
+        if polycrystal:
+            raise ValueError("polycrystal belongs to the derived properties: pass properties=True")
     if shielding:
         from .rank2 import rank2_basis
 
@@ -662,9 +673,10 @@ def predict(
     single = not isinstance(structure, (list, tuple))
     structures = [structure] if single else list(structure)
     if properties:
-        from .elastic import _check_extras, _check_kelvin, _check_per_row, _check_refine
+        from .elastic import _check_extras, _check_kelvin, _check_per_row, _check_polycrystal, _check_refine
 
         _check_kelvin(kelvin)
+        _check_polycrystal(polycrystal, hs_grid, sc_tol, sc_max_iter)
         _check_extras(directions, angles, density, number_density)
         _check_refine(refine, directions, refine_tol, refine_max_iter)
         if isinstance(density, str):
@@ -719,7 +731,8 @@ def predict(
         raise RuntimeError("Cannot successfully convert any structures.")
     if properties:
         props = _properties_of_slabs(device_rows, len(structures), failed, directions, single, angles, density,
-                                     number_density, modulus_unit, refine, refine_tol, refine_max_iter, kelvin)
+                                     number_density, modulus_unit, refine, refine_tol, refine_max_iter, kelvin,
+                                     polycrystal, hs_grid, sc_tol, sc_max_iter)
     if is_elasticity_tensor:
         try:
             from pymatgen.analysis.elasticity import ElasticTensor
