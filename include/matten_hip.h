@@ -964,6 +964,40 @@ int matten_neighbor_fill(const double* pos, const double* cell, const int64_t* p
                          int32_t* rowptr, int32_t* src_sorted, int32_t* perm, matten_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rebuilding the edge list of the SAME atoms at new positions / cells without a host read (reference data/data.py:285-413,
+ * same edge contract and canonical order): the pair search into buffers of fixed capacity, so that "new geometry -> edge
+ * list -> forward" replays as one hipGraph.
+ * matten_neighbor_scan (reference data/data.py:285-413: the running sums behind its edge order): offsets[n + 1] (int64) :=
+ *   exclusive scan of counts[n] (int32), one block, no workspace: the caller's scan of matten_neighbor_count's counts
+ *   (both halves at once, n = 2 pair_ptr[B], as the eager builder scans them) as a launch that captures.
+ * matten_neighbor_fill_capped (reference data/data.py:285-413): matten_neighbor_fill's inputs without n_edges -- the
+ *   kernels read E = offsets[pair_ptr[B]] from device memory -- plus the capacities (N_b, E_b, B_b) of the outputs;
+ *   offsets_t is required.  It writes the padded batch layout of matten_batch_gather_padded (below): edge_index[2,E_b]
+ *   (row stride E_b), edge_cell_shift[E_b,3], num_neigh[N_b], rowptr[N_b + 1], src_sorted[E_b], perm[E_b] and
+ *   n_valid[3] = (n_atoms, E, n_crystals) (int64).  The E real edges and their destination-sorted CSR are
+ *   matten_neighbor_fill's; behind them come the E_b - E padding edges in closed form: with K = B_b - n_crystals and
+ *   P = N_b - n_atoms - (K - 1), padding node q < P owns the edges [floor(q (E_b - E) / P), floor((q + 1) (E_b - E) / P)),
+ *   each q -> q with shift (1, 0, 0); num_neigh of a padding node is its degree, rowptr is closed over the padding nodes.
+ *   The rows of pos, cell, atomic_numbers, batch and ptr are the caller's.
+ *   flags[1] (int32, OR-ed in): MATTEN_CAPPED_OVERFLOW E > E_b; MATTEN_CAPPED_EDGELESS a real crystal without any edge;
+ *   MATTEN_CAPPED_SINGULAR some singular[b] != 0 (matten_graph_prep_pbc's output; NULL: none).  With E > E_b NOTHING is
+ *   stored but the flag: every output keeps the previous call's contents.  Every store is behind its capacity.
+ *   MATTEN_EINVAL: what matten_neighbor_fill refuses, an empty batch, B_b <= n_crystals, N_b < n_atoms + (B_b -
+ *   n_crystals), a capacity of 2^31 or more, a NULL output, flags or n_valid.
+ * ------------------------------------------------------------------------------------------ */
+#define MATTEN_CAPPED_OVERFLOW 1
+#define MATTEN_CAPPED_EDGELESS 2
+#define MATTEN_CAPPED_SINGULAR 4
+int matten_neighbor_scan(const int32_t* counts, int64_t n, int64_t* offsets, matten_stream_t stream);
+int matten_neighbor_fill_capped(const double* pos, const double* cell, const int64_t* ptr, const double* frac,
+                                const double* bound, const int64_t* pair_ptr, double r_cut, int64_t n_crystals,
+                                int64_t max_atoms, const int64_t* offsets, const int64_t* offsets_t, int64_t n_atoms,
+                                const int32_t* singular, int64_t node_capacity, int64_t edge_capacity,
+                                int64_t crystal_capacity, int64_t* edge_index, float* edge_cell_shift, float* num_neigh,
+                                int32_t* rowptr, int32_t* src_sorted, int32_t* perm, int64_t* n_valid, int32_t* flags,
+                                matten_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Batch assembly from a device-resident training set (replaces PyG's collate at reference data/dataset.py:150-152,
  * which concatenates the picked crystals on the host for every batch of every epoch).
  *

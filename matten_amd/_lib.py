@@ -119,6 +119,9 @@ SIGNATURES = {
     "matten_neighbor_summary": (c_int, [P, P, c_int64, P, P]),
     "matten_neighbor_fill": (c_int, [P, P, P, P, P, P, ctypes.c_double, c_int64, c_int64, P, c_int64, P, P, P, P, c_int64,
                                      P, P, P, P]),
+    "matten_neighbor_scan": (c_int, [P, c_int64, P, P]),
+    "matten_neighbor_fill_capped": (c_int, [P, P, P, P, P, P, ctypes.c_double, c_int64, c_int64, P, P, c_int64, P, c_int64,
+                                            c_int64, c_int64, P, P, P, P, P, P, P, P, P]),
     "matten_gate_bn": (c_int, [P, c_int64, P, c_int64, P, P, P, P, P, c_float, c_int64, P, P]),
     "matten_segment_reduce": (c_int, [P, c_int64, P, c_int64, c_int, P, P]),
     "matten_segment_minmax": (c_int, [P, c_int64, P, c_int64, c_int, P, P, P]),

@@ -812,3 +812,188 @@ extern "C" int matten_neighbor_cells_fill(const double* pos, const double* cell,
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }
+
+// ---- capped fill: the pair search into buffers of fixed capacity (N_b, E_b, B_b), edge count read on the device ----
+// What a loop over geometries of the same atoms replays as a hipGraph: no host number depends on the positions.  The
+// result is the padded batch layout of data/store.py (GraphStoreHost.padded_reference): behind the B real crystals come
+// K = B_b - B padding crystals; padding crystal 0 owns P = N_b - N - (K - 1) nodes and all E_b - E padding edges, node q
+// of it the edges [floor(q Ep / P), floor((q + 1) Ep / P)), each a self-image edge q -> q with shift (1, 0, 0).  E =
+// offsets[pair_ptr[B]] is read by every thread; when it exceeds E_b no thread stores anything but the flag, so the
+// arrays keep the previous, structurally valid list.  Flag bits: MATTEN_CAPPED_* (include/matten_hip.h).
+namespace {
+
+struct Capped {
+    int64_t n_atoms, n_crystals;   // N, B: the real part
+    int64_t n_b, e_b, b_b;         // capacities
+};
+
+// exclusive scan of int32 counts into int64 offsets[n + 1] by ONE block: a thread sums a contiguous chunk, the chunk
+// sums are scanned in LDS, the thread writes its chunk's prefixes.  The capped route serves small cells (a few thousand
+// ordered pairs); it replaces the library scan of the eager builder with a launch that is known to capture.
+__global__ __launch_bounds__(1024) void neighbor_scan_kernel(const int32_t* __restrict__ counts, int64_t n,
+                                                             int64_t* __restrict__ offsets) {
+    __shared__ long long part[1024];
+    const int64_t chunk = (n + blockDim.x - 1) / blockDim.x;
+    const int64_t lo = min(n, (int64_t)threadIdx.x * chunk), hi = min(n, lo + chunk);
+    long long s = 0;
+    for (int64_t k = lo; k < hi; ++k) s += counts[k];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < (int)blockDim.x; o <<= 1) {   // Hillis-Steele, inclusive
+        const long long v = threadIdx.x >= (unsigned)o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    long long run = part[threadIdx.x] - s;   // exclusive prefix of this chunk
+    for (int64_t k = lo; k < hi; ++k) {
+        offsets[k] = run;
+        run += counts[k];
+    }
+    if (threadIdx.x == blockDim.x - 1) offsets[n] = part[threadIdx.x];
+}
+
+// neighbor_kernel<true> with the edge count taken from device memory and every store behind its capacity
+__global__ __launch_bounds__(256) void neighbor_fill_capped_kernel(Cry c, double r_cut, const int64_t* __restrict__ offsets,
+                                                                   const int64_t* __restrict__ offsets_t, Capped cap,
+                                                                   int64_t* __restrict__ edge_index,
+                                                                   float* __restrict__ shifts, float* __restrict__ num_neigh,
+                                                                   int32_t* __restrict__ rowptr,
+                                                                   int32_t* __restrict__ src_sorted,
+                                                                   int32_t* __restrict__ perm) {
+    const int64_t n_edges = offsets[c.pair_ptr[cap.n_crystals]];
+    if (n_edges > cap.e_b) return;   // overflow: nothing is stored (the flag is the closing kernel's)
+    const int64_t b = blockIdx.y;
+    const int64_t lo = c.ptr[b];
+    const int64_t n = c.ptr[b + 1] - lo;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * n) return;
+    const int64_t i = lo + t / n, j = lo + t % n;
+    if (i >= cap.n_atoms || j >= cap.n_atoms) return;
+    const int64_t pair = c.pair_ptr[b] + t;
+    const double* cl = c.cell + 9 * b;
+    int x0, x1, y0, y1, z0, z1;
+    shift_range(c.bound[3 * b], c.frac[3 * j] - c.frac[3 * i], x0, x1);
+    shift_range(c.bound[3 * b + 1], c.frac[3 * j + 1] - c.frac[3 * i + 1], y0, y1);
+    shift_range(c.bound[3 * b + 2], c.frac[3 * j + 2] - c.frac[3 * i + 2], z0, z1);
+    const double pi[3] = {c.pos[3 * i], c.pos[3 * i + 1], c.pos[3 * i + 2]};
+    const double pj[3] = {c.pos[3 * j], c.pos[3 * j + 1], c.pos[3 * j + 2]};
+    int64_t out = offsets[pair];
+    if (j == lo) num_neigh[i] = (float)(offsets[pair + n] - offsets[pair]);   // atom i's n pairs
+    const int64_t pair_t = c.pair_ptr[b] + (j - lo) * n + (i - lo);           // the same pair numbered j-major
+    int64_t out_t = offsets_t[pair_t] - offsets_t[0];
+    if (i == lo) rowptr[j] = (int32_t)out_t;
+    const int64_t e_b = cap.e_b;
+    pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [&](int sx, int sy, int sz) {
+        if (out < n_edges) {
+            edge_index[out] = i;
+            edge_index[e_b + out] = j;
+            shifts[3 * out] = (float)sx;
+            shifts[3 * out + 1] = (float)sy;
+            shifts[3 * out + 2] = (float)sz;
+        }
+        if (out_t < n_edges) {
+            perm[out_t] = (int32_t)out;
+            src_sorted[out_t] = (int32_t)i;
+        }
+        ++out_t;
+        ++out;
+    });
+}
+
+// first padding edge of padding node q: floor(q Ep / P) (q <= P, Ep < 2^31, P < 2^31: exact in int64)
+__device__ __forceinline__ int64_t pad_first_edge(int64_t q, int64_t ep, int64_t p) { return q * ep / p; }
+
+// The closing kernel: the flags, and (unless the list overflows) the padding edges, the CSR and the degrees of the padding
+// nodes and the valid counts.  One thread per padding edge / padding node, whichever are more.
+__global__ __launch_bounds__(256) void neighbor_pad_capped_kernel(const int64_t* __restrict__ offsets,
+                                                                  const int64_t* __restrict__ pair_ptr,
+                                                                  const int32_t* __restrict__ singular, Capped cap,
+                                                                  int64_t* __restrict__ edge_index,
+                                                                  float* __restrict__ shifts, float* __restrict__ num_neigh,
+                                                                  int32_t* __restrict__ rowptr,
+                                                                  int32_t* __restrict__ src_sorted,
+                                                                  int32_t* __restrict__ perm, int64_t* __restrict__ n_valid,
+                                                                  int32_t* __restrict__ flags) {
+    const int64_t n_edges = offsets[pair_ptr[cap.n_crystals]];
+    const bool over = n_edges > cap.e_b;
+    if (blockIdx.x == 0) {   // the flag word: one block looks at every real crystal, one thread ORs
+        int bits = 0;
+        for (int64_t b = threadIdx.x; b < cap.n_crystals; b += blockDim.x) {
+            if (offsets[pair_ptr[b + 1]] == offsets[pair_ptr[b]]) bits |= MATTEN_CAPPED_EDGELESS;
+            if (singular && singular[b]) bits |= MATTEN_CAPPED_SINGULAR;
+        }
+        const int edgeless = __syncthreads_or(bits & MATTEN_CAPPED_EDGELESS);
+        const int sing = __syncthreads_or(bits & MATTEN_CAPPED_SINGULAR);
+        if (threadIdx.x == 0) {
+            const int word = (over ? MATTEN_CAPPED_OVERFLOW : 0) | (edgeless ? MATTEN_CAPPED_EDGELESS : 0) |
+                             (sing ? MATTEN_CAPPED_SINGULAR : 0);
+            if (word) flags[0] = flags[0] | word;
+            if (!over) n_valid[0] = cap.n_atoms, n_valid[1] = n_edges, n_valid[2] = cap.n_crystals;
+        }
+    }
+    if (over) return;
+    const int64_t k = cap.b_b - cap.n_crystals;          // padding crystals
+    const int64_t p = cap.n_b - cap.n_atoms - (k - 1);   // nodes of padding crystal 0 (>= 1)
+    const int64_t ep = cap.e_b - n_edges;                // padding edges
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < ep) {   // padding edge t: its owner is the last node q with floor(q Ep / P) <= t
+        const int64_t q = ((t + 1) * p - 1) / ep;
+        const int64_t e = n_edges + t, node = cap.n_atoms + q;
+        edge_index[e] = node;
+        edge_index[cap.e_b + e] = node;
+        shifts[3 * e] = 1.0f, shifts[3 * e + 1] = 0.0f, shifts[3 * e + 2] = 0.0f;
+        perm[e] = (int32_t)e;
+        src_sorted[e] = (int32_t)node;
+    }
+    if (t <= cap.n_b - cap.n_atoms) {   // padding node t (t == N_b - N: the closing entry of rowptr)
+        const int64_t first = t < p ? n_edges + pad_first_edge(t, ep, p) : cap.e_b;
+        rowptr[cap.n_atoms + t] = (int32_t)first;
+        if (t < cap.n_b - cap.n_atoms)
+            num_neigh[cap.n_atoms + t] = t < p ? (float)(pad_first_edge(t + 1, ep, p) - pad_first_edge(t, ep, p)) : 0.0f;
+    }
+}
+
+}  // namespace
+
+extern "C" int matten_neighbor_scan(const int32_t* counts, int64_t n, int64_t* offsets, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || !offsets || (n > 0 && !counts)) return MATTEN_EINVAL;
+    neighbor_scan_kernel<<<1, 1024, 0, stream>>>(counts, n, offsets);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}
+
+extern "C" int matten_neighbor_fill_capped(const double* pos, const double* cell, const int64_t* ptr, const double* frac,
+                                           const double* bound, const int64_t* pair_ptr, double r_cut, int64_t n_crystals,
+                                           int64_t max_atoms, const int64_t* offsets, const int64_t* offsets_t,
+                                           int64_t n_atoms, const int32_t* singular, int64_t node_capacity,
+                                           int64_t edge_capacity, int64_t crystal_capacity, int64_t* edge_index,
+                                           float* edge_cell_shift, float* num_neigh, int32_t* rowptr, int32_t* src_sorted,
+                                           int32_t* perm, int64_t* n_valid, int32_t* flags, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t lim = (int64_t)1 << 31;
+    // what matten_neighbor_fill refuses (its empty batches included: a capped batch has real atoms)
+    if (n_crystals <= 0 || max_atoms <= 0 || n_atoms <= 0 || !(r_cut > 0.0) || n_crystals > 65535) return MATTEN_EINVAL;
+    if (!pos || !cell || !ptr || !frac || !bound || !pair_ptr || !offsets || !offsets_t) return MATTEN_EINVAL;
+    if (!flags || !n_valid) return MATTEN_EINVAL;
+    if (node_capacity < 0 || edge_capacity < 0 || crystal_capacity < 0 || node_capacity >= lim || edge_capacity >= lim ||
+        crystal_capacity >= lim)
+        return MATTEN_EINVAL;
+    // (N_b < N + (B_b - B), written so that no sum can leave int64)
+    if (crystal_capacity <= n_crystals || n_atoms > node_capacity || node_capacity - n_atoms < crystal_capacity - n_crystals)
+        return MATTEN_EINVAL;
+    if (!num_neigh || !rowptr) return MATTEN_EINVAL;
+    if (edge_capacity > 0 && (!edge_index || !edge_cell_shift || !src_sorted || !perm)) return MATTEN_EINVAL;
+    Cry c{pos, cell, ptr, frac, bound, pair_ptr};
+    Capped cap{n_atoms, n_crystals, node_capacity, edge_capacity, crystal_capacity};
+    dim3 grid((unsigned)matten_cdiv(max_atoms * max_atoms, 256), (unsigned)n_crystals);
+    neighbor_fill_capped_kernel<<<grid, 256, 0, stream>>>(c, r_cut, offsets, offsets_t, cap, edge_index, edge_cell_shift,
+                                                          num_neigh, rowptr, src_sorted, perm);
+    MATTEN_LAUNCH_CHECK();
+    const int64_t pad_threads = max(edge_capacity, node_capacity - n_atoms + 1);
+    neighbor_pad_capped_kernel<<<(unsigned)matten_cdiv(pad_threads, 256), 256, 0, stream>>>(
+        offsets, pair_ptr, singular, cap, edge_index, edge_cell_shift, num_neigh, rowptr, src_sorted, perm, n_valid, flags);
+    MATTEN_LAUNCH_CHECK();
+    return MATTEN_OK;
+}

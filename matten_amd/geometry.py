@@ -6,7 +6,8 @@ code, nn/_nequip.py:130-268).  Here the per-edge geometry is a kernel with a han
 (``autograd.EdgeGeomFn`` / ``matten_edge_geom_bwd``), the radial MLP returns dL/d(length)
 (``matten_radial_mlp_bwd_len``) and the tensor product dL/d(harmonics) (``matten_tp_backward_sh``); a forward whose
 ``pos`` or ``cell`` requires grad chains them.  The edge list is fixed: an edge that crosses the cutoff contributes a
-kink, as in the reference.  First derivatives only.
+kink, as in the reference.  First derivatives only.  (A loop that moves the atoms rebuilds the list on the device with
+``data.rebuild.GeometryBatch``; ``graphs.GraphedGeometryStep`` replays rebuild, forward and these gradients as one hipGraph.)
 
     out = geometry_gradients(model, batch, lambda p: elastic_moduli_from_irreps(p["elastic_tensor_full"]).k_vrh.sum())
     out["pos"]     # [N,3]    d k_vrh / d position: which atom moves the bulk modulus

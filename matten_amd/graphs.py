@@ -557,3 +557,97 @@ class GraphedForward:
         if validate:
             _raise_for_flags(self._embeds, self._static)
         return self._out
+
+
+class GraphedGeometryStep:
+    """"New positions / cells -> edge list -> forward (-> gradients)" of a ``data.rebuild.GeometryBatch`` as ONE hipGraph
+    launch, for loops over geometries of the same atoms (strain sweeps, trajectory frames, structure optimisation).
+
+    Captured, on one stream: the copy of the staged inputs into `gb`'s fp64 buffers, ``gb.update`` (prologue, counting
+    pass, scan, capped fill: no host read), the forward on ``dict(gb.batch)`` -- the keys an earlier forward derived from
+    the geometry (``geometry._DERIVED``) are never carried over -- and, with `fn`, ``fn(preds).backward()`` with the batch's
+    ``pos`` / ``cell`` as leaves, as ``geometry.geometry_gradients`` runs it.
+
+    ``step(pos, cell)`` returns the predictions of the REAL crystals (a view of the captured output, overwritten by the
+    next step).  With `fn`, ``grads`` = {"pos" [N,3], "cell" [3B,3], "strain" [B,3,3]} holds the gradients of the scalar
+    ``fn(preds)`` over the real rows (`fn` sees the padded predictions: restrict it to ``[:B]`` itself).  The flags of the
+    replayed update are OR-ed into ``gb.flags`` (``gb.check()`` raises from them) or, with ``flags_out``, copied there.
+    Warm-up and the species checks are those of ``GraphedForward``: validated once on the construction geometry, trusted
+    on replay.  ``gb.grow`` replaces the tensors this step was captured on: build a new step afterwards."""
+
+    def __init__(self, model, gb, fn: Callable = None, task_name: str = "elastic_tensor_full", warmup: int = 3):
+        _check_capturable(gb.batch)
+        self.model, self.gb, self.fn, self.task_name = model, gb, fn, task_name
+        dev = gb.device
+        self._tensors = dict(gb.batch)   # (identity: a grown batch is refused in step())
+        self._pos_in, self._cell_in = gb.pos64.clone(), gb.cell64.clone()
+        self._word = torch.zeros(1, dtype=torch.int32, device=dev)
+        embeds = [m for m in model.modules() if hasattr(m, "check_species")]
+        self._embeds = embeds
+        params = [p for p in model.parameters() if p.requires_grad] if fn is not None else []
+        kept = [p.grad for p in params]   # fn(preds).backward() reaches the parameters too: the caller's gradients stay
+        flags = [(m, m.check_species) for m in embeds]
+        try:
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                for _ in range(max(1, warmup)):
+                    for p in params:
+                        p.grad = None
+                    self._run()   # range checks on: validates the construction geometry
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
+            for m in embeds:
+                m.check_species = False
+            for p in params:
+                p.grad = None   # the capture allocates its own: a replay rewrites them instead of accumulating
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._out, self.grads = self._run()
+        finally:
+            for p, g in zip(params, kept):
+                p.grad = g      # the caller's gradients are left as they were
+            for m, f in flags:
+                m.check_species = f
+        b, n = gb.n_crystals, gb.n_atoms
+        self._real = self._out[:b] if self._out.shape[0] == gb.b_b else self._out[:n]   # per crystal / per atom
+        gb.flags.bitwise_or_(self._word)   # (what warm-up and capture saw: the construction geometry, checked by gb)
+
+    def _run(self):
+        from .geometry import _DERIVED, strain_gradient
+
+        gb = self.gb
+        gb.update(pos=self._pos_in, cell=self._cell_in, flags_out=self._word)
+        batch = {k: v for k, v in gb.batch.items() if k not in _DERIVED}
+        if self.fn is None:
+            with torch.no_grad():
+                return self.model(batch, task_name=self.task_name)[0][self.task_name], None
+        for key in ("pos", "cell"):
+            batch[key] = batch[key].detach().clone().requires_grad_(True)
+        with torch.enable_grad():
+            preds, _ = self.model(batch, task_name=self.task_name)
+            self.fn(preds).backward()
+        n, b = gb.n_atoms, gb.n_crystals
+        grads = {"pos": batch["pos"].grad[:n], "cell": batch["cell"].grad[:3 * b], "strain": strain_gradient(batch)[:b]}
+        return preds[self.task_name].detach(), grads
+
+    def step(self, pos=None, cell=None, flags_out=None) -> torch.Tensor:
+        """``pos`` [N,3] / ``cell`` [B,3,3]: device tensors, fp64 (fp32 is widened: ``GeometryBatch.update``); None keeps the
+        geometry of the step before.  No host sync."""
+        gb = self.gb
+        if any(gb.batch.get(k) is not v for k, v in self._tensors.items()):
+            raise ValueError("the GeometryBatch was grown after this step was captured: build a new GraphedGeometryStep")
+        if pos is not None:
+            if tuple(pos.shape) != tuple(self._pos_in.shape):
+                raise ValueError(f"pos is {tuple(pos.shape)}, the captured step takes {tuple(self._pos_in.shape)}")
+            self._pos_in.copy_(pos, non_blocking=True)
+        if cell is not None:
+            if cell.numel() != self._cell_in.numel():
+                raise ValueError(f"cell is {tuple(cell.shape)}, the captured step takes [{gb.n_crystals}, 3, 3]")
+            self._cell_in.copy_(cell.reshape(self._cell_in.shape), non_blocking=True)
+        self.graph.replay()
+        if flags_out is None:
+            gb.flags.bitwise_or_(self._word)
+        else:
+            flags_out.copy_(self._word.reshape(flags_out.shape))
+        return self._real

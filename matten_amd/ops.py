@@ -1688,19 +1688,37 @@ def valid_loss_bwd_host(pred, target, n_valid: int, kind=0, g: float = 1.0):
     return grad
 
 
-def graph_prep(pos64, cell64, ptr, r_cut: float):
+def _prep_out(out, N: int, B: int, singular: bool):
+    """the caller's output tensors of graph_prep / graph_prep_pbc (``out=``), checked: contiguous, of the sizes the kernel
+    writes (rows of a larger buffer are fine: ``buf[:N]``)"""
+    names = ("frac", "bound", "batch", "pos32", "cell32") + (("singular",) if singular else ())
+    want = ((torch.float64, 3 * N), (torch.float64, 3 * B), (torch.int64, N), (torch.float32, 3 * N), (torch.float32, 9 * B),
+            (torch.int32, B))
+    if len(out) != len(names):
+        raise ValueError(f"out: expected the {len(names)} tensors {names}")
+    for t, name, (dtype, numel) in zip(out, names, want):
+        if _need(t, dtype, name) is not t or t.numel() != numel:
+            raise ValueError(f"out: {name} must be a contiguous {dtype} tensor of {numel} elements")
+    return tuple(out)
+
+
+def graph_prep(pos64, cell64, ptr, r_cut: float, out=None):
     """per-crystal prologue of the device graph builder (include/matten_hip.h matten_graph_prep)
-    -> (frac [N,3] f64, bound [B,3] f64, batch [N] i64, pos [N,3] f32, cell [3B,3] f32)"""
+    -> (frac [N,3] f64, bound [B,3] f64, batch [N] i64, pos [N,3] f32, cell [3B,3] f32); ``out``: these five, allocated by
+    the caller, are written in place (a loop that rebuilds the same atoms: data.rebuild.GeometryBatch)"""
     lib = _lib.load()
     pos64 = _need(pos64, torch.float64, "pos")
     cell64 = _need(cell64, torch.float64, "cell")
     ptr = _need(ptr, torch.int64, "ptr")
     N, B, dev = pos64.shape[0], ptr.shape[0] - 1, pos64.device
-    frac = torch.empty(N, 3, dtype=torch.float64, device=dev)
-    bound = torch.empty(B, 3, dtype=torch.float64, device=dev)
-    batch = torch.empty(N, dtype=torch.int64, device=dev)
-    pos32 = torch.empty(N, 3, dtype=torch.float32, device=dev)
-    cell32 = torch.empty(3 * B, 3, dtype=torch.float32, device=dev)
+    if out is not None:
+        frac, bound, batch, pos32, cell32 = _prep_out(out, N, B, False)
+    else:
+        frac = torch.empty(N, 3, dtype=torch.float64, device=dev)
+        bound = torch.empty(B, 3, dtype=torch.float64, device=dev)
+        batch = torch.empty(N, dtype=torch.int64, device=dev)
+        pos32 = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        cell32 = torch.empty(3 * B, 3, dtype=torch.float32, device=dev)
     _lib.check(lib.matten_graph_prep(_ptr(pos64), _ptr(cell64), _ptr(ptr), B, float(r_cut), _ptr(frac), _ptr(bound),
                                      _ptr(batch), _ptr(pos32), _ptr(cell32), _stream()), "matten_graph_prep")
     return frac, bound, batch, pos32, cell32
@@ -1776,11 +1794,61 @@ def neighbor_list_flagged(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: floa
     return edge_index, shifts, num_neigh, offsets, int(min_edges), csr, host
 
 
-def graph_prep_pbc(pos64, cell64, ptr, pbc, r_cut: float, n_singular: torch.Tensor):
+def neighbor_list_capped(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: float, max_atoms: int, n_pairs: int, capacity,
+                         edge_index, edge_cell_shift, num_neigh, perm, rowptr, src_sorted, n_valid, flags,
+                         counts=None, scan=None, singular=None):
+    """neighbor_list_flagged into the caller's buffers of fixed ``capacity`` = (N_b, E_b, B_b), with the edge count left on
+    the device (include/matten_hip.h matten_neighbor_fill_capped): nothing is read back and nothing is sized by device
+    data, so the call captures into a hipGraph.  Outputs (all written in place, the padded layout of
+    ``GraphStoreHost.padded_reference``): edge_index [2,E_b] i64, edge_cell_shift [E_b,3] f32, num_neigh [N_b] f32,
+    perm [E_b] / rowptr [N_b+1] / src_sorted [E_b] i32, n_valid [3] i64 = (N, E, B); flags: an int32 element the
+    MATTEN_CAPPED_* bits are OR-ed into (1: E > E_b and NOTHING else was written, 2: a crystal without any edge,
+    4: a singular periodic cell, from ``singular`` = graph_prep_pbc's output).  counts [2 n_pairs] i32 / scan
+    [2 n_pairs + 1] i64: scratch the caller may keep between calls.  -> scan (scan[n_pairs] is E, scan[pair_ptr] the
+    first edge of each crystal)."""
+    lib = _lib.load()
+    pos64 = _need(pos64, torch.float64, "pos")
+    cell64 = _need(cell64, torch.float64, "cell")
+    ptr = _need(ptr, torch.int64, "ptr")
+    frac = _need(frac, torch.float64, "frac")
+    bound = _need(bound, torch.float64, "bound")
+    pair_ptr = _need(pair_ptr, torch.int64, "pair_ptr")
+    B, N, dev = ptr.shape[0] - 1, pos64.shape[0], pos64.device
+    n_b, e_b, b_b = (int(v) for v in capacity)
+    outs = (("edge_index", edge_index, torch.int64, 2 * e_b), ("edge_cell_shift", edge_cell_shift, torch.float32, 3 * e_b),
+            ("num_neigh", num_neigh, torch.float32, n_b), ("perm", perm, torch.int32, e_b),
+            ("rowptr", rowptr, torch.int32, n_b + 1), ("src_sorted", src_sorted, torch.int32, e_b),
+            ("n_valid", n_valid, torch.int64, 3), ("flags", flags, torch.int32, 1))
+    for name, t, dtype, numel in outs:
+        if _need(t, dtype, name) is not t or t.numel() != numel:
+            raise ValueError(f"{name}: expected a contiguous {dtype} tensor of {numel} elements for capacity {(n_b, e_b, b_b)}")
+    if counts is None:
+        counts = torch.empty(2 * n_pairs, dtype=torch.int32, device=dev)
+    if scan is None:
+        scan = torch.empty(2 * n_pairs + 1, dtype=torch.int64, device=dev)
+    counts, scan = _need(counts, torch.int32, "counts"), _need(scan, torch.int64, "scan")
+    if counts.numel() != 2 * n_pairs or scan.numel() != 2 * n_pairs + 1 or n_pairs <= 0:
+        raise ValueError(f"counts / scan: expected {2 * n_pairs} and {2 * n_pairs + 1} elements for {n_pairs} > 0 pairs")
+    if singular is not None:
+        singular = _need(singular, torch.int32, "singular")
+    stream = _stream()
+    _lib.check(lib.matten_neighbor_count(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(frac), _ptr(bound), _ptr(pair_ptr),
+                                         float(r_cut), B, int(max_atoms), _ptr(counts), counts.data_ptr() + 4 * n_pairs,
+                                         stream), "matten_neighbor_count")
+    _lib.check(lib.matten_neighbor_scan(_ptr(counts), 2 * n_pairs, _ptr(scan), stream), "matten_neighbor_scan")
+    _lib.check(lib.matten_neighbor_fill_capped(
+        _ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(frac), _ptr(bound), _ptr(pair_ptr), float(r_cut), B, int(max_atoms),
+        _ptr(scan), scan.data_ptr() + 8 * n_pairs, N, _ptr(singular), n_b, e_b, b_b, _ptr(edge_index), _ptr(edge_cell_shift),
+        _ptr(num_neigh), _ptr(rowptr), _ptr(src_sorted), _ptr(perm), _ptr(n_valid), _ptr(flags), stream),
+        "matten_neighbor_fill_capped")
+    return scan
+
+
+def graph_prep_pbc(pos64, cell64, ptr, pbc, r_cut: float, n_singular: torch.Tensor, out=None):
     """graph_prep for open / partly periodic crystals (include/matten_hip.h matten_graph_prep_pbc): pbc [B,3] uint8.
     -> graph_prep's five outputs + singular [B] i32 (1: the periodic vectors of that crystal are linearly dependent).
     n_singular: a zeroed int64 element that receives the number of such crystals (the caller reads it back with the
-    edge count: see neighbor_list(summary=))."""
+    edge count: see neighbor_list(summary=)).  ``out``: the six outputs, allocated by the caller (see graph_prep)."""
     lib = _lib.load()
     pos64 = _need(pos64, torch.float64, "pos")
     cell64 = _need(cell64, torch.float64, "cell")
@@ -1789,12 +1857,15 @@ def graph_prep_pbc(pos64, cell64, ptr, pbc, r_cut: float, n_singular: torch.Tens
     N, B, dev = pos64.shape[0], ptr.shape[0] - 1, pos64.device
     if pbc.numel() != 3 * B or n_singular.dtype != torch.int64 or n_singular.numel() != 1:
         raise ValueError("pbc must hold [B,3] flags, n_singular one int64")
-    frac = torch.empty(N, 3, dtype=torch.float64, device=dev)
-    bound = torch.empty(B, 3, dtype=torch.float64, device=dev)
-    batch = torch.empty(N, dtype=torch.int64, device=dev)
-    pos32 = torch.empty(N, 3, dtype=torch.float32, device=dev)
-    cell32 = torch.empty(3 * B, 3, dtype=torch.float32, device=dev)
-    singular = torch.empty(B, dtype=torch.int32, device=dev)
+    if out is not None:
+        frac, bound, batch, pos32, cell32, singular = _prep_out(out, N, B, True)
+    else:
+        frac = torch.empty(N, 3, dtype=torch.float64, device=dev)
+        bound = torch.empty(B, 3, dtype=torch.float64, device=dev)
+        batch = torch.empty(N, dtype=torch.int64, device=dev)
+        pos32 = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        cell32 = torch.empty(3 * B, 3, dtype=torch.float32, device=dev)
+        singular = torch.empty(B, dtype=torch.int32, device=dev)
     _lib.check(lib.matten_graph_prep_pbc(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(pbc), B, float(r_cut), _ptr(frac),
                                          _ptr(bound), _ptr(batch), _ptr(pos32), _ptr(cell32), _ptr(singular),
                                          n_singular.data_ptr(), _stream()), "matten_graph_prep_pbc")

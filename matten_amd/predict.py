@@ -752,3 +752,89 @@ def predict(
         out = predictions
     out = out[0] if single else out
     return (out, props) if properties else out
+
+
+def evaluate_frames(model, structure, pos_frames, cell_frames=None, r_cut: float = 5.0,
+                    tensor_target_name: str = "elastic_tensor_full", tensor_target_formula: str = "ijkl=jikl=klij",
+                    properties: bool = False, slack: float = 1.25, pbc=None):
+    """The tensors of F geometries of ONE structure -- the frames of a trajectory, a strain or volume sweep -- with the
+    edge list rebuilt on the device per frame and every frame one hipGraph replay (``data.rebuild.GeometryBatch``,
+    ``graphs.GraphedGeometryStep``).
+
+    ``structure`` gives the species and the boundary conditions (and the cell, when ``cell_frames`` is None: a fixed
+    cell); ``pos_frames`` [F,N,3] and ``cell_frames`` [F,3,3] are arrays or tensors (fp64; the search runs in fp64).
+    -> the F Cartesian tensors as a list on the host, like ``evaluate``; with ``properties=True`` ``(tensors, props)``,
+    ``props`` = ``elastic.elastic_properties`` of the stacked tensors (F rows).
+
+    The edge buffers are sized from frame 0 (64 * ceil(slack * E0 / 64) edges).  Per-frame flags are collected on the
+    device and read back ONCE after the last frame: frames with more edges than that are run again after
+    ``GeometryBatch.grow`` to 64 * ceil(1.25 * E / 64) for the largest such frame (E from an eager build of it); a frame
+    without any edge or with a singular cell raises ``EdgelessStructures`` / ``SingularCells`` with the FRAME indices."""
+    from .data.graph import batch_graphs_gpu_soa
+    from .data.rebuild import FLAG_EDGELESS, FLAG_OVERFLOW, FLAG_SINGULAR, EdgeCapacityExceeded, GeometryBatch, edge_capacity_for
+    from .graphs import GraphedGeometryStep
+
+    model.eval()
+    device = model.device
+    p0, lattice, z, flags3 = _raw_fields(structure, pbc)
+    Z = np.asarray(z, dtype=np.int64).reshape(-1)
+    n = len(Z)
+    as_dev = lambda a: (a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(
+        device=device, dtype=torch.float64)
+    pos_d = as_dev(pos_frames)
+    if pos_d.dim() != 3 or tuple(pos_d.shape[1:]) != (n, 3) or pos_d.shape[0] < 1:
+        raise ValueError(f"pos_frames is {tuple(pos_d.shape)}: expected [F, {n}, 3] for the {n} atoms of the structure")
+    F = pos_d.shape[0]
+    if cell_frames is None:
+        if lattice is None and any(flags3):
+            raise ValueError("the structure has no lattice: pass cell_frames, or pbc=False")
+        cell_d = as_dev(np.zeros((3, 3)) if lattice is None else np.asarray(lattice, dtype=np.float64)).reshape(1, 3, 3)
+    else:
+        cell_d = as_dev(cell_frames)
+        if tuple(cell_d.shape) != (F, 3, 3):
+            raise ValueError(f"cell_frames is {tuple(cell_d.shape)}: expected [{F}, 3, 3]")
+    check_species(model, [{"atomic_numbers": Z, "cart_coords": p0, "lattice": lattice}])
+    ptr = np.array([0, n], dtype=np.int64)
+    pbc_rows = None if all(flags3) else np.array([flags3], dtype=bool)
+    cell_of = (lambda f: cell_d[0]) if cell_frames is None else (lambda f: cell_d[f])
+    gb = GeometryBatch(pos_d[0].cpu().numpy(), cell_of(0).cpu().numpy(), Z, ptr, r_cut, device, pbc=pbc_rows, slack=slack)
+    converter = _converter(tensor_target_formula)
+    rows, frame_flags = None, torch.zeros(F, dtype=torch.int32, device=device)
+    counts = torch.zeros(F, dtype=torch.int64, device=device)
+
+    def run(frames):
+        nonlocal rows
+        step = GraphedGeometryStep(model, gb, task_name=tensor_target_name)
+        for f in frames:
+            out = step.step(pos=pos_d[f], cell=None if cell_frames is None else cell_d[f], flags_out=frame_flags[f:f + 1])
+            counts[f:f + 1].copy_(gb.edge_count)
+            if rows is None:
+                rows = torch.full((F,) + tuple(out.shape[1:]), float("nan"), dtype=out.dtype, device=device)
+            rows[f].copy_(out[0])
+        return frame_flags.tolist()   # the one read-back of the pass
+
+    host = run(range(F))
+    for bit, exc in ((FLAG_SINGULAR, SingularCells), (FLAG_EDGELESS, EdgelessStructures)):
+        bad = [f for f, w in enumerate(host) if w & bit]
+        if bad:
+            raise exc(bad)
+    again = [f for f, w in enumerate(host) if w & FLAG_OVERFLOW]
+    if again:
+        worst = again[int(torch.argmax(counts[torch.as_tensor(again, device=device)]))]
+        eager = batch_graphs_gpu_soa(pos_d[worst].cpu().numpy(), cell_of(worst).cpu().numpy(), Z, ptr, r_cut, device,
+                                     pbc=pbc_rows)
+        needed = int(eager["edge_index"].shape[1])
+        gb.grow(edge_capacity_for(needed, 1.25))
+        host = run(again)
+        still = [f for f in again if host[f] & FLAG_OVERFLOW]
+        if still:   # (the worst frame was measured: cannot happen unless the inputs changed under the call)
+            raise EdgeCapacityExceeded(int(counts[still[0]]), gb.e_b)
+    gb.flags.zero_()
+    cartesian_out = getattr(model, "to_cartesian", None) is not None
+    preds = rows if cartesian_out else converter.to_cartesian(rows)
+    tensors = list(preds.cpu())
+    if properties:
+        from .elastic import elastic_properties
+
+        return tensors, elastic_properties(preds)
+    return tensors
