@@ -56,7 +56,9 @@ __device__ __forceinline__ void real_sh(float vx, float vy, float vz, float len,
         y[17] = a1 * ys * zs * (3.0f * xs2 - ys2);
         y[18] = a2 * xs * ys * (7.0f * zs2 - 1.0f);
         y[19] = a3 * ys * zs * (7.0f * zs2 - 3.0f);
-        y[20] = (3.0f / 8.0f) * (35.0f * zs2 * zs2 - 30.0f * zs2 + 3.0f);
+        // (the constant term stands for 3 |n|^4: a zero-length edge normalises to n = 0, where every l >= 1 harmonic is 0)
+        const float y20 = (3.0f / 8.0f) * (35.0f * zs2 * zs2 - 30.0f * zs2 + 3.0f);
+        y[20] = len > 0.0f ? y20 : 0.0f;
         y[21] = a3 * xs * zs * (7.0f * zs2 - 3.0f);
         y[22] = a6 * (xs2 - ys2) * (7.0f * zs2 - 1.0f);
         y[23] = a1 * xs * zs * (xs2 - 3.0f * ys2);

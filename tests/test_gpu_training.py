@@ -588,13 +588,17 @@ def test_instance_normalization_forward_and_gradients(golden_dir):
     assert n > 25
 
 
-@pytest.mark.parametrize("N", [2047, 2048, 5003])
-def test_batchnorm_training_reductions_at_large_row_counts(N):
+@pytest.mark.parametrize("N", [1, 3, 255, 257, 769, 1025, 2047, 2048, 5003])
+def test_batchnorm_training_reductions_at_large_row_counts(N, monkeypatch):
     """matten_bn_train_fwd / _bwd on both sides of the row count where the reductions switch from one workgroup per
     channel to the two-stage column form (16-row blocks, records merged per channel in a fixed order): statistics,
     output, running averages and all three gradients against the e3nn BatchNorm arithmetic written out in fp64; the
-    0e columns sit on an offset 50x their spread (the pairwise mean / squared-deviation merge must not cancel)."""
+    0e columns sit on an offset 50x their spread (the pairwise mean / squared-deviation merge must not cancel).  Below the
+    switch the one-workgroup form runs with a single row, fewer rows than threads, one row past a full pass of its 256
+    threads, and on both sides of the start of its four-rows-in-flight loop (above 768 rows).  A third run on NaN-filled
+    torch.empty buffers gives the same bits."""
     from matten_amd.nn.utils import _IrrepBatchNorm
+    from test_gpu_edge_geom import nan_filled_empty
     from matten_amd.o3 import Irreps
 
     irreps = Irreps("8x0e+4x0o+5x1o+3x2e")
@@ -608,14 +612,18 @@ def test_batchnorm_training_reductions_at_large_row_counts(N):
     x.requires_grad_(True)
     gy = torch.randn(N, irreps.dim, device=DEV, generator=gen)
     outs = []
-    for _ in range(2):
+    for i in range(3):
         bn.running_mean.zero_(), bn.running_var.fill_(1.0)
         x.grad = bn.weight.grad = bn.bias.grad = None
-        y = bn.forward_train(x)
-        y.backward(gy)
-        outs.append([t.detach().clone() for t in (y, x.grad, bn.weight.grad, bn.bias.grad, bn.running_mean, bn.running_var)])
-    for a, b in zip(*outs):
+        with monkeypatch.context() as m:
+            if i == 2:
+                nan_filled_empty(m)
+            y = bn.forward_train(x)
+            y.backward(gy)
+            outs.append([t.detach().clone() for t in (y, x.grad, bn.weight.grad, bn.bias.grad, bn.running_mean, bn.running_var)])
+    for a, b, c in zip(*outs):
         assert torch.equal(a, b)   # fixed summation order
+        assert not torch.isnan(c).any() and torch.equal(a, c)   # nothing read or left unwritten
     # e3nn BatchNorm (training mode, affine, "component" normalisation, mean reduce), fp64
     xr = x.detach().cpu().double().requires_grad_(True)
     w = bn.weight.detach().cpu().double().requires_grad_(True)
