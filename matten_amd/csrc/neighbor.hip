@@ -33,9 +33,9 @@
 //
 // Large structures (matten_neighbor_rows_count / _fill): the pair kernels keep 24 bytes per ordered atom pair.  The rows
 // kernels give one wave to each centre atom i; lanes take j = j0 + lane over the atoms of i's crystal in chunks of 64
-// and call the same pair_walk.  The counting pass writes ONE count per atom; the fill pass recomputes the lane counts,
-// places a chunk's edges with a wave prefix sum plus a running base, and the edges of i come out j-ascending and
-// shift-lexicographic: the canonical order again, with O(N) bookkeeping.  No CSR is emitted on this route.
+// and call the same candidate step and pair_walk.  The counting pass writes ONE count per atom; the fill pass recomputes
+// the lane counts, places a chunk's edges with a wave prefix sum plus a running base, and the edges of i come out
+// j-ascending and shift-lexicographic: the canonical order again, with O(N) bookkeeping.  No CSR is emitted on this route.
 //
 // Larger structures still (matten_neighbor_cells_*): the rows walk tests every atom of the crystal, O(n^2) arithmetic.
 // The cells kernels put a cell list in front of the same walk.  Every crystal gets a grid (cells_grid_kernel): along a
@@ -173,22 +173,43 @@ __device__ __forceinline__ void shift_range(double bound, double df, int& lo, in
     hi = (int)floor(bound - df + slack);
 }
 
-// The distance test of the search, shared by the pair and the rows kernels so that their decisions cannot diverge: walks
-// the shifts [x0,x1] x [y0,y1] x [z0,z1] of one ordered pair in lexicographic order, calls emit(sx, sy, sz) for every
-// edge and returns their number.  `self`: i == j, whose zero shift is no edge.
+// What every route knows of the candidate j of a centre atom i before the distance test: the image shifts that can hold
+// a neighbour, and j's position.  A lane without a candidate (live = false) gets empty ranges, so that it walks nothing
+// and still takes part in the wave's shuffles.  fi: frac of atom i; bx, by, bz: bound of their crystal.
+struct Cand {
+    int x0, x1, y0, y1, z0, z1;
+    double pj[3];
+};
+
+__device__ __forceinline__ Cand candidate(const double* frac, const double* pos, double bx, double by, double bz,
+                                          const double* fi, int64_t j, bool live) {
+    Cand cd{0, -1, 0, -1, 0, -1, {0.0, 0.0, 0.0}};
+    if (live) {
+        shift_range(bx, frac[3 * j] - fi[0], cd.x0, cd.x1);
+        shift_range(by, frac[3 * j + 1] - fi[1], cd.y0, cd.y1);
+        shift_range(bz, frac[3 * j + 2] - fi[2], cd.z0, cd.z1);
+        cd.pj[0] = pos[3 * j], cd.pj[1] = pos[3 * j + 1], cd.pj[2] = pos[3 * j + 2];
+    }
+    return cd;
+}
+
+// The distance test of the search, shared by every route so that their decisions cannot diverge: walks the shifts
+// [x0,x1] x [y0,y1] x [z0,z1] of one ordered pair in lexicographic order, calls emit(sx, sy, sz) for every edge and
+// returns their number.  `self`: i == j, whose zero shift is no edge.
 template <class Emit>
-__device__ __forceinline__ int pair_walk(const double* __restrict__ cl, int x0, int x1, int y0, int y1, int z0, int z1,
-                                         const double* pi, const double* pj, double r_cut, bool self, Emit&& emit) {
+__device__ __forceinline__ int pair_walk(const double* __restrict__ cl, const Cand& cd, const double* pi, double r_cut,
+                                         bool self, Emit&& emit) {
+    const double* pj = cd.pj;
     const double r2 = r_cut * r_cut;
     const double r2_in = r2 * (1.0 - 1e-15), r2_out = r2 * (1.0 + 1e-15);
     int cnt = 0;
-    for (int sx = x0; sx <= x1; ++sx)
-        for (int sy = y0; sy <= y1; ++sy) {
+    for (int sx = cd.x0; sx <= cd.x1; ++sx)
+        for (int sy = cd.y0; sy <= cd.y1; ++sy) {
             // T = S @ cell : ((sx*c0 + sy*c1) + sz*c2) per component, as the host builder's matmul
             const double ax = (double)sx * cl[0] + (double)sy * cl[3];
             const double ay = (double)sx * cl[1] + (double)sy * cl[4];
             const double az = (double)sx * cl[2] + (double)sy * cl[5];
-            for (int sz = z0; sz <= z1; ++sz) {
+            for (int sz = cd.z0; sz <= cd.z1; ++sz) {
                 const double tx = ax + (double)sz * cl[6];
                 const double ty = ay + (double)sz * cl[7];
                 const double tz = az + (double)sz * cl[8];
@@ -213,46 +234,60 @@ struct CsrOut {                // optional outputs of the fill pass: the destina
     int64_t n_atoms;
 };
 
-template <bool FILL>
+__device__ __forceinline__ void write_edge(int64_t* edge_index, int64_t row_stride, float* shifts, int64_t out, int64_t i,
+                                           int64_t j, int sx, int sy, int sz) {
+    edge_index[out] = i;
+    edge_index[row_stride + out] = j;
+    shifts[3 * out] = (float)sx;
+    shifts[3 * out + 1] = (float)sy;
+    shifts[3 * out + 2] = (float)sz;
+}
+
+// PAIR_CAPPED: the fill pass into buffers of fixed capacity (see the capped fill below).  `edge_rows`, the row length of
+// edge_index, is then the capacity E_b and the edge count is read from device memory; every store stays behind that
+// count, the CSR is always written, and rowptr's closing entry is left to the closing kernel.
+enum PairMode { PAIR_COUNT, PAIR_FILL, PAIR_CAPPED };
+
+template <PairMode MODE>
 __global__ __launch_bounds__(256) void neighbor_kernel(Cry c, double r_cut, int32_t* __restrict__ counts,
                                                        int32_t* __restrict__ counts_t,
                                                        const int64_t* __restrict__ offsets,
-                                                       int64_t* __restrict__ edge_index, int64_t n_edges,
+                                                       int64_t* __restrict__ edge_index, int64_t edge_rows,
                                                        float* __restrict__ shifts, float* __restrict__ num_neigh,
                                                        CsrOut csr) {
+    constexpr bool FILL = MODE != PAIR_COUNT, CAPPED = MODE == PAIR_CAPPED;
+    const int64_t n_edges = CAPPED ? offsets[c.pair_ptr[gridDim.y]] : edge_rows;   // (gridDim.y crystals)
+    if (CAPPED && n_edges > edge_rows) return;   // overflow: nothing is stored (the flag is the closing kernel's)
     const int64_t b = blockIdx.y;
     const int64_t lo = c.ptr[b];
     const int64_t n = c.ptr[b + 1] - lo;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * n) return;
     const int64_t i = lo + t / n, j = lo + t % n;
+    if (CAPPED && (i >= csr.n_atoms || j >= csr.n_atoms)) return;
     const int64_t pair = c.pair_ptr[b] + t;
     const double* cl = c.cell + 9 * b;
-    int x0, x1, y0, y1, z0, z1;
-    shift_range(c.bound[3 * b], c.frac[3 * j] - c.frac[3 * i], x0, x1);
-    shift_range(c.bound[3 * b + 1], c.frac[3 * j + 1] - c.frac[3 * i + 1], y0, y1);
-    shift_range(c.bound[3 * b + 2], c.frac[3 * j + 2] - c.frac[3 * i + 2], z0, z1);
+    const double fi[3] = {c.frac[3 * i], c.frac[3 * i + 1], c.frac[3 * i + 2]};
+    const Cand cd = candidate(c.frac, c.pos, c.bound[3 * b], c.bound[3 * b + 1], c.bound[3 * b + 2], fi, j, true);
     const double pi[3] = {c.pos[3 * i], c.pos[3 * i + 1], c.pos[3 * i + 2]};
-    const double pj[3] = {c.pos[3 * j], c.pos[3 * j + 1], c.pos[3 * j + 2]};
     int64_t out = FILL ? offsets[pair] : 0;
-    if (FILL && num_neigh && j == lo) num_neigh[i] = (float)(offsets[pair + n] - offsets[pair]);   // atom i's n pairs
+    if (FILL && (CAPPED || num_neigh) && j == lo) num_neigh[i] = (float)(offsets[pair + n] - offsets[pair]);   // i's n pairs
     const int64_t pair_t = c.pair_ptr[b] + (j - lo) * n + (i - lo);   // the same pair numbered j-major
+    const bool want_csr = FILL && (CAPPED || csr.rowptr);
     int64_t out_t = 0;
-    if (FILL && csr.rowptr) {
+    if (want_csr) {
         out_t = csr.offsets_t[pair_t] - csr.offsets_t[0];   // (a scan that continues the i-major one starts at n_edges)
         if (i == lo) csr.rowptr[j] = (int32_t)out_t;
-        if (pair == 0) csr.rowptr[csr.n_atoms] = (int32_t)n_edges;
+        if (!CAPPED && pair == 0) csr.rowptr[csr.n_atoms] = (int32_t)n_edges;
     }
-    const int cnt = pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [&](int sx, int sy, int sz) {
+    const int cnt = pair_walk(cl, cd, pi, r_cut, i == j, [&](int sx, int sy, int sz) {
         if (FILL) {
-            edge_index[out] = i;
-            edge_index[n_edges + out] = j;
-            shifts[3 * out] = (float)sx;
-            shifts[3 * out + 1] = (float)sy;
-            shifts[3 * out + 2] = (float)sz;
-            if (csr.rowptr) {
-                csr.perm[out_t] = (int32_t)out;
-                csr.src_sorted[out_t] = (int32_t)i;
+            if (!CAPPED || out < n_edges) write_edge(edge_index, edge_rows, shifts, out, i, j, sx, sy, sz);
+            if (want_csr) {
+                if (!CAPPED || out_t < n_edges) {
+                    csr.perm[out_t] = (int32_t)out;
+                    csr.src_sorted[out_t] = (int32_t)i;
+                }
                 ++out_t;
             }
             ++out;
@@ -295,6 +330,17 @@ struct Rows {
     int64_t n_atoms;
 };
 
+// inclusive prefix sum of v over the lanes [0, WIDTH) of a wave (WIDTH a power of two; every lane of the wave calls it,
+// the lanes from WIDTH on get sums nobody reads)
+template <int WIDTH>
+__device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
+    for (int off = 1; off < WIDTH; off <<= 1) {
+        const int up = __shfl_up(v, off, 64);
+        if (lane >= off) v += up;
+    }
+    return v;
+}
+
 // one wave, centre atom i (wave-uniform): every atom of i's crystal in j order.  The whole of the rows route, and the
 // walk the cells route falls back on for a row that outgrows its record buffer.
 template <bool FILL>
@@ -312,33 +358,16 @@ __device__ __forceinline__ void rows_walk(const Rows& c, double r_cut, int64_t i
     int total = 0;
     for (int64_t j0 = lo; j0 < hi; j0 += 64) {   // every lane stays in the loop: the prefix sum below needs all 64
         const int64_t j = j0 + lane;
-        const bool live = j < hi;
-        int x0 = 0, x1 = -1, y0 = 0, y1 = -1, z0 = 0, z1 = -1;   // empty ranges for the lanes past the last atom
-        double pj[3] = {0.0, 0.0, 0.0};
-        if (live) {
-            shift_range(bx, c.frac[3 * j] - fi[0], x0, x1);
-            shift_range(by, c.frac[3 * j + 1] - fi[1], y0, y1);
-            shift_range(bz, c.frac[3 * j + 2] - fi[2], z0, z1);
-            pj[0] = c.pos[3 * j], pj[1] = c.pos[3 * j + 1], pj[2] = c.pos[3 * j + 2];
-        }
-        const int cnt = pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [](int, int, int) {});
+        const Cand cd = candidate(c.frac, c.pos, bx, by, bz, fi, j, j < hi);   // (lanes past the last atom: not live)
+        const int cnt = pair_walk(cl, cd, pi, r_cut, i == j, [](int, int, int) {});
         if (!FILL) {
             total += cnt;
             continue;
         }
-        int incl = cnt;   // inclusive prefix sum of the lane counts across the wave
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
+        const int incl = wave_inclusive_scan<64>(cnt, lane);
         int64_t out = base + (incl - cnt);
-        pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [&](int sx, int sy, int sz) {
-            edge_index[out] = i;
-            edge_index[n_edges + out] = j;
-            shifts[3 * out] = (float)sx;
-            shifts[3 * out + 1] = (float)sy;
-            shifts[3 * out + 2] = (float)sz;
-            ++out;
+        pair_walk(cl, cd, pi, r_cut, i == j, [&](int sx, int sy, int sz) {
+            write_edge(edge_index, n_edges, shifts, out++, i, j, sx, sy, sz);
         });
         base += __shfl(incl, 63, 64);
     }
@@ -529,11 +558,7 @@ __global__ __launch_bounds__(256) void neighbor_cells_kernel(Cells c, double r_c
             len = c.bin_start[gb + 1] - start;
         }
     }
-    int incl = len;
-    for (int off = 1; off < 32; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
+    const int incl = wave_inclusive_scan<32>(len, lane);
     const int n_cand = __shfl(incl, 26, 64);
 
     const double* cl = c.r.cell + 9 * b;
@@ -552,15 +577,8 @@ __global__ __launch_bounds__(256) void neighbor_cells_kernel(Cells c, double r_c
         }
         const bool live = slot >= 0;
         const int64_t j = live ? c.slot_atom[slot] : 0;
-        int x0 = 0, x1 = -1, y0 = 0, y1 = -1, z0 = 0, z1 = -1;
-        double pj[3] = {0.0, 0.0, 0.0};
-        if (live) {
-            shift_range(bx, c.r.frac[3 * j] - fi[0], x0, x1);
-            shift_range(by, c.r.frac[3 * j + 1] - fi[1], y0, y1);
-            shift_range(bz, c.r.frac[3 * j + 2] - fi[2], z0, z1);
-            pj[0] = c.r.pos[3 * j], pj[1] = c.r.pos[3 * j + 1], pj[2] = c.r.pos[3 * j + 2];
-        }
-        const int cnt = pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, live && i == j, [](int, int, int) {});
+        const Cand cd = candidate(c.r.frac, c.r.pos, bx, by, bz, fi, j, live);
+        const int cnt = pair_walk(cl, cd, pi, r_cut, live && i == j, [](int, int, int) {});
         if (!FILL) {
             total += cnt;
             continue;
@@ -599,65 +617,68 @@ __global__ __launch_bounds__(256) void neighbor_cells_kernel(Cells c, double r_c
             before += o.x < me.x ? o.y : 0;
         }
         const int64_t j = me.x;
-        int x0, x1, y0, y1, z0, z1;
-        shift_range(bx, c.r.frac[3 * j] - fi[0], x0, x1);
-        shift_range(by, c.r.frac[3 * j + 1] - fi[1], y0, y1);
-        shift_range(bz, c.r.frac[3 * j + 2] - fi[2], z0, z1);
-        const double pj[3] = {c.r.pos[3 * j], c.r.pos[3 * j + 1], c.r.pos[3 * j + 2]};
+        const Cand cd = candidate(c.r.frac, c.r.pos, bx, by, bz, fi, j, true);
         int64_t out = base + before;
-        pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [&](int sx, int sy, int sz) {
-            edge_index[out] = i;
-            edge_index[n_edges + out] = j;
-            shifts[3 * out] = (float)sx;
-            shifts[3 * out + 1] = (float)sy;
-            shifts[3 * out + 2] = (float)sz;
-            ++out;
+        pair_walk(cl, cd, pi, r_cut, i == j, [&](int sx, int sy, int sz) {
+            write_edge(edge_index, n_edges, shifts, out++, i, j, sx, sy, sz);
         });
     }
 }
 
 }  // namespace
 
-extern "C" int matten_graph_prep(const double* pos, const double* cell, const int64_t* ptr, int64_t n_crystals,
-                                 double r_cut, double* frac, double* bound, int64_t* batch, float* pos_f32,
-                                 float* cell_f32, matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+template <bool PBC>
+static int prep_launch(const double* pos, const double* cell, const int64_t* ptr, const uint8_t* pbc, int64_t n_crystals,
+                       double r_cut, double* frac, double* bound, int64_t* batch, float* pos_f32, float* cell_f32,
+                       int32_t* singular, int64_t* n_singular, hipStream_t stream) {
     if (n_crystals < 0 || !(r_cut > 0.0) || n_crystals >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
     if (n_crystals == 0) return MATTEN_OK;
     if (!pos || !cell || !ptr || !frac || !bound || !batch || !pos_f32 || !cell_f32) return MATTEN_EINVAL;
-    graph_prep_kernel<false><<<(unsigned)n_crystals, 64, 0, stream>>>(pos, cell, ptr, r_cut, frac, bound, batch, pos_f32,
-                                                                      cell_f32, nullptr, nullptr, nullptr);
+    if (PBC && (!pbc || !singular || !n_singular)) return MATTEN_EINVAL;
+    graph_prep_kernel<PBC><<<(unsigned)n_crystals, 64, 0, stream>>>(pos, cell, ptr, r_cut, frac, bound, batch, pos_f32,
+                                                                    cell_f32, pbc, singular, n_singular);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
+}
+
+extern "C" int matten_graph_prep(const double* pos, const double* cell, const int64_t* ptr, int64_t n_crystals,
+                                 double r_cut, double* frac, double* bound, int64_t* batch, float* pos_f32,
+                                 float* cell_f32, matten_stream_t stream) {
+    return prep_launch<false>(pos, cell, ptr, nullptr, n_crystals, r_cut, frac, bound, batch, pos_f32, cell_f32, nullptr,
+                              nullptr, (hipStream_t)stream);
 }
 
 extern "C" int matten_graph_prep_pbc(const double* pos, const double* cell, const int64_t* ptr, const uint8_t* pbc,
                                      int64_t n_crystals, double r_cut, double* frac, double* bound, int64_t* batch,
                                      float* pos_f32, float* cell_f32, int32_t* singular, int64_t* n_singular,
-                                     matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n_crystals < 0 || !(r_cut > 0.0) || n_crystals >= ((int64_t)1 << 31)) return MATTEN_EINVAL;
-    if (n_crystals == 0) return MATTEN_OK;
-    if (!pos || !cell || !ptr || !pbc || !frac || !bound || !batch || !pos_f32 || !cell_f32 || !singular || !n_singular)
-        return MATTEN_EINVAL;
-    graph_prep_kernel<true><<<(unsigned)n_crystals, 64, 0, stream>>>(pos, cell, ptr, r_cut, frac, bound, batch, pos_f32,
-                                                                     cell_f32, pbc, singular, n_singular);
+                                     matten_stream_t stream) {
+    return prep_launch<true>(pos, cell, ptr, pbc, n_crystals, r_cut, frac, bound, batch, pos_f32, cell_f32, singular,
+                             n_singular, (hipStream_t)stream);
+}
+
+// The three entries of the pair search.  n_edges: 0 for the counting pass, the capacity E_b for the capped fill;
+// csr_ok: what the entry found of its CSR arguments, which an empty batch does not look at.
+template <PairMode MODE>
+static int pair_launch(const Cry& c, double r_cut, int64_t n_crystals, int64_t max_atoms, int32_t* counts, int32_t* counts_t,
+                       const int64_t* offsets, int64_t n_edges, int64_t* edge_index, float* shifts, float* num_neigh,
+                       const CsrOut& csr, bool csr_ok, hipStream_t stream) {
+    if (n_crystals < 0 || max_atoms < 0 || n_edges < 0 || !(r_cut > 0.0) || n_crystals > 65535) return MATTEN_EINVAL;
+    if (n_crystals == 0 || max_atoms == 0) return MATTEN_OK;
+    if (!c.pos || !c.cell || !c.ptr || !c.frac || !c.bound || !c.pair_ptr) return MATTEN_EINVAL;
+    if (MODE == PAIR_COUNT ? !counts : !offsets) return MATTEN_EINVAL;
+    if ((n_edges > 0 && (!edge_index || !shifts)) || !csr_ok) return MATTEN_EINVAL;
+    dim3 grid((unsigned)matten_cdiv(max_atoms * max_atoms, 256), (unsigned)n_crystals);
+    neighbor_kernel<MODE><<<grid, 256, 0, stream>>>(c, r_cut, counts, counts_t, offsets, edge_index, n_edges, shifts, num_neigh,
+                                                    csr);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }
 
 extern "C" int matten_neighbor_count(const double* pos, const double* cell, const int64_t* ptr, const double* frac,
                                      const double* bound, const int64_t* pair_ptr, double r_cut, int64_t n_crystals,
-                                     int64_t max_atoms, int32_t* counts, int32_t* counts_t, matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n_crystals < 0 || max_atoms < 0 || !(r_cut > 0.0) || n_crystals > 65535) return MATTEN_EINVAL;
-    if (n_crystals == 0 || max_atoms == 0) return MATTEN_OK;
-    if (!pos || !cell || !ptr || !frac || !bound || !pair_ptr || !counts) return MATTEN_EINVAL;
-    Cry c{pos, cell, ptr, frac, bound, pair_ptr};
-    dim3 grid((unsigned)matten_cdiv(max_atoms * max_atoms, 256), (unsigned)n_crystals);
-    neighbor_kernel<false><<<grid, 256, 0, stream>>>(c, r_cut, counts, counts_t, nullptr, nullptr, 0, nullptr, nullptr, CsrOut{});
-    MATTEN_LAUNCH_CHECK();
-    return MATTEN_OK;
+                                     int64_t max_atoms, int32_t* counts, int32_t* counts_t, matten_stream_t stream) {
+    return pair_launch<PAIR_COUNT>(Cry{pos, cell, ptr, frac, bound, pair_ptr}, r_cut, n_crystals, max_atoms, counts, counts_t,
+                                   nullptr, 0, nullptr, nullptr, nullptr, CsrOut{}, true, (hipStream_t)stream);
 }
 
 extern "C" int matten_neighbor_summary(const int64_t* offsets, const int64_t* pair_ptr, int64_t n_crystals,
@@ -673,23 +694,14 @@ extern "C" int matten_neighbor_fill(const double* pos, const double* cell, const
                                     const double* bound, const int64_t* pair_ptr, double r_cut, int64_t n_crystals,
                                     int64_t max_atoms, const int64_t* offsets, int64_t n_edges, int64_t* edge_index,
                                     float* edge_cell_shift, float* num_neigh, const int64_t* offsets_t, int64_t n_atoms,
-                                    int32_t* rowptr, int32_t* src_sorted, int32_t* perm, matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (n_crystals < 0 || max_atoms < 0 || n_edges < 0 || !(r_cut > 0.0) || n_crystals > 65535) return MATTEN_EINVAL;
-    if (n_crystals == 0 || max_atoms == 0) return MATTEN_OK;
-    if (!pos || !cell || !ptr || !frac || !bound || !pair_ptr || !offsets) return MATTEN_EINVAL;
-    if (n_edges > 0 && (!edge_index || !edge_cell_shift)) return MATTEN_EINVAL;
+                                    int32_t* rowptr, int32_t* src_sorted, int32_t* perm, matten_stream_t stream) {
     const bool want_csr = offsets_t || rowptr || src_sorted || perm;
-    if (want_csr && (!offsets_t || !rowptr || n_atoms < 0 || n_edges >= ((int64_t)1 << 31) ||
-                     (n_edges > 0 && (!src_sorted || !perm))))
-        return MATTEN_EINVAL;
-    Cry c{pos, cell, ptr, frac, bound, pair_ptr};
-    CsrOut csr{offsets_t, want_csr ? rowptr : nullptr, src_sorted, perm, n_atoms};
-    dim3 grid((unsigned)matten_cdiv(max_atoms * max_atoms, 256), (unsigned)n_crystals);
-    neighbor_kernel<true><<<grid, 256, 0, stream>>>(c, r_cut, nullptr, nullptr, offsets, edge_index, n_edges, edge_cell_shift,
-                                                    num_neigh, csr);
-    MATTEN_LAUNCH_CHECK();
-    return MATTEN_OK;
+    const bool csr_ok = !want_csr || (offsets_t && rowptr && n_atoms >= 0 && n_edges < ((int64_t)1 << 31) &&
+                                      (n_edges <= 0 || (src_sorted && perm)));
+    return pair_launch<PAIR_FILL>(Cry{pos, cell, ptr, frac, bound, pair_ptr}, r_cut, n_crystals, max_atoms, nullptr, nullptr,
+                                  offsets, n_edges, edge_index, edge_cell_shift, num_neigh,
+                                  CsrOut{offsets_t, want_csr ? rowptr : nullptr, src_sorted, perm, n_atoms}, csr_ok,
+                                  (hipStream_t)stream);
 }
 
 static int rows_args_ok(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch, const double* frac,
@@ -698,33 +710,36 @@ static int rows_args_ok(const double* pos, const double* cell, const int64_t* pt
     return n_atoms == 0 || (pos && cell && ptr && batch && frac && bound);
 }
 
-extern "C" int matten_neighbor_rows_count(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
-                                          const double* frac, const double* bound, double r_cut, int64_t n_atoms,
-                                          int32_t* counts, matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!rows_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms)) return MATTEN_EINVAL;
+// The count (FILL = false: counts) and fill entries of the rows and of the cells route: one wave per centre atom.
+// args_ok: rows_args_ok / cells_args_ok of the route's inputs `c`.
+template <bool FILL, class Kernel, class Args>
+static int atom_rows_launch(Kernel kernel, const Args& c, bool args_ok, double r_cut, int64_t n_atoms, int32_t* counts,
+                            const int64_t* offsets, int64_t n_edges, int64_t* edge_index, float* shifts, float* num_neigh,
+                            hipStream_t stream) {
+    if (!args_ok || n_edges < 0) return MATTEN_EINVAL;
     if (n_atoms == 0) return MATTEN_OK;
-    if (!counts) return MATTEN_EINVAL;
-    Rows c{pos, cell, ptr, batch, frac, bound, n_atoms};
-    neighbor_rows_kernel<false><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, counts, nullptr, nullptr, 0,
-                                                                                     nullptr, nullptr);
+    if (FILL ? (!offsets || (n_edges > 0 && (!edge_index || !shifts))) : !counts) return MATTEN_EINVAL;
+    kernel<<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, counts, offsets, edge_index, n_edges, shifts,
+                                                                  num_neigh);
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
+}
+
+extern "C" int matten_neighbor_rows_count(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
+                                          const double* frac, const double* bound, double r_cut, int64_t n_atoms,
+                                          int32_t* counts, matten_stream_t stream) {
+    return atom_rows_launch<false>(neighbor_rows_kernel<false>, Rows{pos, cell, ptr, batch, frac, bound, n_atoms},
+                                   rows_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms), r_cut, n_atoms, counts,
+                                   nullptr, 0, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int matten_neighbor_rows_fill(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
                                          const double* frac, const double* bound, double r_cut, int64_t n_atoms,
                                          const int64_t* offsets, int64_t n_edges, int64_t* edge_index,
-                                         float* edge_cell_shift, float* num_neigh, matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!rows_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms) || n_edges < 0) return MATTEN_EINVAL;
-    if (n_atoms == 0) return MATTEN_OK;
-    if (!offsets || (n_edges > 0 && (!edge_index || !edge_cell_shift))) return MATTEN_EINVAL;
-    Rows c{pos, cell, ptr, batch, frac, bound, n_atoms};
-    neighbor_rows_kernel<true><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, nullptr, offsets, edge_index,
-                                                                                    n_edges, edge_cell_shift, num_neigh);
-    MATTEN_LAUNCH_CHECK();
-    return MATTEN_OK;
+                                         float* edge_cell_shift, float* num_neigh, matten_stream_t stream) {
+    return atom_rows_launch<true>(neighbor_rows_kernel<true>, Rows{pos, cell, ptr, batch, frac, bound, n_atoms},
+                                  rows_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms), r_cut, n_atoms, nullptr,
+                                  offsets, n_edges, edge_index, edge_cell_shift, num_neigh, (hipStream_t)stream);
 }
 
 extern "C" int matten_neighbor_cells_row_capacity(void) { return CELLS_ROW_CAP; }
@@ -781,17 +796,12 @@ extern "C" int matten_neighbor_cells_count(const double* pos, const double* cell
                                            const double* frac, const double* bound, const int32_t* grid,
                                            const int64_t* bin_base, const int32_t* bin_of, const int32_t* bin_start,
                                            const int32_t* slot_atom, double r_cut, int64_t n_atoms, int32_t* counts,
-                                           matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!cells_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms, grid, bin_base, bin_of, bin_start, slot_atom))
-        return MATTEN_EINVAL;
-    if (n_atoms == 0) return MATTEN_OK;
-    if (!counts) return MATTEN_EINVAL;
-    Cells c{Rows{pos, cell, ptr, batch, frac, bound, n_atoms}, grid, bin_base, bin_of, bin_start, slot_atom};
-    neighbor_cells_kernel<false><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, counts, nullptr, nullptr, 0,
-                                                                                      nullptr, nullptr);
-    MATTEN_LAUNCH_CHECK();
-    return MATTEN_OK;
+                                           matten_stream_t stream) {
+    return atom_rows_launch<false>(
+        neighbor_cells_kernel<false>,
+        Cells{Rows{pos, cell, ptr, batch, frac, bound, n_atoms}, grid, bin_base, bin_of, bin_start, slot_atom},
+        cells_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms, grid, bin_base, bin_of, bin_start, slot_atom), r_cut,
+        n_atoms, counts, nullptr, 0, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int matten_neighbor_cells_fill(const double* pos, const double* cell, const int64_t* ptr, const int64_t* batch,
@@ -799,27 +809,22 @@ extern "C" int matten_neighbor_cells_fill(const double* pos, const double* cell,
                                           const int64_t* bin_base, const int32_t* bin_of, const int32_t* bin_start,
                                           const int32_t* slot_atom, double r_cut, int64_t n_atoms, const int64_t* offsets,
                                           int64_t n_edges, int64_t* edge_index, float* edge_cell_shift, float* num_neigh,
-                                          matten_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!cells_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms, grid, bin_base, bin_of, bin_start, slot_atom) ||
-        n_edges < 0)
-        return MATTEN_EINVAL;
-    if (n_atoms == 0) return MATTEN_OK;
-    if (!offsets || (n_edges > 0 && (!edge_index || !edge_cell_shift))) return MATTEN_EINVAL;
-    Cells c{Rows{pos, cell, ptr, batch, frac, bound, n_atoms}, grid, bin_base, bin_of, bin_start, slot_atom};
-    neighbor_cells_kernel<true><<<(unsigned)matten_cdiv(n_atoms, 4), 256, 0, stream>>>(c, r_cut, nullptr, offsets, edge_index,
-                                                                                     n_edges, edge_cell_shift, num_neigh);
-    MATTEN_LAUNCH_CHECK();
-    return MATTEN_OK;
+                                          matten_stream_t stream) {
+    return atom_rows_launch<true>(
+        neighbor_cells_kernel<true>,
+        Cells{Rows{pos, cell, ptr, batch, frac, bound, n_atoms}, grid, bin_base, bin_of, bin_start, slot_atom},
+        cells_args_ok(pos, cell, ptr, batch, frac, bound, r_cut, n_atoms, grid, bin_base, bin_of, bin_start, slot_atom), r_cut,
+        n_atoms, nullptr, offsets, n_edges, edge_index, edge_cell_shift, num_neigh, (hipStream_t)stream);
 }
 
 // ---- capped fill: the pair search into buffers of fixed capacity (N_b, E_b, B_b), edge count read on the device ----
 // What a loop over geometries of the same atoms replays as a hipGraph: no host number depends on the positions.  The
 // result is the padded batch layout of data/store.py (GraphStoreHost.padded_reference): behind the B real crystals come
 // K = B_b - B padding crystals; padding crystal 0 owns P = N_b - N - (K - 1) nodes and all E_b - E padding edges, node q
-// of it the edges [floor(q Ep / P), floor((q + 1) Ep / P)), each a self-image edge q -> q with shift (1, 0, 0).  E =
-// offsets[pair_ptr[B]] is read by every thread; when it exceeds E_b no thread stores anything but the flag, so the
-// arrays keep the previous, structurally valid list.  Flag bits: MATTEN_CAPPED_* (include/matten_hip.h).
+// of it the edges [floor(q Ep / P), floor((q + 1) Ep / P)), each a self-image edge q -> q with shift (1, 0, 0).  The
+// real part is neighbor_kernel<PAIR_CAPPED>'s.  E = offsets[pair_ptr[B]] is read by every thread; when it exceeds E_b no
+// thread stores anything but the flag, so the arrays keep the previous, structurally valid list.  Flag bits:
+// MATTEN_CAPPED_* (include/matten_hip.h).
 namespace {
 
 struct Capped {
@@ -851,54 +856,6 @@ __global__ __launch_bounds__(1024) void neighbor_scan_kernel(const int32_t* __re
         run += counts[k];
     }
     if (threadIdx.x == blockDim.x - 1) offsets[n] = part[threadIdx.x];
-}
-
-// neighbor_kernel<true> with the edge count taken from device memory and every store behind its capacity
-__global__ __launch_bounds__(256) void neighbor_fill_capped_kernel(Cry c, double r_cut, const int64_t* __restrict__ offsets,
-                                                                   const int64_t* __restrict__ offsets_t, Capped cap,
-                                                                   int64_t* __restrict__ edge_index,
-                                                                   float* __restrict__ shifts, float* __restrict__ num_neigh,
-                                                                   int32_t* __restrict__ rowptr,
-                                                                   int32_t* __restrict__ src_sorted,
-                                                                   int32_t* __restrict__ perm) {
-    const int64_t n_edges = offsets[c.pair_ptr[cap.n_crystals]];
-    if (n_edges > cap.e_b) return;   // overflow: nothing is stored (the flag is the closing kernel's)
-    const int64_t b = blockIdx.y;
-    const int64_t lo = c.ptr[b];
-    const int64_t n = c.ptr[b + 1] - lo;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * n) return;
-    const int64_t i = lo + t / n, j = lo + t % n;
-    if (i >= cap.n_atoms || j >= cap.n_atoms) return;
-    const int64_t pair = c.pair_ptr[b] + t;
-    const double* cl = c.cell + 9 * b;
-    int x0, x1, y0, y1, z0, z1;
-    shift_range(c.bound[3 * b], c.frac[3 * j] - c.frac[3 * i], x0, x1);
-    shift_range(c.bound[3 * b + 1], c.frac[3 * j + 1] - c.frac[3 * i + 1], y0, y1);
-    shift_range(c.bound[3 * b + 2], c.frac[3 * j + 2] - c.frac[3 * i + 2], z0, z1);
-    const double pi[3] = {c.pos[3 * i], c.pos[3 * i + 1], c.pos[3 * i + 2]};
-    const double pj[3] = {c.pos[3 * j], c.pos[3 * j + 1], c.pos[3 * j + 2]};
-    int64_t out = offsets[pair];
-    if (j == lo) num_neigh[i] = (float)(offsets[pair + n] - offsets[pair]);   // atom i's n pairs
-    const int64_t pair_t = c.pair_ptr[b] + (j - lo) * n + (i - lo);           // the same pair numbered j-major
-    int64_t out_t = offsets_t[pair_t] - offsets_t[0];
-    if (i == lo) rowptr[j] = (int32_t)out_t;
-    const int64_t e_b = cap.e_b;
-    pair_walk(cl, x0, x1, y0, y1, z0, z1, pi, pj, r_cut, i == j, [&](int sx, int sy, int sz) {
-        if (out < n_edges) {
-            edge_index[out] = i;
-            edge_index[e_b + out] = j;
-            shifts[3 * out] = (float)sx;
-            shifts[3 * out + 1] = (float)sy;
-            shifts[3 * out + 2] = (float)sz;
-        }
-        if (out_t < n_edges) {
-            perm[out_t] = (int32_t)out;
-            src_sorted[out_t] = (int32_t)i;
-        }
-        ++out_t;
-        ++out;
-    });
 }
 
 // first padding edge of padding node q: floor(q Ep / P) (q <= P, Ep < 2^31, P < 2^31: exact in int64)
@@ -973,10 +930,9 @@ extern "C" int matten_neighbor_fill_capped(const double* pos, const double* cell
                                            int32_t* perm, int64_t* n_valid, int32_t* flags, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t lim = (int64_t)1 << 31;
-    // what matten_neighbor_fill refuses (its empty batches included: a capped batch has real atoms)
-    if (n_crystals <= 0 || max_atoms <= 0 || n_atoms <= 0 || !(r_cut > 0.0) || n_crystals > 65535) return MATTEN_EINVAL;
-    if (!pos || !cell || !ptr || !frac || !bound || !pair_ptr || !offsets || !offsets_t) return MATTEN_EINVAL;
-    if (!flags || !n_valid) return MATTEN_EINVAL;
+    // pair_launch refuses what matten_neighbor_fill refuses; its empty batches are refused here (a capped batch has atoms)
+    if (n_crystals <= 0 || max_atoms <= 0 || n_atoms <= 0) return MATTEN_EINVAL;
+    if (!offsets_t || !flags || !n_valid) return MATTEN_EINVAL;
     if (node_capacity < 0 || edge_capacity < 0 || crystal_capacity < 0 || node_capacity >= lim || edge_capacity >= lim ||
         crystal_capacity >= lim)
         return MATTEN_EINVAL;
@@ -984,13 +940,12 @@ extern "C" int matten_neighbor_fill_capped(const double* pos, const double* cell
     if (crystal_capacity <= n_crystals || n_atoms > node_capacity || node_capacity - n_atoms < crystal_capacity - n_crystals)
         return MATTEN_EINVAL;
     if (!num_neigh || !rowptr) return MATTEN_EINVAL;
-    if (edge_capacity > 0 && (!edge_index || !edge_cell_shift || !src_sorted || !perm)) return MATTEN_EINVAL;
-    Cry c{pos, cell, ptr, frac, bound, pair_ptr};
+    if (edge_capacity > 0 && (!src_sorted || !perm)) return MATTEN_EINVAL;
+    const int rc = pair_launch<PAIR_CAPPED>(Cry{pos, cell, ptr, frac, bound, pair_ptr}, r_cut, n_crystals, max_atoms, nullptr,
+                                            nullptr, offsets, edge_capacity, edge_index, edge_cell_shift, num_neigh,
+                                            CsrOut{offsets_t, rowptr, src_sorted, perm, n_atoms}, true, stream);
+    if (rc != MATTEN_OK) return rc;
     Capped cap{n_atoms, n_crystals, node_capacity, edge_capacity, crystal_capacity};
-    dim3 grid((unsigned)matten_cdiv(max_atoms * max_atoms, 256), (unsigned)n_crystals);
-    neighbor_fill_capped_kernel<<<grid, 256, 0, stream>>>(c, r_cut, offsets, offsets_t, cap, edge_index, edge_cell_shift,
-                                                          num_neigh, rowptr, src_sorted, perm);
-    MATTEN_LAUNCH_CHECK();
     const int64_t pad_threads = max(edge_capacity, node_capacity - n_atoms + 1);
     neighbor_pad_capped_kernel<<<(unsigned)matten_cdiv(pad_threads, 256), 256, 0, stream>>>(
         offsets, pair_ptr, singular, cap, edge_index, edge_cell_shift, num_neigh, rowptr, src_sorted, perm, n_valid, flags);

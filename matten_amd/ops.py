@@ -1688,18 +1688,63 @@ def valid_loss_bwd_host(pred, target, n_valid: int, kind=0, g: float = 1.0):
     return grad
 
 
-def _prep_out(out, N: int, B: int, singular: bool):
-    """the caller's output tensors of graph_prep / graph_prep_pbc (``out=``), checked: contiguous, of the sizes the kernel
-    writes (rows of a larger buffer are fine: ``buf[:N]``)"""
+def _need_out(t, dtype, numel: int, name: str, why: str = "") -> torch.Tensor:
+    """an output tensor the caller allocated, checked: contiguous, of the size the kernel writes (rows of a larger buffer
+    are fine: ``buf[:N]``)"""
+    if _need(t, dtype, name) is not t or t.numel() != numel:
+        raise ValueError(f"{name}: expected a contiguous {dtype} tensor of {numel} elements{why}")
+    return t
+
+
+def _prep_outputs(out, N: int, B: int, singular: bool, dev):
+    """the outputs of graph_prep / graph_prep_pbc (+ singular): the caller's (``out=``), checked, or new ones"""
     names = ("frac", "bound", "batch", "pos32", "cell32") + (("singular",) if singular else ())
-    want = ((torch.float64, 3 * N), (torch.float64, 3 * B), (torch.int64, N), (torch.float32, 3 * N), (torch.float32, 9 * B),
-            (torch.int32, B))
+    want = ((torch.float64, (N, 3)), (torch.float64, (B, 3)), (torch.int64, (N,)), (torch.float32, (N, 3)),
+            (torch.float32, (3 * B, 3)), (torch.int32, (B,)))[:len(names)]
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=dev) for dtype, shape in want)
     if len(out) != len(names):
         raise ValueError(f"out: expected the {len(names)} tensors {names}")
-    for t, name, (dtype, numel) in zip(out, names, want):
-        if _need(t, dtype, name) is not t or t.numel() != numel:
-            raise ValueError(f"out: {name} must be a contiguous {dtype} tensor of {numel} elements")
-    return tuple(out)
+    return tuple(_need_out(t, dtype, int(np.prod(shape)), name) for t, name, (dtype, shape) in zip(out, names, want))
+
+
+def _search_inputs(pos64, cell64, ptr, frac, bound, index, index_name: str):
+    """what every route of the neighbour search takes, checked -> the six tensors in the order given (index: pair_ptr on
+    the pair route, batch on the others) + (B, N, device)"""
+    pos64 = _need(pos64, torch.float64, "pos")
+    return (pos64, _need(cell64, torch.float64, "cell"), _need(ptr, torch.int64, "ptr"), _need(frac, torch.float64, "frac"),
+            _need(bound, torch.float64, "bound"), _need(index, torch.int64, index_name), ptr.shape[0] - 1, pos64.shape[0],
+            pos64.device)
+
+
+def _edge_outputs(offsets, run_ptr, B: int, N: int, summary, search: bool = True):
+    """The second half of every eager route, between its counting and its fill pass.  offsets: the scanned counts; run_ptr
+    [B+1]: where each crystal's run starts in them; summary: an int64 tensor of two or more elements; search = False:
+    nothing was counted, nothing is read back.  -> (E, min_edges, host, edge_index [2,E], shifts [E,3], num_neigh [N])
+    through the one host sync of graph construction: the edge count sizes the outputs; the smallest edge count of a
+    crystal (0: the caller has to find and report the edgeless ones) and whatever else ``summary`` holds ride on the same
+    read-back, ``host``."""
+    host = [0] * summary.numel()
+    if search:
+        _lib.check(_lib.load().matten_neighbor_summary(_ptr(offsets), _ptr(run_ptr), B, _ptr(summary), _stream()),
+                   "matten_neighbor_summary")
+        host = summary.tolist()
+    E, min_edges, dev = host[0], int(host[1]), offsets.device
+    edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
+    shifts = torch.empty(E, 3, dtype=torch.float32, device=dev)
+    num_neigh = torch.empty(N, dtype=torch.float32, device=dev)
+    return E, min_edges, host, edge_index, shifts, num_neigh
+
+
+def _edge_outputs_by_atom(counts, ptr, summary):
+    """_edge_outputs for the routes that count per centre atom (rows, cells): crystals are runs of atoms, as they are runs
+    of pairs on the pair route, so ptr takes pair_ptr's place.  -> offsets [N+1] i64 + _edge_outputs' results"""
+    N, dev = counts.shape[0], counts.device
+    offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    if summary is None:
+        summary = torch.zeros(3, dtype=torch.int64, device=dev)
+    return (offsets,) + _edge_outputs(offsets, ptr, ptr.shape[0] - 1, N, summary, search=N > 0)
 
 
 def graph_prep(pos64, cell64, ptr, r_cut: float, out=None):
@@ -1710,18 +1755,11 @@ def graph_prep(pos64, cell64, ptr, r_cut: float, out=None):
     pos64 = _need(pos64, torch.float64, "pos")
     cell64 = _need(cell64, torch.float64, "cell")
     ptr = _need(ptr, torch.int64, "ptr")
-    N, B, dev = pos64.shape[0], ptr.shape[0] - 1, pos64.device
-    if out is not None:
-        frac, bound, batch, pos32, cell32 = _prep_out(out, N, B, False)
-    else:
-        frac = torch.empty(N, 3, dtype=torch.float64, device=dev)
-        bound = torch.empty(B, 3, dtype=torch.float64, device=dev)
-        batch = torch.empty(N, dtype=torch.int64, device=dev)
-        pos32 = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        cell32 = torch.empty(3 * B, 3, dtype=torch.float32, device=dev)
+    B = ptr.shape[0] - 1
+    frac, bound, batch, pos32, cell32 = outs = _prep_outputs(out, pos64.shape[0], B, False, pos64.device)
     _lib.check(lib.matten_graph_prep(_ptr(pos64), _ptr(cell64), _ptr(ptr), B, float(r_cut), _ptr(frac), _ptr(bound),
                                      _ptr(batch), _ptr(pos32), _ptr(cell32), _stream()), "matten_graph_prep")
-    return frac, bound, batch, pos32, cell32
+    return outs
 
 
 def neighbor_list(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: float, max_atoms: int, n_pairs: int, want_csr: bool = True):
@@ -1742,15 +1780,7 @@ def neighbor_list_flagged(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: floa
     (flags of the prologue, e.g. graph_prep_pbc's n_singular) cross in the same copy.  The read-back as a host list is
     the seventh result, always (as in neighbor_list_rows)."""
     lib = _lib.load()
-    pos64 = _need(pos64, torch.float64, "pos")
-    cell64 = _need(cell64, torch.float64, "cell")
-    ptr = _need(ptr, torch.int64, "ptr")
-    frac = _need(frac, torch.float64, "frac")
-    bound = _need(bound, torch.float64, "bound")
-    pair_ptr = _need(pair_ptr, torch.int64, "pair_ptr")
-    B = ptr.shape[0] - 1
-    N = pos64.shape[0]
-    dev = pos64.device
+    pos64, cell64, ptr, frac, bound, pair_ptr, B, N, dev = _search_inputs(pos64, cell64, ptr, frac, bound, pair_ptr, "pair_ptr")
     # i-major counts in the first half, the same counts numbered j-major in the second: ONE scan serves both orders
     counts = torch.empty((2 if want_csr else 1) * n_pairs, dtype=torch.int32, device=dev)
     with _timed("neighbor_count"):
@@ -1763,21 +1793,9 @@ def neighbor_list_flagged(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: floa
     scan = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, dtype=torch.int64, out=scan[1:])
     offsets = scan[: n_pairs + 1]
-    # the one host sync of graph construction: the edge count sizes the outputs; the smallest edge count of a crystal
-    # (0: the caller has to find and report the edgeless ones) rides on the same read-back
-    extra = summary is not None
-    if n_pairs:
-        if not extra:
-            summary = torch.empty(2, dtype=torch.int64, device=dev)
-        _lib.check(lib.matten_neighbor_summary(_ptr(offsets), _ptr(pair_ptr), B, _ptr(summary), _stream()),
-                   "matten_neighbor_summary")
-        host = summary.tolist()
-        E, min_edges = host[0], host[1]
-    else:
-        E, min_edges, host = 0, 0, [0] * (len(summary) if extra else 2)
-    edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
-    shifts = torch.empty(E, 3, dtype=torch.float32, device=dev)
-    num_neigh = torch.empty(N, dtype=torch.float32, device=dev)
+    if summary is None:
+        summary = torch.empty(2, dtype=torch.int64, device=dev)
+    E, min_edges, host, edge_index, shifts, num_neigh = _edge_outputs(offsets, pair_ptr, B, N, summary, search=n_pairs > 0)
     csr = offsets_t = None
     if want_csr and n_pairs and E < 2 ** 31:
         offsets_t = scan[n_pairs:]               # the j-major half of the scan (starts at E: the kernel subtracts it)
@@ -1791,7 +1809,7 @@ def neighbor_list_flagged(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: floa
                                      _ptr(csr[2]) if csr else None, _ptr(csr[0]) if csr else None, _stream()),
             "matten_neighbor_fill",
         )
-    return edge_index, shifts, num_neigh, offsets, int(min_edges), csr, host
+    return edge_index, shifts, num_neigh, offsets, min_edges, csr, host
 
 
 def neighbor_list_capped(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: float, max_atoms: int, n_pairs: int, capacity,
@@ -1807,21 +1825,14 @@ def neighbor_list_capped(pos64, cell64, ptr, frac, bound, pair_ptr, r_cut: float
     [2 n_pairs + 1] i64: scratch the caller may keep between calls.  -> scan (scan[n_pairs] is E, scan[pair_ptr] the
     first edge of each crystal)."""
     lib = _lib.load()
-    pos64 = _need(pos64, torch.float64, "pos")
-    cell64 = _need(cell64, torch.float64, "cell")
-    ptr = _need(ptr, torch.int64, "ptr")
-    frac = _need(frac, torch.float64, "frac")
-    bound = _need(bound, torch.float64, "bound")
-    pair_ptr = _need(pair_ptr, torch.int64, "pair_ptr")
-    B, N, dev = ptr.shape[0] - 1, pos64.shape[0], pos64.device
+    pos64, cell64, ptr, frac, bound, pair_ptr, B, N, dev = _search_inputs(pos64, cell64, ptr, frac, bound, pair_ptr, "pair_ptr")
     n_b, e_b, b_b = (int(v) for v in capacity)
-    outs = (("edge_index", edge_index, torch.int64, 2 * e_b), ("edge_cell_shift", edge_cell_shift, torch.float32, 3 * e_b),
-            ("num_neigh", num_neigh, torch.float32, n_b), ("perm", perm, torch.int32, e_b),
-            ("rowptr", rowptr, torch.int32, n_b + 1), ("src_sorted", src_sorted, torch.int32, e_b),
-            ("n_valid", n_valid, torch.int64, 3), ("flags", flags, torch.int32, 1))
-    for name, t, dtype, numel in outs:
-        if _need(t, dtype, name) is not t or t.numel() != numel:
-            raise ValueError(f"{name}: expected a contiguous {dtype} tensor of {numel} elements for capacity {(n_b, e_b, b_b)}")
+    for name, t, dtype, numel in (("edge_index", edge_index, torch.int64, 2 * e_b),
+                                  ("edge_cell_shift", edge_cell_shift, torch.float32, 3 * e_b),
+                                  ("num_neigh", num_neigh, torch.float32, n_b), ("perm", perm, torch.int32, e_b),
+                                  ("rowptr", rowptr, torch.int32, n_b + 1), ("src_sorted", src_sorted, torch.int32, e_b),
+                                  ("n_valid", n_valid, torch.int64, 3), ("flags", flags, torch.int32, 1)):
+        _need_out(t, dtype, numel, name, f" for capacity {(n_b, e_b, b_b)}")
     if counts is None:
         counts = torch.empty(2 * n_pairs, dtype=torch.int32, device=dev)
     if scan is None:
@@ -1848,28 +1859,20 @@ def graph_prep_pbc(pos64, cell64, ptr, pbc, r_cut: float, n_singular: torch.Tens
     """graph_prep for open / partly periodic crystals (include/matten_hip.h matten_graph_prep_pbc): pbc [B,3] uint8.
     -> graph_prep's five outputs + singular [B] i32 (1: the periodic vectors of that crystal are linearly dependent).
     n_singular: a zeroed int64 element that receives the number of such crystals (the caller reads it back with the
-    edge count: see neighbor_list(summary=)).  ``out``: the six outputs, allocated by the caller (see graph_prep)."""
+    edge count: see neighbor_list_flagged(summary=)).  ``out``: the six outputs, allocated by the caller (see graph_prep)."""
     lib = _lib.load()
     pos64 = _need(pos64, torch.float64, "pos")
     cell64 = _need(cell64, torch.float64, "cell")
     ptr = _need(ptr, torch.int64, "ptr")
     pbc = _need(pbc, torch.uint8, "pbc")
-    N, B, dev = pos64.shape[0], ptr.shape[0] - 1, pos64.device
+    B = ptr.shape[0] - 1
     if pbc.numel() != 3 * B or n_singular.dtype != torch.int64 or n_singular.numel() != 1:
         raise ValueError("pbc must hold [B,3] flags, n_singular one int64")
-    if out is not None:
-        frac, bound, batch, pos32, cell32, singular = _prep_out(out, N, B, True)
-    else:
-        frac = torch.empty(N, 3, dtype=torch.float64, device=dev)
-        bound = torch.empty(B, 3, dtype=torch.float64, device=dev)
-        batch = torch.empty(N, dtype=torch.int64, device=dev)
-        pos32 = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        cell32 = torch.empty(3 * B, 3, dtype=torch.float32, device=dev)
-        singular = torch.empty(B, dtype=torch.int32, device=dev)
+    frac, bound, batch, pos32, cell32, singular = outs = _prep_outputs(out, pos64.shape[0], B, True, pos64.device)
     _lib.check(lib.matten_graph_prep_pbc(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(pbc), B, float(r_cut), _ptr(frac),
                                          _ptr(bound), _ptr(batch), _ptr(pos32), _ptr(cell32), _ptr(singular),
                                          n_singular.data_ptr(), _stream()), "matten_graph_prep_pbc")
-    return frac, bound, batch, pos32, cell32, singular
+    return outs
 
 
 def neighbor_list_rows(pos64, cell64, ptr, batch, frac, bound, r_cut: float, summary: torch.Tensor = None):
@@ -1878,35 +1881,16 @@ def neighbor_list_rows(pos64, cell64, ptr, batch, frac, bound, r_cut: float, sum
     -> (edge_index [2,E] i64, edge_cell_shift [E,3] f32, num_neigh [N] f32, offsets [N+1] i64 (first edge of each centre
         atom), smallest edge count of a crystal, summary [3] i64 on the host).  No CSR on this route (ops.csr_build)."""
     lib = _lib.load()
-    pos64 = _need(pos64, torch.float64, "pos")
-    cell64 = _need(cell64, torch.float64, "cell")
-    ptr = _need(ptr, torch.int64, "ptr")
-    batch = _need(batch, torch.int64, "batch")
-    frac = _need(frac, torch.float64, "frac")
-    bound = _need(bound, torch.float64, "bound")
-    B, N, dev = ptr.shape[0] - 1, pos64.shape[0], pos64.device
+    pos64, cell64, ptr, frac, bound, batch, B, N, dev = _search_inputs(pos64, cell64, ptr, frac, bound, batch, "batch")
+    search = (_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound), float(r_cut), N)
     counts = torch.empty(N, dtype=torch.int32, device=dev)
     with _timed("neighbor_rows_count"):
-        _lib.check(lib.matten_neighbor_rows_count(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound),
-                                                  float(r_cut), N, _ptr(counts), _stream()), "matten_neighbor_rows_count")
-    offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
-    if summary is None:
-        summary = torch.zeros(3, dtype=torch.int64, device=dev)
-    if N:   # crystals are runs of atoms, as they are runs of pairs on the other route: ptr takes pair_ptr's place
-        _lib.check(lib.matten_neighbor_summary(_ptr(offsets), _ptr(ptr), B, _ptr(summary), _stream()), "matten_neighbor_summary")
-        host = summary.tolist()   # the one host sync of graph construction
-    else:
-        host = [0, 0, 0]
-    E, min_edges = host[0], host[1]
-    edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
-    shifts = torch.empty(E, 3, dtype=torch.float32, device=dev)
-    num_neigh = torch.empty(N, dtype=torch.float32, device=dev)
+        _lib.check(lib.matten_neighbor_rows_count(*search, _ptr(counts), _stream()), "matten_neighbor_rows_count")
+    offsets, E, min_edges, host, edge_index, shifts, num_neigh = _edge_outputs_by_atom(counts, ptr, summary)
     with _timed("neighbor_rows_fill"):
-        _lib.check(lib.matten_neighbor_rows_fill(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound),
-                                                 float(r_cut), N, _ptr(offsets), E, _ptr(edge_index), _ptr(shifts),
-                                                 _ptr(num_neigh), _stream()), "matten_neighbor_rows_fill")
-    return edge_index, shifts, num_neigh, offsets, int(min_edges), host
+        _lib.check(lib.matten_neighbor_rows_fill(*search, _ptr(offsets), E, _ptr(edge_index), _ptr(shifts), _ptr(num_neigh),
+                                                 _stream()), "matten_neighbor_rows_fill")
+    return edge_index, shifts, num_neigh, offsets, min_edges, host
 
 
 def neighbor_cells_row_capacity() -> int:
@@ -1923,17 +1907,11 @@ def neighbor_list_cells(pos64, cell64, ptr, batch, frac, bound, r_cut: float, su
     pbc [B,3] uint8 and singular [B] i32 are ops.graph_prep_pbc's (None: every axis periodic).  Scratch is O(N): about
     65 bytes per atom."""
     lib = _lib.load()
-    pos64 = _need(pos64, torch.float64, "pos")
-    cell64 = _need(cell64, torch.float64, "cell")
-    ptr = _need(ptr, torch.int64, "ptr")
-    batch = _need(batch, torch.int64, "batch")
-    frac = _need(frac, torch.float64, "frac")
-    bound = _need(bound, torch.float64, "bound")
+    pos64, cell64, ptr, frac, bound, batch, B, N, dev = _search_inputs(pos64, cell64, ptr, frac, bound, batch, "batch")
     if pbc is not None:
         pbc = _need(pbc, torch.uint8, "pbc")
     if singular is not None:
         singular = _need(singular, torch.int32, "singular")
-    B, N, dev = ptr.shape[0] - 1, pos64.shape[0], pos64.device
     if (pbc is not None and pbc.numel() != 3 * B) or (singular is not None and singular.numel() != B):
         raise ValueError("pbc must hold [B,3] flags, singular [B]")
     grid = torch.empty(B, 8, dtype=torch.int32, device=dev)
@@ -1957,27 +1935,13 @@ def neighbor_list_cells(pos64, cell64, ptr, batch, frac, bound, r_cut: float, su
                                                      _ptr(bin_count), _ptr(slot_atom), _stream()),
                    "matten_neighbor_cells_scatter")
     del bin_count, n_bins, grid_f
+    search = (_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound), _ptr(grid), _ptr(bin_base),
+              _ptr(bin_of), _ptr(bin_start), _ptr(slot_atom), float(r_cut), N)
     counts = torch.empty(N, dtype=torch.int32, device=dev)
     with _timed("neighbor_cells_count"):
-        _lib.check(lib.matten_neighbor_cells_count(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound),
-                                                   _ptr(grid), _ptr(bin_base), _ptr(bin_of), _ptr(bin_start), _ptr(slot_atom),
-                                                   float(r_cut), N, _ptr(counts), _stream()), "matten_neighbor_cells_count")
-    offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
-    if summary is None:
-        summary = torch.zeros(3, dtype=torch.int64, device=dev)
-    if N:
-        _lib.check(lib.matten_neighbor_summary(_ptr(offsets), _ptr(ptr), B, _ptr(summary), _stream()), "matten_neighbor_summary")
-        host = summary.tolist()   # the one host sync of graph construction
-    else:
-        host = [0, 0, 0]
-    E, min_edges = host[0], host[1]
-    edge_index = torch.empty(2, E, dtype=torch.int64, device=dev)
-    shifts = torch.empty(E, 3, dtype=torch.float32, device=dev)
-    num_neigh = torch.empty(N, dtype=torch.float32, device=dev)
+        _lib.check(lib.matten_neighbor_cells_count(*search, _ptr(counts), _stream()), "matten_neighbor_cells_count")
+    offsets, E, min_edges, host, edge_index, shifts, num_neigh = _edge_outputs_by_atom(counts, ptr, summary)
     with _timed("neighbor_cells_fill"):
-        _lib.check(lib.matten_neighbor_cells_fill(_ptr(pos64), _ptr(cell64), _ptr(ptr), _ptr(batch), _ptr(frac), _ptr(bound),
-                                                  _ptr(grid), _ptr(bin_base), _ptr(bin_of), _ptr(bin_start), _ptr(slot_atom),
-                                                  float(r_cut), N, _ptr(offsets), E, _ptr(edge_index), _ptr(shifts),
-                                                  _ptr(num_neigh), _stream()), "matten_neighbor_cells_fill")
-    return edge_index, shifts, num_neigh, offsets, int(min_edges), host
+        _lib.check(lib.matten_neighbor_cells_fill(*search, _ptr(offsets), E, _ptr(edge_index), _ptr(shifts), _ptr(num_neigh),
+                                                  _stream()), "matten_neighbor_cells_fill")
+    return edge_index, shifts, num_neigh, offsets, min_edges, host

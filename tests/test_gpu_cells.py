@@ -262,3 +262,49 @@ def test_g8_errors_and_predict_go_through_the_cells_route(monkeypatch):
     off = P.predict([sup, ball], model=model, config=cfg, is_elasticity_tensor=False)
     assert len(on) == len(off) == 2 and on[0].shape == (3, 3, 3, 3)
     assert all(np.array_equal(a, b) for a, b in zip(on, off)) and float(np.abs(on[0]).max()) > 0
+
+
+def test_g9_pair_rows_cells_and_capped_routes_on_one_batch(monkeypatch):
+    """The four search routes on ONE batch, each against the host builder and the CSR of the pair route against the
+    capped one: a 2-atom Si primitive cell (56 edges over 4 ordered pairs: several images per pair), fcc_supercell(3, 4, 5)
+    with a = 5.2 (240 atoms: four wave chunks and a running base on the rows route; at the default a = 4.05 the grid at
+    5 A would be [1, 3, 4], at 5.2 it is [3, 4, 5]) and a slab (open z).  The capped buffers hold 5 edges, 3 atoms and
+    2 crystals more than the list; their real prefix is compared."""
+    from matten_amd.data import synthetic
+    from matten_amd.data._key import AMD_N_VALID, AMD_PERM, AMD_ROWPTR, AMD_SRC
+    from matten_amd.data.graph import batch_graphs_gpu, collate, neighbor_list, normalize_pbc
+    from matten_amd.data.rebuild import GeometryBatch
+
+    r_cut, a = 5.0, 5.43
+    si = {"lattice": 0.5 * a * np.array([[0.0, 1, 1], [1, 0, 1], [1, 1, 0]]), "atomic_numbers": np.array([14, 14]),
+          "cart_coords": np.array([[0.0, 0.0, 0.0], [0.25 * a] * 3])}
+    items = [_item(si), _item(synthetic.fcc_supercell(3, 4, 5, a=5.2)), _item(synthetic.fcc_slabs(1)[0])]
+    # the case is the one intended (host only)
+    assert [len(it[0]) for it in items] == [2, 240, 54] and normalize_pbc(items[2][3]) == SLAB
+    assert _grid(items[1], r_cut) == [3, 4, 5]
+    counts = [neighbor_list(p, c, r_cut, f)[0].shape[1] for p, c, _, f in items]
+    assert counts[0] == 56 and min(counts) > 0
+    want = collate(_host(items, r_cut))
+    N, E = int(want["pos"].shape[0]), int(want["edge_index"].shape[1])
+    assert E == sum(counts)
+
+    monkeypatch.delenv("MATTEN_NEIGHBOR_ROWS_MIN_ATOMS", raising=False)
+    monkeypatch.delenv("MATTEN_NEIGHBOR_CELLS_MIN_ATOMS", raising=False)
+    pair = batch_graphs_gpu(items, r_cut, DEV)
+    _assert_same_graph(pair, want)
+    ptr = np.concatenate([[0], np.cumsum([len(it[0]) for it in items])])
+    gb = GeometryBatch(np.concatenate([it[0] for it in items]), np.stack([it[1] for it in items]),
+                       np.concatenate([it[2] for it in items]), ptr, r_cut, DEV,
+                       pbc=np.array([normalize_pbc(it[3]) for it in items]), edge_capacity=E + 5, pad_nodes=3, pad_crystals=2)
+    assert gb.capacity == (N + 3, E + 5, 5) and gb.batch[AMD_N_VALID].tolist() == [N, E, 3]
+    capped = {"edge_index": gb.batch["edge_index"][:, :E], "edge_cell_shift": gb.batch["edge_cell_shift"][:E],
+              "num_neigh": gb.batch["num_neigh"][:N]}
+    lists = {"pair": pair, "capped": capped, "rows": _build(items, r_cut, "rows", monkeypatch),
+             "cells": _build(items, r_cut, "cells", monkeypatch)}
+    for route, got in lists.items():
+        for k in ("edge_index", "edge_cell_shift", "num_neigh"):
+            assert got[k].dtype == want[k].dtype and torch.equal(got[k].cpu(), want[k]), (route, k)
+    _assert_same_graph(lists["rows"], want, csr=False)
+    _assert_same_graph(lists["cells"], want, csr=False)
+    assert torch.equal(gb.batch[AMD_PERM][:E], pair[AMD_PERM]) and torch.equal(gb.batch[AMD_SRC][:E], pair[AMD_SRC])
+    assert torch.equal(gb.batch[AMD_ROWPTR][:N + 1], pair[AMD_ROWPTR])
