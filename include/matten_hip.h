@@ -656,6 +656,49 @@ int matten_rank2_props_bwd(const double* vals, const double* axes, const double*
                            const double* g_vals, const double* g_props, int is_fp64, int64_t n, void* g_t,
                            matten_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Rotations and symmetry of irreps tensors (the reference's own equivariance check, tests/model/test_tfn_tensor.py:98-139,
+ * converts the prediction with utils.py:110-133 to_cartesian and rotates it on the host with a rank-4 einsum; here rows
+ * stay in the irreps basis on the device).  fp64 arithmetic.  One convention for the harmonics, the Cartesian bases
+ * (o3.cartesian_tensor_basis) and parity: for an orthogonal M the block of irrep (l, p) is
+ *   D_{l,p}(M) = p^[det M < 0] D^l(det(M) M),   Y_l(R v) = D^l(R) Y_l(v) with the harmonics of csrc/sh.h.
+ * matten_wigner_d:
+ *   R [G,9] (= [G,3,3] row-major) fp64 -> D [G,165]: the blocks D^0..D^lmax (lmax <= 4) of the PROPER part det(M) M,
+ *   row-major, at the offsets 0, 1, 10, 35, 84 of a row; the row stride is 165 whatever lmax, blocks above lmax are not
+ *   written.  D^l = Y_l(R P) Y_l(P)^-1 over 2l+1 fixed unit vectors (constants of csrc/rotate.hip; the harmonics are
+ *   restated there in fp64 and normalise their argument).
+ *   flags [G] int32: bit 0 = an entry is not finite; bit 1 = max|M^T M - I| > orth_tol; bit 2 = det M < 0 (improper).
+ *   A row with bit 0 or bit 1 is NaN throughout (its blocks up to lmax).
+ * matten_irreps_rotate:
+ *   out[r] = D(M_g) x[r] (transpose = 0) or D(M_g)^T x[r] (1, the adjoint), g = index[r], or with index = NULL g = 0
+ *   (G == 1) or g = r (G == n).  x, out [n,dim] fp32 (is_fp64 = 0) or fp64 (1), rounded once on the store; out may be x.
+ *   layout [K,4] int32 HOST rows (offset, mul, l, parity): mul copies of irrep (l, parity) from column `offset`, copy u at
+ *   offset + u (2l+1); K <= 16; the rows' column ranges must be disjoint (overlapping rows are MATTEN_EINVAL: two thread
+ *   groups would write the same columns).  Columns that no layout row covers are not written.  A row whose g lies outside [0, G) is
+ *   NaN; a flagged rotation hands on the NaN of its D row.  D must hold the blocks up to the layout's largest l.
+ * matten_irreps_average:
+ *   out[r] = sum_j w_j D(M_op_idx[j]) x[r] / sum_j w_j over j in [op_ptr[r], op_ptr[r+1]), in list order; op_ptr [n+1]
+ *   int64, op_idx [nnz] int32 into the G rows of D (shared: all cubic crystals of a batch point at the same 48 rows),
+ *   weights [nnz] fp64 or NULL (= 1).  transpose = 1 applies every D^T: the adjoint with respect to x.
+ *   The extra argument G (the rows of D) bounds op_idx.  The library cannot see nnz, so with G > 0 op_idx must be a valid
+ *   pointer even when every list is empty (nnz = 0: any device word will do, it is not read; ops.irreps_average passes
+ *   one); the caller vouches for op_ptr (ascending from 0, op_ptr[n] <= nnz).
+ *   deviation [n] fp64 or NULL: |x[r] - out[r]|_2 / |x[r]|_2 from out as stored, 0 where x[r] = 0.
+ *   An empty list is the trivial group: out = x, deviation 0.  A flagged operation (bit 0 or 1), an op_idx outside [0, G),
+ *   a weight that is not finite or sum_j w_j not greater than 0: the row and its deviation are NaN.
+ * All: no atomics, no allocation, nothing read back, sums in list order: bitwise reproducible and capturable.  n = 0 (and
+ * G = 0 for the first two) is a no-op.  MATTEN_EINVAL without a launch: a negative size, lmax outside 0..4, K > 16, a
+ * layout row with l > 4, parity outside +-1 or a block past dim, is_fp64 or transpose outside {0, 1}, index = NULL with G
+ * neither 1 nor n, a NULL required pointer with n > 0.
+ * ------------------------------------------------------------------------------------------ */
+int matten_wigner_d(const double* R, int64_t G, int lmax, double orth_tol, double* D, int32_t* flags, matten_stream_t stream);
+int matten_irreps_rotate(const void* x, int is_fp64, int64_t n, int64_t dim, const int32_t* layout, int K, const double* D,
+                         const int32_t* flags, const int32_t* index, int64_t G, int transpose, void* out,
+                         matten_stream_t stream);
+int matten_irreps_average(const void* x, int is_fp64, int64_t n, int64_t dim, const int32_t* layout, int K, const double* D,
+                          const int32_t* flags, int64_t G, const int64_t* op_ptr, const int32_t* op_idx,
+                          const double* weights, int transpose, void* out, double* deviation, matten_stream_t stream);
+
 
 /* ==========================================================================================
  * Adjoint (backward) operators for the training step (reference: autograd through

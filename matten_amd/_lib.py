@@ -143,6 +143,9 @@ SIGNATURES = {
     "matten_elastic_polycrystal_bwd": (c_int, [P, P, P, P, P, c_int64, P, P]),
     "matten_rank2_props": (c_int, [P, c_int, c_int64, P, P, P, P, P]),
     "matten_rank2_props_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int64, P, P]),
+    "matten_wigner_d": (c_int, [P, c_int64, c_int, ctypes.c_double, P, P, P]),
+    "matten_irreps_rotate": (c_int, [P, c_int, c_int64, c_int64, P, c_int, P, P, P, c_int64, c_int, P, P]),
+    "matten_irreps_average": (c_int, [P, c_int, c_int64, c_int64, P, c_int, P, P, c_int64, P, P, P, c_int, P, P, P]),
     "matten_batch_gather_lds_rows": (c_int, []),
     "matten_batch_gather_max_streams": (c_int, []),
     "matten_batch_gather": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P]),

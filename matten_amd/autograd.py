@@ -606,6 +606,42 @@ class Rank2PropsFn(torch.autograd.Function):
         return ops.rank2_props_bwd(vals, axes, props, flags, g_vals, g_props, ctx.dtype)
 
 
+class IrrepsRotateFn(torch.autograd.Function):
+    """out = matten_irreps_rotate(x): linear in x, the backward is the same kernel with transpose = 1.  The rotation table
+    (D, flags), the layout and the index carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, layout, D, flags, index):
+        ctx.layout = layout
+        ctx.save_for_backward(D, flags, index)
+        return ops.irreps_rotate(x, layout, D, flags, index)
+
+    @staticmethod
+    def backward(ctx, g):
+        D, flags, index = ctx.saved_tensors
+        return ops.irreps_rotate(g.contiguous(), ctx.layout, D, flags, index, transpose=True), None, None, None, None
+
+
+class IrrepsAverageFn(torch.autograd.Function):
+    """(out, deviation) = matten_irreps_average(x): out is linear in x, its backward the same kernel with transpose = 1 and
+    the same lists and weights.  ``deviation`` is a diagnostic and carries no gradient, nor do the rotations and weights."""
+
+    @staticmethod
+    def forward(ctx, x, layout, D, flags, op_ptr, op_idx, weights):
+        ctx.layout = layout
+        ctx.save_for_backward(D, flags, op_ptr, op_idx, weights)
+        out, deviation = ops.irreps_average(x, layout, D, flags, op_ptr, op_idx, weights)
+        ctx.mark_non_differentiable(deviation)
+        return out, deviation
+
+    @staticmethod
+    def backward(ctx, g, _g_deviation):
+        D, flags, op_ptr, op_idx, weights = ctx.saved_tensors
+        g_x, _ = ops.irreps_average(g.contiguous(), ctx.layout, D, flags, op_ptr, op_idx, weights, transpose=True,
+                                    want_deviation=False)
+        return g_x, None, None, None, None, None, None
+
+
 class DenseRowsFn(torch.autograd.Function):
     """out = x @ q (matten_dense_rows) for a constant q [n_in, n_out]; the adjoint is the same kernel with q^T, which the
     caller keeps next to q (``qt`` [n_out, n_in])."""

@@ -965,6 +965,98 @@ def rank2_props_bwd(vals, axes, props, flags, g_vals, g_props, dtype):
     return g_t
 
 
+WIGNER_STRIDE = 165      # doubles per rotation in the table of matten_wigner_d: the blocks D^0..D^4, 1 + 9 + 25 + 49 + 81
+WIGNER_MAX_LAYOUT = 16   # layout rows per call of matten_irreps_rotate / matten_irreps_average
+
+
+def wigner_d(R, lmax: int = 4, orth_tol: float = 1e-6, out=None):
+    """R [G,3,3] (or [G,9]) fp64 -> (D [G,165] fp64, flags [G] int32): the packed blocks D^0..D^lmax of the proper part of
+    every matrix; flags bit 0 non-finite, bit 1 not orthogonal to orth_tol (both: the row is NaN), bit 2 improper
+    (include/matten_hip.h: matten_wigner_d).  ``out`` = (D, flags) to write into (a captured graph's buffers)."""
+    lib = _lib.load()
+    R = _need(R, torch.float64, "R")
+    if R.dim() < 2 or R.numel() != R.shape[0] * 9:
+        raise ValueError(f"R: expected [G,3,3], got {tuple(R.shape)}")
+    G = R.shape[0]
+    if out is None:
+        D = torch.empty(G, WIGNER_STRIDE, dtype=torch.float64, device=R.device)
+        flags = torch.empty(G, dtype=torch.int32, device=R.device)
+    else:
+        D, flags = _need(out[0], torch.float64, "D"), _need(out[1], torch.int32, "flags")
+        if D.shape != (G, WIGNER_STRIDE) or flags.shape != (G,) or D is not out[0] or flags is not out[1]:
+            raise ValueError("out: expected contiguous (D [G,165] fp64, flags [G] int32)")
+    _lib.check(lib.matten_wigner_d(_ptr(R), G, int(lmax), float(orth_tol), _ptr(D), _ptr(flags), _stream()), "matten_wigner_d")
+    return D, flags
+
+
+def _irreps_rows(x, layout, D, flags):
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.float64):
+        raise TypeError("x: expected an fp32 or fp64 tensor")
+    x = _need(x, x.dtype, "x")
+    if x.dim() != 2:
+        raise ValueError(f"x: expected [n,dim], got {tuple(x.shape)}")
+    layout = np.ascontiguousarray(layout, dtype=np.int32).reshape(-1, 4)     # host rows (offset, mul, l, parity)
+    D = _need(D, torch.float64, "D")
+    flags = _need(flags, torch.int32, "flags")
+    if D.dim() != 2 or D.shape[1] != WIGNER_STRIDE or flags.shape != (D.shape[0],):
+        raise ValueError(f"expected D [G,165] and flags [G], got {tuple(D.shape)}, {tuple(flags.shape)}")
+    return x, layout, D, flags
+
+
+def _irreps_out(x, out):
+    if out is None:
+        return torch.empty_like(x)
+    if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise ValueError("out: expected a contiguous tensor of x's shape, dtype and device")
+    return out
+
+
+def irreps_rotate(x, layout, D, flags, index=None, transpose: bool = False, out=None):
+    """out[r] = D(M_g) x[r] (``transpose``: D^T, the adjoint) with g = index[r], or without index g = 0 (one rotation) or
+    g = r (one per row).  x [n,dim] fp32 or fp64, layout [K,4] host int32 rows (offset, mul, l, parity), (D, flags) of
+    ``wigner_d`` (matten_irreps_rotate)"""
+    lib = _lib.load()
+    x, layout, D, flags = _irreps_rows(x, layout, D, flags)
+    n, G = x.shape[0], D.shape[0]
+    if index is not None:
+        index = _need(index, torch.int32, "index")
+        if index.shape != (n,):
+            raise ValueError(f"index: expected [{n}], got {tuple(index.shape)}")
+    elif n > 0 and G not in (1, n):
+        raise ValueError(f"without index the {n} rows need 1 or {n} rotations, got {G}")
+    out = _irreps_out(x, out)
+    _lib.check(lib.matten_irreps_rotate(_ptr(x), int(x.dtype == torch.float64), n, x.shape[1], layout.ctypes.data, len(layout),
+                                        _ptr(D), _ptr(flags), _ptr(index), G, int(bool(transpose)), _ptr(out), _stream()),
+               "matten_irreps_rotate")
+    return out
+
+
+def irreps_average(x, layout, D, flags, op_ptr, op_idx, weights=None, transpose: bool = False, want_deviation: bool = True,
+                   out=None):
+    """out[r] = sum_j w_j D(M_op_idx[j]) x[r] / sum_j w_j over j in [op_ptr[r], op_ptr[r+1]) and deviation[r] =
+    |x[r] - out[r]| / |x[r]| (fp64, or None).  op_ptr [n+1] int64 and op_idx [nnz] int32 on the device; the caller vouches
+    for op_ptr (ascending, op_ptr[n] <= nnz), as for every CSR here; weights [nnz] fp64 or None (matten_irreps_average)"""
+    lib = _lib.load()
+    x, layout, D, flags = _irreps_rows(x, layout, D, flags)
+    n = x.shape[0]
+    op_ptr = _need(op_ptr, torch.int64, "op_ptr")
+    op_idx = _need(op_idx, torch.int32, "op_idx")
+    if op_ptr.shape != (n + 1,) or op_idx.dim() != 1:
+        raise ValueError(f"expected op_ptr [{n + 1}] and op_idx [nnz], got {tuple(op_ptr.shape)}, {tuple(op_idx.shape)}")
+    if weights is not None:
+        weights = _need(weights, torch.float64, "weights")
+        if weights.shape != op_idx.shape:
+            raise ValueError(f"weights: expected {tuple(op_idx.shape)}, got {tuple(weights.shape)}")
+    out = _irreps_out(x, out)
+    # nnz = 0 (every list empty): an empty tensor has no address, and the library asks for one; flags stands in, unread
+    idx_ptr = _ptr(op_idx) if op_idx.numel() else _ptr(flags)
+    deviation = torch.empty(n, dtype=torch.float64, device=x.device) if want_deviation else None
+    _lib.check(lib.matten_irreps_average(_ptr(x), int(x.dtype == torch.float64), n, x.shape[1], layout.ctypes.data, len(layout),
+                                         _ptr(D), _ptr(flags), D.shape[0], _ptr(op_ptr), idx_ptr, _ptr(weights),
+                                         int(bool(transpose)), _ptr(out), _ptr(deviation), _stream()), "matten_irreps_average")
+    return out, deviation
+
+
 def _kelvin_rows(voigt, flags):
     voigt = _need(voigt, torch.float64, "voigt")
     flags = _need(flags, torch.int32, "flags")

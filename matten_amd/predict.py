@@ -493,6 +493,82 @@ def evaluate_atomic(model, graphs: List, batch_size: int = 200, tensor_target_na
     return list(torch.cat(outs, dim=0).cpu())
 
 
+def equivariance_report(model, structures, rotations=None, n_random: int = 2, seed: int = 0, r_cut: float = None,
+                        formula: str = "ijkl=jikl=klij", is_atomic_tensor: bool = False) -> Dict[str, Any]:
+    """Is this model, on this build, still equivariant?  Every structure is predicted as given and with positions and cell
+    rotated (r' = M r) by every rotation; the unrotated prediction is rotated on the device in the irreps basis
+    (``symmetry.rotate_irreps``; per-atom tensors by their structure's rotation through the ``index`` path) and compared
+    with the prediction of the rotated structure -- the reference's own check (tests/model/test_tfn_tensor.py:98-139)
+    without the trip to the host and the rank-4 einsum.
+
+    ``rotations`` [G,3,3] (orthogonal, proper or improper); by default ``n_random`` seeded random proper rotations plus
+    one improper one (the negative of a further random rotation).  ``r_cut`` defaults to the model's radial cutoff
+    (``radial_basis_end``).  The forwards are those of ``evaluate`` / ``evaluate_atomic`` (``collate`` of host graphs, eval
+    mode, no grad); one read-back at the end.
+    -> {"rotations" [G,3,3], "max_abs" [S,G] = max|D y(x) - y(M x)|, "max_rel" [S,G] = that over max|y(x)|, both in the
+    irreps basis, "worst_abs", "worst_rel", "worst" = (structure, rotation) of worst_rel}."""
+    from .symmetry import irreps_of, rotate_irreps
+
+    structures = list(structures) if isinstance(structures, (list, tuple)) else [structures]
+    if not structures:
+        raise ValueError("equivariance_report: no structure")
+    if rotations is None:
+        rng = np.random.default_rng(seed)
+        mats = []
+        for k in range(n_random + 1):
+            q, r = np.linalg.qr(rng.standard_normal((3, 3)))
+            q = q * np.sign(np.diag(r))
+            q = q if np.linalg.det(q) > 0 else -q
+            mats.append(-q if k == n_random else q)
+        rotations = np.stack(mats)
+    rotations = np.asarray(rotations, dtype=np.float64).reshape(-1, 3, 3)
+    G, S = len(rotations), len(structures)
+    if r_cut is None:
+        r_cut = float(model.hparams["backbone_hparams"]["radial_basis_end"])
+    check_species(model, structures)
+    device = model.device
+    name = list(model.tasks.keys())[0]
+    converter = _converter(formula)
+    dim = irreps_of(formula).dim
+    cartesian_out = getattr(model, "to_cartesian", None) is not None
+
+    def graph(s, M):
+        f = _fields(s)
+        return crystal_graph(f["cart_coords"] @ M.T, f["lattice"] @ M.T, f["atomic_numbers"], r_cut, pbc=f["pbc"])
+
+    def rows(graphs):
+        batch = collate(graphs, device=device)
+        preds, _ = model(batch, task_name=name)
+        p = preds[name]
+        if cartesian_out:
+            p = converter.from_cartesian(p)
+        return p.reshape(-1, dim), batch["batch"]
+
+    model.eval()
+    R = torch.as_tensor(rotations, device=device)
+    max_abs = torch.empty(S, G, dtype=torch.float64, device=device)
+    scale = torch.empty(S, dtype=torch.float64, device=device)
+    with torch.no_grad():
+        for i, s in enumerate(structures):
+            # ONE forward per structure: graph 0 of the batch is the structure as given, graph 1 + g its copy under rotation g
+            # (eval mode: a prediction does not depend on its batch)
+            y_all, owner = rows([graph(s, np.eye(3))] + [graph(s, M) for M in rotations])
+            n = y_all.shape[0] // (G + 1)                                 # rows per copy: atoms, or 1
+            y, y_rot = y_all[:n], y_all[n:]
+            # row r of y_rot belongs to rotation g: the per-atom path maps atoms to rotations, the crystal path is one row each
+            index = owner[n:] - 1 if is_atomic_tensor else None
+            want = rotate_irreps(y.repeat(G, 1), formula, R, index=index)
+            diff = (want - y_rot).abs().double().reshape(G, -1).amax(dim=1)
+            max_abs[i].copy_(diff)
+            scale[i] = y.abs().double().amax()
+    max_abs, scale = max_abs.cpu().numpy(), scale.cpu().numpy()      # the one read-back
+    with np.errstate(invalid="ignore", divide="ignore"):
+        max_rel = max_abs / scale[:, None]
+    worst = np.unravel_index(int(np.nanargmax(max_rel)), max_rel.shape) if np.isfinite(max_rel).any() else (0, 0)
+    return {"rotations": rotations, "max_abs": max_abs, "max_rel": max_rel, "worst_abs": float(np.nanmax(max_abs)),
+            "worst_rel": float(np.nanmax(max_rel)), "worst": (int(worst[0]), int(worst[1]))}
+
+
 PREDICT_SLAB = int(__import__("os").environ.get("MATTEN_PREDICT_SLAB", "1024"))   # structures packed per slab
 # (a small first slab with 4x growth -- device started after 0.3 ms of packing -- was measured in round 5 and dropped: every
 # forward costs the host ~1 ms (graph-build read-back + ~45 launches), so three forwards instead of one gave back what the
