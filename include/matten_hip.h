@@ -315,6 +315,14 @@ int matten_species_linear_rows(const float* x, int64_t d_in, const int32_t* orde
                                const float* wp, int64_t w_stride, const int32_t* segs, int64_t n_segs, int64_t d_out,
                                const float* add, int64_t add_ld, int64_t n_rows, float* out, matten_stream_t stream);
 
+/* The launchers' own thresholds (the constants they branch on), for routing checks on the host: */
+int matten_species_linear_walk_all_blocks(void);      /* cdiv(n_rows, 64) + n_species (0 for a plain linear) from which ONE
+                                                         workgroup walks all irrep blocks; below it one block per blockIdx.y */
+int64_t matten_species_linear_lds_w_floats(void);     /* largest w_stride (rounded up to 4) whose table is kept in LDS; above
+                                                         it the A operand is read from global memory */
+int64_t matten_species_linear_rows_lds_bytes(void);   /* matten_species_linear_rows refuses layouts above this many bytes:
+                                                         4 * (16 * (d_in | 1) + round4(w_stride) + 8 * n_segs) */
+
 /* ------------------------------------------------------------------------------------------
  * e3nn Gate (nn/utils.py:134-140,158-159 <- nn/conv.py:209) fused with e3nn BatchNorm in eval
  * mode (nn/utils.py:418,432-433 <- nn/conv.py:211).

@@ -72,6 +72,9 @@ SIGNATURES = {
     "matten_radial_h_scale_deep": (c_int, [P, P, c_int, c_int, c_float, c_float, c_float, P, P]),
     "matten_split_a_tiles": (c_int, [P, c_int64, P, c_int64, P, P, P, P]),
     "matten_gather_scale": (c_int, [P, P, P, c_int64, c_int64, c_int, P, P, P, P]),
+    "matten_species_linear_walk_all_blocks": (c_int, []),
+    "matten_species_linear_lds_w_floats": (c_int64, []),
+    "matten_species_linear_rows_lds_bytes": (c_int64, []),
     "matten_species_linear_wgrad_scratch_floats": (c_int64, [c_int64, c_int64, c_int64]),
     "matten_tp_backward": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, c_int64, P, P, P, c_int64, c_float, P, c_int64, P, P, c_int64,
                                    P, P, c_int64, c_int, P]),

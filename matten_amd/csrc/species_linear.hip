@@ -45,6 +45,10 @@ constexpr int NACC = 9;       // accumulator tiles: max(NVT * d)
 constexpr int XS_RS = 16 * NB + 4;  // LDS row stride of the transpose tile (== 4 mod 32: conflict-free b128)
 constexpr uint32_t SRD_WORD3 = 0x00020000u;
 constexpr int64_t SRD_SPAN = ((int64_t)1 << 32) - (1 << 20);  // addressable bytes per descriptor, with slack
+constexpr int SL_WALK_ALL_BLOCKS = 512;   // workgroups (row tiles + species) from which one workgroup walks ALL irrep blocks
+constexpr size_t SL_LDS_BYTES = 160 * 1024;                                    // dynamic LDS the kernel may ask for
+constexpr size_t SL_LDS_TILES = sizeof(float) * SL_WAVES * SL_ROWS * XS_RS;    // the four waves' transpose tiles
+constexpr int64_t SL_LDS_W_FLOATS = (int64_t)((SL_LDS_BYTES - SL_LDS_TILES) / sizeof(float));   // largest w_stride kept in LDS
 typedef float sl_f32x4 __attribute__((ext_vector_type(4)));
 typedef int sl_i32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(4))) sl_f4u {
@@ -68,8 +72,10 @@ namespace {
 // (load - MFMA - scratch_store).  With the builtin the compiler pads the MFMA -> store hazard itself but shuffles
 // tuples; with inline asm its hazard recogniser is blind and the scratch store reads a result that is not there yet.
 // The file is therefore built with -mllvm -simplifycfg-sink-common=false (Makefile): every accumulator stays in
-// registers.  The tied form below leaves the register allocator nothing to move; it passes the full sweep
-// (tests/test_gpu_parity.py::test_species_linear_shape_sweep, tools/sl_fuzz.py).
+// registers.  The tied form below leaves the register allocator nothing to move; it passes the per-block tests that
+// force this kernel (tests/test_gpu_species_linear.py: output tiles, input chunks, the cross-block cursor walk, exact
+// integer twins; the older test_gpu_parity.py::test_species_linear_shape_sweep now mostly reaches the rows kernel) and
+// tools/sl_fuzz.py.
 // The hazard recogniser does not look inside inline asm, hence the explicit wait states: s_nop 1 in front (VALU
 // write of an operand -> MFMA read) and mfma_drain() after the last MFMA of every straight-line group, before
 // anything else may read, copy or store an accumulator.
@@ -445,20 +451,20 @@ extern "C" int matten_species_linear(const float* x, int64_t d_in, const int32_t
     if (!add) add_ld = d_out;
     if ((order == nullptr) != (seg == nullptr)) return MATTEN_EINVAL;
     if (!order && n_species != 1) return MATTEN_EINVAL;
-    const size_t lds_tiles = sizeof(float) * SL_WAVES * SL_ROWS * XS_RS;
-    const bool w_lds = lds_tiles + sizeof(float) * (size_t)((w_stride + 3) & ~3) <= 160 * 1024;
+    const size_t lds_tiles = SL_LDS_TILES;
+    const bool w_lds = ((w_stride + 3) & ~(int64_t)3) <= SL_LDS_W_FLOATS;
     const size_t lds = lds_tiles + (w_lds ? sizeof(float) * (size_t)((w_stride + 3) & ~3) : 0);
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute((const void*)species_linear_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
+                                (int)SL_LDS_BYTES) != hipSuccess)
             return MATTEN_ELAUNCH;
         attr_set = true;
     }
     constexpr int BR = SL_ROWS * SL_WAVES;
     const int64_t blocks = matten_cdiv(n_rows, BR) + (order ? n_species : 0);
     // few rows: spread the irrep blocks over blockIdx.y so the chip still sees enough waves
-    const int segs_per_block = blocks >= 512 ? (int)n_segs : 1;
+    const int segs_per_block = blocks >= SL_WALK_ALL_BLOCKS ? (int)n_segs : 1;
     dim3 grid((unsigned)blocks, (unsigned)matten_cdiv(n_segs, segs_per_block));
     if (w_lds)
         species_linear_kernel<true><<<grid, SL_WAVES * 64, lds, stream>>>(
@@ -471,3 +477,7 @@ extern "C" int matten_species_linear(const float* x, int64_t d_in, const int32_t
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }
+
+// the launcher's own thresholds, for the planner-side routing checks and the tests (tests/species_linear_cases.py)
+extern "C" int matten_species_linear_walk_all_blocks(void) { return SL_WALK_ALL_BLOCKS; }
+extern "C" int64_t matten_species_linear_lds_w_floats(void) { return SL_LDS_W_FLOATS; }

@@ -9,7 +9,10 @@
 // four waves split the (irrep block, 16-channel output tile) items round-robin.  An item is a plain K loop of
 // v_mfma_f32_16x16x4_f32 with rows as N, output channels as M, input channels as the contraction, both operands
 // read from LDS; the addend and the result go straight from / to memory in the D-fragment layout (4 d contiguous
-// floats per lane).  Same arithmetic and summation order per output element as matten_species_linear.
+// floats per lane).  Same arithmetic as matten_species_linear but NOT the same summation order per output element: a
+// matrix instruction here contracts the four channels u = k0 + g, there u = 16 st + 4 g + j, so the two kernels' fp32
+// sums may differ in the last bits (55 of the 123 shapes of tests/test_gpu_species_linear.py that fit both kernels, by
+// at most 1.8e-7 of the output's maximum); each is exact on integer inputs and within the same bound of fp64.
 #include "common.h"
 
 namespace {
@@ -28,6 +31,7 @@ constexpr int WAVES = 4;
 #endif
 constexpr int TPB = SLR_TPB;  // 16-row tiles per workgroup: the weight fill and the species look-up are paid once for 32 rows
                               // (2 and 4 measure the same, 3 and 6 are 20 % slower: tools/slr_tpb_ab.sh)
+constexpr size_t SLR_LDS_BYTES = 64 * 1024;   // rows + weights + segment table of one workgroup
 
 // accumulate-in-place MFMA through inline asm with explicit wait states, see species_linear.hip
 __device__ __forceinline__ void mfma_16x16x4(f32x4& acc, float a, float b) {
@@ -271,7 +275,7 @@ extern "C" int matten_species_linear_rows(const float* x, int64_t d_in, const in
     const int xs_stride = (int)(d_in | 1);  // odd row stride: the 16 rows of a column fall into 16 different LDS banks
     size_t lds = sizeof(float) * ((size_t)ROWS * xs_stride + (size_t)((w_stride + 3) & ~3) + 8 * (size_t)n_segs);
     lds = lds < sizeof(int) * (WAVES * 64 + 4) ? sizeof(int) * (WAVES * 64 + 4) : lds;   // (the species look-up's scratch)
-    if (lds > 64 * 1024) return MATTEN_EINVAL;  // rows or weight table too large for this variant: use matten_species_linear
+    if (lds > SLR_LDS_BYTES) return MATTEN_EINVAL;  // rows or weight table too large for this variant: use matten_species_linear
     const int64_t blocks = matten_cdiv(n_rows, TPB * ROWS) + (order ? n_species : 0);
     species_linear_rows_kernel<<<(unsigned)blocks, WAVES * 64, lds, stream>>>(
         x, (int)d_in, order, seg, (int)n_species, wp, (int)w_stride, (const LinSeg*)segs, (int)n_segs, (int)d_out, add,
@@ -279,3 +283,5 @@ extern "C" int matten_species_linear_rows(const float* x, int64_t d_in, const in
     MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }
+
+extern "C" int64_t matten_species_linear_rows_lds_bytes(void) { return (int64_t)SLR_LDS_BYTES; }   // the limit tested above

@@ -734,6 +734,15 @@ def agg_linear_gate(agg, species_order, wtab, io_table, blocks, d_out: int, cmet
 _SL_ROWS_LDS_BYTES = 52 * 1024  # three workgroups of matten_species_linear_rows per CU
 
 
+def species_linear_route(d_in: int, w_stride: int, n_items_per_pass) -> str:
+    """"rows" (matten_species_linear_rows: rows and weights resident in LDS) or "stream" (matten_species_linear) for a
+    call with rows of d_in floats, w_stride packed weights per species and segment tables of n_items_per_pass items (one
+    entry per pass).  Pure: the MATTEN_SL_ROWS override and species_linear's variant= argument act on top of it."""
+    n_items = list(n_items_per_pass)
+    fits = len(n_items) == 1 and 4 * (16 * (d_in | 1) + w_stride + 8 * n_items[0] + 4) <= _SL_ROWS_LDS_BYTES
+    return "rows" if fits else "stream"
+
+
 def species_linear(x, species_order, wp, w_stride: int, item_tables, d_out: int, add=None,
                    fully_covered: bool = True, variant: Optional[str] = None) -> torch.Tensor:
     """species_order: None (plain linear) or (order[N] i32, seg[S+1] i32) = nodes sorted by species.
@@ -755,7 +764,7 @@ def species_linear(x, species_order, wp, w_stride: int, item_tables, d_out: int,
     else:  # irreps without an input path stay zero (e3nn output_mask semantics)
         out = cur_add.clone() if cur_add is not None else torch.zeros(n_rows, d_out, dtype=torch.float32, device=x.device)
     # short rows (node features: lin1 / self-connection, first-layer lin2, read-out): rows and weights resident in LDS
-    rows_fits = len(item_tables) == 1 and 4 * (16 * (d_in | 1) + w_stride + 8 * item_tables[0].shape[0] + 4) <= _SL_ROWS_LDS_BYTES
+    rows_fits = species_linear_route(d_in, w_stride, [t.shape[0] for t in item_tables]) == "rows"
     rows_variant = rows_fits and os.environ.get("MATTEN_SL_ROWS", "1") != "0"
     if variant is not None:
         rows_variant = rows_fits and variant == "rows"

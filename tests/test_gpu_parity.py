@@ -962,7 +962,14 @@ def test_species_linear_shape_sweep():
     model, output multiplicities across the 16/32-channel tile boundaries (with and without the streamed addend),
     input multiplicities across the 16-channel step and 160-float window boundaries, all l <= 4, ragged species
     groups.  Reference: the oracle's FullyConnectedTensorProduct(x, one_hot(species)) with the same flat weights, in
-    fp64 (not the plan's own segment tables: the plan is part of what is under test)."""
+    fp64 (not the plan's own segment tables: the plan is part of what is under test).
+
+    Which kernel each family reaches under today's routing (ops.species_linear_route; recomputed on the CPU by
+    test_species_linear_host.py::test_shape_sweep_routing_is_what_its_docstring_records): the output-multiplicity sweep
+    runs on the ROWS kernel in all 159 cases, the input-multiplicity sweep on the rows kernel in 99 cases and on the
+    streaming kernel in 16 (mi >= 159 at l >= 2, mi = 321 at l >= 1), the two "big W" cases on the streaming kernel with
+    the A operand in global memory.  The streaming kernel's tile boundaries, chunk boundaries and cross-block walk are
+    forced in tests/test_gpu_species_linear.py."""
     from matten_amd.model_factory.tfn_scalar_tensor import create_model
     from matten_amd.data import synthetic
 
