@@ -707,6 +707,62 @@ int matten_irreps_average(const void* x, int is_fp64, int64_t n, int64_t dim, co
                           const int32_t* flags, int64_t G, const int64_t* op_ptr, const int32_t* op_idx,
                           const double* weights, int transpose, void* out, double* deviation, matten_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Finding a crystal's symmetry (csrc/spacegroup.hip; the reference has no search of its own: it takes space groups from
+ * pymatgen on the host).  fp64.  Per crystal: L = the cell (rows = lattice vectors), G = L L^T, a_max = the longest lattice
+ * vector, f = pos L^-1, symprec a length in the units of the positions.  INTEGRATION.md, "Finding a crystal's symmetry",
+ * has the definitions in full; matten_amd.symmetry.find_symmetry_host restates them in numpy.
+ * matten_lattice_group:
+ *   N_out [B,48,9] int8: the integer matrices N with |(N G N^T)_ij - G_ij| <= 2 symprec a_max for every entry, the identity
+ *   first, then ascending in the nine entries row-major; n_lat [B] their number; slots from n_lat on are zero.  The rows of
+ *   N are searched among |n_j| <= m_j = floor((a_max + symprec) |a*_j|), a*_j = column j of L^-1.
+ *   flags [B]: MATTEN_SYM_NOT_FINITE (a non-finite entry or |det L| <= 1e-12), MATTEN_SYM_RANGE (an m_j > 4: hand in a
+ *   reduced cell), MATTEN_SYM_AMBIGUOUS (more than 48 matrices pass: symprec is too large); each gives the identity only.
+ * matten_crystal_symmetry:
+ *   pos [N_total,3], cell [B,9], Z [N_total] int64, ptr [B+1] int64, pbc [B,3] bytes or NULL (all periodic), (N_in, n_lat,
+ *   lat_flags) of matten_lattice_group at the same symprec.  Pivot atom p = the lowest-indexed atom of the species with the
+ *   fewest atoms (ties: the smallest Z).  For lattice operation N and pivot-species atom j (ascending) the translation
+ *   t = f_j - f_p N is accepted when every atom i has an atom k of its species with |(d - round(d)) L| <= symprec,
+ *   d = f_i N + t - f_k; the first accepted j represents N.  Fractional rows transform as f' = f N + t, positions as
+ *   r' = M r + t L with M = the polar factor of (L^-1 N L)^T.
+ *   rot [B,48,9] (M), rot_int [B,48,9] int8 (N), trans [B,48,3] (t, wrapped to [-1/2, 1/2]), n_rot [B]: the accepted
+ *   operations in lattice order; absent slots are zero.  src [48,N_total] int32: src[g,k] = the atom (global index) whose
+ *   image under operation g lands on atom k; -1 in absent slots.  n_trans [B], ttrans [B,max_trans,3], tsrc
+ *   [max_trans,N_total]: the same for the pure translations (N = identity, every accepted j, j = p first), of which the
+ *   first max_trans are kept; n_trans counts all.
+ *   flags [B]: lat_flags, and MATTEN_SYM_NOT_FINITE (a non-finite coordinate, no atoms), MATTEN_SYM_TOO_LARGE (more than
+ *   MATTEN_SYM_MAX_ATOMS atoms), MATTEN_SYM_AMBIGUOUS (an accepted operation images two atoms onto one, or one atom has two
+ *   images within symprec), MATTEN_SYM_NOT_PERIODIC (an open axis): each gives n_rot = n_trans = 1 and identity maps.
+ *   MATTEN_SYM_TRUNC: n_trans > max_trans, the point group is complete, the translation list is not.
+ * matten_irreps_average_atoms:
+ *   out[k] = (1 / n_ops[b]) sum_{g < n_ops[b]} D(R_{b,g}) x[src[g,k]], b = row_struct[k], in the order of g; x, out [n,dim]
+ *   fp32 or fp64 (out must not be x), layout as for matten_irreps_rotate, (D, flags) the table of matten_wigner_d over the
+ *   B * G_cap rotations [B,G_cap,9], or D = NULL for identity blocks (the average over pure translations); src [G_cap,n].
+ *   A source that is -1, outside [0, n) or of another crystal, a flagged D row (bit 0 or 1), an n_ops[b] outside 1..G_cap
+ *   or a row_struct[k] outside [0, B): the row is NaN.
+ * All: no atomics, no allocation, nothing read back, one writer per output word: bitwise reproducible and capturable.
+ * MATTEN_EINVAL without a launch: a NULL required pointer, a negative count, max_trans < 1, symprec not positive and finite,
+ * K > 16, a bad layout row, G_cap < 1, out == x.
+ * ------------------------------------------------------------------------------------------ */
+#define MATTEN_SYM_MAX_OPS 48
+#define MATTEN_SYM_MAX_ATOMS 1024
+#define MATTEN_SYM_NOT_FINITE 1
+#define MATTEN_SYM_RANGE 2
+#define MATTEN_SYM_TOO_LARGE 4
+#define MATTEN_SYM_AMBIGUOUS 8
+#define MATTEN_SYM_TRUNC 16
+#define MATTEN_SYM_NOT_PERIODIC 32
+int matten_lattice_group(const double* cell, int64_t B, double symprec, int8_t* N_out, int32_t* n_lat, int32_t* flags,
+                         matten_stream_t stream);
+int matten_crystal_symmetry(const double* pos, const double* cell, const int64_t* Z, const int64_t* ptr, const uint8_t* pbc,
+                            int64_t B, int64_t N_total, double symprec, int max_trans, const int8_t* N_in,
+                            const int32_t* n_lat, const int32_t* lat_flags, double* rot, int8_t* rot_int, double* trans,
+                            int32_t* n_rot, int32_t* src, int32_t* n_trans, double* ttrans, int32_t* tsrc, int32_t* flags,
+                            matten_stream_t stream);
+int matten_irreps_average_atoms(const void* x, int is_fp64, int64_t n, int64_t dim, const int32_t* layout, int K,
+                                const double* D, const int32_t* flags, int64_t B, int64_t G_cap, const int32_t* n_ops,
+                                const int32_t* row_struct, const int32_t* src, void* out, matten_stream_t stream);
+
 
 /* ==========================================================================================
  * Adjoint (backward) operators for the training step (reference: autograd through

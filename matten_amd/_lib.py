@@ -149,6 +149,10 @@ SIGNATURES = {
     "matten_wigner_d": (c_int, [P, c_int64, c_int, ctypes.c_double, P, P, P]),
     "matten_irreps_rotate": (c_int, [P, c_int, c_int64, c_int64, P, c_int, P, P, P, c_int64, c_int, P, P]),
     "matten_irreps_average": (c_int, [P, c_int, c_int64, c_int64, P, c_int, P, P, c_int64, P, P, P, c_int, P, P, P]),
+    "matten_lattice_group": (c_int, [P, c_int64, ctypes.c_double, P, P, P, P]),
+    "matten_crystal_symmetry": (c_int, [P, P, P, P, P, c_int64, c_int64, ctypes.c_double, c_int, P, P, P, P, P, P, P, P, P, P, P,
+                                        P, P]),
+    "matten_irreps_average_atoms": (c_int, [P, c_int, c_int64, c_int64, P, c_int, P, P, c_int64, c_int64, P, P, P, P, P]),
     "matten_batch_gather_lds_rows": (c_int, []),
     "matten_batch_gather_max_streams": (c_int, []),
     "matten_batch_gather": (c_int, [P, c_int64, P, c_int64, c_int64, c_int64, P]),

@@ -3,6 +3,8 @@
 //   rot_rotate_kernel    : out[r] = D(M_index[r]) x[r] (or D^T), one irrep copy of one row per thread
 //   rot_average_kernel   : out[r] = sum_j w_j D(M_op_idx[j]) x[r] / sum_j w_j over the row's list of operations
 //   rot_deviation_kernel : |x[r] - out[r]| / |x[r]| per row
+//   rot_average_atoms_kernel : out[k] = mean_g D(R_{b,g}) x[src[g,k]]: per-atom rows over their crystal's operations, sources
+//                          gathered through the atom permutation of csrc/spacegroup.hip
 // The reference rotates in the Cartesian basis on the host (tests/model/test_tfn_tensor.py:98-139, a rank-4 einsum after
 // utils.py:110-133 to_cartesian); here the rows stay in the irreps basis on the device.
 // D^l comes from the harmonics themselves: Y_l(R p_k) = D^l Y_l(p_k) over 2l+1 fixed unit vectors p_k, so
@@ -370,6 +372,70 @@ __global__ void __launch_bounds__(ROT_THREADS) rot_average_kernel(const T* x, in
     }
 }
 
+// out[k] = (1 / n) sum_g s D(R_{b,g}) x[src[g,k]] for one block of degree L of atom row k of crystal b, g = 0 .. n-1 in order
+template <typename T, int L>
+__device__ __forceinline__ void rot_average_atoms_block(const T* x, int64_t dim, int off, T* out, const double* __restrict__ D,
+                                                        const int32_t* __restrict__ flags, int par, int64_t n_rows, int64_t k,
+                                                        int32_t b, int64_t n_ops, int64_t G_cap,
+                                                        const int32_t* __restrict__ row_struct, const int32_t* __restrict__ src) {
+    constexpr int N = 2 * L + 1;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    double xin[N], acc[N], y[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) acc[i] = 0.0;
+    bool bad = n_ops < 1 || n_ops > G_cap;
+    const int64_t G = bad ? 0 : n_ops;
+    for (int64_t g = 0; g < G; ++g) {
+        const int64_t s = src[g * n_rows + k];
+        if (s < 0 || s >= n_rows || row_struct[s] != b) {   // no source, or one of another crystal: nothing is read
+            bad = true;
+            continue;
+        }
+#pragma unroll
+        for (int j = 0; j < N; ++j) xin[j] = (double)x[s * dim + off + j];
+        if (D) {
+            const int64_t r = (int64_t)b * G_cap + g;
+            const int32_t f = flags[r];
+            bad = bad || (f & 3) != 0;
+            rot_matvec<L>(D + r * ROT_STRIDE + rot_block_offset(L), xin, (par < 0 && (f & 4)) ? -1.0 : 1.0, 0, y);
+        } else {
+#pragma unroll
+            for (int i = 0; i < N; ++i) y[i] = xin[i];
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) acc[i] += y[i];
+    }
+    const double count = (double)n_ops;
+#pragma unroll
+    for (int i = 0; i < N; ++i) out[i] = (T)(bad ? nan : acc[i] / count);
+}
+
+// the grid of rot_rotate_kernel: rows (b / C) * ROT_THREADS .., irrep copy b % C.  out must not be x (rows read their neighbours').
+template <typename T>
+__global__ void __launch_bounds__(ROT_THREADS) rot_average_atoms_kernel(const T* __restrict__ x, int64_t n, int64_t dim, RotLayout lay,
+                                                                        int K, int C, const double* __restrict__ D,
+                                                                        const int32_t* __restrict__ flags, int64_t B, int64_t G_cap,
+                                                                        const int32_t* __restrict__ n_ops,
+                                                                        const int32_t* __restrict__ row_struct,
+                                                                        const int32_t* __restrict__ src, T* __restrict__ out) {
+    const int c = (int)(blockIdx.x % (unsigned)C);
+    const int64_t r = (int64_t)(blockIdx.x / (unsigned)C) * ROT_THREADS + threadIdx.x;
+    if (r >= n) return;
+    int off, l, par;
+    rot_find_copy(lay, K, c, off, l, par);
+    const int32_t b = row_struct[r];
+    const bool inside = b >= 0 && b < B;                   // a row of no crystal comes back NaN
+    const int64_t ops = inside ? (int64_t)n_ops[b] : 0;
+    T* outr = out + r * dim + off;
+    switch (l) {
+        case 0: rot_average_atoms_block<T, 0>(x, dim, off, outr, D, flags, par, n, r, b, ops, G_cap, row_struct, src); break;
+        case 1: rot_average_atoms_block<T, 1>(x, dim, off, outr, D, flags, par, n, r, b, ops, G_cap, row_struct, src); break;
+        case 2: rot_average_atoms_block<T, 2>(x, dim, off, outr, D, flags, par, n, r, b, ops, G_cap, row_struct, src); break;
+        case 3: rot_average_atoms_block<T, 3>(x, dim, off, outr, D, flags, par, n, r, b, ops, G_cap, row_struct, src); break;
+        default: rot_average_atoms_block<T, 4>(x, dim, off, outr, D, flags, par, n, r, b, ops, G_cap, row_struct, src); break;
+    }
+}
+
 // one row per thread, columns in order; reads out as stored (rounded once for fp32 rows)
 template <typename T>
 __global__ void __launch_bounds__(ROT_THREADS) rot_deviation_kernel(const T* __restrict__ x, const T* __restrict__ out, int64_t n,
@@ -481,5 +547,29 @@ extern "C" int matten_irreps_average(const void* x, int is_fp64, int64_t n, int6
         else rot_deviation_kernel<float><<<grid, ROT_THREADS, 0, stream>>>((const float*)x, (const float*)out, n, dim, deviation);
         MATTEN_LAUNCH_CHECK();
     }
+    return MATTEN_OK;
+}
+
+extern "C" int matten_irreps_average_atoms(const void* x, int is_fp64, int64_t n, int64_t dim, const int32_t* layout, int K,
+                                           const double* D, const int32_t* flags, int64_t B, int64_t G_cap, const int32_t* n_ops,
+                                           const int32_t* row_struct, const int32_t* src, void* out, matten_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n < 0 || dim < 0 || K < 0 || K > ROT_MAX_K || B < 0 || G_cap < 1) return MATTEN_EINVAL;
+    if (is_fp64 != 0 && is_fp64 != 1) return MATTEN_EINVAL;
+    if (K > 0 && !layout) return MATTEN_EINVAL;
+    RotLayout lay;
+    int64_t C;
+    if (!rot_layout_ok(layout, K, dim, lay, C)) return MATTEN_EINVAL;
+    if (!x || !out || x == out || !n_ops || !row_struct || !src || (D && !flags)) return MATTEN_EINVAL;
+    if (n > (int64_t)0x7fffffff || !rot_grid_ok(n, C > 0 ? C : 1)) return MATTEN_EINVAL;   // sources are int32 row numbers
+    if (n == 0 || C == 0) return MATTEN_OK;
+    const unsigned grid = (unsigned)(matten_cdiv(n, ROT_THREADS) * C);
+    if (is_fp64)
+        rot_average_atoms_kernel<double><<<grid, ROT_THREADS, 0, stream>>>((const double*)x, n, dim, lay, K, (int)C, D, flags, B, G_cap,
+                                                                           n_ops, row_struct, src, (double*)out);
+    else
+        rot_average_atoms_kernel<float><<<grid, ROT_THREADS, 0, stream>>>((const float*)x, n, dim, lay, K, (int)C, D, flags, B, G_cap,
+                                                                          n_ops, row_struct, src, (float*)out);
+    MATTEN_LAUNCH_CHECK();
     return MATTEN_OK;
 }

@@ -1066,6 +1066,102 @@ def irreps_average(x, layout, D, flags, op_ptr, op_idx, weights=None, transpose:
     return out, deviation
 
 
+SYM_MAX_OPS = 48        # operations per crystal (MATTEN_SYM_MAX_OPS): the order of the largest point group
+SYM_MAX_ATOMS = 1024    # atoms per crystal that the symmetry search takes (MATTEN_SYM_MAX_ATOMS)
+
+
+def _sym_out(out, specs, dev):
+    """the output buffers of a symmetry entry: fresh ones, or the caller's ``out`` tuple checked against (shape, dtype)"""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in specs)
+    if len(out) != len(specs):
+        raise ValueError(f"out: expected {len(specs)} tensors")
+    for t, (shape, dtype) in zip(out, specs):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != dev \
+                or not t.is_contiguous():
+            raise ValueError(f"out: expected a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}")
+    return tuple(out)
+
+
+def lattice_group(cell, symprec: float = 1e-3, out=None):
+    """cell [B,3,3] fp64 -> (N [B,48,9] int8, n_lat [B] int32, flags [B] int32): the integer matrices that keep each
+    cell's metric to ``symprec``, the identity first, then in ascending order (matten_lattice_group)"""
+    lib = _lib.load()
+    cell = _need(cell, torch.float64, "cell")
+    if cell.dim() != 3 or cell.shape[1:] != (3, 3):
+        raise ValueError(f"cell: expected [B,3,3], got {tuple(cell.shape)}")
+    B = cell.shape[0]
+    N, n_lat, flags = _sym_out(out, (((B, SYM_MAX_OPS, 9), torch.int8), ((B,), torch.int32), ((B,), torch.int32)), cell.device)
+    if B:
+        _lib.check(lib.matten_lattice_group(_ptr(cell), B, float(symprec), _ptr(N), _ptr(n_lat), _ptr(flags), _stream()),
+                   "matten_lattice_group")
+    return N, n_lat, flags
+
+
+def crystal_symmetry(pos, cell, Z, ptr, lattice, pbc=None, symprec: float = 1e-3, max_trans: int = 64, out=None):
+    """The operations of every crystal of a packed batch (pos [N,3] fp64, cell [B,3,3] fp64, Z [N] int64, ptr [B+1] int64,
+    pbc [B,3] uint8 or None) among the lattice operations ``lattice`` = ``lattice_group(cell, symprec)`` ->
+    (rot [B,48,9] fp64, rot_int [B,48,9] int8, trans [B,48,3] fp64, n_rot [B] int32, src [48,N] int32, n_trans [B] int32,
+    ttrans [B,max_trans,3] fp64, tsrc [max_trans,N] int32, flags [B] int32) (matten_crystal_symmetry)"""
+    lib = _lib.load()
+    pos, cell = _need(pos, torch.float64, "pos"), _need(cell, torch.float64, "cell")
+    Z, ptr = _need(Z, torch.int64, "Z"), _need(ptr, torch.int64, "ptr")
+    N_in, n_lat, lat_flags = (_need(lattice[0], torch.int8, "lattice N"), _need(lattice[1], torch.int32, "lattice n_lat"),
+                              _need(lattice[2], torch.int32, "lattice flags"))
+    B, n = cell.shape[0], pos.shape[0]
+    if pos.shape != (n, 3) or cell.shape != (B, 3, 3) or Z.shape != (n,) or ptr.shape != (B + 1,):
+        raise ValueError("expected pos [N,3], cell [B,3,3], Z [N], ptr [B+1]")
+    if N_in.shape != (B, SYM_MAX_OPS, 9) or n_lat.shape != (B,) or lat_flags.shape != (B,):
+        raise ValueError("lattice: expected the (N [B,48,9], n_lat [B], flags [B]) of lattice_group")
+    if pbc is not None:
+        pbc = _need(pbc, torch.uint8, "pbc")
+        if pbc.shape != (B, 3):
+            raise ValueError(f"pbc: expected [{B},3], got {tuple(pbc.shape)}")
+    max_trans = int(max_trans)
+    if max_trans < 1:
+        raise ValueError("max_trans: expected at least 1")
+    f64, i32 = torch.float64, torch.int32
+    specs = (((B, SYM_MAX_OPS, 9), f64), ((B, SYM_MAX_OPS, 9), torch.int8), ((B, SYM_MAX_OPS, 3), f64), ((B,), i32),
+             ((SYM_MAX_OPS, n), i32), ((B,), i32), ((B, max_trans, 3), f64), ((max_trans, n), i32), ((B,), i32))
+    bufs = _sym_out(out, specs, pos.device)
+    if B and n:
+        _lib.check(lib.matten_crystal_symmetry(_ptr(pos), _ptr(cell), _ptr(Z), _ptr(ptr), _ptr(pbc), B, n, float(symprec), max_trans,
+                                               _ptr(N_in), _ptr(n_lat), _ptr(lat_flags), *[_ptr(t) for t in bufs], _stream()),
+                   "matten_crystal_symmetry")
+    return bufs
+
+
+def irreps_average_atoms(x, layout, D, flags, n_ops, row_struct, src, out=None):
+    """out[k] = (1 / n_ops[b]) sum_{g < n_ops[b]} D(R_{b,g}) x[src[g,k]], b = row_struct[k]: per-atom rows averaged over their
+    crystal's operations.  x [n,dim] fp32 or fp64, (D [B*G_cap,165], flags) of ``wigner_d`` over the rotations [B,G_cap,3,3]
+    or D = None for identity blocks, n_ops [B] int32, row_struct [n] int32, src [G_cap,n] int32 (matten_irreps_average_atoms)"""
+    lib = _lib.load()
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.float64):
+        raise TypeError("x: expected an fp32 or fp64 tensor")
+    x = _need(x, x.dtype, "x")
+    if x.dim() != 2:
+        raise ValueError(f"x: expected [n,dim], got {tuple(x.shape)}")
+    layout = np.ascontiguousarray(layout, dtype=np.int32).reshape(-1, 4)
+    n_ops, row_struct, src = _need(n_ops, torch.int32, "n_ops"), _need(row_struct, torch.int32, "row_struct"), _need(src, torch.int32, "src")
+    n, B = x.shape[0], n_ops.shape[0]
+    if n_ops.dim() != 1 or row_struct.shape != (n,) or src.dim() != 2 or src.shape[1] != n or src.shape[0] < 1:
+        raise ValueError("expected n_ops [B], row_struct [n] and src [G_cap,n]")
+    G_cap = src.shape[0]
+    if D is not None:
+        D, flags = _need(D, torch.float64, "D"), _need(flags, torch.int32, "flags")
+        if D.shape != (B * G_cap, WIGNER_STRIDE) or flags.shape != (B * G_cap,):
+            raise ValueError(f"expected D [{B * G_cap},165] and flags [{B * G_cap}], got {tuple(D.shape)}, {tuple(flags.shape)}")
+    out = _irreps_out(x, out)
+    if out.data_ptr() == x.data_ptr() and n:
+        raise ValueError("out: must not be x (rows are gathered from other atoms)")
+    if n:
+        _lib.check(lib.matten_irreps_average_atoms(_ptr(x), int(x.dtype == torch.float64), n, x.shape[1], layout.ctypes.data,
+                                                   len(layout), _ptr(D), _ptr(flags) if D is not None else None, B, G_cap,
+                                                   _ptr(n_ops), _ptr(row_struct), _ptr(src), _ptr(out), _stream()),
+                   "matten_irreps_average_atoms")
+    return out
+
+
 def _kelvin_rows(voigt, flags):
     voigt = _need(voigt, torch.float64, "voigt")
     flags = _need(flags, torch.int32, "flags")

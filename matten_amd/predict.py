@@ -569,6 +569,54 @@ def equivariance_report(model, structures, rotations=None, n_random: int = 2, se
             "worst_rel": float(np.nanmax(max_rel)), "worst": (int(worst[0]), int(worst[1]))}
 
 
+def symmetry_report(model, structures, symprec: float = 1e-3, r_cut: float = None, formula: str = "ijkl=jikl=klij",
+                    is_atomic_tensor: bool = False, batch_size: int = 200) -> Dict[str, Any]:
+    """Does this model's prediction have the symmetry of its crystal?  Every structure is predicted (the forwards of
+    ``evaluate`` / ``evaluate_atomic``: ``collate`` of host graphs, eval mode, no grad), its symmetry is found on the device
+    (``symmetry.find_symmetry`` at ``symprec``) and the prediction is compared with its symmetrised self in the irreps basis:
+    a crystal-level tensor with the average over the point group (``CrystalSymmetry.average_crystal_rows``), per-atom
+    tensors with ``symmetry.symmetrize_atoms`` (the worst atom of each structure).  One read-back at the end.
+    -> {"order" [S], "n_trans" [S], "flags" [S] (symmetry.SYM_*), "deviation" [S] = |y - P y| / |y|, "worst" = the largest
+    deviation, "worst_structure", "predictions" (the device rows in the irreps basis), "symmetry" (the CrystalSymmetry)}."""
+    from .symmetry import find_symmetry, irreps_of, symmetrize_atoms
+
+    structures = list(structures) if isinstance(structures, (list, tuple)) else [structures]
+    if not structures:
+        raise ValueError("symmetry_report: no structure")
+    if r_cut is None:
+        r_cut = float(model.hparams["backbone_hparams"]["radial_basis_end"])
+    check_species(model, structures)
+    device = model.device
+    name = list(model.tasks.keys())[0]
+    converter = _converter(formula)
+    dim = irreps_of(formula).dim
+    cartesian_out = getattr(model, "to_cartesian", None) is not None
+    fields = [_fields(s) for s in structures]
+    sym = find_symmetry([dict(f) for f in fields], symprec=symprec, device=device)
+    graphs = [crystal_graph(f["cart_coords"], f["lattice"], f["atomic_numbers"], r_cut, pbc=f["pbc"]) for f in fields]
+    model.eval()
+    rows = []
+    with torch.no_grad():
+        for lo in range(0, len(graphs), batch_size):
+            preds, _ = model(collate(graphs[lo:lo + batch_size], device=device), task_name=name)
+            p = preds[name]
+            if cartesian_out:
+                p = converter.from_cartesian(p)
+            rows.append(p.reshape(-1, dim))
+        y = torch.cat(rows).contiguous()
+        if is_atomic_tensor:
+            _, per_atom = symmetrize_atoms(y, formula, sym)
+            deviation = torch.zeros(len(structures), dtype=torch.float64, device=device)
+            deviation = deviation.scatter_reduce(0, sym.row_struct.long(), per_atom, "amax", include_self=False)
+        else:
+            deviation = sym.average_crystal_rows(y, formula)[1]
+        table = torch.stack([sym.n_rot.double(), sym.n_trans.double(), sym.flags.double(), deviation]).cpu().numpy()   # the read-back
+    dev = table[3]
+    worst = int(np.nanargmax(dev)) if np.isfinite(dev).any() else 0
+    return {"order": table[0].astype(np.int64), "n_trans": table[1].astype(np.int64), "flags": table[2].astype(np.int64),
+            "deviation": dev, "worst": float(dev[worst]), "worst_structure": worst, "predictions": y, "symmetry": sym}
+
+
 PREDICT_SLAB = int(__import__("os").environ.get("MATTEN_PREDICT_SLAB", "1024"))   # structures packed per slab
 # (a small first slab with 4x growth -- device started after 0.3 ms of packing -- was measured in round 5 and dropped: every
 # forward costs the host ~1 ms (graph-build read-back + ~45 launches), so three forwards instead of one gave back what the
