@@ -277,6 +277,26 @@ int matten_tp_fused(const float* x, int64_t d_in, const uint16_t* h2s, const flo
                     int64_t units_per_tile, int64_t lds_floats_per_wave, int64_t d_mid, float avg_num_neighbors,
                     const float* num_neigh, const uint16_t* a_split, const float* a_scale_inv,
                     float* agg /*[N,d_mid]*/, matten_stream_t stream);
+/* matten_tp_fused for the entries of plan.plan_agg_narrow (word 0 + 1024: the entry has narrowed couplings).  lin2 maps the mul
+ * channels of a coupling onto the mo channels of its output irrep; where mo < mul the entry's lanes apply their own slice of
+ * lin2 to their sums -- partial[v][k] = sum_u W[species][u][v] * sum[u][k], added over the node's lanes in a fixed order
+ * -- and store mo floats per component at out_off[c] + k * t_off[c] instead of mul (matten_agg_linear then reads them with
+ * the A value 1).  Narrowed entries have mul == lanes per node == 8 or 16, l1 <= matten_tp_narrow_max_l1(), the coupling-major
+ * flag (+ 512) and mo in {1, 2, 4}; every other coupling is written as by matten_tp_fused.
+ *   group_entries: ONE buffer [entries n_entries x 32 | weights] (plan.narrow_blob): the kernel has no scalar registers for
+ *                  further pointers and finds the weights from the entry record.  The two words of a narrowed coupling c:
+ *                  t_off[c] = floats between components | mo << 20, out_off[c] = first float (< 65536) | distance of the
+ *                  coupling's weight block [species][u < mul][v < mo] (fp32, lin2's fan-in normalisation included) from the
+ *                  ENTRY in units of four floats << 16; mo == 0: a plain coupling
+ *   species[n_nodes] int32: species index per destination node (required; all 0 for one species)
+ *   d_mid a multiple of 4, out_off[c] of a narrowed coupling a multiple of its mo (pieces of 4 mo bytes) */
+int matten_tp_fused_narrow(const float* x, int64_t d_in, const uint16_t* h2s, const float* w2p, int64_t w_pad,
+                           const float* sh_sorted, int64_t sh_stride, const int32_t* rowptr, const int32_t* src_sorted,
+                           int64_t n_nodes, const int32_t* group_entries, const int32_t* unit_map, int64_t n_entries,
+                           int64_t units_per_tile, int64_t lds_floats_per_wave, int64_t d_mid, float avg_num_neighbors,
+                           const float* num_neigh, const uint16_t* a_split, const float* a_scale_inv,
+                           const int32_t* species, float* agg /*[N,d_mid]*/, matten_stream_t stream);
+int matten_tp_narrow_max_l1(void);   /* largest l1 of an input block whose entries may carry narrowed couplings */
 
 int matten_tp_wreg(void);       /* 0: no entry may carry the coupling-major flag (built with -DTPF_WREG=0); else 1 + the largest l1 that may */
 int matten_tp_max_cols(void);   /* weight columns (mul * couplings) a group entry of matten_tp_fused may have */

@@ -54,6 +54,8 @@ SIGNATURES = {
     "matten_tp_max_cols_l1": (c_int, []),
     "matten_tp_groups_hash": (c_int, []),
     "matten_tp_fused": (c_int, [P, c_int64, P, P, c_int64, P, c_int64, P, P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P, P, P, P, P]),
+    "matten_tp_fused_narrow": (c_int, [P, c_int64, P, P, c_int64, P, c_int64, P, P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P, P, P, P, P, P]),
+    "matten_tp_narrow_max_l1": (c_int, []),
     "matten_species_linear": (c_int, [P, c_int64, P, P, c_int64, P, c_int64, P, c_int64, c_int64, P, c_int64, c_int64, P, P]),
     "matten_species_linear_rows": (c_int, [P, c_int64, P, P, c_int64, P, c_int64, P, c_int64, c_int64, P, c_int64, c_int64, P, P]),
     "matten_radial_mlp_bwd_small_slices": (c_int64, [c_int64]),

@@ -51,10 +51,152 @@ using namespace matten_walk;
 constexpr int KIND_MERGED = 256;   // == plan.TP_KIND_MERGED
 constexpr int KIND_WREG = 512;     // == plan.TP_KIND_WREG: the entry's weight columns are coupling-major (column mul * c + u, mul == lanes
                                    // per node): shared and paired workgroups hand its weights over in registers (tp_walk.h, WR)
+constexpr int KIND_NARROW = 1024;  // == plan.TP_KIND_NARROW: at least one coupling of the entry is narrowed (plan.plan_agg_narrow):
+                                   // the entry's lanes apply their slice of lin2 to their sums and store mo floats per component
+#ifndef TPF_NARROW_MAX_L1
+#define TPF_NARROW_MAX_L1 1        // == plan.AGG_NARROW_MAX_L1: compiled for the scalar and vector input blocks only
+#endif
+
+// d = s[lane chosen by CTRL] + s on the lanes of the 4-lane banks in BANKS (of every row of 16); d stays elsewhere.  Inline asm:
+// the compiler does not fold a bank-masked lane move into the add.  Its hazard recogniser does not see the instruction either, so
+// the two wait states a DPP read needs behind the vector write of its source are spent right here.
+#define TPF_DPP_ADD(d, s, CTRL, BANKS) \
+    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 " CTRL " row_mask:0xf bank_mask:" BANKS : "+v"(d) : "v"(s))
+
+// Sum of t[k] over the 1 << CUL channel lanes of a node (CUL = 4: one row of 16 lanes; 3: half a row), for D3 values at once,
+// as a reduce-scatter over the node's NB = 4 (2) banks followed by a sum inside each bank: every lane of bank b ends with
+// q[m] = the sum of t[b + NB * m].  About 2.4 D3 instructions against 4 D3 (3 D3) for D3 butterflies.  The order of the
+// additions is fixed by the lane numbers alone: the result is deterministic and the same in every walk form.
+template <int CUL, int D3>
+__device__ __forceinline__ void narrow_sum(const float (&t)[D3], float* __restrict__ q) {
+    constexpr int NB = CUL == 4 ? 4 : 2;
+    constexpr int M = (D3 + NB - 1) / NB;
+    if constexpr (CUL == 4) {
+        // lanes 0-7 take the components with bit 1 clear, lanes 8-15 those with it set (partner: lane ^ 8) ...
+        float h[2 * M];
+#pragma unroll
+        for (int i = 0; i < 2 * M; ++i) {
+            const int k0 = (i >> 1) * 4 + (i & 1);
+            if (k0 < D3) {
+                h[i] = t[k0];
+                TPF_DPP_ADD(h[i], t[k0], "row_ror:8", "0x3");
+                if (k0 + 2 < D3) TPF_DPP_ADD(h[i], t[k0 + 2 < D3 ? k0 + 2 : 0], "row_ror:8", "0xc");
+            }
+        }
+        // ... then the even banks those with bit 0 clear, the odd ones those with it set (partner: lane 7 - i of the half row)
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            q[m] = h[2 * m];
+            TPF_DPP_ADD(q[m], h[2 * m], "row_half_mirror", "0x5");
+            if (4 * m + 1 < D3) TPF_DPP_ADD(q[m], h[2 * m + 1], "row_half_mirror", "0xa");
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            q[m] = t[2 * m];
+            TPF_DPP_ADD(q[m], t[2 * m], "row_half_mirror", "0x5");
+            if (2 * m + 1 < D3) TPF_DPP_ADD(q[m], t[2 * m + 1 < D3 ? 2 * m + 1 : 0], "row_half_mirror", "0xa");
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        TPF_DPP_ADD(q[m], q[m], "quad_perm:[1,0,3,2]", "0xf");
+        TPF_DPP_ADD(q[m], q[m], "quad_perm:[2,3,0,1]", "0xf");
+    }
+}
+
+// One narrowed coupling: partial[v][k] = sum_u W[species][u][v] * norm * acc[k] over the node's lanes; (node, k) then leaves as
+// one piece of mo floats from the lane narrow_sum left it on (bank b, lane m & 3 of the bank <-> k = b + NB * m).
+template <int CUL, int D3>
+__device__ __forceinline__ void narrow_coupling(const float* __restrict__ accp, const float* __restrict__ wp, int mo, float norm,
+                                                float* __restrict__ op, int ks, int u, bool valid) {
+    constexpr int NB = CUL == 4 ? 4 : 2;
+    constexpr int M = (D3 + NB - 1) / NB;
+    float w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (mo == 4) {
+        const f32x4 v4 = *reinterpret_cast<const f32x4*>(wp);
+        w[0] = v4[0], w[1] = v4[1], w[2] = v4[2], w[3] = v4[3];
+    } else if (mo == 2) {
+        const float2 v2 = *reinterpret_cast<const float2*>(wp);
+        w[0] = v2.x, w[1] = v2.y;
+    } else {
+        w[0] = wp[0];
+    }
+    float q[4][M];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+#pragma unroll
+        for (int m = 0; m < M; ++m) q[v][m] = 0.0f;
+        if (v < mo) {   // wave-uniform
+            const float wv = w[v] * norm;
+            float t[D3];
+#pragma unroll
+            for (int k = 0; k < D3; ++k) t[k] = accp[k] * wv;
+            narrow_sum<CUL, D3>(t, q[v]);
+        }
+    }
+    const int l = u & 3, b = (u >> 2) & (NB - 1);
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const int k = b + NB * m;
+        if (valid && l == (m & 3) && k < D3) {
+            float* p = op + k * ks;
+            if (mo == 4) {
+                const f32x4 r = {q[0][m], q[1][m], q[2][m], q[3][m]};
+                *reinterpret_cast<f32x4*>(p) = r;
+            } else if (mo == 2) {
+                *reinterpret_cast<float2*>(p) = make_float2(q[0][m], q[1][m]);
+            } else {
+                *p = q[0][m];
+            }
+        }
+    }
+}
+
 struct StoreAgg {
-    template <class G>
-    __device__ __forceinline__ void store(const Args& a, const GroupEntry& ge, const float* __restrict__ acc,
+    // the narrowed couplings of an entry; -> their mask.  Every lane of the wave takes part (the lanes of a node group past the
+    // end of the batch carry zero sums and store nothing): the lane exchanges need their partners.
+    template <class G, int CULH>
+    __device__ __forceinline__ unsigned store_narrow(const Args& a, const GroupEntry& ge, const float* __restrict__ acc,
+                                                     float a_scale_inv, int node, int u, bool valid) const {
+        // A narrowed coupling carries its own record in the entry's words (no table, no further pointer: the kernel has no scalar
+        // registers to spare): t_off[c] = floats between components | mo << 20, out_off[c] = first float | distance of the
+        // coupling's weight block [species][channel u][output channel v] from the ENTRY in units of four floats << 16 -- the
+        // weights sit behind the entry array (plan.narrow_blob)
+        const int nsafe = min(node, a.n_nodes - 1);
+        const float nn = a.avg_nn > 0.0f ? a.avg_nn : a.num_neigh[nsafe];
+        const float norm = nn > 0.0f ? a_scale_inv / sqrtf(nn) : 0.0f;
+        const int sp = a.species[nsafe];
+        float* orow = a.agg + (int64_t)node * a.d_mid;
+        const int cul = CULH ? CULH : ge.cu_log2;   // 3 or 4 (the plan narrows full entries of 8 or 16 lanes per node only)
+        unsigned done = 0;
+        for_slots<0, G::NC, 1>([&](auto cc_) {
+            constexpr int cc = decltype(cc_)::value;
+            constexpr int D3 = 2 * G::L3[cc] + 1;
+            const unsigned tw = (unsigned)ge.t_off[cc];
+            const int mo = (int)(tw >> 20);
+            if (mo != 0) {   // wave-uniform
+                done |= 1u << cc;
+                const unsigned ow = (unsigned)ge.out_off[cc];
+                const float* wp = reinterpret_cast<const float*>(&ge) + 4 * (int)(ow >> 16) + ((sp << cul) + u) * mo;
+                float* op = orow + (int)(ow & 0xffffu);
+                const int ks = (int)(tw & 0xfffffu);
+                if (cul == 4) narrow_coupling<4, D3>(acc + G::OFF[cc], wp, mo, norm, op, ks, u, valid);
+                else narrow_coupling<3, D3>(acc + G::OFF[cc], wp, mo, norm, op, ks, u, valid);
+            }
+        });
+        return done;
+    }
+
+    // CULH: log2 of the entry's lanes per node where the walk knows it at compile time (the register hand-over), 0 = read it from
+    // the entry (the plain walk), -1 = a walk form no narrowed entry reaches (the plan narrows KIND_WREG entries only)
+    template <class G, int CULH>
+    __device__ __forceinline__ void store(const Args& a, const GroupEntry& ge, const float* acc,
                                           float a_scale_inv, int node, int j, int u, bool valid) const {
+        unsigned narrowed = 0;
+        if constexpr (CULH >= 0 && G::D1 <= 2 * TPF_NARROW_MAX_L1 + 1 && !TPF_LAB_NO_STORE) {
+            if (a.species && (ge.kind & KIND_NARROW)) narrowed = store_narrow<G, CULH>(a, ge, acc, a_scale_inv, node, u, valid);
+        }
         if (TPF_LAB_NO_STORE ? (valid && acc[0] == 12345.678f) : valid) {
             const float nn = a.avg_nn > 0.0f ? a.avg_nn : a.num_neigh[node];
             // num_neigh = 0 (per-node normalisation, nothing arrives): the empty sum stays 0, not 0 x 1/sqrt(0) = NaN
@@ -63,7 +205,7 @@ struct StoreAgg {
             const bool merged = (ge.kind & KIND_MERGED) != 0;          // wave-uniform
             const GroupEntry& g2 = (&ge)[merged ? 1 : 0];
             const bool second = merged && u >= 2;
-            const unsigned mask = merged ? (second ? g2.mask : (unsigned)g2.w_base) : ge.mask;
+            const unsigned mask = (merged ? (second ? g2.mask : (unsigned)g2.w_base) : ge.mask) & ~narrowed;
             const int uc = second ? u - 2 : u;
 #pragma unroll
             for (int cc = 0; cc < G::NC; ++cc) {
@@ -226,7 +368,7 @@ __device__ __forceinline__ void run_group(const Args& a, const GroupEntry& ge, f
         }
         __builtin_amdgcn_wave_barrier();  // LDS is in order per wave: the next chunk's stores follow these reads
     }
-    StoreAgg{}.store<G>(a, ge, acc, a_scale_inv, node, j, u, valid);   // (a_scale_inv undoes the power-of-two scale of the A tile)
+    StoreAgg{}.store<G, 0>(a, ge, acc, a_scale_inv, node, j, u, valid);   // (a_scale_inv undoes the power-of-two scale of the A tile)
 }
 
 #define MATTEN_RGS_ARGS a, ge, tile, stage, (um >> 8) & 0xffff, tile_id, r, reps, lane, StoreAgg{}
@@ -677,13 +819,13 @@ extern "C" int matten_lab_tp_trace(unsigned* buf, int64_t n_waves, int64_t skip)
 }
 #endif
 
-extern "C" int matten_tp_fused(const float* x, int64_t d_in, const uint16_t* h2s, const float* w2p, int64_t w_pad,
-                               const float* sh_sorted, int64_t sh_stride, const int32_t* rowptr,
-                               const int32_t* src_sorted, int64_t n_nodes, const int32_t* group_entries,
-                               const int32_t* unit_map, int64_t n_entries, int64_t units_per_tile,
-                               int64_t lds_floats_per_wave, int64_t d_mid, float avg_num_neighbors,
-                               const float* num_neigh, const uint16_t* a_split, const float* a_scale_inv, float* agg,
-                               matten_stream_t stream_) {
+static int tp_fused_launch(const float* x, int64_t d_in, const uint16_t* h2s, const float* w2p, int64_t w_pad,
+                           const float* sh_sorted, int64_t sh_stride, const int32_t* rowptr,
+                           const int32_t* src_sorted, int64_t n_nodes, const int32_t* group_entries,
+                           const int32_t* unit_map, int64_t n_entries, int64_t units_per_tile,
+                           int64_t lds_floats_per_wave, int64_t d_mid, float avg_num_neighbors,
+                           const float* num_neigh, const uint16_t* a_split, const float* a_scale_inv,
+                           const int32_t* species, float* agg, matten_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_nodes < 0 || d_in <= 0 || w_pad <= 0 || sh_stride < 32 || (sh_stride & 3) || n_entries <= 0 ||
         units_per_tile <= 0 || d_mid <= 0 || lds_floats_per_wave <= 0 || (lds_floats_per_wave & 3))
@@ -696,7 +838,8 @@ extern "C" int matten_tp_fused(const float* x, int64_t d_in, const uint16_t* h2s
     if (lds > 64 * 1024) return MATTEN_EINVAL;
     if ((a_split == nullptr) != (a_scale_inv == nullptr)) return MATTEN_EINVAL;
     Args a{x, (const _Float16*)h2s, w2p, (const _Float16*)a_split, a_scale_inv, sh_sorted, rowptr, src_sorted, num_neigh, agg, (int)d_in, (int)w_pad, (int)sh_stride,
-           (int)d_mid, (int)n_nodes, (int)lds_floats_per_wave, avg_num_neighbors};
+           (int)d_mid, (int)n_nodes, (int)lds_floats_per_wave, avg_num_neighbors,
+           species};
     const int n_tiles = (int)matten_cdiv(n_nodes, TILE_NODES);
     const int blocks_per_tile = (int)matten_cdiv(units_per_tile, WAVES_PER_BLOCK);
     const int64_t grid = matten_cdiv(n_tiles, N_XCD) * N_XCD * (int64_t)blocks_per_tile;
@@ -715,6 +858,32 @@ extern "C" int matten_tp_fused(const float* x, int64_t d_in, const uint16_t* h2s
     return MATTEN_OK;
 }
 
+extern "C" int matten_tp_fused(const float* x, int64_t d_in, const uint16_t* h2s, const float* w2p, int64_t w_pad,
+                               const float* sh_sorted, int64_t sh_stride, const int32_t* rowptr,
+                               const int32_t* src_sorted, int64_t n_nodes, const int32_t* group_entries,
+                               const int32_t* unit_map, int64_t n_entries, int64_t units_per_tile,
+                               int64_t lds_floats_per_wave, int64_t d_mid, float avg_num_neighbors,
+                               const float* num_neigh, const uint16_t* a_split, const float* a_scale_inv, float* agg,
+                               matten_stream_t stream_) {
+    return tp_fused_launch(x, d_in, h2s, w2p, w_pad, sh_sorted, sh_stride, rowptr, src_sorted, n_nodes, group_entries, unit_map,
+                           n_entries, units_per_tile, lds_floats_per_wave, d_mid, avg_num_neighbors, num_neigh, a_split,
+                           a_scale_inv, nullptr, agg, stream_);
+}
+
+extern "C" int matten_tp_fused_narrow(const float* x, int64_t d_in, const uint16_t* h2s, const float* w2p, int64_t w_pad,
+                                      const float* sh_sorted, int64_t sh_stride, const int32_t* rowptr,
+                                      const int32_t* src_sorted, int64_t n_nodes, const int32_t* group_entries,
+                                      const int32_t* unit_map, int64_t n_entries, int64_t units_per_tile,
+                                      int64_t lds_floats_per_wave, int64_t d_mid, float avg_num_neighbors,
+                                      const float* num_neigh, const uint16_t* a_split, const float* a_scale_inv,
+                                      const int32_t* species, float* agg, matten_stream_t stream_) {
+    if (n_nodes > 0 && (!species || (d_mid & 3))) return MATTEN_EINVAL;
+    return tp_fused_launch(x, d_in, h2s, w2p, w_pad, sh_sorted, sh_stride, rowptr, src_sorted, n_nodes, group_entries, unit_map,
+                           n_entries, units_per_tile, lds_floats_per_wave, d_mid, avg_num_neighbors, num_neigh, a_split,
+                           a_scale_inv, species, agg, stream_);
+}
+
+extern "C" int matten_tp_narrow_max_l1(void) { return TPF_NARROW_MAX_L1; }   // == plan.AGG_NARROW_MAX_L1
 extern "C" int matten_tp_wreg(void) { return TPF_WREG ? TPF_WREG_MAX_L1 + 1 : 0; }   // 0, or 1 + the largest l1 compiled for it
 extern "C" int matten_tp_max_cols(void) { return TPF_MAX_COLS; }
 extern "C" int matten_tp_max_cols_l0(void) { return TPF_MAX_COLS_L0; }

@@ -202,6 +202,11 @@ struct Args {
     float* agg;
     int d_in, w_pad, sh_stride, d_mid, n_nodes, lds_per_wave;
     float avg_nn;
+    // matten_tp_fused_narrow (plan.plan_agg_narrow; NULL in matten_tp_fused): species index per destination node.  The one new
+    // field: every further kernel argument stays live in scalar registers through the whole walk, and the kernel has none to
+    // spare -- the narrow table and the writer's weights therefore sit BEHIND the entry array, found from the entry itself
+    // (StoreAgg::store_narrow)
+    const int* species;
 #if TPF_TRACING
     unsigned* trace;   // [waves of the launch][16]
 #endif
@@ -943,7 +948,7 @@ __device__ __forceinline__ void run_group_shared(const Args& a, const GroupEntry
 #if TPF_TRACING
     tr_epi_sg += (unsigned)(tpf_stamp() - tr_end);
 #endif
-    epi.template store<G>(a, ge, acc, a_scale_inv, node_done, j, u, valid_done);
+    epi.template store<G, (WR ? WR : -1)>(a, ge, acc, a_scale_inv, node_done, j, u, valid_done);   // (narrowed entries are KIND_WREG: WR != 0 here)
     if (!TPF_REP_PREFETCH && more) start_group(unit_nodes_finish(raw_next));
 #if TPF_TRACING
     if (a.trace && lane == 0) {

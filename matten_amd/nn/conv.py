@@ -14,6 +14,7 @@ import numpy as np
 
 from .. import autograd as _ag
 from .. import ops
+from .. import plan as _plan_mod
 from ..data.irreps import DataKey, ModuleIrreps
 from ..o3 import Irreps
 from ._tables import DerivedWeight, DeviceTables, WeightSlice
@@ -79,10 +80,21 @@ class PointConv(ModuleIrreps, torch.nn.Module):
         self.agg_plan = None
         if self.tp.impl == "fused" and os.environ.get("MATTEN_AGG_LAYOUT", "km") == "km":
             ap = _plan.plan_agg_linear(self.tp.plan, n_species, conv_layer_irreps)
+            # narrowed neighbour sums (plan.plan_agg_narrow: the tensor-product wave applies lin2 where it has fewer output than
+            # input channels); MATTEN_AGG_NARROW=0 keeps the full-width rows of plan.plan_agg_linear, for the A/B
+            if ap is not None and os.environ.get("MATTEN_AGG_NARROW", "1") != "0":
+                apn = _plan.plan_agg_narrow(self.tp.plan, n_species, conv_layer_irreps)
+                # (only where the row gets shorter: the first layer's pieces round up to the same 416 floats, and there the
+                # writer's lane sums cost 0.016 ms for nothing -- docs/LAB_NOTES.md round 8)
+                if apn is not None and apn.ld < ap.ld and self._agg_fits(apn):
+                    ap = apn
             if ap is not None and self._agg_fits(ap):
-                self.agg_plan = ap
-                self._agg_tables = DeviceTables(entries=ap.entries, io=ap.io_table, blocks=ap.blocks, gather=ap.gather,
-                                                scale=ap.scale)
+                self.agg_plan = ap      # the plan that is launched
+                tables = dict(entries=ap.entries, io=ap.io_table, blocks=ap.blocks, gather=ap.gather, scale=ap.scale)
+                if ap.narrow is not None:
+                    tables.update(narrow_gather=ap.narrow_gather, narrow_scale=ap.narrow_scale)
+                    self._agg_narrow_w = DerivedWeight(self._pack_narrow_weights)
+                self._agg_tables = DeviceTables(**tables)
                 self._agg_wtab = DerivedWeight(self._pack_agg_weights)
 
     def _pack_lin1_sc(self, w1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
@@ -119,7 +131,26 @@ class PointConv(ModuleIrreps, torch.nn.Module):
         """lin2.weight (flat, reference layout) -> [S, w_stride] MFMA A fragments of matten_agg_linear"""
         t, dev = self._agg_tables, w.device
         gather, scale = t.get("gather", dev), t.get("scale", dev)
-        return torch.where(gather >= 0, w[gather.clamp(min=0)] * scale[None, :], w.new_zeros(())).contiguous()
+        one = (gather == _plan_mod.AGG_GATHER_ONE).to(w.dtype)   # slots a narrowed coupling wrote: lin2 is applied already
+        return torch.where(gather >= 0, w[gather.clamp(min=0)] * scale[None, :], one).contiguous()
+
+    def _pack_narrow_weights(self, w: torch.Tensor) -> torch.Tensor:
+        """lin2.weight -> what matten_tp_fused_narrow takes as group_entries (plan.narrow_blob): the plan's entries and behind
+        them the writer's weight blocks [species][u][v] per narrowed coupling, fan-in normalisation included, in ONE int32
+        buffer (the kernel finds the weights from the entry record)"""
+        t, dev = self._agg_tables, w.device
+        wn = (w[t.get("narrow_gather", dev)] * t.get("narrow_scale", dev)).to(torch.float32).contiguous()
+        return torch.cat([t.get("entries", dev).reshape(-1), wn.view(torch.int32)])
+
+    def _agg_out_layout(self, data, dev):
+        """what the tensor product needs to write the rows of self.agg_plan"""
+        ap, t = self.agg_plan, self._agg_tables
+        if ap.narrow is None:
+            return (t.get("entries", dev), ap.ld)
+        species = data.get(DataKey.AMD_SPECIES_I32)
+        if species is None:
+            raise ValueError("narrowed neighbour sums need the per-node species index (DataKey.AMD_SPECIES_I32)")
+        return (self._agg_narrow_w.get(self.lin2.weight), ap.ld, (species, len(ap.entries)))
 
     # ---- dead-output elimination (inference) ------------------------------------------------------------------------
     def build_inference_view(self, kept_irreps) -> bool:
@@ -213,7 +244,7 @@ class PointConv(ModuleIrreps, torch.nn.Module):
                 and not _ag.needs_grad_lazy(lambda: (x1, self_connection, self.lin2.weight, *_geometry(data),
                                                      *_ag.params_of(self.tp.weight_nn)))):
             ap, t, dev = self.agg_plan, self._agg_tables, x1.device
-            agg = self.tp(x1, data, self.avg_num_neighbors, out_layout=(t.get("entries", dev), ap.ld))
+            agg = self.tp(x1, data, self.avg_num_neighbors, out_layout=self._agg_out_layout(data, dev))
             gate = self.__dict__.get("_gate_fuse")   # set per call by PointConvWithActivation: (cmeta, act_cst, d_act, bn)
             if gate is not None:
                 cmeta, act_cst, d_act, bn_scale, bn_shift = gate

@@ -355,7 +355,8 @@ class UVUTensorProduct(torch.nn.Module):
 
     def forward(self, node_feats: Tensor, data: DataKey.Type, avg_num_neighbors=None, out_layout=None) -> Tensor:
         """sum over incoming edges of TP(x[src], Y(edge), MLP(rbf(edge))), normalised; [N, d_mid].
-        out_layout = (group entries with component-major output offsets, row stride): plan.AggLinearPlan (fused path only)"""
+        out_layout = (group entries with component-major output offsets, row stride[, (species index per node, entries)]): plan.AggLinearPlan;
+        with the third item the first is the buffer of plan.narrow_blob, for a plan of plan.plan_agg_narrow (fused path only)"""
         nb, r0, r1 = data[DataKey.AMD_RBF].tolist()
         dev = node_feats.device
         avg = avg_num_neighbors if avg_num_neighbors is not None else 0.0
@@ -411,6 +412,7 @@ class UVUTensorProduct(torch.nn.Module):
                 self._tables.get("gumap", dev), len(self.plan.fused_unit_map),
                 self.plan.fused_lds_floats_per_wave, out_layout[1] if out_layout is not None else self.plan.d_mid, avg,
                 num_neigh if split is None else split[2], a_split=self.a_split(r0, r1),
+                narrow=out_layout[2] if out_layout is not None and len(out_layout) > 2 else None,
             )
             return agg if split is None else ops.segment_reduce(agg, split[1], mean=False)
         # "paths": one wave per path over a materialised w[E, W] in the reference's column order (the training forward; kept

@@ -627,8 +627,11 @@ _GROUPS_CHECKED = False
 
 def tp_fused(x, h2p, w2p, sh_sorted, rowptr, src_sorted, entries, unit_map, units_per_tile: int,
              lds_floats_per_wave: int, d_mid: int, avg_num_neighbors: float, num_neigh=None,
-             a_split=None) -> torch.Tensor:
-    """a_split: optional (fragments, scale_inv) from split_a_tiles(w2p, plan.group_entries)"""
+             a_split=None, narrow=None) -> torch.Tensor:
+    """a_split: optional (fragments, scale_inv) from split_a_tiles(w2p, plan.group_entries)
+    narrow: optional (species index i32 [N], number of group entries) for a plan of plan.plan_agg_narrow: `entries` is then
+    the 1-D int32 buffer of plan.narrow_blob (that plan's entries and the writer's weights), and the narrowed couplings
+    leave with lin2 applied (matten_tp_fused_narrow)"""
     lib = _lib.load()
     from .plan import TP_TILE_NODES
 
@@ -656,15 +659,33 @@ def tp_fused(x, h2p, w2p, sh_sorted, rowptr, src_sorted, entries, unit_map, unit
     sh_sorted = _need(sh_sorted, torch.float32, "sh_sorted")
     # destination rows = segments of rowptr (virtual nodes when the segments were cut by ops.csr_split); x rows are sources
     N, d_in = rowptr.shape[0] - 1, x.stride(0)
+    n_entries = entries.shape[0] if narrow is None else int(narrow[1])
     if num_neigh is not None:
         num_neigh = _need(num_neigh, torch.float32, "num_neigh")
     if a_split is not None:
         a_split = (_need(a_split[0], torch.float16, "a_split"), _need(a_split[1], torch.float32, "a_scale_inv"))
-        if a_split[1].numel() != entries.shape[0]:
+        if a_split[1].numel() != n_entries:
             raise ValueError("a_scale_inv needs one value per group entry")
     if unit_map.numel() != units_per_tile:
         raise ValueError(f"unit_map has {unit_map.numel()} units, expected {units_per_tile} (plan.fused_unit_map)")
     agg = torch.empty(N, d_mid, dtype=torch.float32, device=x.device)
+    if narrow is not None:
+        from .plan import AGG_NARROW_MAX_L1
+        if lib.matten_tp_narrow_max_l1() != AGG_NARROW_MAX_L1:
+            raise _lib.MattenHipError("plan.AGG_NARROW_MAX_L1 does not match the library (-DTPF_NARROW_MAX_L1)")
+        sp = _need(narrow[0], torch.int32, "species")
+        if sp.numel() != N or d_mid % 4 or entries.dim() != 1 or entries.numel() <= n_entries * 32:
+            raise ValueError("narrow: one species index per destination row, d_mid a multiple of 4, and `entries` the buffer of "
+                             "plan.narrow_blob (entries | weights)")
+        with _timed(f"tp_scatter/d_mid={d_mid}/d_in={x.shape[1]}"):
+            rc = lib.matten_tp_fused_narrow(_ptr(x), d_in, _ptr(h2p), _ptr(w2p), w2p.shape[1], _ptr(sh_sorted),
+                                            sh_sorted.shape[1], _ptr(rowptr), _ptr(src_sorted), N, _ptr(entries),
+                                            _ptr(unit_map), n_entries, units_per_tile, lds_floats_per_wave, d_mid,
+                                            float(avg_num_neighbors or 0.0), _ptr(num_neigh),
+                                            _ptr(a_split[0]) if a_split is not None else None,
+                                            _ptr(a_split[1]) if a_split is not None else None, _ptr(sp), _ptr(agg), _stream())
+        _lib.check(rc, "matten_tp_fused_narrow")
+        return agg
     with _timed(f"tp_scatter/d_mid={d_mid}/d_in={x.shape[1]}"):
         rc = lib.matten_tp_fused(_ptr(x), d_in, _ptr(h2p), _ptr(w2p), w2p.shape[1], _ptr(sh_sorted),
                                  sh_sorted.shape[1], _ptr(rowptr), _ptr(src_sorted), N, _ptr(entries),

@@ -927,6 +927,12 @@ class AggLinearPlan:
     scale: np.ndarray          # f32 [w_stride]
     d_out: int
     max_mt: int
+    # plan_agg_narrow only (None in a plan of plan_agg_linear): what the writer needs to apply lin2 to its own sums
+    narrow: Optional[np.ndarray] = None          # int32 [n_entries, TP_MAX_COMBOS]: 0, or mo | first float of the coupling's block
+                                                 # in the writer's weights << 8 (host-side description; the kernel reads the
+                                                 # same from the packed words of `entries`, see _plan_agg)
+    narrow_gather: Optional[np.ndarray] = None   # int64 [narrow weights]: index into the flat lin2 weight; blocks [species][u][v]
+    narrow_scale: Optional[np.ndarray] = None    # f32 [narrow weights]: fan[io] ** -0.5 (the reader's A value of these slots is 1)
 
 
 AGG_GATE_SETS = 3   # == matten_agg_linear_gate_sets(): table rows of lin2 that may hold gate scalars
@@ -996,6 +1002,53 @@ def plan_agg_gate(ap: "AggLinearPlan", gate: "GatePlan") -> Optional[np.ndarray]
 
 def plan_agg_linear(uvu: UVUPlan, n_species: int, irreps_out) -> Optional[AggLinearPlan]:
     """None when an output irrep of lin2 has no input path (the mul_ir path handles those layers)."""
+    return _plan_agg(uvu, n_species, irreps_out, narrow=False)
+
+
+# Narrowed couplings (plan_agg_narrow): lin2 maps the `mul` channels of a path onto the `mo` channels of its output irrep.
+# Where mo < mul the tensor-product wave applies its own [mul x mo] slice of lin2 to its sums before they leave (the sum over
+# the channel lanes of a node: matten_tp_fused_narrow) and the row carries mo floats per component instead of mul.
+TP_KIND_NARROW = 1024       # == KIND_NARROW of tp_fused.hip: the entry has at least one narrowed coupling
+AGG_NARROW_MAX_L1 = 1       # == TPF_NARROW_MAX_L1: the scalar and vector input blocks (the heavier kinds sit at the kernel's register cap)
+AGG_NARROW_MULS = (8, 16)   # lanes per node the writer's reduction is written for: a full entry of a light kind
+AGG_NARROW_MO = (1, 2, 4)   # output channels a narrowed piece may have: one store of 4, 8 or 16 bytes per (node, component)
+AGG_GATHER_ONE = -2         # sentinel of AggLinearPlan.gather beside -1 (structural zero): the A value 1.0
+
+
+def plan_agg_narrow(uvu: UVUPlan, n_species: int, irreps_out) -> Optional[AggLinearPlan]:
+    """plan_agg_linear with the narrowed couplings' pieces mo wide (see above); io_table, blocks, gather and scale mean
+    what they mean there, so matten_agg_linear and plan_agg_gate take the plan unchanged.  None when plan_agg_linear
+    gives None, or when no coupling of the layer narrows (the caller keeps the plain plan)."""
+    ap = _plan_agg(uvu, n_species, irreps_out, narrow=True)
+    return ap if ap is not None and ap.narrow is not None and ap.narrow.any() else None
+
+
+def narrow_blob(ap: AggLinearPlan, weights: np.ndarray) -> np.ndarray:
+    """int32 [n x 32 + weights]: what matten_tp_fused_narrow takes as group_entries -- the plan's entries with the writer's
+    weights (fp32 bits; flat_lin2_weight[ap.narrow_gather] * ap.narrow_scale) behind them in one buffer"""
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    assert w.shape == ap.narrow_gather.shape
+    return np.concatenate([ap.entries.reshape(-1).astype(np.int32), w.view(np.int32)])
+
+
+def narrow_unpack(t_off_word: int, out_off_word: int):
+    """(floats between components, first float, mo, distance of the weight block from the entry in floats) of a coupling's two
+    words in a plan of plan_agg_narrow; mo == 0: not narrowed (plain words)"""
+    t, o = int(t_off_word) & 0xFFFFFFFF, int(out_off_word) & 0xFFFFFFFF
+    mo = t >> 20
+    return (t & 0xFFFFF, o & 0xFFFF, mo, 4 * (o >> 16)) if mo else (t, o, 0, 0)
+
+
+def _narrows(ent_row, mul_c: int, mo: int) -> bool:
+    kind = int(ent_row[0])
+    # (TP_KIND_WREG: exactly the full 8- and 16-lane entries of the light kinds; the kernel compiles the narrowed epilogue into
+    # the walk forms such entries take)
+    return ((kind & 255) // TP_KIND_STRIDE <= AGG_NARROW_MAX_L1 and not kind & TP_KIND_MERGED and bool(kind & TP_KIND_WREG)
+            and mul_c in AGG_NARROW_MULS and (1 << int(ent_row[3])) == mul_c and int(ent_row[2]) == mul_c
+            and mo < mul_c and mo in AGG_NARROW_MO)
+
+
+def _plan_agg(uvu: UVUPlan, n_species: int, irreps_out, narrow: bool) -> Optional[AggLinearPlan]:
     irreps_out = Irreps(irreps_out).simplify()
     S = n_species
     ent = np.asarray(uvu.group_entries).reshape(-1, 32).copy()
@@ -1021,6 +1074,7 @@ def plan_agg_linear(uvu: UVUPlan, n_species: int, irreps_out) -> Optional[AggLin
     o_offs = irreps_out.offsets()
     # pieces per output irrep: (entry, coupling, channels)
     pieces: Dict[int, List[Tuple[int, int, int]]] = {}
+    narrowed: Dict[Tuple[int, int], int] = {}     # (entry, coupling) -> mo
     for e in range(len(ent)):
         for c, pi in sorted(uvu.group_entry_paths[e].items()):
             pth = uvu.paths[pi]
@@ -1028,10 +1082,18 @@ def plan_agg_linear(uvu: UVUPlan, n_species: int, irreps_out) -> Optional[AggLin
             ios = [io for io, (_, iro) in enumerate(irreps_out) if iro == ir3]
             if len(ios) != 1:
                 return None
-            pieces.setdefault(ios[0], []).append((e, c, int(uvu.group_entry_mul[e])))
+            mul_c = int(uvu.group_entry_mul[e])
+            mo_c = int(irreps_out[ios[0]].mul)
+            if narrow and _narrows(ent[e], mul_c, mo_c):
+                narrowed[(e, c)] = mo_c
+                mul_c = mo_c          # the piece is mo slots wide
+            pieces.setdefault(ios[0], []).append((e, c, mul_c))
     if any(io not in pieces for io in range(len(irreps_out)) if irreps_out[io].dim > 0):
         return None
     io_rows, gather_parts, scale_parts = [], [], []
+    narrow_woff: Dict[Tuple[int, int], int] = {}   # (entry, coupling) -> first float of its block in the writer's weights
+    narrow_gather: List[np.ndarray] = []
+    narrow_scale: List[np.ndarray] = []
     chunk0, a_off, max_mt = 0, 0, 1
     for io, (mo, iro) in enumerate(irreps_out):
         if iro.dim == 0 or mo == 0:
@@ -1047,9 +1109,18 @@ def plan_agg_linear(uvu: UVUPlan, n_species: int, irreps_out) -> Optional[AggLin
             piece_off[(e, c)] = len(slot_src)
             pth = uvu.paths[uvu.group_entry_paths[e][c]]
             ib = blk_of_slot[pth.slot]
+            if (e, c) in narrowed:
+                # slot v of the piece already holds output channel v of lin2 (fan-in normalisation included)
+                slot_src.extend((AGG_GATHER_ONE, v) for v in range(mul_c))
+                mul_e, u_first = int(uvu.group_entry_mul[e]), uoff_of_slot[pth.slot] + uvu.group_entry_u0[e]
+                s_, u_, v_ = np.meshgrid(np.arange(S), np.arange(mul_e), np.arange(mo), indexing="ij")
+                narrow_woff[(e, c)] = sum(g.size for g in narrow_gather)
+                narrow_gather.append((flat_of[(ib, io)] + (u_first + u_) * S * mo + s_ * mo + v_).reshape(-1))
+                narrow_scale.append(np.full(narrow_gather[-1].size, fan[io] ** -0.5, dtype=np.float32))
+                continue
             for uu in range(mul_c):
                 slot_src.append((ib, uoff_of_slot[pth.slot] + uvu.group_entry_u0[e] + uu))
-        if any(sb < 0 for sb, _ in slot_src):
+        if any(sb == -1 for sb, _ in slot_src):
             # alignment holes inside the region (a piece whose channel count is not a power of two): nobody writes those
             # slots of agg, and the reader only masks the slots PAST the region's end -- 0 x garbage is NaN when the
             # garbage is.  Such layers keep the mul_ir row and matten_species_linear.  (Found by the model fuzzer with
@@ -1083,8 +1154,10 @@ def plan_agg_linear(uvu: UVUPlan, n_species: int, irreps_out) -> Optional[AggLin
             base = np.array([flat_of.get((int(b), io), 0) for b in ib_], dtype=np.int64)
             g0 = base + u_ * S * mo + v                     # W[u, s = 0, v]; + s * mo per species
             valid = (ib_ >= 0) & (v < mo)
-            gather_parts.append(np.where(valid[None, :], g0[None, :] + np.arange(S)[:, None] * mo, -1))
-            scale_parts.append(np.full(slot.size, fan[io] ** -0.5, dtype=np.float32))
+            one = (ib_ == AGG_GATHER_ONE) & (u_ == v)     # a narrowed slot: 1 for its own output channel, 0 elsewhere
+            gather_parts.append(np.where(valid[None, :], g0[None, :] + np.arange(S)[:, None] * mo,
+                                         np.where(one, AGG_GATHER_ONE, -1)[None, :]))
+            scale_parts.append(np.where(one, 1.0, fan[io] ** -0.5).astype(np.float32))
             kmax = max(1, AGG_STAGE_W // mo_p)
             for k0 in range(0, d3, kmax):
                 kk = min(kmax, d3 - k0)
@@ -1104,7 +1177,26 @@ def plan_agg_linear(uvu: UVUPlan, n_species: int, irreps_out) -> Optional[AggLin
                                | (int(last and k == k0 + kk - 1) << 10) | (k << 12) | (ii << 20), t0, 0))
     gather = np.concatenate(gather_parts, axis=1).astype(np.int64)
     assert gather.max() < flat
+    extra = {}
+    if narrowed:
+        # The writer finds everything from the entry record (the kernel has no scalar register for another pointer or a table):
+        # the weights sit behind the entry array, [entries n x 32 | weights] (narrow_blob), and a narrowed coupling's words
+        # carry its record: t_off[c] = floats between components | mo << 20, out_off[c] = first float | distance of its weight
+        # block from the ENTRY in units of four floats << 16.
+        n = len(ent)
+        ng = np.concatenate(narrow_gather).astype(np.int64)
+        narrow_tab = np.zeros((n, TP_MAX_COMBOS), dtype=np.int64)
+        for (e, c), mo_c in narrowed.items():
+            rel = 32 * (n - e) + narrow_woff[(e, c)]
+            if rel % 4 or rel // 4 >= 1 << 15 or ent[e][8 + 12 + c] >= 1 << 16 or ent[e][8 + c] >= 1 << 20:
+                return None   # (does not fit the words: the caller keeps the plain plan)
+            narrow_tab[e][c] = mo_c | (narrow_woff[(e, c)] << 8)
+            ent[e][0] |= TP_KIND_NARROW
+            ent[e][8 + c] |= mo_c << 20
+            ent[e][8 + 12 + c] |= (rel // 4) << 16
+        assert 0 <= ng.min() and ng.max() < flat
+        extra = dict(narrow=narrow_tab.astype(np.int32), narrow_gather=ng, narrow_scale=np.concatenate(narrow_scale))
     return AggLinearPlan(entries=ent.astype(np.int32), ld=ld, n_chunks=chunk0,
                          io_table=np.array(io_rows, dtype=np.int32).reshape(-1, 8),
                          blocks=np.array(blocks, dtype=np.int32).reshape(-1, 4), w_stride=a_off, gather=gather,
-                         scale=np.concatenate(scale_parts), d_out=irreps_out.dim, max_mt=max_mt)
+                         scale=np.concatenate(scale_parts), d_out=irreps_out.dim, max_mt=max_mt, **extra)
