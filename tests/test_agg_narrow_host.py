@@ -5,7 +5,11 @@ FullyConnectedTensorProduct of the mul_ir sums.  No GPU; test_gpu_agg_narrow.py 
 
 Also held here: plan_agg_linear itself returns what it returned before the narrowed planner was added (digests of its arrays
 for every case of agg_linear_cases, recorded from the parent commit in tests/golden/agg_linear_plan_digests.json), the Gate
-assignment does not depend on the layout, and the row length equals a count made from the instruction list alone."""
+assignment does not depend on the layout, and the row length equals a count made from the instruction list alone.
+
+For the operator-level GPU file test_gpu_tp_narrow.py: its case table (agg_narrow_cases.py) reaches exactly the 54 template
+instances the planner can emit, its cases pass the host walk, and a record that does not fit the bit fields of the packed
+entry words gives no plan instead of wrapped words."""
 import hashlib
 import json
 import os
@@ -14,6 +18,7 @@ import numpy as np
 import pytest
 
 import agg_linear_cases as alc
+import agg_narrow_cases as anc
 from common import LMAX2, PAPER
 from matten_amd import plan as mplan
 
@@ -33,6 +38,8 @@ LAYERS = {
     "paper_view_S3": (PAPER["conv_layer_irreps"], VIEW, alc.SH4, False, 3),
     "paper_like_S3": (*alc.CASES["paper_like"], False, 3),
 }
+# the operator-level cases of test_gpu_tp_narrow.py: 8-lane scalar entries, 16-lane vector entries, mo = 1, every D3
+LAYERS.update({name: (in1, target, anc.SH4, False, 3) for name, (in1, target, _) in anc.CASES.items()})
 
 
 def _layer(name):
@@ -46,16 +53,7 @@ def _layer(name):
     return lay, alc.Layer(name, S, lay.uvu, apn, lay.irreps_out, lay.gate, cm)
 
 
-def _narrow_weights(ap, w):
-    """PointConv._pack_narrow_weights: gathered from the flat weight, scaled in fp32"""
-    return (np.asarray(w, dtype=np.float32)[ap.narrow_gather] * ap.narrow_scale).astype(np.float32)
-
-
-def _wtab(ap, w):
-    """PointConv._pack_agg_weights with the sentinel: 1.0 where a narrowed coupling wrote lin2's output channel itself"""
-    w = np.asarray(w, dtype=np.float32)
-    one = (ap.gather == mplan.AGG_GATHER_ONE).astype(np.float32)
-    return np.where(ap.gather >= 0, w[np.clip(ap.gather, 0, None)] * ap.scale[None, :].astype(np.float32), one).astype(np.float32)
+_narrow_weights, _wtab = anc.narrow_weights, anc.wtab      # (shared with test_gpu_tp_narrow.py)
 
 
 def _write_rows(lay, agg, species, w):
@@ -106,8 +104,11 @@ def _check_blocks(out, want, blocks, what):
 @pytest.mark.parametrize("name", list(LAYERS))
 def test_narrowed_writer_and_unchanged_reader_match_fp64_lin2(name):
     _, lay = _layer(name)
+    _walk_writer_and_reader(lay, name, 9)
+
+
+def _walk_writer_and_reader(lay, name, N):
     ap = lay.ap
-    N = 9
     species = np.random.default_rng(1).integers(0, lay.S, N)
     agg, w = alc.make_inputs(lay, species)
     row, written = _write_rows(lay, agg, species, w)
@@ -137,7 +138,15 @@ def _count_from_instructions(uvu, irreps_out):
     8- or 16-lane entry of a scalar or vector input block whose output irrep has mo in {1, 2, 4} < mul channels takes mo slots
     per component, every other one its channels"""
     out = mplan.Irreps(irreps_out).simplify()
-    K = {}
+    K, _ = _slots_per_irrep(uvu, out)
+    data = sum(K[io] * out[io].ir.dim for io in K)
+    chunks = sum(-(-K[io] // 16) * out[io].ir.dim for io in K)
+    return data, -(-(16 * chunks) // 32) * 32
+
+
+def _slots_per_irrep(uvu, out):
+    """({output irrep: channel slots per component}, {output irrep: it has a narrowed piece}) by the rule above"""
+    K, narrowed = {}, {}
     for e, paths in enumerate(uvu.group_entry_paths):
         mul, lanes = int(uvu.group_entry_mul[e]), 1 << int(uvu.group_entries[e][3])
         for c, pi in paths.items():
@@ -145,9 +154,8 @@ def _count_from_instructions(uvu, irreps_out):
             (io, mo), = [(i, int(m)) for i, (m, ir) in enumerate(out) if (ir.l, ir.p) == (p.l3, p.p3)]
             narrow = p.l1 <= 1 and mul == lanes and mul in (8, 16) and mo < mul and mo in (1, 2, 4)
             K[io] = K.get(io, 0) + (mo if narrow else mul)
-    data = sum(K[io] * out[io].ir.dim for io in K)
-    chunks = sum(-(-K[io] // 16) * out[io].ir.dim for io in K)
-    return data, -(-(16 * chunks) // 32) * 32
+            narrowed[io] = narrowed.get(io, False) or narrow
+    return K, narrowed
 
 
 def test_row_length_equals_the_count_from_the_instruction_list():
@@ -192,3 +200,98 @@ def test_plan_agg_linear_returns_what_it_returned_before(golden_dir):
     ap = alc.layer("paper_like", 3).ap
     assert ap.narrow is None and ap.narrow_gather is None and not (ap.entries[:, 0] & mplan.TP_KIND_NARROW).any()
     assert ap.gather.min() == -1                  # (no sentinel in a plain plan)
+
+
+# ---- the operator-level case table -------------------------------------------------------------------------------------------
+def test_case_table_reaches_every_instance_the_planner_emits():
+    """the mirror of test_gpu_tp_narrow.py's coverage assertion: the (input l1, lanes per node, D3, mo) of the narrowed
+    couplings of agg_narrow_cases.CASES are exactly the 54 instances; a case dropped there shows here, without a GPU"""
+    anc.assert_every_instance_has_a_case()
+    assert anc.instances("s8_1") >= {(0, 8, d3, 1) for d3 in (1, 3, 5, 7, 9)}                  # 8-lane scalar entries, mo = 1
+    assert anc.instances("even_4") >= {(1, 16, d3, 4) for d3 in (1, 5, 9)}                     # 16-lane vector entries
+    assert {mo for _, _, _, mo in anc.instances("head2")} == {1, 2}                            # mixed mo in one plan
+    assert all(S == 3 for n, S in anc.PARAMS if n != "full_2") and {S for n, S in anc.PARAMS if n == "full_2"} == {1, 3, 5}
+    # view: narrowed and un-narrowed couplings side by side in one entry
+    uvu, ap = anc.uvu_plan("view"), anc.narrow_plan("view", 3)
+    per_entry = {}
+    for e, _, _, _, _, mo in anc.couplings(uvu, ap):
+        per_entry.setdefault(e, set()).add(bool(mo))
+    assert any(v == {True, False} for v in per_entry.values())
+    for name, S in anc.PARAMS:                                        # far from the packed words' limits
+        uvu, ap = anc.uvu_plan(name), anc.narrow_plan(name, S)
+        _assert_words_round_trip(uvu, ap, S)
+        assert max(o for *_, o, mo in anc.couplings(uvu, ap) if mo) <= 2606
+
+
+# ---- the packed words ---------------------------------------------------------------------------------------------------------
+def _assert_words_round_trip(uvu, ap, S):
+    """the two words of every coupling unpack to what the host-side table says, every field inside its bits, the weight block
+    inside the buffer of plan.narrow_blob; nothing reaches the sign bit"""
+    n = len(ap.entries)
+    for e, c, _, ks, o, mo in anc.couplings(uvu, ap):
+        nw, t, ow = int(ap.narrow[e][c]), int(ap.entries[e][8 + c]), int(ap.entries[e][20 + c])
+        assert t >= 0 and ow >= 0
+        if not nw:
+            assert mo == 0 and t < 1 << 20        # (a plain word must not read as a narrowed one)
+            continue
+        rel = mplan.narrow_unpack(t, ow)[3]
+        assert mo == nw & 255 and 32 * e + rel == 32 * n + (nw >> 8)
+        assert rel // 4 < 1 << 15 and o < 1 << 16 and ks < 1 << 20 and o + (mo - 1) < ap.ld
+        assert 32 * e + rel + S * int(uvu.group_entry_mul[e]) * mo <= 32 * n + ap.narrow_gather.size
+
+
+def test_weight_distance_past_its_field_gives_no_plan():
+    """a narrowed coupling's weight block lies rel floats behind its entry, rel / 4 in 15 bits: full_4's 2816 S floats of
+    writer weights pass 2^17 between S = 46 and 47.  Below: a plan whose words round-trip; from there on None, never a
+    wrapped distance (the caller keeps the plain plan)"""
+    uvu, target = anc.uvu_plan("full_4"), anc.CASES["full_4"][1]
+    ap3 = anc.narrow_plan("full_4", 3)
+    n = len(ap3.entries)
+    first = [(e, c, int(ap3.narrow[e][c]) >> 8) for e in range(n) for c in range(ap3.narrow.shape[1]) if ap3.narrow[e][c]]
+    assert all(w % 3 == 0 for _, _, w in first)        # blocks [species][u][v]: every offset is a multiple of S
+
+    def need(S):
+        return max(32 * (n - e) + w // 3 * S for e, _, w in first)
+
+    assert need(46) < 1 << 17 <= need(47)
+    for S in (40, 45, 46, 47, 48, 64, 200):
+        ap = mplan.plan_agg_narrow(uvu, S, target)
+        if need(S) >= 1 << 17:
+            assert ap is None, S
+            continue
+        assert ap is not None, S
+        _assert_words_round_trip(uvu, ap, S)
+        assert max(mplan.narrow_unpack(ap.entries[e][8 + c], ap.entries[e][20 + c])[3] for e, c, _ in first) == need(S)
+
+
+WIDE_TARGET = "32x0e+32x0o+16x1o+16x1e+16x2e+16x2o+16x3o+16x3e+1x4e+1x4o"    # only 4e and 4o narrow: the END of the row
+
+
+def _wide(mul):
+    in1 = f"{mul}x0e+{mul}x0o+{mul // 2}x1o+{mul // 2}x1e"
+    lay = alc.plan_case(in1, WIDE_TARGET, alc.SH4, 1, False, f"wide_{mul}")
+    out = lay.irreps_out
+    K, narrowed = _slots_per_irrep(lay.uvu, out)
+    start, starts = 0, {}
+    for io, (_, ir) in enumerate(out):                  # regions in the order of lin2's output irreps, [component][Kpad]
+        starts[io] = start
+        start += 16 * -(-K[io] // 16) * ir.dim
+    return lay, max(starts[io] for io in K if narrowed[io])
+
+
+def test_row_offset_past_its_field_gives_no_plan():
+    """a narrowed piece's first float has 16 bits.  A synthetic layer (816 / 832 scalar channels per parity, a wide target
+    whose only narrow irreps are the last two) puts the narrowed regions just below / above float 2^16 of the row: below, a
+    plan whose words round-trip and whose writer and reader walk to the fp64 lin2; above, None.  (The third field, floats
+    between components < 2^20, needs a region of a million channel slots: no irreps within the planner's other limits reach
+    it; _assert_words_round_trip pins it for every plan seen here.)"""
+    lay, start = _wide(816)
+    assert (1 << 16) - 1024 <= start < 1 << 16
+    ap = mplan.plan_agg_narrow(lay.uvu, 1, lay.irreps_out)
+    assert ap is not None and ap.ld > 1 << 16
+    _assert_words_round_trip(lay.uvu, ap, 1)
+    assert start <= max(o for *_, o, mo in anc.couplings(lay.uvu, ap) if mo) < 1 << 16
+    _walk_writer_and_reader(alc.Layer(lay.name, 1, lay.uvu, ap, lay.irreps_out, None, None), lay.name, 2)
+    lay, start = _wide(832)
+    assert start >= 1 << 16 and lay.ap is not None
+    assert mplan.plan_agg_narrow(lay.uvu, 1, lay.irreps_out) is None

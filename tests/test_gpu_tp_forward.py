@@ -98,11 +98,14 @@ def _sh_irreps(lmax):
     return Irreps.spherical_harmonics(lmax)
 
 
-def _plan(name):
+def _plan_of(irreps_in, lmax, target):
     from matten_amd import plan as mplan
 
-    irreps_in, lmax, target = IRREPS[name]
     return mplan.plan_uvu(irreps_in, _sh_irreps(lmax), target or irreps_in)
+
+
+def _plan(name):
+    return _plan_of(*IRREPS[name])
 
 
 def _kinds(p):
@@ -138,9 +141,13 @@ def _graph(kind, gen):
 
 
 def _oracle_tp(name):
+    return _oracle_tp_of(*IRREPS[name])
+
+
+def _oracle_tp_of(irreps_in, lmax, target):
+    """(fp64, fp32) copies of the oracle's tensor product (test_gpu_tp_narrow.py builds its own irreps with it)"""
     from oracle.matten_ref import nn as rnn
 
-    irreps_in, lmax, target = IRREPS[name]
     ref = rnn.UVUTensorProduct(irreps_in, str(_sh_irreps(lmax)), target or irreps_in, mlp_input_size=8,
                                mlp_hidden_size=32, mlp_num_hidden_layers=2, mlp_activation=torch.nn.functional.silu)
     return copy.deepcopy(ref.tp).double(), copy.deepcopy(ref.tp).float()
@@ -164,9 +171,7 @@ class Case:
 
 
 def _build(param, shared):
-    from matten_amd import ops
     from matten_amd.nn._tables import DeviceTables
-    from oracle.e3nn_lite.o3 import spherical_harmonics
 
     irreps_name, graph, norm = param
     _, lmax, target = IRREPS[irreps_name]
@@ -183,6 +188,34 @@ def _build(param, shared):
     c.p, c.t = p, tables
     c.target = target or IRREPS[irreps_name][0]
     edge_index, N = _graph(graph, gen)
+    x, Y, w64, w32 = _operands(c, lmax, edge_index, N, gen)
+    num_neigh = c.in_deg.float()                          # 0 where nothing arrives, as in production
+    c.avg = AVG if norm == "avg" else 0.0
+    nrm = torch.full((N,), AVG ** -0.5, dtype=torch.float64) if norm == "avg" else \
+        torch.where(c.rows_in, num_neigh.double().clamp(min=1) ** -0.5, torch.zeros((), dtype=torch.float64))
+    c.nn = num_neigh.to(DEV) if norm == "node" else None
+
+    # ---- the references: fp64, and the same oracle in fp32 whose distance from it sets the scale of the tolerance ----
+    c.ref = _reference(tp64, x.double(), Y.double(), w64, edge_index, N, nrm)
+    assert c.ref.shape == (N, p.d_mid)
+    c.ref32 = ref32 = _reference(tp32, x, Y, w32, edge_index, N, nrm.float()).double()
+    c.blocks = [(f"{q.l1},{q.l2},{q.l3}", slice(q.out_off, q.out_off + q.mul * (2 * q.l3 + 1))) for q in p.paths]
+    c.r32 = max(_ratio((ref32[c.rows_in][:, sl] - c.ref[c.rows_in][:, sl]).abs().max().item(),
+                       c.ref[c.rows_in][:, sl].abs().max().item()) for _, sl in c.blocks)
+    assert 0 < c.r32 < 1e-5, c.r32                            # an fp32 evaluation of a few hundred terms per output
+    c.rtol = min(FWD_RTOL, R32_FACTOR * c.r32)
+    c.results = {}
+    return c
+
+
+def _operands(c, lmax, edge_index, N, gen):
+    """the operands of one launch of plan c.p on a graph, set on c: everything but the normalisation.  -> the host values
+    (x, Y, w fp64, w fp32 in the original edge order) the references are evaluated on (test_gpu_tp_narrow.py builds its
+    cases with this too)"""
+    from matten_amd import ops
+    from oracle.e3nn_lite.o3 import spherical_harmonics
+
+    p = c.p
     E, W = edge_index.shape[1], p.weight_numel
     c.N, c.E, c.W = N, E, W
     src, dst = edge_index
@@ -197,10 +230,6 @@ def _build(param, shared):
     assert Y.shape[1] == p.sh_dim
     h2 = torch.randn(E, 32, generator=gen)
     W2 = torch.randn(32, W, generator=gen) / 32 ** 0.5    # uniform over columns: the A fragments are scaled per entry
-    num_neigh = c.in_deg.float()                          # 0 where nothing arrives, as in production
-    c.avg = AVG if norm == "avg" else 0.0
-    nrm = torch.full((N,), AVG ** -0.5, dtype=torch.float64) if norm == "avg" else \
-        torch.where(c.rows_in, num_neigh.double().clamp(min=1) ** -0.5, torch.zeros((), dtype=torch.float64))
 
     # ---- device operands, built the way production builds them ----
     perm, rowptr, src_sorted, err = ops.csr_build(edge_index.to(DEV), N)
@@ -214,7 +243,6 @@ def _build(param, shared):
     Yd = torch.full((E, SH_STRIDE), nan)
     Yd[:, : p.sh_dim] = Y
     c.Y = Yd[c.perm].to(DEV)
-    c.nn = num_neigh.to(DEV) if norm == "node" else None
     cols = torch.as_tensor(p.fused_cols)
     w2f = torch.where(cols[None, :] >= 0, W2[:, cols.clamp(min=0)], W2.new_zeros(()))
     c.w2f = torch.nn.functional.pad(w2f, (0, (-w2f.shape[1]) % 16 + 16)).contiguous().to(DEV)   # >= 16 zero pad columns
@@ -234,18 +262,7 @@ def _build(param, shared):
     wd = torch.full((E, c.w_pad), nan)
     wd[:, :W] = w32
     c.w32 = wd[c.perm].to(DEV)
-
-    # ---- the references: fp64, and the same oracle in fp32 whose distance from it sets the scale of the tolerance ----
-    c.ref = _reference(tp64, x.double(), Y.double(), w64, edge_index, N, nrm)
-    assert c.ref.shape == (N, p.d_mid)
-    c.ref32 = ref32 = _reference(tp32, x, Y, w32, edge_index, N, nrm.float()).double()
-    c.blocks = [(f"{q.l1},{q.l2},{q.l3}", slice(q.out_off, q.out_off + q.mul * (2 * q.l3 + 1))) for q in p.paths]
-    c.r32 = max(_ratio((ref32[c.rows_in][:, sl] - c.ref[c.rows_in][:, sl]).abs().max().item(),
-                       c.ref[c.rows_in][:, sl].abs().max().item()) for _, sl in c.blocks)
-    assert 0 < c.r32 < 1e-5, c.r32                            # an fp32 evaluation of a few hundred terms per output
-    c.rtol = min(FWD_RTOL, R32_FACTOR * c.r32)
-    c.results = {}
-    return c
+    return x, Y, w64, w32
 
 
 @pytest.fixture(scope="module")
