@@ -650,6 +650,66 @@ int matten_elastic_polycrystal_bwd(const double* voigt, const int32_t* flags, co
                                    const double* g_sc, int64_t n, double* g_voigt, matten_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Textured polycrystals (csrc/texture.hip): the effective anisotropic tensor of an aggregate under an orientation
+ * distribution -- the Voigt, Reuss, Hill and geometric (Matthies & Humbert) means.  Replaces a host loop over crystals x
+ * orientations on the ElasticTensor(t) objects the reference hands back (predict.py:217-218).  A rotation R maps
+ * crystal-frame to sample-frame components, C'_ijkl = R_ia R_jb R_kc R_ld C_abcd; an improper R acts like -R.  Mandel form
+ * as above; N(R) = D Q(R) D^-1 (Q: Bond's matrix) is the orthogonal 6x6 matrix with C'^ = N C^ N^T.  A texture is G
+ * orientations with weights normalised to sum 1; its operator is <X> = sum_g w_g N_g X N_g^T on symmetric 6x6 matrices.
+ * An aggregate is a list of members (crystal, texture, volume fraction), fractions normalised per aggregate.  With
+ * S^ = (C^)^-1 and L^ = log C^:
+ *     voigt = sum_m f_m <C^_m>_t      reuss = (sum_m f_m <S^_m>_t)^-1      hill = (voigt + reuss) / 2
+ *     geometric = exp(sum_m f_m <L^_m>_t)                                  (geometric(C)^-1 == geometric(S))
+ * each returned as a Voigt stiffness matrix D^-1 X^ D^-1 (the convention of matten_elastic_props' voigt).  fp64.
+ * matten_texture_operator: the cost of a texture must not depend on the number of crystals, so G orientations are reduced
+ *   once to op [T,441]: op[t] acts on the 21 upper-triangle entries of a Mandel matrix in row-major order (0,0), (0,1), ...
+ *   (0,5), (1,1), ... (5,5), X'_p = sum_q op[p,q] X_q, op[(I,J),(K,L)] = sum_g w_g (N_IK N_JL + [K != L] N_IL N_JK).
+ *   R [G,9] row-major, weights [G] or NULL (equal), tex_ptr [T+1] int64: texture t owns orientations tex_ptr[t] ..
+ *   tex_ptr[t+1]; tex_flags [T] int32.  A texture gets flag bit 0 and a NaN operator when it is empty (or its range is not
+ *   inside 0..G), its weight sum is not positive, a weight is negative or not finite, or an R has a non-finite entry or
+ *   max|R R^T - 1| > orth_tol.  A texture is cut into slices of slice_len orientations, one workgroup each (one thread
+ *   per operator entry, the slice's N_g built 64 at a time into LDS); a slice adds its orientations in order, the partial
+ *   sums go to workspace [T * ceil(G / slice_len) * 448] doubles and are added in slice order, then divided by the weight
+ *   sum: fixed order, no atomics, bitwise reproducible for a given slice_len.  (Beyond the sketch of the issue: orth_tol,
+ *   slice_len and the workspace are arguments.)
+ * matten_texture_average: voigt [n,36], flags [n] as matten_elastic_props wrote them, moduli [n,6], vectors [n,36] as
+ *   matten_elastic_kelvin wrote them for that voigt (Jacobi does not run on the inputs again: S^ = U diag(1/l) U^T,
+ *   L^ = U diag(log l) U^T; the Voigt mean takes C^ from voigt itself).  op, tex_flags as above; member_crystal [M] int32,
+ *   member_texture [M] int32, member_fraction [M]; agg_ptr [A+1] int64: aggregate a owns members agg_ptr[a] .. agg_ptr[a+1],
+ *   added in list order.  out [A,4,36] = voigt, reuss, hill, geometric; status [A] int32.  The inverse of the mean
+ *   compliance and the exponential of the mean logarithm are one cyclic Jacobi (csrc/sym6.h) each.  status -1 (all four
+ *   NaN): a member with flag bit 0 or a decomposition that is not finite, a flagged member texture, a member index out of
+ *   range, a fraction negative or not finite, a fraction sum not positive, an empty aggregate (or a range outside 0..M);
+ *   status 2 (voigt computed, the other three NaN): a member with flag bit 1 or l_min <= 0; else 0.
+ * matten_texture_average_bwd: g_out [A,4,36] -> g_voigt [n,36] = D g_C^ D, every element written, symmetric.  voigt: op^T g;
+ *   reuss: g_S = -C_R g C_R, op^T, g_C = -S g_S S; hill: half of each; geometric: Daleckii-Krein at exp and at log,
+ *   U (Delta o (U^T g U)) U^T with divided differences that stay finite at equal eigenvalues (log1p / expm1, a series below
+ *   a relative gap of 1e-6).  The eigenvectors of the mean logarithm are those of the geometric mean in `out`, found by
+ *   one Jacobi per aggregate.  Parts that the forward wrote as NaN contribute exact zeros (selects, not products); the
+ *   voigt part of a status-2 aggregate still flows.  A crystal may belong to several aggregates: each member writes a row
+ *   of 21, and crystal c adds the rows of members crystal_member[crystal_ptr[c] .. crystal_ptr[c+1]] (int32 / int64, the
+ *   caller's inverse of member_crystal, ascending) in that order.  workspace: A * 64 + M * 21 doubles.  Textures, weights
+ *   and fractions receive no gradient.  (Beyond the sketch: the inverse list and the workspace are arguments; voigt and
+ *   flags are not needed.)
+ * All three: no atomics, nothing read back, capturable; each aggregate independent of the others.  T = 0, A = 0 and n = 0
+ * (bwd) are no-ops.  MATTEN_EINVAL: a negative count, n, M or A above 2^31 - 1 workgroups, T or T * slices above 2^31 - 1,
+ * slice_len < 1, orth_tol negative or not finite, a NULL required pointer for a non-zero count; MATTEN_ENOMEM: a workspace
+ * that is NULL or too small.  All checks return before anything touches a device.
+ * ------------------------------------------------------------------------------------------ */
+int matten_texture_operator(const double* R, const double* weights, const int64_t* tex_ptr, int64_t G, int64_t T,
+                            double orth_tol, int64_t slice_len, double* workspace, int64_t workspace_doubles, double* op,
+                            int32_t* tex_flags, matten_stream_t stream);
+int matten_texture_average(const double* voigt, const int32_t* flags, const double* moduli, const double* vectors, int64_t n,
+                           const double* op, const int32_t* tex_flags, int64_t T, const int32_t* member_crystal,
+                           const int32_t* member_texture, const double* member_fraction, int64_t M, const int64_t* agg_ptr,
+                           int64_t A, double* out, int32_t* status, matten_stream_t stream);
+int matten_texture_average_bwd(const double* moduli, const double* vectors, int64_t n, const double* op, int64_t T,
+                               const int32_t* member_crystal, const int32_t* member_texture, const double* member_fraction,
+                               int64_t M, const int64_t* agg_ptr, int64_t A, const double* out, const int32_t* status,
+                               const double* g_out, const int64_t* crystal_ptr, const int32_t* crystal_member,
+                               double* workspace, int64_t workspace_doubles, double* g_voigt, matten_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Derived quantities of per-atom rank-2 tensors (predict.py:117-148: the reference hands back one 3x3 array per atom;
  * NMR users read the isotropic value, span and skew or the Haeberlen anisotropy and asymmetry off it, with the
  * principal axes).  fp64 arithmetic, one atom per thread, values in the units of the input.

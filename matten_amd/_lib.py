@@ -146,6 +146,10 @@ SIGNATURES = {
     "matten_elastic_kelvin_clamp": (c_int, [P, P, P, ctypes.c_double, c_int64, P, P]),
     "matten_elastic_polycrystal": (c_int, [P, P, P, P, c_int64, c_int, ctypes.c_double, c_int, P, P, P, P]),
     "matten_elastic_polycrystal_bwd": (c_int, [P, P, P, P, P, c_int64, P, P]),
+    "matten_texture_operator": (c_int, [P, P, P, c_int64, c_int64, ctypes.c_double, c_int64, P, c_int64, P, P, P]),
+    "matten_texture_average": (c_int, [P, P, P, P, c_int64, P, P, c_int64, P, P, P, c_int64, P, c_int64, P, P, P]),
+    "matten_texture_average_bwd": (c_int, [P, P, c_int64, P, c_int64, P, P, P, c_int64, P, c_int64, P, P, P, P, P, P, c_int64,
+                                           P, P]),
     "matten_rank2_props": (c_int, [P, c_int, c_int64, P, P, P, P, P]),
     "matten_rank2_props_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int64, P, P]),
     "matten_wigner_d": (c_int, [P, c_int64, c_int, ctypes.c_double, P, P, P]),

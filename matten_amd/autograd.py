@@ -586,6 +586,34 @@ class ElasticPolycrystalFn(torch.autograd.Function):
                 None, None)
 
 
+class TextureAverageFn(torch.autograd.Function):
+    """(out, status) = matten_texture_average(voigt, flags, moduli, vectors, ...) with its adjoint
+    (matten_texture_average_bwd).  Only ``voigt`` receives a gradient -- ``moduli`` and ``vectors`` are the decomposition of
+    that same ``voigt``, the adjoint is the total derivative with respect to it --; the operators, the member lists and the
+    fractions carry none.  ``crystal_ptr`` / ``crystal_member`` are the inverse of ``member_crystal``, built once by the
+    caller.  When nothing downstream used ``out`` no kernel runs."""
+
+    @staticmethod
+    def forward(ctx, voigt, flags, moduli, vectors, op, tex_flags, member_crystal, member_texture, member_fraction, agg_ptr,
+                crystal_ptr, crystal_member):
+        out, status = ops.texture_average(voigt, flags, moduli, vectors, op, tex_flags, member_crystal, member_texture,
+                                          member_fraction, agg_ptr)
+        ctx.save_for_backward(moduli, vectors, op, tex_flags, member_crystal, member_texture, member_fraction, agg_ptr, out,
+                              status, crystal_ptr, crystal_member)
+        ctx.mark_non_differentiable(status)
+        ctx.set_materialize_grads(False)
+        return out, status
+
+    @staticmethod
+    def backward(ctx, g_out, _g_status):
+        if g_out is None:
+            return (None,) * 12
+        moduli, vectors, op, tex_flags, mc, mt, mf, agg_ptr, out, status, crystal_ptr, crystal_member = ctx.saved_tensors
+        g = ops.texture_average_bwd(moduli, vectors, op, tex_flags, mc, mt, mf, agg_ptr, out, status, g_out.contiguous(),
+                                    crystal_ptr, crystal_member)
+        return (g,) + (None,) * 11
+
+
 class Rank2PropsFn(torch.autograd.Function):
     """(vals, axes, props, flags) = matten_rank2_props(t) with its adjoint kernel (matten_rank2_props_bwd): the backward
     works from the four outputs alone, so the input is not kept and Jacobi is not run again.  An output that nothing

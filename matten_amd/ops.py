@@ -1290,6 +1290,107 @@ def elastic_polycrystal_bwd(voigt, flags, out, status, g_sc) -> torch.Tensor:
     return g_voigt
 
 
+TEXTURE_SLICE = 1024          # orientations per workgroup of matten_texture_operator
+_TEXTURE_PART = 448           # doubles per (texture, slice) partial sum
+
+
+def texture_operator(R, weights, tex_ptr, orth_tol: float = 1e-6, slice_len: int = TEXTURE_SLICE):
+    """R [G,3,3] fp64, weights [G] fp64 or None (equal), tex_ptr [T+1] int64 (texture t owns orientations tex_ptr[t] ..
+    tex_ptr[t+1]) -> (op [T,21,21] fp64, tex_flags [T] int32): the operator of every texture on the 21 upper-triangle
+    entries of a Mandel matrix; a bad texture is NaN with flag bit 0.  ``slice_len`` orientations go to one workgroup, the
+    slices' partial sums are added in order (include/matten_hip.h: matten_texture_operator)"""
+    lib = _lib.load()
+    slice_len, orth_tol = int(slice_len), float(orth_tol)
+    if slice_len < 1:
+        raise ValueError(f"slice_len: expected an int >= 1, got {slice_len!r}")
+    if not (np.isfinite(orth_tol) and orth_tol >= 0.0):
+        raise ValueError(f"orth_tol: expected a finite number >= 0, got {orth_tol!r}")
+    R = _need(R, torch.float64, "R")
+    tex_ptr = _need(tex_ptr, torch.int64, "tex_ptr")
+    if R.dim() != 3 or R.shape[1:] != (3, 3) or tex_ptr.dim() != 1 or tex_ptr.numel() < 1:
+        raise ValueError(f"expected R [G,3,3], tex_ptr [T+1]; got {tuple(R.shape)}, {tuple(tex_ptr.shape)}")
+    G, T = R.shape[0], tex_ptr.numel() - 1
+    if weights is not None:
+        weights = _need(weights, torch.float64, "weights")
+        if weights.shape != (G,):
+            raise ValueError(f"weights: expected {(G,)}, got {tuple(weights.shape)}")
+    op = torch.empty(T, 21, 21, dtype=torch.float64, device=R.device)
+    tex_flags = torch.empty(T, dtype=torch.int32, device=R.device)
+    n_ws = T * ((G + slice_len - 1) // slice_len) * _TEXTURE_PART
+    ws = torch.empty(n_ws, dtype=torch.float64, device=R.device) if n_ws else None
+    _lib.check(lib.matten_texture_operator(_ptr(R), _ptr(weights), _ptr(tex_ptr), G, T, orth_tol, slice_len, _ptr(ws), n_ws,
+                                           _ptr(op), _ptr(tex_flags), _stream()), "matten_texture_operator")
+    return op, tex_flags
+
+
+def _texture_members(op, tex_flags, member_crystal, member_texture, member_fraction, agg_ptr):
+    op, tex_flags = _need(op, torch.float64, "op"), _need(tex_flags, torch.int32, "tex_flags")
+    member_crystal = _need(member_crystal, torch.int32, "member_crystal")
+    member_texture = _need(member_texture, torch.int32, "member_texture")
+    member_fraction = _need(member_fraction, torch.float64, "member_fraction")
+    agg_ptr = _need(agg_ptr, torch.int64, "agg_ptr")
+    T, M = tex_flags.shape[0] if tex_flags.dim() == 1 else -1, member_crystal.numel()
+    if op.shape != (T, 21, 21):
+        raise ValueError(f"expected op [T,21,21], tex_flags [T]; got {tuple(op.shape)}, {tuple(tex_flags.shape)}")
+    if member_crystal.shape != (M,) or member_texture.shape != (M,) or member_fraction.shape != (M,) or agg_ptr.dim() != 1 \
+            or agg_ptr.numel() < 1:
+        raise ValueError("expected member_crystal, member_texture, member_fraction [M] and agg_ptr [A+1]")
+    return op, tex_flags, member_crystal, member_texture, member_fraction, agg_ptr, T, M, agg_ptr.numel() - 1
+
+
+def texture_average(voigt, flags, moduli, vectors, op, tex_flags, member_crystal, member_texture, member_fraction, agg_ptr):
+    """voigt [n,6,6] fp64, flags [n] int32 as ``elastic_props`` returns them, moduli [n,6], vectors [n,6,6] as
+    ``elastic_kelvin`` returns them for it; (op, tex_flags) of ``texture_operator``; the members (crystal [M] int32, texture
+    [M] int32, fraction [M] fp64) of the aggregates agg_ptr [A+1] int64 -> (out [A,4,6,6] = the voigt, reuss, hill and
+    geometric means as Voigt matrices, status [A] int32: 0, 2 not positive definite, -1 no value)
+    (include/matten_hip.h: matten_texture_average)"""
+    lib = _lib.load()
+    voigt, flags, n = _kelvin_rows(voigt, flags)
+    moduli, vectors = _need(moduli, torch.float64, "moduli"), _need(vectors, torch.float64, "vectors")
+    if moduli.shape != (n, 6) or vectors.shape != (n, 6, 6):
+        raise ValueError(f"expected moduli [n,6], vectors [n,6,6]; got {tuple(moduli.shape)}, {tuple(vectors.shape)}")
+    op, tex_flags, mc, mt, mf, agg_ptr, T, M, A = _texture_members(op, tex_flags, member_crystal, member_texture,
+                                                                  member_fraction, agg_ptr)
+    out = torch.empty(A, 4, 6, 6, dtype=torch.float64, device=voigt.device)
+    status = torch.empty(A, dtype=torch.int32, device=voigt.device)
+    _lib.check(lib.matten_texture_average(_ptr(voigt), _ptr(flags), _ptr(moduli), _ptr(vectors), n, _ptr(op), _ptr(tex_flags), T,
+                                          _ptr(mc), _ptr(mt), _ptr(mf), M, _ptr(agg_ptr), A, _ptr(out), _ptr(status), _stream()),
+               "matten_texture_average")
+    return out, status
+
+
+def texture_average_bwd(moduli, vectors, op, tex_flags, member_crystal, member_texture, member_fraction, agg_ptr, out, status,
+                        g_out, crystal_ptr, crystal_member) -> torch.Tensor:
+    """the adjoint of ``texture_average``: its inputs, its outputs (out [A,4,6,6], status [A]), the upstream gradient g_out
+    [A,4,6,6] and the inverse of member_crystal (crystal_ptr [n+1] int64, crystal_member [M] int32: the members of every
+    crystal, ascending) -> g_voigt [n,6,6] fp64, symmetric; a crystal's memberships are added in member order
+    (matten_texture_average_bwd)"""
+    lib = _lib.load()
+    moduli, vectors = _need(moduli, torch.float64, "moduli"), _need(vectors, torch.float64, "vectors")
+    n = moduli.shape[0]
+    if moduli.shape != (n, 6) or vectors.shape != (n, 6, 6):
+        raise ValueError(f"expected moduli [n,6], vectors [n,6,6]; got {tuple(moduli.shape)}, {tuple(vectors.shape)}")
+    op, tex_flags, mc, mt, mf, agg_ptr, T, M, A = _texture_members(op, tex_flags, member_crystal, member_texture,
+                                                                  member_fraction, agg_ptr)
+    out, g_out = _need(out, torch.float64, "out"), _need(g_out, torch.float64, "g_out")
+    status = _need(status, torch.int32, "status")
+    crystal_ptr, crystal_member = _need(crystal_ptr, torch.int64, "crystal_ptr"), _need(crystal_member, torch.int32, "crystal_member")
+    if out.shape != (A, 4, 6, 6) or g_out.shape != (A, 4, 6, 6) or status.shape != (A,):
+        raise ValueError(f"expected out, g_out [A,4,6,6], status [A]; got {tuple(out.shape)}, {tuple(g_out.shape)}, "
+                         f"{tuple(status.shape)}")
+    if crystal_ptr.shape != (n + 1,) or crystal_member.shape != (M,):
+        raise ValueError(f"expected crystal_ptr [{n + 1}], crystal_member [{M}]; got {tuple(crystal_ptr.shape)}, "
+                         f"{tuple(crystal_member.shape)}")
+    g_voigt = torch.empty(n, 6, 6, dtype=torch.float64, device=moduli.device)
+    n_ws = A * 64 + M * 21
+    ws = torch.empty(n_ws, dtype=torch.float64, device=moduli.device) if n_ws else None
+    _lib.check(lib.matten_texture_average_bwd(_ptr(moduli), _ptr(vectors), n, _ptr(op), T, _ptr(mc), _ptr(mt), _ptr(mf), M,
+                                              _ptr(agg_ptr), A, _ptr(out), _ptr(status), _ptr(g_out), _ptr(crystal_ptr),
+                                              _ptr(crystal_member), _ptr(ws), n_ws, _ptr(g_voigt), _stream()),
+               "matten_texture_average_bwd")
+    return g_voigt
+
+
 def elastic_directional(compliance, flags, dirs, keep: bool = False):
     """compliance [B,6,6] fp64, flags [B] int32, unit directions dirs [D,3] fp64 -> (young [B,D] or None, beta [B,D] or
     None, ext [B,4] = E_min, E_max, beta_min, beta_max, arg [B,4] int32) (matten_elastic_directional)"""

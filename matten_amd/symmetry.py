@@ -29,8 +29,8 @@ translations and atom permutations in a ``CrystalSymmetry``), ``symmetrize_atoms
 ``symmetrize_atoms_host`` restate both in numpy ("Finding a crystal's symmetry").
 
 Not here: cell reduction (a cell outside the search range is flagged), crystals above 1024 atoms, refinement of
-positions, space-group symbols, gradients through ``symmetrize_atoms`` or with respect to rotations, Reuss / Hill texture
-averages, Euler-angle and quaternion front ends, l > 4.
+positions, space-group symbols, gradients through ``symmetrize_atoms`` or with respect to rotations, Euler-angle and
+quaternion front ends, l > 4.  The Reuss, Hill and geometric texture averages are in ``matten_amd/texture.py``.
 """
 import functools
 import re
