@@ -710,6 +710,41 @@ int matten_texture_average_bwd(const double* moduli, const double* vectors, int6
                                double* workspace, int64_t workspace_doubles, double* g_voigt, matten_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Group velocities, polarisations and phonon focusing (csrc/waves.hip): what the eigenvectors of the Christoffel matrix
+ * give beyond the phase velocities of matten_elastic_acoustic.  fp64.
+ * matten_elastic_waves: the launch shape of matten_elastic_acoustic -- one workgroup per crystal over unit directions dirs
+ *   [n_dirs,3], the lanes striding the directions, the crystal's 21 constants read once.  voigt [n,36] (the mean of its two
+ *   triangles is C_ijkl), flags [n], density [n], modulus_unit as there; s = modulus_unit / density.  Per direction n:
+ *   Gamma_ik = C_ijkl n_j n_l, its eigenpairs (lambda_k, u_k), lambda ascending, k = 0, 1, 2, by the cyclic Jacobi of
+ *   matten_elastic_acoustic_bwd (the eigenvalues are those of matten_elastic_acoustic); v_k = sqrt(lambda_k s).
+ *   Unstable direction (an eigenvalue that is not positive and finite): every output of the direction is NaN and it is
+ *   counted in n_unstable [n].  Degenerate mode: gap_k = min_{m != k} |lambda_k - lambda_m| / lambda_2 < deg_tol; the phase
+ *   velocity of the branch is still written, everything else of it is NaN (undefined: conical refraction), and it is
+ *   counted in n_degenerate [n,3] (modes of unstable directions are not).
+ *   Polarisation: the unit vector u_k with u.n >= 0; where |u.n| <= 1e-9, u.e1 >= 0; where that is <= 1e-9 too, u.e2 >= 0,
+ *   (e1, e2) the frame of n of matten_elastic_pair (e1 x e2 = n).  Longitudinal character (u_k.n)^2.
+ *   Group velocity g_k = (s / v_k) P, P_j = C_ijml u_i u_m n_l (m/s; g_k.n = v_k); power-flow angle
+ *   psi_k = acos(min(1, v_k / |g_k|)).  Focusing Jacobian J_k = g^ . (d_e1 g^ x d_e2 g^), g^ = g_k / |g_k|: the signed
+ *   Jacobian of n -> g^ between unit spheres (1 / |J| is the phonon-focusing enhancement factor, infinite on a caustic; J < 0
+ *   on a folded sheet), with the analytic derivative along e of (e1, e2):
+ *     dGamma_ik = C_ijkl (e_j n_l + n_j e_l),  du = sum_{m != k} u_m (u_m^T dGamma u_k) / (lambda_k - lambda_m),
+ *     dlambda = u_k^T dGamma u_k,  dv = s dlambda / (2 v_k),
+ *     dP_j = C_ijml (du_i u_m + u_i du_m) n_l + C_ijml u_i u_m e_l  (two different du terms),
+ *     dg = s dP / v_k - g dv / v_k,  dg^ = (dg - g^ (g^.dg)) / |g|.
+ *   pol, group [n,n_dirs,3,3] (branch, component), scal [n,n_dirs,3,5] = v_k, |g_k|, psi_k, character, J_k: each optional,
+ *   NULL = not written.  ext [n,6] = the largest psi of branch 0, 1, 2, then the smallest |J| of branch 0, 1, 2 over the
+ *   directions; arg [n,6] int32 = their direction indices (NaN ignored, equal values resolved to the lowest index, NaN and
+ *   -1 if no finite value).  Rows with flag bit 0 or a density that is not positive and finite: NaN in every floating-point
+ *   output, -1 in every integer output.  No atomics; lane-strided, xor butterfly, waves in index order: bitwise
+ *   reproducible.  Nothing is read back or allocated: capturable.
+ *   MATTEN_EINVAL before any launch: n < 0 or > 2^31 - 1 (one workgroup per crystal), n_dirs < 1 or > (2^31 - 1) / 3, deg_tol negative or not finite, a NULL required
+ *   pointer with n > 0; n == 0 returns MATTEN_OK.
+ * ------------------------------------------------------------------------------------------ */
+int matten_elastic_waves(const double* voigt, const int32_t* flags, const double* density, const double* dirs, int64_t n,
+                         int64_t n_dirs, double modulus_unit, double deg_tol, double* pol, double* group, double* scal,
+                         double* ext, int32_t* arg, int32_t* n_degenerate, int32_t* n_unstable, matten_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Derived quantities of per-atom rank-2 tensors (predict.py:117-148: the reference hands back one 3x3 array per atom;
  * NMR users read the isotropic value, span and skew or the Haeberlen anisotropy and asymmetry off it, with the
  * principal axes).  fp64 arithmetic, one atom per thread, values in the units of the input.

@@ -150,6 +150,7 @@ SIGNATURES = {
     "matten_texture_average": (c_int, [P, P, P, P, c_int64, P, P, c_int64, P, P, P, c_int64, P, c_int64, P, P, P]),
     "matten_texture_average_bwd": (c_int, [P, P, c_int64, P, c_int64, P, P, P, c_int64, P, c_int64, P, P, P, P, P, P, c_int64,
                                            P, P]),
+    "matten_elastic_waves": (c_int, [P, P, P, P, c_int64, c_int64, ctypes.c_double, ctypes.c_double, P, P, P, P, P, P, P, P]),
     "matten_rank2_props": (c_int, [P, c_int, c_int64, P, P, P, P, P]),
     "matten_rank2_props_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int64, P, P]),
     "matten_wigner_d": (c_int, [P, c_int64, c_int, ctypes.c_double, P, P, P]),

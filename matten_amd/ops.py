@@ -1435,6 +1435,32 @@ def elastic_acoustic(voigt, flags, density, dirs, modulus_unit: float = 1e9, kee
     return vel, ext, arg, n_unstable
 
 
+def elastic_waves(voigt, flags, density, dirs, modulus_unit: float = 1e9, deg_tol: float = 1e-6, keep: bool = True):
+    """voigt [B,6,6] fp64, flags [B] int32, density [B] fp64 (kg/m^3), unit directions dirs [D,3] fp64, modulus_unit in Pa
+    per unit of voigt, deg_tol the relative eigenvalue gap below which a mode counts as degenerate -> (pol [B,D,3,3],
+    group [B,D,3,3], scal [B,D,3,5] = v, |g|, psi, character, J -- each None without ``keep`` --, ext [B,6] = psi_max per
+    branch, then min |J| per branch, arg [B,6] int32, n_degenerate [B,3] int32, n_unstable [B] int32)
+    (matten_elastic_waves)"""
+    lib = _lib.load()
+    voigt, flags, dirs, density, _, B, D = _dir_set_args(voigt, "voigt", flags, dirs, density=density)
+    deg_tol = float(deg_tol)
+    if not (0.0 <= deg_tol < float("inf")):
+        raise ValueError(f"deg_tol: expected a finite value >= 0, got {deg_tol}")
+    dev = dirs.device
+    pol = torch.empty(B, D, 3, 3, dtype=torch.float64, device=dev) if keep else None
+    group = torch.empty(B, D, 3, 3, dtype=torch.float64, device=dev) if keep else None
+    scal = torch.empty(B, D, 3, 5, dtype=torch.float64, device=dev) if keep else None
+    ext = torch.empty(B, 6, dtype=torch.float64, device=dev)
+    arg = torch.empty(B, 6, dtype=torch.int32, device=dev)
+    n_degenerate = torch.empty(B, 3, dtype=torch.int32, device=dev)
+    n_unstable = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.matten_elastic_waves(_ptr(voigt), _ptr(flags), _ptr(density), _ptr(dirs), B, D, float(modulus_unit), deg_tol,
+                                        _ptr(pol), _ptr(group), _ptr(scal), _ptr(ext), _ptr(arg), _ptr(n_degenerate),
+                                        _ptr(n_unstable), _stream()),
+               "matten_elastic_waves")
+    return pol, group, scal, ext, arg, n_degenerate, n_unstable
+
+
 def elastic_refine(compliance, flags, dirs, ext_dir, arg_dir, cos_sin=None, ext_pair=None, arg_pair=None, tol: float = 1e-9,
                    max_iter: int = 32):
     """the extremes of ``elastic_directional`` (ext_dir / arg_dir [B,4]) and, with cos_sin [M,2] and ext_pair / arg_pair

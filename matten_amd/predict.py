@@ -740,6 +740,8 @@ def predict(
     hs_grid: int = 64,
     sc_tol: float = 1e-12,
     sc_max_iter: int = 200,
+    waves: bool = False,
+    deg_tol: float = 1e-6,
     shielding: bool = False,
 ):
     """See the module docstring.  ``model`` / ``config`` let a caller reuse an already loaded model.
@@ -758,6 +760,10 @@ def predict(
     ``elastic.elastic_properties(polycrystal=True)``: the Hashin-Shtrikman bounds ``k_hs_lower`` / ``g_hs_lower`` / ``k_hs_upper``
     / ``g_hs_upper`` with ``hs_media``, the self-consistent ``k_sc`` / ``g_sc`` / ``y_sc`` / ``poisson_sc``, ``sc_status`` and
     ``sc_iterations``.
+    ``waves=True`` (needs ``properties=True``, ``directions`` and ``density``; with ``deg_tol``) returns ``(tensors, props, waves)``,
+    ``waves`` a ``waves.AcousticWaves`` with one row per input structure: polarisations, group velocities, power-flow angles
+    and phonon-focusing Jacobians per direction and branch, from the Voigt matrices ``props`` holds on the device.  Tensors
+    and ``props`` are what they are without it.
     ``batch_size`` (reference predict.py:155) is the memory knob it is there: consecutive batches are merged into one forward
     only while the merged batch stays within ``node_budget`` atoms (default MATTEN_PREDICT_NODE_BUDGET = 65536, ~2 GB) and
     only when batch_size is at least the reference's default of 200; ``node_budget=0`` never merges.  A merged forward
@@ -785,6 +791,8 @@ def predict(
             raise ValueError("kelvin belongs to the derived properties: pass properties=True")
         if polycrystal:
             raise ValueError("polycrystal belongs to the derived properties: pass properties=True")
+        if waves:
+            raise ValueError("waves belongs to the derived properties: pass properties=True")
     if shielding:
         from .rank2 import rank2_basis
 
@@ -803,6 +811,16 @@ def predict(
         _check_polycrystal(polycrystal, hs_grid, sc_tol, sc_max_iter)
         _check_extras(directions, angles, density, number_density)
         _check_refine(refine, directions, refine_tol, refine_max_iter)
+        if not isinstance(waves, (bool, np.bool_)):
+            raise ValueError(f"waves: expected True or False, got {waves!r}")
+        if waves:
+            from .waves import check_deg_tol
+
+            if directions is None:
+                raise ValueError("waves: the acoustic modes need a direction set, pass directions")
+            if density is None:
+                raise ValueError("waves: the velocities need the mass density, pass density")
+            deg_tol = check_deg_tol(deg_tol)
         if isinstance(density, str):
             if density != "structure":
                 raise ValueError(f'density: expected values in kg/m^3 or "structure", got {density!r}')
@@ -857,6 +875,11 @@ def predict(
         props = _properties_of_slabs(device_rows, len(structures), failed, directions, single, angles, density,
                                      number_density, modulus_unit, refine, refine_tol, refine_max_iter, kelvin,
                                      polycrystal, hs_grid, sc_tol, sc_max_iter)
+        if waves:      # (from the Voigt matrices and the direction set that props holds on the device)
+            from .waves import waves_from_voigt
+
+            wave_props = waves_from_voigt(props.voigt.reshape(-1, 6, 6), props.flags.reshape(-1), density, props.directions,
+                                          modulus_unit, deg_tol, True, single)
     if is_elasticity_tensor:
         try:
             from pymatgen.analysis.elasticity import ElasticTensor
@@ -875,6 +898,8 @@ def predict(
     else:
         out = predictions
     out = out[0] if single else out
+    if properties and waves:
+        return out, props, wave_props
     return (out, props) if properties else out
 
 
